@@ -6,15 +6,20 @@ One "step" = what the reference does per cloud pair on this path (src/comparator
 query per point of the query cloud.  Inputs (raw AoS clouds) are resident in HBM
 when the timed region starts; outputs (idx int32, d2 float32) stay in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure and nothing else.  --full adds
+everything below (roofline, CPU baseline, exhaustive kernel, breakdowns, `extra`, pair counts, the full record in
+bench_out/bench_full.json).  --dump-outputs DIR writes what the timed path returned in its last timed step as
+DIR/<name>.npy (float32 / float64; k = 1: a fixed seeded sample of at most DUMP_MAX_QUERIES queries, rank 0's shard).
 
 Workload (BASELINE.json configs):
   default       C3, 10M x 10M XYZRGB (north_star's target size).  N = 1: the whole configuration on one GPU.  N > 1: the SAME
                 10M queries sharded over the ranks against the replicated 10M references -- north_star's partition, STRONG
                 scaling: `value` = 10M / (slowest rank's step).  The index build (0.4 ms at 10M) is replicated on every rank,
-                so the whole step cannot scale linearly (Amdahl); `scaling_terms` carries step / query-only / build times so
-                the curve can be read both ways, `extra.c3_weak` is the weak form (every rank its own 10M queries).
-                `extra` adds, at N = 1: C2 (1M x 1M, with the exhaustive north-star kernel on the same data), the C3
+                so the whole step cannot scale linearly (Amdahl); with --full `scaling_terms` carries step / query-only / build
+                times so the curve can be read both ways, `extra.c3_weak` is the weak form (every rank its own 10M queries).
+                With --full `extra` adds, at N = 1: C2 (1M x 1M, with the exhaustive north-star kernel on the same data), the C3
                 radius-0.05 clustering leg (-e path, 5M object points), C4 (50 fixed ICP iterations, 2M x 2M), the C5 shard
                 and `scaling_projection` (one GPU doing a G-th of the queries, G = 1, 2, 4, 8: a PROJECTION of the
                 strong-scaling curve from one device, never a measurement of it); at every N: C5 (32M queries sharded over
@@ -27,7 +32,7 @@ Multi GPU: one rank per GPU over RCCL.  `--gpus N` without a torch.distributed e
   cloud is broadcast once (outside the timed region; 16 B per point -- the packed form, SURVEY.md 8e -- whatever the
   workload's stride), queries are sharded, no collective inside a step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit..., "roofline"
+Prints ONE JSON line on rank 0: metric/value/unit/higher_is_better/dtype/ms_per_step..., with --full also "roofline"
 (dominant kernel of the measured path, HIP-event timed on the library's stream) and "cpu_baseline"
 (the oracle's FLANN-restatement kd-tree on this host, reported only).
 """
@@ -76,7 +81,34 @@ def parse_args():
     ap.add_argument("--no-exhaustive", action="store_true", help="skip the exhaustive-kernel leg")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra configurations of the default run")
     ap.add_argument("--no-pairs", action="store_true", help="skip the pair count by the profiling build (roofline then carries the HBM figure only)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: roofline, CPU baseline, exhaustive "
+                    "kernel, breakdowns, extra configurations, pair counts (the --no-* options above apply to this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     return ap.parse_args()
+
+
+# --dump-outputs: at most this many queries' results (8 B query number + 8 B index + 4 B d2 each: 40 MB, under 64 MB)
+DUMP_MAX_QUERIES = 2_000_000
+DUMP_SEED = 0xD0517
+
+
+def dump_positions(q_total):
+    """the global query numbers a dump holds: all of them up to DUMP_MAX_QUERIES, else a fixed seeded sample (sorted),
+    the same in every run of the same workload"""
+    import numpy as np
+    if q_total <= DUMP_MAX_QUERIES:
+        return np.arange(q_total, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(q_total, DUMP_MAX_QUERIES, replace=False))
+
+
+def write_outputs(d, arrays):
+    import numpy as np
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(d / f"{name}.npy", a)
 
 
 def check_device_count(ranks: int) -> None:
@@ -199,7 +231,7 @@ def compact(x):
     return x
 
 
-def short_line(out):
+def short_line(out, full=True):
     """the one JSON line: contract keys + roofline / cpu_baseline as flat scalars + every extra leg as {ms, value, ...}"""
     keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
             "data", "config", "query_only_queries_per_sec", "build_ms", "search_call_ms", "query_sort_ms", "fallback_queries",
@@ -260,10 +292,11 @@ def short_line(out):
             if name in ex:
                 e[name] = ex[name]
         line["extra"] = e
-    line["note"] = ("pruned exact k = 1 search (k_grid_nn1_flat2 + k_nn1_open_flat): roofline = SURVEY 8d bytes (12 B per reference and query, 8 B "
-                    "per result) over the kernels' HIP-event time; `traffic` = FETCH_SIZE x 2 + WRITE_SIZE per call from the committed PMC pass; "
-                    "exhaustive_* = the tiled brute-force kernel north_star names, on C2, against the non-FMA fp32 roof.  Full record: "
-                    "gpurun_out/bench_full.json")
+    if full:
+        line["note"] = ("pruned exact k = 1 search (k_grid_nn1_flat2 + k_nn1_open_flat): roofline = SURVEY 8d bytes (12 B per reference and query, 8 B "
+                        "per result) over the kernels' HIP-event time; `traffic` = FETCH_SIZE x 2 + WRITE_SIZE per call from the committed PMC pass; "
+                        "exhaustive_* = the tiled brute-force kernel north_star names, on C2, against the non-FMA fp32 roof.  Full record: "
+                        "bench_out/bench_full.json")
     return line
 
 
@@ -275,10 +308,10 @@ def main():
     # Pair counts of the workloads this run measures: the PROFILING build of the library in a CHILD process -- started here,
     # before this process initialises the GPU or joins a process group (a child forked later would inherit a profiler's
     # preload and keep the other ranks waiting in their first collective).  One-GPU runs only: the counts price the
-    # single-GPU rooflines; under rocprofv3 the child is skipped altogether.
+    # single-GPU rooflines (--full); under rocprofv3 the child is skipped altogether.
     primary_cfg = "c3" if args.config == "auto" else args.config
     pairs = {}
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pairs:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and not args.no_pairs:
         want = [primary_cfg] if primary_cfg != "c1" else []
         if args.config == "auto" and not args.no_extra:
             want += ["c2", "c4", "c5_shard", "c5"]
@@ -380,9 +413,11 @@ def main():
         return ref, ref_host, ms, nbytes
 
     # ---- k = 1 NN step of one configuration -----------------------------------------------------------------
-    def run_nn(cfg, n_per_rank=None, total_queries=None, steps=K, warmup=W, with_exhaustive=False, with_cpu=False, project=False):
+    def run_nn(cfg, n_per_rank=None, total_queries=None, steps=K, warmup=W, with_exhaustive=False, with_cpu=False, project=False,
+               full=True, dump=None):
         """total_queries: that many queries sharded over the ranks (strong scaling); else n_per_rank (or the config's size)
-        on every rank (weak).  project (one GPU only): the same step with a G-th of the queries, G in PROJECTION_G."""
+        on every rank (weak).  project (one GPU only): the same step with a G-th of the queries, G in PROJECTION_G.
+        full=False: the timed steps alone (the headline).  dump: directory for the last timed step's results."""
         M, N, floats, desc = CONFIGS[cfg]
         if total_queries is not None:
             q_start, N = shard_range(total_queries, rank, n_gpus)
@@ -406,10 +441,31 @@ def main():
         for _ in range(warmup):
             step()
         # timed region: only the dominant kernel is bracketed by HIP events (2 per step, recorded by the library
-        # on its own stream into a ring, no sync); the full breakdown costs ~48 us per step and runs untimed after
+        # on its own stream into a ring, no sync); the full breakdown costs ~48 us per step and runs untimed after.
+        # The region is the same with and without --full, so ms_per_step means the same in both
         ix.enable_timing(1)
         dt = timed(ix, step, steps)
         tm_main = ix.timing()
+        r = {
+            "workload": f"{desc}; step = index build over {M} references + {N} queries on each GPU "
+                        f"({q_total} over {n_gpus} GPU{'s' if n_gpus > 1 else ''})",
+            "value": q_total / (dt / steps), "unit": "queries/s", "ms_per_step": dt / steps * 1e3,
+            "steps": steps, "engine": engine_name, "references": M, "queries_per_gpu": N,
+            "queries_total": q_total, "point_stride_bytes": floats * 4, "broadcast_ms": bcast_ms, "broadcast_bytes": bcast_bytes,
+        }
+        if dump is not None and rank == 0:
+            # what a caller of the step receives (idx, d2) at the same fixed query numbers in every run; rank 0's shard
+            pos = dump_positions(q_total)
+            pos = pos[(pos >= q_start) & (pos < q_start + N)]
+            sel = torch.from_numpy(pos - q_start).to(dev)
+            write_outputs(dump, {"nn1_query": pos.astype(np.float64),
+                                 "nn1_index": idx.index_select(0, sel).cpu().numpy().astype(np.float64),
+                                 "nn1_d2": d2.index_select(0, sel).cpu().numpy()})
+        if not full:
+            ix.close()
+            del ref, qry, idx, d2
+            torch.cuda.empty_cache()
+            return r
         t0 = time.perf_counter()
         step()
         ix.sync()
@@ -433,16 +489,10 @@ def main():
             t[rank] = rank_ms
             dist.all_reduce(t)
             per_rank_ms = [round(float(v), 4) for v in t.tolist()]
-        r = {
-            "workload": f"{desc}; step = index build over {M} references + {N} queries on each GPU "
-                        f"({q_total} over {n_gpus} GPU{'s' if n_gpus > 1 else ''})",
-            "value": q_total / (dt / steps), "unit": "queries/s", "ms_per_step": dt / steps * 1e3,
-            "steps": steps, "engine": engine_name, "references": M, "queries_per_gpu": N,
-            "queries_total": q_total, "point_stride_bytes": floats * 4,
+        r.update({
             "query_only_queries_per_sec": q_total / (dtq / steps),
             "build_ms": dtb / steps * 1e3, "search_call_ms": tm[2], "query_sort_ms": tm[4], "main_kernel_ms": tm[0],
             "fallback_queries": stats[1] if engine_name == "grid" else 0,
-            "broadcast_ms": bcast_ms, "broadcast_bytes": bcast_bytes,
             # the terms of the scaling curve: the whole step (max over ranks), the query half alone (index kept: ICP's case) and
             # the index build, which every rank repeats whatever its share of the queries -- the Amdahl term of query sharding
             "scaling_terms": {"step_ms": dt / steps * 1e3, "query_only_ms": dtq / steps * 1e3, "build_ms": dtb / steps * 1e3,
@@ -453,7 +503,7 @@ def main():
                                       "sorted on a second stream beside the build's sort (PCC_OPT_OVERLAP_PREP: 2 % of the step in a same-box "
                                       "A/B, DESIGN.md 4.3), so the build's events inside a step (build_ms_inside_step) span the staging's "
                                       "kernels too and are no measure of the build"},
-        }
+        })
         if per_rank_ms is not None:
             r["per_rank_ms_per_step"] = per_rank_ms
         if project and n_gpus == 1:
@@ -665,12 +715,13 @@ def main():
         return r
 
     # ---- C4: -i ICP, 50 fixed iterations, 2M x 2M -------------------------------------------------------------
-    def run_icp(reps=2, iters=50):
+    def run_icp(reps=2, iters=50, warmup=1, dump=None):
         M, N, floats, desc = CONFIGS["c4"]
         tgt = torch.from_numpy(make_cloud(M, synth.SEED_A, floats)).to(dev)
         src = torch.from_numpy(synth.rigid_offset(make_cloud(N, synth.SEED_B, floats))).to(dev)
         ix = capi.Index(tgt, auto_sync=False)
-        ix.icp_align(src, max_iter=iters, fixed=True)
+        for _ in range(warmup):
+            ix.icp_align(src, max_iter=iters, fixed=True)
         ix.enable_timing(2)
         best = 1e9
         for _ in range(reps):
@@ -678,6 +729,9 @@ def main():
             t0 = time.perf_counter()
             T, fit, it, conv = ix.icp_align(src, max_iter=iters, fixed=True)
             best = min(best, time.perf_counter() - t0)
+        if dump is not None and rank == 0:
+            write_outputs(dump, {"icp_transform": T.astype(np.float64), "icp_fitness": np.array([fit], np.float64),
+                                 "icp_iterations": np.array([it], np.float64), "icp_converged": np.array([conv], np.float64)})
         tm = ix.timing()  # averages over the passes of the last calls: [0] NN kernel, [1] far/fallback, [2] whole pass
         ix.enable_timing(0)
         ix.close()
@@ -834,12 +888,13 @@ def main():
     strong_total = {"c3": C3_TOTAL_QUERIES, "c5": C5_TOTAL_QUERIES}.get(primary_cfg)
     if primary_cfg == "c4":
         prim = None
-        icp = run_icp()
+        icp = run_icp(reps=K, warmup=W, dump=args.dump_outputs)   # ms_per_step: the best of the K timed calls
         value, ms_per_step, workload = icp["nn_queries_per_sec"], icp["ms"], icp["workload"]
     else:
         prim = run_nn(primary_cfg, total_queries=strong_total,
-                      with_exhaustive=(not args.no_exhaustive and args.config != "auto"), with_cpu=not args.no_cpu,
-                      project=(args.config == "auto" and not args.no_extra))
+                      with_exhaustive=(args.full and not args.no_exhaustive and args.config != "auto"),
+                      with_cpu=args.full and not args.no_cpu,
+                      project=(args.full and args.config == "auto" and not args.no_extra), full=args.full, dump=args.dump_outputs)
         value, ms_per_step, workload = prim["value"], prim["ms_per_step"], prim["workload"]
 
     out = {
@@ -860,7 +915,7 @@ def main():
     else:
         out["icp"] = icp
 
-    if args.config == "auto" and not args.no_extra:
+    if args.full and args.config == "auto" and not args.no_extra:
         extra = {}
         if n_gpus == 1:
             extra["c2"] = run_nn("c2", with_exhaustive=not args.no_exhaustive, with_cpu=False)
@@ -902,8 +957,8 @@ def main():
     # the C-ABI's own RCCL path (pcc_comm_create_rank + pcc_index_create_broadcast: what a C++ host without torch uses),
     # beside torch.distributed's: the same cloud broadcast through libpcc_nn, one shard searched, bits compared with the
     # index built from torch's broadcast.  Opt-in (PCC_BENCH_CABI_COMM=1; tests/test_bench_gpu.py runs it with one rank):
-    # a second communicator on an untried node is not worth risking the headline line for
-    if dist is not None and os.environ.get("PCC_BENCH_CABI_COMM", "0") == "1" and backend == "nccl":
+    # a second communicator on an untried node is not worth risking the headline line for.  --full only
+    if args.full and dist is not None and os.environ.get("PCC_BENCH_CABI_COMM", "0") == "1" and backend == "nccl":
         M, N = 1_000_000, 250_000
         uid = [capi.comm_unique_id() if rank == 0 else None]
         dist.broadcast_object_list(uid, src=0)
@@ -933,17 +988,18 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        # the full record goes to a file (whoever wants every leg's detail reads it there); the LINE is what the driver keeps --
-        # the contract's keys, flat scalars, one note: under 7 KB
-        full = compact(out)
-        for d in (ROOT / "gpurun_out", Path(os.environ.get("TMPDIR", "/tmp"))):
-            try:
-                d.mkdir(exist_ok=True)
-                (d / "bench_full.json").write_text(json.dumps(full, indent=1))
-                break
-            except Exception:
-                continue
-        print(json.dumps(compact(short_line(out)), separators=(",", ":")))
+        # --full: the full record goes to a file (whoever wants every leg's detail reads it there); the LINE is what the driver
+        # keeps -- the contract's keys, flat scalars, one note: under 7 KB
+        if args.full:
+            full = compact(out)
+            for d in (ROOT / "bench_out", Path(os.environ.get("TMPDIR", "/tmp"))):
+                try:
+                    d.mkdir(exist_ok=True)
+                    (d / "bench_full.json").write_text(json.dumps(full, indent=1))
+                    break
+                except Exception:
+                    continue
+        print(json.dumps(compact(short_line(out, full=args.full)), separators=(",", ":")))
 
 
 if __name__ == "__main__":

@@ -38,7 +38,7 @@ def _run_rank(extra_args, timeout=600, more_env=None):
 
 
 def test_single_rank_rccl_group_runs_the_multi_gpu_path():
-    out = _run_rank(["--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-exhaustive"], more_env={"PCC_BENCH_CABI_COMM": "1"})
+    out = _run_rank(["--config", "c2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-exhaustive"], more_env={"PCC_BENCH_CABI_COMM": "1"})
     cabi = out["extra"]["c_abi_comm"]               # the library's own RCCL communicator next to torch's
     assert cabi["ranks"] == 1 and cabi["shard_results_equal_torch_broadcast_index"] and cabi["create_broadcast_ms"] > 0
     assert out["n_gpus"] == 1                      # the size RCCL's process group reported
@@ -61,7 +61,7 @@ def test_headline_leg_shards_the_ten_million_queries_and_ships_the_packed_cloud(
     """the N > 1 headline is north_star's partition: C3's 10M queries SHARDED over the ranks present (strong scaling; with the
     forced one-rank group the shard is all of them), the reference cloud broadcast at 16 B per point although the workload's
     stride is 32, and the line carries the terms a scaling curve has to be read with"""
-    out = _run_rank(["--config", "c3", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-exhaustive", "--no-pairs"])
+    out = _run_rank(["--config", "c3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-exhaustive", "--no-pairs"])
     assert out["scaling"] == "strong" and out["config"]["name"] == "c3"
     assert out["config"]["queries_total"] == 10_000_000 and out["config"]["queries_per_gpu"] == 10_000_000
     assert out["config"]["point_stride_bytes"] == 32 and out["broadcast_bytes"] == 10_000_000 * 16
@@ -76,7 +76,7 @@ def test_two_ranks_shard_the_headline_queries_between_them():
     the broadcast references (strong scaling) and report both ranks' step times; the times themselves mean nothing here."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update({"PCC_BENCH_SHARE_DEVICES": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
-    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "c3", "--steps", "2", "--warmup", "1", "--no-cpu",
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--config", "c3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
                         "--no-exhaustive", "--no-pairs"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -87,6 +87,30 @@ def test_two_ranks_shard_the_headline_queries_between_them():
     assert out["broadcast_bytes"] == 10_000_000 * 16 and len(out["per_rank_ms_per_step"]) == 2
     assert out["scaling_terms"]["queries_per_gpu"] == 5_000_000 and out["fallback_queries"] == 0
 
+
+
+def test_plain_run_times_the_steps_and_dumps_what_they_returned(tmp_path):
+    """`bench.py` without --full: the headline keys and nothing measured beyond the timed steps; --dump-outputs writes the
+    last timed step's results (C1: all 10k queries), bit-identical to the oracle's exhaustive search"""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import oracle
+    from pointcloudcomparator_amd import synth
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--config", "c1", "--steps", "4", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["metric"] == "nn_queries_per_sec" and out["unit"] == "queries/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["steps"] == 4 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"roofline", "cpu_baseline", "exhaustive", "extra", "scaling_terms", "note"} & set(out)
+    q, idx, d2 = (np.load(tmp_path / f"nn1_{n}.npy") for n in ("query", "index", "d2"))
+    assert q.dtype == np.float64 and idx.dtype == np.float64 and d2.dtype == np.float32
+    assert (q == np.arange(10_000)).all()
+    oi, od = oracle.nn1_exhaustive(synth.corridor_cloud(10_000, synth.SEED_A), synth.corridor_cloud(10_000, synth.SEED_B))
+    assert (idx == oi).all() and (d2.view(np.uint32) == od.view(np.uint32)).all()
 
 def test_more_ranks_than_gpus_is_refused_with_a_message():
     """`--gpus 8` on a box with fewer devices must fail at once and say why (no hang in the first collective)"""

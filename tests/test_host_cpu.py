@@ -87,6 +87,27 @@ def test_bench_line_helpers(monkeypatch):
     assert bench.under_profiler()
 
 
+
+def test_bench_is_plain_by_default_and_its_dump_is_fixed_and_small(monkeypatch, tmp_path):
+    """a plain bench run measures the headline only (--full adds the rest); --dump-outputs holds the same seeded sample of query
+    numbers in every run, float32 / float64 arrays only, within 64 MB"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    args = bench.parse_args()
+    assert not args.full and args.dump_outputs is None and args.steps == 5 and args.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    args = bench.parse_args()
+    assert args.full and args.dump_outputs == str(tmp_path)
+    a, b = bench.dump_positions(10_000_000), bench.dump_positions(10_000_000)
+    assert len(a) == bench.DUMP_MAX_QUERIES and (a == b).all() and (np.diff(a) > 0).all() and 0 <= a[0] and a[-1] < 10_000_000
+    assert (bench.dump_positions(10_000) == np.arange(10_000)).all()
+    assert bench.DUMP_MAX_QUERIES * (8 + 8 + 4) <= 64 << 20          # query number, index (float64), d2 (float32)
+    bench.write_outputs(tmp_path / "d", {"x": np.ones(3, np.float32)})
+    assert (np.load(tmp_path / "d" / "x.npy") == 1).all()
+    with pytest.raises(AssertionError):
+        bench.write_outputs(tmp_path / "d", {"i": np.ones(3, np.int32)})
+
 def _flann_tree_answers(tmp_path, pts, qs, rule, threads):
     """indices and d2 bits from the PRODUCT's tree (csrc/flann_tree.hpp: iterative build, flat nodes, explicit-stack
     walk) through its g++-built self-test program"""

@@ -14,13 +14,13 @@ mkdir -p $S
 PART=${PART:-AB}
 if [ "$PART" != B ]; then
 for c in c2 c3 c4 c5 c5_shard; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$c -- python3 bench.py --config $c --no-cpu --no-pairs > $S/${TAG}_${c}_trace_bench.json 2> $O/trace_$c.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$c -- python3 bench.py --full --config $c --no-cpu --no-pairs > $S/${TAG}_${c}_trace_bench.json 2> $O/trace_$c.err
   cp $(find $O/trace_$c -name "*kernel_stats.csv" | head -1) $S/${TAG}_${c}_kernel_stats.csv
   echo "trace $c done"
 done
 for c in c2 c3 c4 c5 c5_shard; do
   for k in FETCH_SIZE WRITE_SIZE; do
-    timeout -k 10 300 rocprofv3 --pmc $k --kernel-trace --output-format csv -d $O/pmc_${c}_$k -- python3 bench.py --config $c --steps 6 --warmup 2 --no-cpu --no-exhaustive --no-pairs > $O/pmc_${c}_$k.json 2> $O/pmc_${c}_$k.err
+    timeout -k 10 300 rocprofv3 --pmc $k --kernel-trace --output-format csv -d $O/pmc_${c}_$k -- python3 bench.py --full --config $c --steps 6 --warmup 2 --no-cpu --no-exhaustive --no-pairs > $O/pmc_${c}_$k.json 2> $O/pmc_${c}_$k.err
   done
   python3 tools/pmc_to_json.py $TAG $c $O/pmc_${c}_FETCH_SIZE $O/pmc_${c}_WRITE_SIZE > $O/pmc_$c.log
   echo "pmc $c done"
@@ -28,16 +28,16 @@ done
 cp profiles/${TAG}_pmc_traffic.json $S/
 # the C3 step on ONE stream (query staging behind the build): per-pass durations and bytes that can be ranked
 export PCC_OVERLAP_PREP=0
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_c3_serial -- python3 bench.py --config c3 --no-cpu --no-pairs --no-exhaustive > $O/trace_c3_serial.json 2> $O/trace_c3_serial.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_c3_serial -- python3 bench.py --full --config c3 --no-cpu --no-pairs --no-exhaustive > $O/trace_c3_serial.json 2> $O/trace_c3_serial.err
 cp $(find $O/trace_c3_serial -name "*kernel_stats.csv" | head -1) $S/${TAG}_c3_serial_kernel_stats.csv
 for k in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $k --kernel-trace --output-format csv -d $O/pmc_c3_serial_$k -- python3 bench.py --config c3 --steps 6 --warmup 2 --no-cpu --no-exhaustive --no-pairs > $O/pmc_c3_serial_$k.json 2> $O/pmc_c3_serial_$k.err
+  timeout -k 10 300 rocprofv3 --pmc $k --kernel-trace --output-format csv -d $O/pmc_c3_serial_$k -- python3 bench.py --full --config c3 --steps 6 --warmup 2 --no-cpu --no-exhaustive --no-pairs > $O/pmc_c3_serial_$k.json 2> $O/pmc_c3_serial_$k.err
 done
 unset PCC_OVERLAP_PREP
 python3 tools/pass_table.py $S/${TAG}_c3_serial_kernel_stats.csv $O/pmc_c3_serial_FETCH_SIZE $O/pmc_c3_serial_WRITE_SIZE $S/${TAG}_c3_serial_pass_table.txt > $O/pass_table.log
 echo "serial trace done"
 # the unprofiled default run last: its roofline.traffic is read from the PMC file written just above
-python3 bench.py > $S/${TAG}_bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $S/${TAG}_bench_default.json 2> $O/bench_default.err
 echo "default bench done"
 fi
 [ "$PART" = A ] && exit 0
