@@ -238,7 +238,7 @@ int check_points(const void* pts, size_t n, size_t stride, int mem) {
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem) {
     PCC_TRY(ix->q_packed.reserve(nq * sizeof(float4)));
     PCC_TRY(ix->out_packed.reserve(nq * sizeof(unsigned long long)));
-    // the pack kernel also zeroes the GRID engine's fallback counter (small + 32) and presets the result key of
+    // the pack kernel also zeroes the GRID engine's search counters (clear_search_counters) and presets the result key of
     // every non-finite query to "nothing found"
     ix->fb_zeroed = true;
     // clouds that will take the three-level sort: the pack kernel also writes every query's grid cell (4 B), which level 1 of
@@ -251,7 +251,7 @@ int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int me
         ix->q_cells_n = nq;
     }
     return stage_points(ix, q, nq, stride, mem, ix->q_raw, ix->q_packed.as<float4>(), nullptr, nullptr,
-                        ix->small.as<unsigned int>() + 32, nullptr, ix->out_packed.as<unsigned long long>(), cells,
+                        &ix->words()->fb_count, nullptr, ix->out_packed.as<unsigned long long>(), cells,
                         cells ? ix->d_grid.as<GridDev>() : nullptr);
 }
 
@@ -490,7 +490,7 @@ int pcc_index_destroy(pcc_index* ix) {
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
     DevBuf* bufs[] = {&ix->refs, &ix->cell_refs, &ix->cell_start, &ix->q_raw, &ix->q_packed, &ix->out_packed,
                       &ix->out_idx, &ix->out_d2, &ix->scratch_a, &ix->scratch_b, &ix->scratch_c, &ix->scratch_d, &ix->scratch_e, &ix->scratch_f, &ix->scratch_g,
-                      &ix->small, &ix->blk_stats, &ix->icp_src, &ix->icp_state, &ix->d_grid, &ix->seeds, &ix->vox_a, &ix->vox_b, &ix->vox_c, &ix->tie_buf, &ix->knn_fb, &ix->occ, &ix->self_rows, &ix->flann_nodes, &ix->flann_leaf, &ix->mp_a, &ix->mp_b, &ix->mp_c, &ix->rows_idx, &ix->rows_d2, &ix->scan_flags, &ix->q_cells,
+                      &ix->words_buf, &ix->blk_stats, &ix->icp_src, &ix->icp_state, &ix->d_grid, &ix->seeds, &ix->vox_a, &ix->vox_b, &ix->vox_c, &ix->tie_buf, &ix->knn_fb, &ix->occ, &ix->self_rows, &ix->flann_nodes, &ix->flann_leaf, &ix->mp_a, &ix->mp_b, &ix->mp_c, &ix->rows_idx, &ix->rows_d2, &ix->scan_flags, &ix->q_cells,
                       &ix->side.a, &ix->side.b, &ix->side.c, &ix->side.e, &ix->side.mp_a, &ix->side.mp_b, &ix->side.mp_c, &ix->side.scan_flags};
     for (DevBuf* b : bufs) b->release();
     for (int sl = 0; sl < PCC_EV_SLOTS; ++sl)
@@ -522,13 +522,13 @@ static int new_handle(int device, int engine, pcc_index** out) {
     if (!g.ok) { set_error("hipSetDevice(%d) failed", device); return fail(PCC_ERR_DEVICE); }
     if (hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(PCC_ERR_DEVICE); }
     ix->stream = ix->own_stream;
-    if (hipHostMalloc(&ix->pinned, PACK_MAX_BLOCKS * 8 * sizeof(float) + 4096, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
-    if ((st = ix->small.reserve(PCC_SMALL_BYTES)) != PCC_OK) return fail(st);
-    if (hipMemset(ix->small.p, 0, PCC_SMALL_BYTES) != hipSuccess) { set_error("hipMemset failed"); return fail(PCC_ERR_DEVICE); }  // (the pack kernel's ticket word starts at 0)
+    if (hipHostMalloc((void**)&ix->pinned, sizeof(PinnedWords), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
+    if ((st = ix->words_buf.reserve(sizeof(DevWords))) != PCC_OK) return fail(st);
+    if (hipMemset(ix->words_buf.p, 0, sizeof(DevWords)) != hipSuccess) { set_error("hipMemset failed"); return fail(PCC_ERR_DEVICE); }  // (the ticket words start at 0)
     if ((st = ix->blk_stats.reserve(PACK_MAX_BLOCKS * 8 * sizeof(float))) != PCC_OK) return fail(st);
     ix->engine_requested = engine;
     ix->engine = engine;
-    memset(ix->pinned, 0, PACK_MAX_BLOCKS * 8 * sizeof(float) + 4096);
+    memset(ix->pinned, 0, sizeof(PinnedWords));
     if (hipHostMalloc((void**)&ix->h_grid, sizeof(GridDev), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
     memset(ix->h_grid, 0, sizeof(GridDev));
     *out = ix;
@@ -790,12 +790,12 @@ int pcc_index_stats(const pcc_index* cix, uint64_t stats[8]) {
     if (ix->stats_pending) {
         PCC_HIP(hipStreamSynchronize(ix->stream));
         ix->stats_pending = false;
-        ix->stats[1] = static_cast<unsigned int*>(ix->pinned)[40];
+        ix->stats[1] = ix->pinned->fb_mirror;
         ix->stats[0] = ix->last_nq - ix->stats[1];
     }
     if (ix->ties_pending) {  // the sharded counters of the last search in FLANN mode
         unsigned int h[PCC_TIE_SHARDS * PCC_OPEN_CTR_STRIDE];
-        PCC_HIP(hipMemcpyAsync(h, ix->small.as<unsigned int>() + PCC_TIE_CTR0, sizeof(h), hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipMemcpyAsync(h, ix->words()->tie, sizeof(h), hipMemcpyDeviceToHost, ix->stream));
         PCC_HIP(hipStreamSynchronize(ix->stream));
         ix->ties_flagged = ix->ties_changed = 0;
         for (int sh = 0; sh < PCC_TIE_SHARDS; ++sh) {
@@ -806,7 +806,7 @@ int pcc_index_stats(const pcc_index* cix, uint64_t stats[8]) {
     }
     if (ix->open_pending) {  // lanes the 3x3x3 cube left open in the last listed k = 1 search (sharded counters)
         unsigned int h[PCC_OPEN_SHARDS * PCC_OPEN_CTR_STRIDE];
-        PCC_HIP(hipMemcpyAsync(h, ix->small.as<unsigned int>() + PCC_OPEN_CTR0, sizeof(h), hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipMemcpyAsync(h, ix->words()->open, sizeof(h), hipMemcpyDeviceToHost, ix->stream));
         PCC_HIP(hipStreamSynchronize(ix->stream));
         ix->stats[7] = 0;
         for (int sh = 0; sh < PCC_OPEN_SHARDS; ++sh) ix->stats[7] += h[sh * PCC_OPEN_CTR_STRIDE];
@@ -860,7 +860,7 @@ int pcc_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
         dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
     }
     PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, didx, dd2,
-                          ix->small.as<unsigned int>() + 32, static_cast<unsigned int*>(ix->pinned) + 40));
+                          &ix->words()->fb_count, &ix->pinned->fb_mirror));
     ev_mark(ix, EV_CALL1);
     if (direct) {
         PCC_HIP(hipStreamSynchronize(ix->stream));
@@ -1315,12 +1315,12 @@ int pcc_sor(pcc_index* ix, int mean_k, double stddev_mult, int mem, float* mean_
     PCC_HIP(hipMemsetAsync(dmean, 0, no * sizeof(float), ix->stream));
     PCC_TRY(launch_sor_mean(ix->stream, keys, ix->refs.as<float4>(), n, K, dmean, d2_rows));
     // statistics, threshold and mask on the device (pack.hip: exact whenever no addition of PCL's in-order sums rounds);
-    // the host sees 48 bytes.  Round 3 copied the means back, added them up on one host thread and sent a mask: 0.94 ms
+    // the host sees one SorStats.  Round 3 copied the means back, added them up on one host thread and sent a mask: 0.94 ms
     // beside a 1.2 ms search at 1M points
-    struct { double sum, sq, thr; unsigned long long kept; unsigned int exact, pad; } hs{};
+    SorStats hs{};
     PCC_TRY(ix->scratch_a.reserve((size_t)(3 * 1024 + 4) * sizeof(double) + 64));
     PCC_TRY(ix->scratch_b.reserve(no + 64));
-    void* st_dev = ix->small.as<char>() + 256;  // (words 64..75 of the small block: free of the search counters)
+    SorStats* st_dev = &ix->words()->sor;
     uint8_t* dmask = mem == PCC_MEM_DEVICE && inlier ? inlier : ix->scratch_b.as<uint8_t>();
     PCC_TRY(launch_sor_stats(ix->stream, dmean, no, ix->d_grid.as<GridDev>(), K, stddev_mult, ix->scratch_a.as<double>(), st_dev, dmask));
     ev_mark(ix, EV_CALL1);
@@ -1382,8 +1382,7 @@ static int icp_reduce(pcc_index* ix, size_t n, double sums[17], const double* ce
     int nb = 0;
     PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
                             ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb,
-                            ix->engine == PCC_ENGINE_GRID ? ix->small.as<unsigned int>() + 32 : nullptr,
-                            static_cast<unsigned int*>(ix->pinned) + 40, center));
+                            ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr, &ix->pinned->fb_mirror, center));
     std::vector<double> h((size_t)nb * 17);
     PCC_HIP(hipMemcpyAsync(h.data(), ix->scratch_a.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipStreamSynchronize(ix->stream));
@@ -1527,7 +1526,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
             unsigned int *order = nullptr, *n_sorted = nullptr;
             PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), n, &order, &n_sorted));
             PCC_TRY(launch_gather_sorted(ix->stream, ix->q_packed.as<float4>(), order, n_sorted, n, ix->icp_src.as<float4>(),
-                                         ix->small.as<unsigned int>() + 48));
+                                         &ix->words()->icp_nsorted));
             PCC_HIP(hipMemcpyAsync(ix->q_packed.p, ix->icp_src.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
         } else
         PCC_HIP(hipMemcpyAsync(ix->icp_src.p, ix->q_packed.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
@@ -1557,7 +1556,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
         ix->order_valid = true;
         ix->order_nq = n;
         ix->order_ptr = nullptr;
-        ix->order_nsorted = ix->small.as<unsigned int>() + 48;
+        ix->order_nsorted = &ix->words()->icp_nsorted;
     }
     if (loop_env) {
         // The loop lives on the device: every pass is NN -> sums -> k_icp_solve (one workgroup: the transform, the running
@@ -1589,14 +1588,14 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
                 ix->pre_transform = nullptr;
                 ix->warm_start = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
                 int nb = 0;
-                unsigned int* zw = ix->engine == PCC_ENGINE_GRID ? ix->small.as<unsigned int>() + 32 : nullptr;
-                // (one GPU: the sums kernel's last workgroup solves the pass itself -- [53] of `small` is its ticket word;
+                unsigned int* zw = ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr;
+                // (one GPU: the sums kernel's last workgroup solves the pass itself -- DevWords::icp_ticket is its ticket word;
                 // PCC_OPT_FUSE_PARAMS bit 1; the sharded loop keeps the solver's own launch: its sums pass through an all-reduce)
                 const bool fuse_solve = !hooks && (ix->opt.fuse_params & 2) != 0;
-                const IcpFuse fuse{ix->small.as<unsigned int>() + 53, st, max_iter, fixed, fold ? zw : nullptr};
+                const IcpFuse fuse{&ix->words()->icp_ticket, st, max_iter, fixed, fold ? zw : nullptr};
                 PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
                                         ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb, zw,
-                                        static_cast<unsigned int*>(ix->pinned) + 40, center_dev, fuse_solve ? &fuse : nullptr));
+                                        &ix->pinned->fb_mirror, center_dev, fuse_solve ? &fuse : nullptr));
                 if (fuse_solve) {
                 } else if (hooks) {  // rows -> 17 sums (workgroup order, as the solver adds them) -> sum over the ranks -> solve
                     PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));

@@ -606,7 +606,7 @@ static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint3
     int* id_of_root = ix->scratch_e.as<int>();
     unsigned int* minidx = ix->scratch_f.as<unsigned int>();
     uint4* list = ix->scratch_b.as<uint4>();
-    unsigned int* d_count = ix->small.as<unsigned int>() + 40;
+    unsigned int* d_count = ix->words()->op;
     const float4* cr2 = ix->vox_a.as<float4>();
     const unsigned int* cs2 = ix->vox_c.as<unsigned int>();
     const GridDev* gd2 = ix->vox_b.as<GridDev>();
@@ -627,10 +627,8 @@ static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint3
     hipLaunchKernelGGL(k_ecc_sizes, gp, blk, 0, s, cr2, cs2, gd2, cparent, size, minidx);
     hipLaunchKernelGGL(k_ecc_collect, dim3(g1(n)), blk, 0, s, cparent, size, minidx, n, min_size, max_size, list, d_count, cap);
     PCC_HIP(hipGetLastError());
-    unsigned int* h = static_cast<unsigned int*>(ix->pinned);
-    PCC_HIP(hipMemcpyAsync(h, d_count, 4, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    const unsigned int ncl = h[0];
+    unsigned int ncl;
+    PCC_TRY(read_back(ix, d_count, &ncl));
     if (ncl > cap) { set_error("cluster list overflow (%u > %u)", ncl, cap); return PCC_ERR_OVERFLOW; }
     std::vector<uint4> host_list(ncl);
     if (ncl) {
@@ -718,7 +716,7 @@ int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t 
     unsigned int* size = ix->scratch_d.as<unsigned int>();
     int* id_of_root = ix->scratch_e.as<int>();
     uint2* list = ix->scratch_b.as<uint2>();
-    unsigned int* d_count = ix->small.as<unsigned int>() + 40;
+    unsigned int* d_count = ix->words()->op;
     ev_mark(ix, EV_MAIN0);
     hipLaunchKernelGGL(k_uf_init, dim3(g1(n)), dim3(256), 0, s, parent, n);
     PCC_HIP(hipMemsetAsync(size, 0, (size_t)n * 4, s));
@@ -743,10 +741,8 @@ int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t 
         hipLaunchKernelGGL(k_uf_flatten_count, dim3(g1(n)), dim3(256), 0, s, ix->refs.as<float4>(), parent, n, size);
     hipLaunchKernelGGL(k_uf_collect, dim3(g1(n)), dim3(256), 0, s, parent, size, n, min_size, max_size, list, d_count, cap);
     PCC_HIP(hipGetLastError());
-    unsigned int* h = static_cast<unsigned int*>(ix->pinned);
-    PCC_HIP(hipMemcpyAsync(h, d_count, 4, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    unsigned int ncl = h[0];
+    unsigned int ncl;
+    PCC_TRY(read_back(ix, d_count, &ncl));
     if (ncl > cap) { set_error("cluster list overflow (%u > %u)", ncl, cap); return PCC_ERR_OVERFLOW; }
     std::vector<uint2> host_list(ncl);
     if (ncl) {

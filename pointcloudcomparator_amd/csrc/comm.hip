@@ -369,14 +369,13 @@ int pcc_sor_sharded(pcc_index* ix, pcc_comm* c, size_t start, size_t count, int 
     // allocation -- is folded into an agreed status before the next one.)
     PCC_NCCL(rccl()->AllReduce(out4, out4, 2, ncclDouble, ncclSum, c->nccl, s));
     PCC_NCCL(rccl()->AllReduce(out4 + 2, out4 + 2, 2, ncclDouble, ncclMin, c->nccl, s));
-    struct { double sum, sq, thr; unsigned long long kept; unsigned int exact, pad; } hs{};
-    void* st_dev = ix->small.as<char>() + 256;
+    SorStats hs{};
+    SorStats* st_dev = &ix->words()->sor;
     {
         const int st = agree_status(c, launch_sor_threshold_mask(s, dmean, count, ix->d_grid.as<GridDev>(), K, stddev_mult, out4, st_dev, dmask));
         if (st != PCC_OK) return st;
     }
-    unsigned long long* kept_dev = reinterpret_cast<unsigned long long*>(static_cast<char*>(st_dev) + 24);
-    PCC_NCCL(rccl()->AllReduce(kept_dev, kept_dev, 1, ncclUint64, ncclSum, c->nccl, s));
+    PCC_NCCL(rccl()->AllReduce(&st_dev->kept, &st_dev->kept, 1, ncclUint64, ncclSum, c->nccl, s));
     {   // (hs.exact decides whether the big all-reduce below happens: every rank must have read it)
         int st = PCC_OK;
         if (hipMemcpyAsync(&hs, st_dev, sizeof(hs), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {

@@ -172,8 +172,8 @@ int resolve_ties_flann(pcc_index* ix, const float4* q, unsigned long long* keys,
     const unsigned int shard_cap = (blocks + PCC_TIE_SHARDS - 1) / PCC_TIE_SHARDS * 256;  // what a slice's blocks could append
     PCC_TRY(ix->tie_buf.reserve((size_t)shard_cap * PCC_TIE_SHARDS * sizeof(unsigned int) + 256));
     unsigned int* list = ix->tie_buf.as<unsigned int>();
-    unsigned int* counters = ix->small.as<unsigned int>() + PCC_TIE_CTR0;
-    PCC_HIP(hipMemsetAsync(counters, 0, PCC_TIE_SHARDS * PCC_OPEN_CTR_STRIDE * 4, ix->stream));
+    unsigned int* counters = ix->words()->tie[0];
+    PCC_HIP(hipMemsetAsync(counters, 0, sizeof(DevWords::tie), ix->stream));
     PCC_TRY(launch_tie_list(ix, q, keys, nq, list, counters, shard_cap));
     if (may_wait && !ix->flann_valid) {
         unsigned int h[PCC_TIE_SHARDS * PCC_OPEN_CTR_STRIDE];

@@ -56,11 +56,11 @@ int grid_params(pcc_index* ix, const float* blk_stats_dev, int n_blocks) {
     return PCC_OK;
 }
 
-// [52] of pcc_index::small: the ticket word of the fused form (zeroed with the handle, reset by the kernel itself)
+// DevWords::grid_ticket: the ticket word of the fused form (zeroed with the handle, reset by the kernel itself)
 int grid_params_fused(pcc_index* ix, PackGrid* pg) {
     PCC_TRY(ix->d_grid.reserve(sizeof(GridDev)));
     ix->nc_cap = grid_nc_cap(ix->n_orig, ix->opt.grid_ppc);
-    *pg = PackGrid{ix->small.as<unsigned int>() + 52, (float)ix->opt.grid_ppc, ix->nc_cap, ix->opt.grid_trim, ix->opt.grid_axes,
+    *pg = PackGrid{&ix->words()->grid_ticket, (float)ix->opt.grid_ppc, ix->nc_cap, ix->opt.grid_trim, ix->opt.grid_axes,
                    ix->d_grid.as<GridDev>(), ix->h_grid};
     ix->info_pending = true;
     return PCC_OK;
@@ -999,12 +999,12 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
     const unsigned int n = (unsigned int)nq;
     PCC_TRY(ix->scratch_d.reserve(((size_t)n * 2 + 128) * sizeof(unsigned int) + 256));
     unsigned int* fb_list = ix->scratch_d.as<unsigned int>();
-    unsigned int* fb_count = ix->small.as<unsigned int>() + 32;
+    unsigned int* fb_count = &ix->words()->fb_count;
     // zeroed by the query pack kernel of this call; searches that re-use packed queries (the ICP
     // loop transforms them in place) have no pack and zero it here
     if (!ix->fb_zeroed) {  // fallback and far counters, the sharded open-lane counters
-        PCC_HIP(hipMemsetAsync(fb_count, 0, 8, s));
-        PCC_HIP(hipMemsetAsync(ix->small.as<unsigned int>() + PCC_OPEN_CTR0, 0, PCC_OPEN_SHARDS * PCC_OPEN_CTR_STRIDE * 4, s));
+        PCC_HIP(hipMemsetAsync(fb_count, 0, sizeof(DevWords::fb_count) + sizeof(DevWords::far_count), s));
+        PCC_HIP(hipMemsetAsync(ix->words()->open, 0, sizeof(DevWords::open), s));
     }
     ix->fb_zeroed = false;
     unsigned int *order = nullptr, *n_sorted = nullptr;
@@ -1052,7 +1052,7 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
         const size_t list_cap = (size_t)shard_cap * PCC_OPEN_SHARDS;
         unsigned int* open_list = nullptr;
         unsigned long long* open_keys = nullptr;
-        unsigned int* open_total = ix->small.as<unsigned int>() + PCC_OPEN_CTR0;
+        unsigned int* open_total = ix->words()->open[0];
         if (listed) {
             PCC_TRY(ix->scratch_f.reserve(list_cap * 12 + 64));
             open_list = ix->scratch_f.as<unsigned int>();
@@ -1092,14 +1092,14 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
     // steers the choice), take the seed + ball-walk route; otherwise go straight to the exhaustive
     // kernel, which costs one launch when the list is empty
     ev_mark(ix, EV_FB0);
-    const unsigned int seen = static_cast<volatile unsigned int*>(ix->pinned)[40];
+    const unsigned int seen = *static_cast<volatile unsigned int*>(&ix->pinned->fb_mirror);
     if (seen > ix->last_fallback_seen) ix->last_fallback_seen = seen;
     const int far_mode = ix->opt.far_mode;  // -1 auto, 0 off, 1 on
     // (ICP passes always take it: their loop may be enqueued as a whole before the first count comes back)
     const bool far = far_mode == 1 || (far_mode == -1 && (ix->last_fallback_seen >= 64 || ix->keep_order));
     if (far) {
         unsigned int* fb2_list = fb_list + n + 64;
-        unsigned int* fb2_count = ix->small.as<unsigned int>() + 33;
+        unsigned int* fb2_count = &ix->words()->far_count;
         // (fb2_count is the second of the two words zeroed at the top of this call -- or by the pack / transform kernel before it)
         const size_t n_seeds = (ix->n_orig + SEED_STRIDE - 1) / SEED_STRIDE;
         // (a warm-started query brings its bound along: no seed scan)

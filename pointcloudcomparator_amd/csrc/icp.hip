@@ -25,12 +25,8 @@ template <bool AGENT>
 __device__ __forceinline__ void icp_solve_block(const double* __restrict__ partials, int n_blocks, IcpState* __restrict__ st, int max_iter,
                                                 int fixed, const double* __restrict__ center_dev, unsigned int* __restrict__ zero_word,
                                                 double* __restrict__ part /* LDS, n_blocks * 17 doubles */) {
-    // (the counters of the search that follows -- fallback list, far list, the sharded open-lane counters -- as k_pack / k_transform
-    // zero them: when the next pass's search applies the transform itself there is no k_transform in between)
-    if (zero_word && threadIdx.x < 64) {
-        if (threadIdx.x < 2) zero_word[threadIdx.x] = 0u;
-        zero_word[PCC_OPEN_CTR0 - 32 + threadIdx.x * PCC_OPEN_CTR_STRIDE] = 0u;
-    }
+    // (as k_pack / k_transform do: when the next pass's search applies the transform itself there is no k_transform in between)
+    if (zero_word) clear_search_counters(zero_word);
     __shared__ double sums[17];
     // all partial rows, staged with coalesced loads, 8 per thread in flight (the rows come from other XCDs' write-backs: read
     // one by one in a dependent loop they cost 120 us)

@@ -158,14 +158,12 @@ int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out)
     int64_t* off64 = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ix->vox_a.p) + (((n + 1) * sizeof(unsigned int) + 15) & ~(size_t)15));
     PCC_HIP(hipMemsetAsync(off32, 0, (n + 1) * sizeof(unsigned int), s));
     PCC_TRY(grid_radius(ix, self, n, (float)radius, r2, reinterpret_cast<int32_t*>(off32), nullptr, nullptr, 0));
-    unsigned long long* d_total = reinterpret_cast<unsigned long long*>(ix->small.as<unsigned int>() + 44);
+    unsigned long long* d_total = &ix->words()->radius_total;
     PCC_HIP(hipMemsetAsync(d_total, 0, 8, s));
     const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_sum_counts, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const int32_t*>(off32), (unsigned int)n, d_total);
-    unsigned long long* h_total = reinterpret_cast<unsigned long long*>(static_cast<unsigned int*>(ix->pinned) + 44);
-    PCC_HIP(hipMemcpyAsync(h_total, d_total, 8, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    const unsigned long long total = *h_total;
+    unsigned long long total;
+    PCC_TRY(read_back(ix, d_total, &total));
     if (total >= (1ull << 32)) { set_error("radius neighbourhoods hold %llu entries: more than a 32-bit CSR takes", total); return PCC_ERR_OVERFLOW; }
     PCC_TRY(launch_exclusive_scan(ix, s, off32, n + 1, ix->vox_b));
     hipLaunchKernelGGL(k_widen_offsets, dim3(blocks), dim3(256), 0, s, off32, (unsigned int)(n + 1), off64);

@@ -39,10 +39,7 @@ k_pack(const char* __restrict__ aos, size_t n, size_t stride, float4* __restrict
        float* __restrict__ blk, unsigned int* __restrict__ zero_word, float4* __restrict__ seeds,
        unsigned long long* __restrict__ invalid_keys, unsigned int* __restrict__ cells, const GridDev* __restrict__ gd,
        PackGrid pg) {
-    if (zero_word && blockIdx.x == 0 && threadIdx.x < 64) {  // counters of the search that follows: saves a 5 us memset node
-        if (threadIdx.x < 2) zero_word[threadIdx.x] = 0u;                      // fallback list, far list
-        zero_word[PCC_OPEN_CTR0 - 32 + threadIdx.x * PCC_OPEN_CTR_STRIDE] = 0u;  // the sharded open-lane counters (grid.hip)
-    }
+    if (zero_word && blockIdx.x == 0) clear_search_counters(zero_word);  // saves a 5 us memset node
     unsigned int bad = 0;
     float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
@@ -385,10 +382,7 @@ struct Mat34 { float m[12]; };
 __global__ void __launch_bounds__(256)
 k_transform(Mat34 T, const float* __restrict__ Tdev, const char* __restrict__ src, size_t n,
             size_t sstride, char* __restrict__ dst, size_t dstride, unsigned int* __restrict__ zero_word) {
-    if (zero_word && blockIdx.x == 0 && threadIdx.x < 64) {  // counters of the search that follows (as k_pack does): an ICP pass
-        if (threadIdx.x < 2) zero_word[threadIdx.x] = 0u;     // otherwise spends three 4-us memset nodes on them
-        zero_word[PCC_OPEN_CTR0 - 32 + threadIdx.x * PCC_OPEN_CTR_STRIDE] = 0u;
-    }
+    if (zero_word && blockIdx.x == 0) clear_search_counters(zero_word);  // an ICP pass otherwise spends three 4-us memset nodes on them
     float m[12];
     for (int k = 0; k < 12; ++k) m[k] = Tdev ? Tdev[k] : T.m[k];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
@@ -553,12 +547,7 @@ int launch_sor_mean(hipStream_t s, const unsigned long long* keys, const float4*
 // every partial sum of ANY order is exact and all orders give the same double.  The kernels below add in a tree, track the
 // smallest positive term of both sums and say whether that condition held (means of centimetres over a million points:
 // it does, by ten bits); when it does not -- mean distances of micrometres next to metres -- pcc_sor falls back to the
-// in-order host loop.  Threshold and inlier mask follow on the device: no cloud-sized copy, one 48-byte read-back.
-struct SorStats {
-    double sum, sq, thr;
-    unsigned long long kept;
-    unsigned int exact, pad;
-};
+// in-order host loop.  Threshold and inlier mask follow on the device: no cloud-sized copy, one SorStats read back.
 constexpr int SOR_RED_BLOCKS = 1024;
 __device__ __forceinline__ double wave_sum_f64(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -683,17 +672,17 @@ int launch_sor_partial(hipStream_t s, const float* m, size_t n, double* scratch,
 }
 // threshold from in4 (the sums of the WHOLE cloud) -> stats_dev; mask + kept count of the n means given
 int launch_sor_threshold_mask(hipStream_t s, const float* m, size_t n, const GridDev* gd, int K, double stddev_mult,
-                              const double* in4_dev, void* stats_dev, uint8_t* inlier_dev) {
+                              const double* in4_dev, SorStats* stats_dev, uint8_t* inlier_dev) {
     const int nb = (int)std::min<size_t>((n + 255) / 256, SOR_RED_BLOCKS);
-    hipLaunchKernelGGL(k_sor_threshold, dim3(1), dim3(1), 0, s, in4_dev, gd, K, stddev_mult, static_cast<SorStats*>(stats_dev));
-    hipLaunchKernelGGL(k_sor_mask, dim3(nb < 1 ? 1 : nb), dim3(256), 0, s, m, n, static_cast<SorStats*>(stats_dev), inlier_dev);
+    hipLaunchKernelGGL(k_sor_threshold, dim3(1), dim3(1), 0, s, in4_dev, gd, K, stddev_mult, stats_dev);
+    hipLaunchKernelGGL(k_sor_mask, dim3(nb < 1 ? 1 : nb), dim3(256), 0, s, m, n, stats_dev, inlier_dev);
     PCC_HIP(hipGetLastError());
     return PCC_OK;
 }
-// statistics + threshold + mask of the mean distances m[n] of a whole cloud; stats (device, 48 bytes) and scratch (>= 3 *
+// statistics + threshold + mask of the mean distances m[n] of a whole cloud; stats (device) and scratch (>= 3 *
 // SOR_RED_BLOCKS + 4 doubles) are the caller's
 int launch_sor_stats(hipStream_t s, const float* m, size_t n, const GridDev* gd, int K, double stddev_mult, double* scratch,
-                     void* stats_dev, uint8_t* inlier_dev) {
+                     SorStats* stats_dev, uint8_t* inlier_dev) {
     double* out4 = scratch + 3 * SOR_RED_BLOCKS;
     PCC_TRY(launch_sor_partial(s, m, n, scratch, out4));
     return launch_sor_threshold_mask(s, m, n, gd, K, stddev_mult, out4, stats_dev, inlier_dev);

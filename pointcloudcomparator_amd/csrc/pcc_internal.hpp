@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <string.h>
 #include <mutex>
 #include <string>
 #include "pcc_nn.h"
@@ -11,15 +12,10 @@
 // every PCC_SEED_STRIDE-th reference is a "seed": the exhaustive scan of the seeds bounds a far query's ball
 #define PCC_SEED_SHIFT 6
 #define PCC_SEED_STRIDE (1 << PCC_SEED_SHIFT)
-// pcc_index::small (uint32 words): [32] fallback count, [33] far-list count, [52] ticket of the build's pack kernel (grid.hip), [53] ticket of k_icp_sums (fused solve), [PCC_OPEN_CTR0 + s * PCC_OPEN_CTR_STRIDE] open-lane
-// count of shard s -- one 128-byte line each, PCC_OPEN_SHARDS of them (a single word takes ~88 atomics per microsecond)
+// sharded device counters (pcc::DevWords): shard s owns words [s * PCC_OPEN_CTR_STRIDE ...], one 128-byte line each
 #define PCC_OPEN_SHARDS 64
-#define PCC_OPEN_CTR0 1024
 #define PCC_OPEN_CTR_STRIDE 32
-// [PCC_TIE_CTR0 + s * PCC_OPEN_CTR_STRIDE + {0, 1}] queries listed as tied / indices changed, per slice of the tie list (PCC_TIES_FLANN)
 #define PCC_TIE_SHARDS 16
-#define PCC_TIE_CTR0 (PCC_OPEN_CTR0 + PCC_OPEN_SHARDS * PCC_OPEN_CTR_STRIDE)
-#define PCC_SMALL_BYTES ((PCC_TIE_CTR0 + PCC_TIE_SHARDS * PCC_OPEN_CTR_STRIDE) * 4)
 #define FLANN_DEV_STACK_MAX 256  // deepest tree k_tie_walk takes (20 bytes of scratch per level and lane)
 
 namespace pcc {
@@ -172,6 +168,73 @@ struct Options {
     void from_env();
 };
 
+// SOR statistics on the device (pack.hip): exact == 0 -> the tree sums may differ from PCL's in-order sums
+struct SorStats {
+    double sum, sq, thr;
+    unsigned long long kept;
+    unsigned int exact, pad;
+};
+
+// The handle's device words (pcc_index::words(), zeroed at creation).  Kernels are handed addresses inside it, so every offset
+// is fixed (asserted below); pad* are free words.
+struct DevWords {
+    unsigned int pad0[32];
+    unsigned int fb_count;            // k = 1 search: queries on the fallback list (grid.hip)
+    unsigned int far_count;           // ... on the far list: directly behind fb_count, the two are cleared together
+    unsigned int pad1[6];
+    unsigned int op[4];               // scalars of one operation: cluster count (cluster.hip), region growing's four words (region.hip)
+    unsigned long long radius_total;  // CSR total of pcc_normals_radius
+    unsigned int pad2[2];
+    unsigned int icp_nsorted;         // valid points of the cell-ordered ICP source
+    unsigned int pad3[3];
+    unsigned int grid_ticket;         // ticket of the grid derivation fused into the build's pack kernel (grid_params_fused)
+    unsigned int icp_ticket;          // ticket of the pass solve fused into k_icp_sums
+    unsigned int pad4[10];
+    SorStats sor;                     // pcc_sor's statistics
+    unsigned int pad5[1024 - 64 - sizeof(SorStats) / 4];
+    // open lanes of a listed k = 1 search, count of shard s in open[s][0] (a single word takes ~88 atomics per microsecond)
+    unsigned int open[PCC_OPEN_SHARDS][PCC_OPEN_CTR_STRIDE];
+    // PCC_TIES_FLANN, per slice s of the tie list: tie[s][0] queries listed as tied, [1] indices changed, [2] walks too deep
+    unsigned int tie[PCC_TIE_SHARDS][PCC_OPEN_CTR_STRIDE];
+};
+static_assert(offsetof(DevWords, fb_count) == 4 * 32, "DevWords layout");
+static_assert(offsetof(DevWords, far_count) == offsetof(DevWords, fb_count) + 4, "far_count directly behind fb_count");
+static_assert(offsetof(DevWords, op) == 4 * 40, "DevWords layout");
+static_assert(offsetof(DevWords, radius_total) == 4 * 44, "DevWords layout");
+static_assert(offsetof(DevWords, icp_nsorted) == 4 * 48, "DevWords layout");
+static_assert(offsetof(DevWords, grid_ticket) == 4 * 52, "DevWords layout");
+static_assert(offsetof(DevWords, icp_ticket) == 4 * 53, "DevWords layout");
+static_assert(offsetof(DevWords, sor) == 4 * 64, "DevWords layout");
+static_assert(offsetof(DevWords, open) == 4 * 1024, "DevWords layout");
+static_assert(offsetof(DevWords, tie) == 4 * 3072, "DevWords layout");
+static_assert(sizeof(DevWords) == 14336, "DevWords layout");
+
+// Clear the counters a k = 1 search starts from (fb_count, far_count, the open-lane shards) in the kernel in front of it, which
+// saves the search its memset nodes; lanes 0..63 of one workgroup take part.  fb_count: &DevWords::fb_count of the handle.
+__device__ __forceinline__ void clear_search_counters(unsigned int* __restrict__ fb_count) {
+    constexpr unsigned int open0 = (offsetof(DevWords, open) - offsetof(DevWords, fb_count)) / 4;
+    if (threadIdx.x < 64) {
+        if (threadIdx.x < 2) fb_count[threadIdx.x] = 0u;
+        fb_count[open0 + threadIdx.x * PCC_OPEN_CTR_STRIDE] = 0u;
+    }
+}
+
+constexpr int PACK_MAX_BLOCKS = 1024;  // rows of per-workgroup statistics launch_pack writes at most
+
+// The handle's pinned host words (pcc_index::pinned).  fb_mirror and vox_count are written behind the host's back (by a kernel,
+// by a copy nobody waits for) and read later, so they share no byte with anything else.
+struct PinnedWords {
+    alignas(8) unsigned int readback[4];  // read_back()
+    unsigned int fb_mirror;               // fb_count of the last GRID k = 1 search, copied by k_unpack / k_icp_sums (grid_nn1 reads it
+                                          // without a wait, pcc_index_stats after one)
+    unsigned int vox_count;               // voxel_grid: the voxel count, copied without a wait and read after a later one
+    float vox_rows[PACK_MAX_BLOCKS * 8];  // voxel_grid: the pack kernel's per-workgroup rows
+};
+static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) &&
+                  offsetof(PinnedWords, vox_count) >= offsetof(PinnedWords, fb_mirror) + 4 &&
+                  offsetof(PinnedWords, vox_rows) >= offsetof(PinnedWords, vox_count) + 4,
+              "PinnedWords: the asynchronously written words overlap");
+
 }  // namespace pcc
 
 namespace pcc { struct HostPipe; }  // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
@@ -207,7 +270,7 @@ struct pcc_index {
     unsigned int nc_cap = 0;           // upper bound of the grid's cell count the host sizes launches with
     pcc::DevBuf d_grid;                // GridDev on the device
     pcc::GridDev* h_grid = nullptr;    // pinned host mirror, filled asynchronously
-    bool stats_pending = false;        // fallback counter of the last GRID search in flight to pinned[40]
+    bool stats_pending = false;        // fallback counter of the last GRID search in flight to pinned->fb_mirror
     size_t last_nq = 0;
     bool info_pending = false;         // h_grid copy in flight: sync before reading n_valid / grid / bbox
     int engine = PCC_ENGINE_BRUTE;     // resolved engine
@@ -235,7 +298,7 @@ struct pcc_index {
     unsigned int last_fallback_seen = 0;  // fallback count of an earlier search (heuristic only, may be stale)
     // scratch (grow-only, reused across calls on the index's stream)
     pcc::DevBuf q_raw, q_packed, out_packed, out_idx, out_d2, scratch_a, scratch_b,
-        scratch_c, scratch_d, scratch_e, scratch_f, scratch_g, small, blk_stats, icp_src, icp_state, vox_a, vox_b, vox_c,
+        scratch_c, scratch_d, scratch_e, scratch_f, scratch_g, blk_stats, icp_src, icp_state, vox_a, vox_b, vox_c,
         mp_a, mp_b, mp_c,  // cellsort_mp.hip: two intermediate point buffers, bucket counters
         q_cells,     // grid cell of every staged query (k_pack), read by level 1 of the three-level sort instead of the points
         scan_flags,  // k_scan_chained: one tagged total per workgroup (pack.hip); nothing else ever writes here
@@ -259,7 +322,9 @@ struct pcc_index {
     bool open_pending = false;                    // the open-lane counters of the last listed k = 1 search are still on the device
     bool ties_pending = false;                    // the tie counters of the last search are still on the device
     uint64_t ties_flagged = 0, ties_changed = 0;  // of the last search in FLANN mode
-    void* pinned = nullptr;  // small pinned host block for scalar read-backs
+    pcc::DevBuf words_buf;                                                   // pcc::DevWords, zeroed at creation
+    pcc::DevWords* words() const { return words_buf.as<pcc::DevWords>(); }  // (a device pointer)
+    pcc::PinnedWords* pinned = nullptr;
     pcc::HostBuf host_a, host_b;  // large pinned read-back buffers
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
@@ -303,11 +368,20 @@ inline void ev_next(pcc_index* ix) {
     for (int k = 0; k < PCC_EV_KINDS; ++k) ix->ev_rec[s][k] = false;
 }
 
+// N device values read back synchronously: copied into the handle's pinned read-back words, the handle's stream waited for
+template <int N = 1, class T>
+int read_back(pcc_index* ix, const T* dev, T* out) {
+    static_assert(N * sizeof(T) <= sizeof(PinnedWords::readback) && alignof(T) <= alignof(PinnedWords), "read_back: too large");
+    PCC_HIP(hipMemcpyAsync(ix->pinned->readback, dev, N * sizeof(T), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    memcpy(out, ix->pinned->readback, N * sizeof(T));
+    return PCC_OK;
+}
+
 // ---- kernels / launchers (pack.hip) -------------------------------------------
 // AoS (stride bytes, 3 floats at offset 0) -> float4(x,y,z,bits(i)); non-finite points are
 // written with w = -1.  With blk_stats != nullptr every workgroup b also writes 8 floats:
 // [0] bits(invalid count), [1..3] min xyz, [4..6] max xyz of its valid points; *n_blocks rows.
-constexpr int PACK_MAX_BLOCKS = 1024;
 // grid (index builds, with blk_stats): the pack kernel's last workgroup also derives the index's grid (what k_grid_params does in
 // a launch of its own): ticket = a zeroed device word, the rest are k_grid_params' arguments
 struct PackGrid {
@@ -342,13 +416,12 @@ int launch_copy_w(hipStream_t s, const float4* src, float4* dst, size_t n);
 // the self query; rows with fewer than K neighbours keep 0
 int launch_sor_mean(hipStream_t s, const unsigned long long* keys, const float4* refs, size_t n, int K,
                     float* mean_dist, const float* d2_rows = nullptr);
-// SOR: sum / sq_sum / threshold / inlier mask of the mean distances on the device (pack.hip); stats_dev receives
-// {double sum, sq, thr; uint64 kept; uint32 exact, pad}: exact == 0 -> the tree sums may differ from PCL's in-order sums
+// SOR: sum / sq_sum / threshold / inlier mask of the mean distances on the device (pack.hip) into *stats_dev
 int launch_sor_stats(hipStream_t s, const float* m, size_t n, const GridDev* gd, int K, double stddev_mult, double* scratch,
-                     void* stats_dev, uint8_t* inlier_dev);
+                     SorStats* stats_dev, uint8_t* inlier_dev);
 int launch_sor_partial(hipStream_t s, const float* m, size_t n, double* scratch, double* out4_dev);
 int launch_sor_threshold_mask(hipStream_t s, const float* m, size_t n, const GridDev* gd, int K, double stddev_mult,
-                              const double* in4_dev, void* stats_dev, uint8_t* inlier_dev);
+                              const double* in4_dev, SorStats* stats_dev, uint8_t* inlier_dev);
 void sor_threshold_host(const double in4[4], double n_valid, int K, double stddev_mult, double* thr, int* exact);
 int launch_clamp_counts(hipStream_t s, int32_t* counts, size_t n, int32_t cap);
 int launch_knn_rows_to_csr(hipStream_t s, const unsigned long long* keys, const int32_t* ridx, const float* rd2, int K, float r2,

@@ -279,16 +279,15 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
     auto* id_of_seed = ix->scratch_e.as<int>();
     auto* kth = ix->scratch_f.as<unsigned long long>();
     auto* has_cross = ix->scratch_g.as<unsigned char>();
-    unsigned int* d_words = ix->small.as<unsigned int>() + 40;  // [0] no-spread count, [1] changed, [2] list count, [3] points with a cross edge
-    unsigned int* h = static_cast<unsigned int*>(ix->pinned);
+    unsigned int* d_words = ix->words()->op;  // [0] no-spread count, [1] changed, [2] list count, [3] points with a cross edge
     ev_mark(ix, EV_MAIN0);
-    PCC_HIP(hipMemsetAsync(d_words, 0, 16, s));
+    PCC_HIP(hipMemsetAsync(d_words, 0, sizeof(DevWords::op), s));
     hipLaunchKernelGGL(k_rg_prepare, dim3(g1(n)), dim3(256), 0, s, keys, normals, n, K, curvature_threshold, parent,
                        comp_label, kth, size, id_of_seed, has_cross, d_words);
     PCC_HIP(hipGetLastError());
-    PCC_HIP(hipMemcpyAsync(h, d_words, 4, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    const bool general = h[0] != 0;  // some point would join a region without spreading
+    unsigned int no_spread;
+    PCC_TRY(read_back(ix, d_words, &no_spread));
+    const bool general = no_spread != 0;  // some point would join a region without spreading
     const unsigned int wave_blocks = (n + 3) / 4;
     hipLaunchKernelGGL(k_rg_link, dim3(wave_blocks), dim3(256), 0, s, keys, normals, kth, ix->cell_refs.as<float4>(),
                        ix->d_grid.as<GridDev>(), K, cos_thr, curvature_threshold, parent);
@@ -314,10 +313,10 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
                                    lab[cur], lab[cur ^ 1], has_cross);
             hipLaunchKernelGGL(k_rg_diff, dim3(g1(n)), dim3(256), 0, s, lab[cur], lab[cur ^ 1], n, d_words + 1);
             PCC_HIP(hipGetLastError());
-            PCC_HIP(hipMemcpyAsync(h, d_words + 1, 4, hipMemcpyDeviceToHost, s));
-            PCC_HIP(hipStreamSynchronize(s));
+            unsigned int changed;
+            PCC_TRY(read_back(ix, d_words + 1, &changed));
             cur ^= 1;
-            if (h[0] == 0) break;
+            if (changed == 0) break;
         }
         PCC_HIP(hipMemcpyAsync(comp_label, lab[cur], (size_t)n * 8, hipMemcpyDeviceToDevice, s));
     } else {
@@ -335,18 +334,17 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
                                    ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), K, cos_thr, parent, comp_label, has_cross,
                                    d_words + 1, cross_list, d_words + 3, n_cross);
             PCC_HIP(hipGetLastError());
-            PCC_HIP(hipMemcpyAsync(h, d_words + 1, 12, hipMemcpyDeviceToHost, s));  // changed, (list count of collect), cross count
-            PCC_HIP(hipStreamSynchronize(s));
-            if (sweep == 0) n_cross = h[2];
-            if (h[0] == 0 || n_cross == 0) break;
+            unsigned int w[3];  // changed, (list count of collect), cross count
+            PCC_TRY(read_back<3>(ix, d_words + 1, w));
+            if (sweep == 0) n_cross = w[2];
+            if (w[0] == 0 || n_cross == 0) break;
         }
     }
     hipLaunchKernelGGL(k_rg_count, dim3(g1(n)), dim3(256), 0, s, comp_label, n, parent, size);
     hipLaunchKernelGGL(k_rg_collect, dim3(g1(n)), dim3(256), 0, s, normals, size, n, min_size, max_size, list, d_words + 2, cap);
     PCC_HIP(hipGetLastError());
-    PCC_HIP(hipMemcpyAsync(h, d_words + 2, 4, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    const unsigned int ncl = h[0];
+    unsigned int ncl;
+    PCC_TRY(read_back(ix, d_words + 2, &ncl));
     if (ncl > cap) { set_error("region list overflow (%u > %u)", ncl, cap); return PCC_ERR_OVERFLOW; }
     std::vector<SeedRec> host_list(ncl);
     if (ncl) {

@@ -158,10 +158,9 @@ int select_inliers(pcc_index* ix, const float4* pts, unsigned int n, const float
     PCC_TRY(launch_exclusive_scan(ix, s, pos, (size_t)n + 1, ix->scratch_d));
     hipLaunchKernelGGL(k_sac_scatter, dim3(g1(n)), dim3(256), 0, s, pts, n, model, threshold, pos, out_dev);
     PCC_HIP(hipGetLastError());
-    unsigned int* h = static_cast<unsigned int*>(ix->pinned);
-    PCC_HIP(hipMemcpyAsync(h, pos + n, 4, hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    *m = h[0];
+    unsigned int count;
+    PCC_TRY(read_back(ix, pos + n, &count));
+    *m = count;
     return PCC_OK;
 }
 
@@ -226,7 +225,7 @@ int sac_plane(pcc_index* ix, const float4* pts_dev, size_t n_, const char* host_
     std::vector<unsigned int> part((size_t)count_blocks * SAC_BATCH);
     float4* d_models = ix->scratch_a.as<float4>();
     unsigned int* d_counts = ix->scratch_b.as<unsigned int>();
-    // the sampled points of a batch: indices up, coordinates back (pinned staging in the handle's small block)
+    // the sampled points of a batch: indices up, coordinates back (staged in scratch_e)
     int32_t* d_smp_idx = nullptr;
     float* d_smp_xyz = nullptr;
     if (gathered) {

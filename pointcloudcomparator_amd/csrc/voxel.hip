@@ -83,7 +83,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
     }
     int nblk = 0;
     PCC_TRY(launch_pack(s, src, n, stride, ix->vox_a.as<float4>(), ix->blk_stats.as<float>(), &nblk));
-    float* h_blk = static_cast<float*>(ix->pinned) + 64;
+    float* h_blk = ix->pinned->vox_rows;
     PCC_HIP(hipMemcpyAsync(h_blk, ix->blk_stats.p, (size_t)nblk * 8 * sizeof(float), hipMemcpyDeviceToHost, s));
     PCC_HIP(hipStreamSynchronize(s));
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -131,8 +131,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
     hipLaunchKernelGGL(k_vox_heads, dim3(g1), dim3(256), 0, s, ix->vox_a.as<float4>(), order, n_sorted, d_gd, flags, (unsigned int)n);
     PCC_HIP(hipGetLastError());
     PCC_TRY(launch_exclusive_scan(ix, s, flags, n + 1, ix->vox_c));
-    unsigned int* h_cnt = static_cast<unsigned int*>(ix->pinned) + 48;
-    PCC_HIP(hipMemcpyAsync(h_cnt, flags + n, 4, hipMemcpyDeviceToHost, s));
+    PCC_HIP(hipMemcpyAsync(&ix->pinned->vox_count, flags + n, 4, hipMemcpyDeviceToHost, s));
     // 5. centroids
     char* dout = static_cast<char*>(out);
     if (mem == PCC_MEM_HOST) {
@@ -144,7 +143,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
                        has_rgb, order, n_sorted, d_gd, flags, dout, out_stride, (unsigned int)n);
     PCC_HIP(hipGetLastError());
     PCC_HIP(hipStreamSynchronize(s));
-    const size_t nv = h_cnt[0];
+    const size_t nv = ix->pinned->vox_count;
     *out_n = nv;
     if (mem == PCC_MEM_HOST && nv) {
         PCC_HIP(hipMemcpyAsync(out, dout, nv * out_stride, hipMemcpyDeviceToHost, s));
