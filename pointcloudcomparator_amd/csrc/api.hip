@@ -163,18 +163,6 @@ void HostBuf::release() {
     cap = 0;
 }
 
-struct DeviceGuard {
-    int prev = -1;
-    bool ok = true;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
-    }
-    ~DeviceGuard() {
-        int cur;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
 #define PCC_ENTER(ix)                                                         \
     if (!(ix)) { pcc::set_error("null index"); return PCC_ERR_INVALID; }      \
     std::lock_guard<std::mutex> _lock((ix)->mu);                              \
@@ -226,8 +214,13 @@ static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride,
     return launch_pack(ix->stream, src, n, stride, packed, blk_stats, n_blocks, zero_word, seeds, invalid_keys, cells, gd, grid);
 }
 
-int check_points(const void* pts, size_t n, size_t stride, int mem) {
+int check_mem(int mem) {
     if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space %d", mem); return PCC_ERR_INVALID; }
+    return PCC_OK;
+}
+
+int check_points(const void* pts, size_t n, size_t stride, int mem) {
+    PCC_TRY(check_mem(mem));
     if (n && !pts) { set_error("null point pointer"); return PCC_ERR_INVALID; }
     if (stride < 12 || stride % 4) { set_error("stride %zu must be a multiple of 4 and >= 12", stride); return PCC_ERR_INVALID; }
     if (n >= (1ull << 31)) { set_error("more than 2^31 points"); return PCC_ERR_UNSUPPORTED; }
@@ -255,23 +248,71 @@ int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int me
                         cells ? ix->d_grid.as<GridDev>() : nullptr);
 }
 
-// deliver device results to the caller's memory space
+// ---- caller arrays that are not point clouds (PCC_MEM_HOST or PCC_MEM_DEVICE) -----------------------------------------------
+// An input on the device: the caller's own array, or for host memory a copy in `buf`.
 template <class T>
-static int deliver(pcc_index* ix, const T* dev, T* user, size_t count, int mem) {
-    if (!user || count == 0) return PCC_OK;
-    if (mem == PCC_MEM_HOST) {
-        if (ix->opt.host_pipe && count * sizeof(T) >= PIPE_MIN_BYTES && !host_pointer_is_pinned(user)) {
-            if (!ix->pipe) ix->pipe = new HostPipe();
-            ix->small_raw_n = 0;  // (as in stage_points)
-            PCC_TRY(ix->pipe->download(ix->stream, reinterpret_cast<const char*>(dev), reinterpret_cast<char*>(user), count * sizeof(T)));
-        } else
-        PCC_HIP(hipMemcpyAsync(user, dev, count * sizeof(T), hipMemcpyDeviceToHost, ix->stream));
-    } else if (user != dev) {
-        PCC_HIP(hipMemcpyAsync(user, dev, count * sizeof(T), hipMemcpyDeviceToDevice, ix->stream));
-    }
+static int stage_in(pcc_index* ix, const T* user, size_t count, int mem, DevBuf& buf, const T** dev) {
+    *dev = user;
+    if (mem != PCC_MEM_HOST) return PCC_OK;
+    PCC_TRY(buf.reserve(count * sizeof(T)));
+    PCC_HIP(hipMemcpyAsync(buf.p, user, count * sizeof(T), hipMemcpyHostToDevice, ix->stream));
+    *dev = buf.as<T>();
     return PCC_OK;
 }
 
+// A radius fill's row offsets (nq + 1 of them) on the device, and their total offsets[nq] on the host.
+static int stage_offsets(pcc_index* ix, const int64_t* offsets, size_t nq, int mem, const int64_t** doff, int64_t* total) {
+    PCC_TRY(stage_in(ix, offsets, nq + 1, mem, ix->scratch_d, doff));
+    if (mem == PCC_MEM_HOST) {
+        *total = offsets[nq];
+    } else {
+        PCC_HIP(hipMemcpyAsync(total, offsets + nq, sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));
+    }
+    if (*total < 0) { set_error("negative total"); return PCC_ERR_INVALID; }
+    return PCC_OK;
+}
+
+// A result array: the kernels write `dev`, which is the caller's own array in device memory and `buf` in host memory (nullptr
+// when the caller passed none).  finish() hands the results of a call over.
+template <class T>
+struct Out {
+    T* user = nullptr;
+    size_t count = 0;
+    T* dev = nullptr;
+    int stage(T* u, size_t n, int mem, DevBuf& buf) {
+        user = dev = u;
+        count = n;
+        if (mem != PCC_MEM_HOST) return PCC_OK;
+        PCC_TRY(buf.reserve(count * sizeof(T)));
+        if (user) dev = buf.as<T>();
+        return PCC_OK;
+    }
+};
+
+// one result into the caller's host array: large pageable arrays through the host pipe (host_pipe.hpp), else one copy
+template <class T>
+static int deliver(pcc_index* ix, const Out<T>& o) {
+    if (!o.user || o.count == 0) return PCC_OK;
+    const size_t bytes = o.count * sizeof(T);
+    if (ix->opt.host_pipe && bytes >= PIPE_MIN_BYTES && !host_pointer_is_pinned(o.user)) {
+        if (!ix->pipe) ix->pipe = new HostPipe();
+        ix->small_raw_n = 0;  // (as in stage_points)
+        return ix->pipe->download(ix->stream, reinterpret_cast<const char*>(o.dev), reinterpret_cast<char*>(o.user), bytes);
+    }
+    PCC_HIP(hipMemcpyAsync(o.user, o.dev, bytes, hipMemcpyDeviceToHost, ix->stream));
+    return PCC_OK;
+}
+// host memory: every result in turn, then one wait.  Device memory: nothing to do.
+template <class... T>
+static int finish(pcc_index* ix, int mem, const Out<T>&... outs) {
+    if (mem != PCC_MEM_HOST) return PCC_OK;
+    int st = PCC_OK;
+    (void)(... && ((st = deliver(ix, outs)) == PCC_OK));  // (up to the first failure)
+    PCC_TRY(st);
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
 
 // k = 1 search of ix->q_packed[0..nq) into ix->out_packed (u64 per query)
 // The small-call form (small.hip): host queries against a small exhaustively searched cloud -- the reference's descriptor
@@ -333,6 +374,20 @@ static int small_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, boo
     PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), nq));
     PCC_TRY(ix->host_a.reserve((nq + 2 * nblk) * sizeof(int32_t)));
     PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, ix->host_a.as<int32_t>(), nullptr));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+
+// Small host results of a k = 1 search in out_packed: the unpack kernel writes them into pinned memory itself (host_a: indices,
+// host_b: squared distances, where small_nn1 leaves them too), no copy command; EV_CALL1, then one wait.  fb_mirror: it also
+// mirrors the GRID search's fallback count into the pinned words (pcc_index_stats).
+static int unpack_pinned(pcc_index* ix, size_t nq, bool want_idx, bool want_d2, bool fb_mirror) {
+    PCC_TRY(ix->host_a.reserve(nq * sizeof(int32_t)));
+    PCC_TRY(ix->host_b.reserve(nq * sizeof(float)));
+    PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, want_idx ? ix->host_a.as<int32_t>() : nullptr,
+                          want_d2 ? ix->host_b.as<float>() : nullptr, fb_mirror ? &ix->words()->fb_count : nullptr,
+                          fb_mirror ? &ix->pinned->fb_mirror : nullptr));
+    ev_mark(ix, EV_CALL1);
     PCC_HIP(hipStreamSynchronize(ix->stream));
     return PCC_OK;
 }
@@ -827,50 +882,37 @@ int pcc_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
     ev_mark(ix, EV_CALL0);
     if (small_call(ix, nq, stride, mem)) {
         PCC_TRY(small_nn1(ix, q, nq, stride, idx != nullptr, d2 != nullptr));
-        if (idx) memcpy(idx, ix->host_a.p, nq * sizeof(int32_t));
-        if (d2) memcpy(d2, ix->host_b.p, nq * sizeof(float));
-        return PCC_OK;
-    }
-    {
-        PrepOverlap beside(ix);
-        if (PrepOverlap::wanted(ix, nq)) PCC_TRY(beside.begin());
-        PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-        if (beside.on) {
-            PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), nq, &ix->pre_order, &ix->pre_nsorted));
-            ix->pre_order_nq = nq;
-            PCC_TRY(beside.end());
+    } else {
+        {
+            PrepOverlap beside(ix);
+            if (PrepOverlap::wanted(ix, nq)) PCC_TRY(beside.begin());
+            PCC_TRY(stage_queries(ix, q, nq, stride, mem));
+            if (beside.on) {
+                PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), nq, &ix->pre_order, &ix->pre_nsorted));
+                ix->pre_order_nq = nq;
+                PCC_TRY(beside.end());
+            }
         }
+        PCC_TRY(nn1_packed(ix, nq));
+        if (ix->tie_mode == PCC_TIES_FLANN)
+            PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), nq, mem == PCC_MEM_HOST));
+        // small host results: straight into pinned memory (unpack_pinned)
+        const bool direct = mem == PCC_MEM_HOST && ix->opt.host_pipe && nq * sizeof(float) <= SMALL_RESULT_BYTES;
+        if (!direct) {
+            Out<int32_t> ri;
+            Out<float> rd;
+            PCC_TRY(ri.stage(idx, nq, mem, ix->out_idx));
+            PCC_TRY(rd.stage(d2, nq, mem, ix->out_d2));
+            PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, ri.dev, rd.dev,
+                                  &ix->words()->fb_count, &ix->pinned->fb_mirror));
+            ev_mark(ix, EV_CALL1);
+            return finish(ix, mem, ri, rd);
+        }
+        PCC_TRY(unpack_pinned(ix, nq, idx != nullptr, d2 != nullptr, true));
     }
-    PCC_TRY(nn1_packed(ix, nq));
-    if (ix->tie_mode == PCC_TIES_FLANN)
-        PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), nq, mem == PCC_MEM_HOST));
-    int32_t* didx = idx;
-    float* dd2 = d2;
-    // small host results: the unpack kernel writes them into pinned host memory itself (no copy command, one wait)
-    const bool direct = mem == PCC_MEM_HOST && ix->opt.host_pipe && nq * sizeof(float) <= SMALL_RESULT_BYTES;
-    if (direct) {
-        PCC_TRY(ix->host_a.reserve(nq * sizeof(int32_t)));
-        PCC_TRY(ix->host_b.reserve(nq * sizeof(float)));
-        didx = idx ? ix->host_a.as<int32_t>() : nullptr;
-        dd2 = d2 ? ix->host_b.as<float>() : nullptr;
-    } else if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->out_idx.reserve(nq * sizeof(int32_t)));
-        PCC_TRY(ix->out_d2.reserve(nq * sizeof(float)));
-        didx = idx ? ix->out_idx.as<int32_t>() : nullptr;
-        dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
-    }
-    PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, didx, dd2,
-                          &ix->words()->fb_count, &ix->pinned->fb_mirror));
-    ev_mark(ix, EV_CALL1);
-    if (direct) {
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-        if (idx) memcpy(idx, didx, nq * sizeof(int32_t));
-        if (d2) memcpy(d2, dd2, nq * sizeof(float));
-    } else if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, didx, idx, nq, mem));
-        PCC_TRY(deliver(ix, dd2, d2, nq, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
+    // (small_nn1 and unpack_pinned leave the results in host_a / host_b)
+    if (idx) memcpy(idx, ix->host_a.p, nq * sizeof(int32_t));
+    if (d2) memcpy(d2, ix->host_b.p, nq * sizeof(float));
     return PCC_OK;
 }
 
@@ -890,31 +932,22 @@ int pcc_knn(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-    int32_t* didx = idx;
-    float* dd2 = d2;
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->out_idx.reserve(nq * (size_t)k * sizeof(int32_t)));
-        PCC_TRY(ix->out_d2.reserve(nq * (size_t)k * sizeof(float)));
-        didx = idx ? ix->out_idx.as<int32_t>() : nullptr;
-        dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
-    }
+    Out<int32_t> ri;
+    Out<float> rd;
+    PCC_TRY(ri.stage(idx, nq * (size_t)k, mem, ix->out_idx));
+    PCC_TRY(rd.stage(d2, nq * (size_t)k, mem, ix->out_d2));
     if (grid_knn_delivers(k)) {
         // the search writes indices and distances itself (no key array, no unpack pass)
-        PCC_TRY(grid_knn(ix, ix->q_packed.as<float4>(), nq, k, nullptr, didx, dd2));
+        PCC_TRY(grid_knn(ix, ix->q_packed.as<float4>(), nq, k, nullptr, ri.dev, rd.dev));
     } else {
         PCC_TRY(ix->out_packed.reserve(nq * (size_t)k * sizeof(unsigned long long)));
         auto* keys = ix->out_packed.as<unsigned long long>();
         PCC_TRY(grid_knn(ix, ix->q_packed.as<float4>(), nq, k, keys));
         // rows of invalid queries were never touched (all ~0) and unpack to -1 / +inf
-        PCC_TRY(launch_unpack(ix->stream, keys, nullptr, nq * (size_t)k, didx, dd2));
+        PCC_TRY(launch_unpack(ix->stream, keys, nullptr, nq * (size_t)k, ri.dev, rd.dev));
     }
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, didx, idx, nq * (size_t)k, mem));
-        PCC_TRY(deliver(ix, dd2, d2, nq * (size_t)k, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, ri, rd);
 }
 
 // radiusSearch(pt, double radius): r2 = float(radius*radius) evaluated in double
@@ -947,19 +980,15 @@ int pcc_radius_count_max(pcc_index* ix, const void* q, size_t nq, size_t stride,
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-    int32_t* dcnt = counts;
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_idx.reserve(nq * sizeof(int32_t))); dcnt = ix->out_idx.as<int32_t>(); }
-    PCC_HIP(hipMemsetAsync(dcnt, 0, nq * sizeof(int32_t), ix->stream));
-    PCC_TRY(grid_radius(ix, ix->q_packed.as<float4>(), nq, (float)radius, radius2(radius), dcnt, nullptr, nullptr, 0));
+    Out<int32_t> rc;
+    PCC_TRY(rc.stage(counts, nq, mem, ix->out_idx));
+    PCC_HIP(hipMemsetAsync(rc.dev, 0, nq * sizeof(int32_t), ix->stream));
+    PCC_TRY(grid_radius(ix, ix->q_packed.as<float4>(), nq, (float)radius, radius2(radius), rc.dev, nullptr, nullptr, 0));
     // KdTreeFLANN::radiusSearch(..., max_nn): 0 or anything from the cloud's size on means "all" -- the size PCL compares
     // with is total_nr_points_, the FINITE points --; else FLANN keeps the max_nn nearest within the radius
-    if (!max_nn_is_all) PCC_TRY(launch_clamp_counts(ix->stream, dcnt, nq, (int32_t)max_nn));
+    if (!max_nn_is_all) PCC_TRY(launch_clamp_counts(ix->stream, rc.dev, nq, (int32_t)max_nn));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, dcnt, counts, nq, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, rc);
 }
 
 int pcc_radius_fill_max(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, double radius, int sorted, unsigned int max_nn,
@@ -979,17 +1008,8 @@ int pcc_radius_fill_max(pcc_index* ix, const void* q, size_t nq, size_t stride, 
     PCC_TRY(stage_queries(ix, q, nq, stride, mem));
     const int K = (int)max_nn;
     int64_t total = 0;
-    const int64_t* doff = offsets;
-    if (mem == PCC_MEM_HOST) {
-        total = offsets[nq];
-        PCC_TRY(ix->scratch_d.reserve((nq + 1) * sizeof(int64_t)));
-        PCC_HIP(hipMemcpyAsync(ix->scratch_d.p, offsets, (nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
-        doff = ix->scratch_d.as<int64_t>();
-    } else {
-        PCC_HIP(hipMemcpyAsync(&total, offsets + nq, sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    if (total < 0) { set_error("negative total"); return PCC_ERR_INVALID; }
+    const int64_t* doff = nullptr;
+    PCC_TRY(stage_offsets(ix, offsets, nq, mem, &doff, &total));
     if (total == 0) return PCC_OK;
     const bool rows = grid_knn_delivers(K);
     unsigned long long* keys = nullptr;
@@ -1009,21 +1029,12 @@ int pcc_radius_fill_max(pcc_index* ix, const void* q, size_t nq, size_t stride, 
         keys = ix->out_packed.as<unsigned long long>();
         PCC_TRY(grid_knn(ix, ix->q_packed.as<float4>(), nq, K, keys));
     }
-    int32_t* didx = idx;
-    float* dd2 = d2;
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->out_idx.reserve((size_t)total * sizeof(int32_t)));
-        PCC_TRY(ix->out_d2.reserve((size_t)total * sizeof(float)));
-        didx = idx ? ix->out_idx.as<int32_t>() : nullptr;
-        dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
-    }
-    PCC_TRY(launch_knn_rows_to_csr(ix->stream, keys, ridx, rd2, K, radius2(radius), doff, nq, didx, dd2));
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, didx, idx, (size_t)total, mem));
-        PCC_TRY(deliver(ix, dd2, d2, (size_t)total, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    Out<int32_t> ri;
+    Out<float> rd;
+    PCC_TRY(ri.stage(idx, (size_t)total, mem, ix->out_idx));
+    PCC_TRY(rd.stage(d2, (size_t)total, mem, ix->out_d2));
+    PCC_TRY(launch_knn_rows_to_csr(ix->stream, keys, ridx, rd2, K, radius2(radius), doff, nq, ri.dev, rd.dev));
+    return finish(ix, mem, ri, rd);
 }
 
 int pcc_radius_fill(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, double radius, int sorted,
@@ -1041,45 +1052,26 @@ static int radius_fill_impl(pcc_index* ix, const void* q, size_t nq, size_t stri
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-    // total = offsets[nq]; offsets live in the caller's memory space
     int64_t total = 0;
-    const int64_t* doff = offsets;
-    if (mem == PCC_MEM_HOST) {
-        total = offsets[nq];
-        PCC_TRY(ix->scratch_d.reserve((nq + 1) * sizeof(int64_t)));
-        PCC_HIP(hipMemcpyAsync(ix->scratch_d.p, offsets, (nq + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ix->stream));
-        doff = ix->scratch_d.as<int64_t>();
-    } else {
-        PCC_HIP(hipMemcpyAsync(&total, offsets + nq, sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    if (total < 0) { set_error("negative total"); return PCC_ERR_INVALID; }
+    const int64_t* doff = nullptr;
+    PCC_TRY(stage_offsets(ix, offsets, nq, mem, &doff, &total));
     if (total == 0) return PCC_OK;
     PCC_TRY(ix->out_packed.reserve((size_t)total * sizeof(unsigned long long)));
     auto* keys = ix->out_packed.as<unsigned long long>();
-    int32_t* didx = idx;
-    float* dd2 = d2;
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->out_idx.reserve((size_t)total * sizeof(int32_t)));
-        PCC_TRY(ix->out_d2.reserve((size_t)total * sizeof(float)));
-        didx = idx ? ix->out_idx.as<int32_t>() : nullptr;
-        dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
-    }
+    Out<int32_t> ri;
+    Out<float> rd;
+    PCC_TRY(ri.stage(idx, (size_t)total, mem, ix->out_idx));
+    PCC_TRY(rd.stage(d2, (size_t)total, mem, ix->out_d2));
     // rows of 24 neighbours and more on average: the fill delivers index and distance itself (sorted in registers, no
     // key array in between); otherwise keys -> sort -> unpack.  (Slots a fill does not reach read "nothing found".)
-    const bool wave_fill = (size_t)total >= 24 * nq && (didx || dd2);
+    const bool wave_fill = (size_t)total >= 24 * nq && (ri.dev || rd.dev);
     if (!wave_fill) PCC_HIP(hipMemsetAsync(keys, 0xff, (size_t)total * sizeof(unsigned long long), ix->stream));
     bool delivered = false;
     PCC_TRY(grid_radius(ix, ix->q_packed.as<float4>(), nq, (float)radius, radius2(radius), nullptr, doff, keys, sorted, (size_t)total,
-                        didx, dd2, &delivered));
-    if (!delivered) PCC_TRY(launch_unpack(ix->stream, keys, nullptr, (size_t)total, didx, dd2));
+                        ri.dev, rd.dev, &delivered));
+    if (!delivered) PCC_TRY(launch_unpack(ix->stream, keys, nullptr, (size_t)total, ri.dev, rd.dev));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, didx, idx, (size_t)total, mem));
-        PCC_TRY(deliver(ix, dd2, d2, (size_t)total, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, ri, rd);
 }
 
 int pcc_voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, float leaf, int has_rgb,
@@ -1116,11 +1108,11 @@ int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int m
     // the sampling and the refit read single points on the host: from the caller's array when it is a host array; for a
     // cloud in device memory the few points needed are gathered there (sac.hip) -- round 3 copied the whole cloud back
     // (16 B x n per call; the -e plane-removal loop calls this a handful of times per cloud)
-    int32_t* di = inliers;
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_idx.reserve(n * sizeof(int32_t))); di = ix->out_idx.as<int32_t>(); }
+    Out<int32_t> ri;
+    PCC_TRY(ri.stage(inliers, n, mem, ix->out_idx));
     size_t m = 0;
     int st = sac_plane(ix, dp, n, mem == PCC_MEM_HOST ? static_cast<const char*>(pts) : nullptr, stride, max_iterations, threshold,
-                       probability, optimize, di, &m, coeff, iterations);
+                       probability, optimize, ri.dev, &m, coeff, iterations);
     if (st == PCC_ERR_RETRY_HOST) {
         // a degenerate sample (PCL redraws it at once, which the gathered form cannot replay): with a host copy of the cloud
         std::vector<float4> hp(n);
@@ -1130,14 +1122,12 @@ int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int m
         for (size_t i = 0; i < n; ++i)  // the staged copy zeroes non-finite points; PCL would see them as they are
             if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
         st = sac_plane(ix, dp, n, reinterpret_cast<const char*>(hp.data()), sizeof(float4), max_iterations, threshold, probability,
-                       optimize, di, &m, coeff, iterations);
+                       optimize, ri.dev, &m, coeff, iterations);
     }
     PCC_TRY(st);
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST && m) {
-        PCC_TRY(deliver(ix, di, inliers, m, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
+    ri.count = m;  // (the first m of the n reserved)
+    if (m) PCC_TRY(finish(ix, mem, ri));
     *n_inliers = m;
     return PCC_OK;
 }
@@ -1170,7 +1160,7 @@ static int self_knn_keys(pcc_index* ix, int k, const unsigned long long** keys) 
 
 int pcc_normals(pcc_index* ix, int k, const float viewpoint[3], int mem, float* out) {
     PCC_ENTER(ix);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    PCC_TRY(check_mem(mem));
     if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
     if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
     PCC_TRY(ensure_grid(ix));
@@ -1181,21 +1171,17 @@ int pcc_normals(pcc_index* ix, int k, const float viewpoint[3], int mem, float* 
     // self query on the packed references, as pcc_sor does
     const unsigned long long* keys = nullptr;
     PCC_TRY(self_knn_keys(ix, k, &keys));
-    float4* dout = reinterpret_cast<float4*>(out);
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_d2.reserve(n * sizeof(float4))); dout = ix->out_d2.as<float4>(); }
+    Out<float4> rn;
+    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
     PCC_TRY(launch_normals(ix->stream, keys, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, k,
-                           viewpoint ? viewpoint : origin, dout));
+                           viewpoint ? viewpoint : origin, rn.dev));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, reinterpret_cast<const float*>(dout), out, n * 4, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, rn);
 }
 
 int pcc_normals_radius(pcc_index* ix, double radius, const float viewpoint[3], int mem, float* out) {
     PCC_ENTER(ix);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    PCC_TRY(check_mem(mem));
     if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
     if (!(radius >= 0)) { set_error("bad radius"); return PCC_ERR_INVALID; }
     PCC_TRY(ensure_grid(ix));
@@ -1203,22 +1189,18 @@ int pcc_normals_radius(pcc_index* ix, double radius, const float viewpoint[3], i
     ev_mark(ix, EV_CALL0);
     const size_t n = ix->n_orig;
     const float origin[3] = {0.f, 0.f, 0.f};
-    float4* dout = reinterpret_cast<float4*>(out);
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_d2.reserve(n * sizeof(float4))); dout = ix->out_d2.as<float4>(); }
-    PCC_TRY(normals_radius(ix, radius, viewpoint ? viewpoint : origin, dout));
+    Out<float4> rn;
+    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
+    PCC_TRY(normals_radius(ix, radius, viewpoint ? viewpoint : origin, rn.dev));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, reinterpret_cast<const float*>(dout), out, n * 4, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, rn);
 }
 
 int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels,
                        int32_t* n_clusters) {
     PCC_ENTER(ix);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    PCC_TRY(check_mem(mem));
     if (!normals || !labels || !n_clusters) { set_error("null argument"); return PCC_ERR_INVALID; }
     if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
     PCC_TRY(ensure_grid(ix));
@@ -1228,22 +1210,13 @@ int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, floa
     // findPointNeighbours: one batched self k-NN over the packed references
     const unsigned long long* keys = nullptr;
     PCC_TRY(self_knn_keys(ix, k, &keys));
-    const float4* dn = reinterpret_cast<const float4*>(normals);
-    int32_t* dl = labels;
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->out_d2.reserve(n * sizeof(float4)));
-        PCC_HIP(hipMemcpyAsync(ix->out_d2.p, normals, n * sizeof(float4), hipMemcpyHostToDevice, ix->stream));
-        dn = ix->out_d2.as<float4>();
-        PCC_TRY(ix->q_raw.reserve(n * sizeof(int32_t)));
-        dl = ix->q_raw.as<int32_t>();
-    }
-    PCC_TRY(grid_region_growing(ix, keys, dn, k, smoothness, curvature_threshold, min_size, max_size, dl, n_clusters));
+    const float4* dn = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const float4*>(normals), n, mem, ix->out_d2, &dn));
+    Out<int32_t> rl;
+    PCC_TRY(rl.stage(labels, n, mem, ix->q_raw));
+    PCC_TRY(grid_region_growing(ix, keys, dn, k, smoothness, curvature_threshold, min_size, max_size, rl.dev, n_clusters));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, dl, labels, n, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, rl);
 }
 
 int pcc_first_within(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, double radius, int32_t* idx) {
@@ -1256,21 +1229,17 @@ int pcc_first_within(pcc_index* ix, const void* q, size_t nq, size_t stride, int
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-    int32_t* didx = idx;
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_idx.reserve(nq * sizeof(int32_t))); didx = ix->out_idx.as<int32_t>(); }
-    PCC_TRY(grid_first_within(ix, ix->q_packed.as<float4>(), nq, radius, didx));
+    Out<int32_t> ri;
+    PCC_TRY(ri.stage(idx, nq, mem, ix->out_idx));
+    PCC_TRY(grid_first_within(ix, ix->q_packed.as<float4>(), nq, radius, ri.dev));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, didx, idx, nq, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, ri);
 }
 
 int pcc_euclidean_clusters(pcc_index* ix, double tolerance, uint32_t min_size, uint32_t max_size, int mem,
                            int32_t* labels, int32_t* n_clusters, int32_t* sizes, int max_sizes) {
     PCC_ENTER(ix);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    PCC_TRY(check_mem(mem));
     if (!labels) { set_error("null labels"); return PCC_ERR_INVALID; }
     if (!(tolerance >= 0)) { set_error("bad tolerance"); return PCC_ERR_INVALID; }
     PCC_TRY(ensure_grid(ix));
@@ -1280,21 +1249,17 @@ int pcc_euclidean_clusters(pcc_index* ix, double tolerance, uint32_t min_size, u
     // it as float, radiusSearch squares it in double: r2 = float(double(float(tol))^2)
     const float tol_f = (float)tolerance;
     const float r2 = radius2((double)tol_f);
-    int32_t* dl = labels;
-    if (mem == PCC_MEM_HOST) { PCC_TRY(ix->out_idx.reserve(ix->n_orig * sizeof(int32_t))); dl = ix->out_idx.as<int32_t>(); }
-    PCC_TRY(grid_clusters(ix, tol_f, r2, min_size, max_size, dl, n_clusters, sizes, max_sizes));
+    Out<int32_t> rl;
+    PCC_TRY(rl.stage(labels, ix->n_orig, mem, ix->out_idx));
+    PCC_TRY(grid_clusters(ix, tol_f, r2, min_size, max_size, rl.dev, n_clusters, sizes, max_sizes));
     ev_mark(ix, EV_CALL1);
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(deliver(ix, dl, labels, ix->n_orig, mem));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    return PCC_OK;
+    return finish(ix, mem, rl);
 }
 
 int pcc_sor(pcc_index* ix, int mean_k, double stddev_mult, int mem, float* mean_dist, uint8_t* inlier,
             double* threshold, size_t* kept) {
     PCC_ENTER(ix);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    PCC_TRY(check_mem(mem));
     if (mean_k < 1 || mean_k + 1 > PCC_KNN_MAX_K) { set_error("mean_k=%d outside [1, %d]", mean_k, PCC_KNN_MAX_K - 1); return PCC_ERR_UNSUPPORTED; }
     PCC_TRY(ensure_grid(ix));
     ev_next(ix);
@@ -1432,20 +1397,12 @@ int pcc_icp_step_about(pcc_index* ix, const void* src, size_t n, size_t stride, 
     PCC_TRY(icp_reduce(ix, n, sums, center_dev));
     ev_mark(ix, EV_CALL1);
     if (idx || d2) {
-        int32_t* didx = idx;
-        float* dd2 = d2;
-        if (mem == PCC_MEM_HOST) {
-            PCC_TRY(ix->out_idx.reserve(n * sizeof(int32_t)));
-            PCC_TRY(ix->out_d2.reserve(n * sizeof(float)));
-            didx = idx ? ix->out_idx.as<int32_t>() : nullptr;
-            dd2 = d2 ? ix->out_d2.as<float>() : nullptr;
-        }
-        PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, n, didx, dd2));
-        if (mem == PCC_MEM_HOST) {
-            PCC_TRY(deliver(ix, didx, idx, n, mem));
-            PCC_TRY(deliver(ix, dd2, d2, n, mem));
-            PCC_HIP(hipStreamSynchronize(ix->stream));
-        }
+        Out<int32_t> ri;
+        Out<float> rd;
+        PCC_TRY(ri.stage(idx, n, mem, ix->out_idx));
+        PCC_TRY(rd.stage(d2, n, mem, ix->out_d2));
+        PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, n, ri.dev, rd.dev));
+        PCC_TRY(finish(ix, mem, ri, rd));
     }
     return PCC_OK;
 }
@@ -1688,12 +1645,7 @@ int pcc_match_knn(pcc_index* ix, const void* des2, size_t n2, size_t stride, int
         PCC_TRY(stage_queries(ix, des2, n2, stride, mem));
         PCC_TRY(nn1_packed(ix, n2));
         if (ix->tie_mode == PCC_TIES_FLANN) PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), n2, true));
-        // (the unpack kernel writes the result arrays into pinned host memory itself: no copy command, one wait)
-        PCC_TRY(ix->host_a.reserve(n2 * sizeof(int32_t)));
-        PCC_TRY(ix->host_b.reserve(n2 * sizeof(float)));
-        PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, n2, ix->host_a.as<int32_t>(), ix->host_b.as<float>()));
-        ev_mark(ix, EV_CALL1);
-        PCC_HIP(hipStreamSynchronize(ix->stream));
+        PCC_TRY(unpack_pinned(ix, n2, true, true, false));
     }
     const int32_t* hi = ix->host_a.as<int32_t>();
     const float* hd = ix->host_b.as<float>();

@@ -74,18 +74,6 @@ struct pcc_comm {
 
 namespace pcc {
 
-struct SetDevice {
-    int prev = -1;
-    bool ok = true;
-    explicit SetDevice(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess || (prev != dev && hipSetDevice(dev) != hipSuccess)) ok = false;
-    }
-    ~SetDevice() {
-        int cur;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
 static int allreduce_sum_f64(void* ctx, double* dev, int count, hipStream_t s) {
     pcc_comm* c = static_cast<pcc_comm*>(ctx);
     PCC_NCCL(rccl()->AllReduce(dev, dev, (size_t)count, ncclDouble, ncclSum, c->nccl, s));
@@ -139,7 +127,7 @@ int pcc_comm_create_rank(const void* id, size_t bytes, int world, int rank, int 
     if (!rccl()) { set_error("librccl.so.1 not found (dlopen)"); return PCC_ERR_DEVICE; }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { set_error("device %d out of range (%d present)", device, ndev); return PCC_ERR_INVALID; }
-    SetDevice g(device);
+    DeviceGuard g(device);
     if (!g.ok) { set_error("hipSetDevice(%d) failed", device); return PCC_ERR_DEVICE; }
     ncclUniqueId u;
     memcpy(&u, id, sizeof(u));
@@ -176,7 +164,7 @@ int pcc_comm_create_local(const int* devices, int count, pcc_comm** out) {
         out[k] = c;
     }
     for (int k = 0; k < count; ++k) {  // the scalar-exchange words of every rank, or no communicator at all
-        SetDevice g(devices[k]);
+        DeviceGuard g(devices[k]);
         if (!g.ok || out[k]->word.reserve(256) != PCC_OK) {
             if (!g.ok) set_error("hipSetDevice(%d) failed", devices[k]);
             for (int j = 0; j < count; ++j) { pcc_comm_destroy(out[j]); out[j] = nullptr; }
@@ -188,7 +176,7 @@ int pcc_comm_create_local(const int* devices, int count, pcc_comm** out) {
 
 int pcc_comm_destroy(pcc_comm* c) {
     if (!c) return PCC_OK;
-    SetDevice g(c->device);
+    DeviceGuard g(c->device);
     c->word.release();
     if (c->nccl && rccl()) (void)rccl()->CommDestroy(c->nccl);
     delete c;
@@ -212,7 +200,7 @@ int pcc_index_create_broadcast(pcc_comm* c, int root, const void* pts, size_t n,
     *out = nullptr;
     PCC_TRY(check_comm(c));
     if (root < 0 || root >= c->world) { set_error("root %d outside the communicator (%d ranks)", root, c->world); return PCC_ERR_INVALID; }
-    SetDevice g(c->device);
+    DeviceGuard g(c->device);
     if (!g.ok) { set_error("hipSetDevice(%d) failed", c->device); return PCC_ERR_DEVICE; }
     pcc_index* ix = nullptr;
     unsigned long long n64 = 0;
@@ -308,8 +296,8 @@ int pcc_sor_partial(pcc_index* ix, size_t start, size_t count, int mean_k, int m
     if (!ix) { set_error("null index"); return PCC_ERR_INVALID; }
     std::lock_guard<std::mutex> lock(ix->mu);
     pcc::entered(ix);
-    SetDevice g(ix->device);
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return PCC_ERR_INVALID; }
+    DeviceGuard g(ix->device);
+    PCC_TRY(check_mem(mem));
     if (!sums) { set_error("null sums"); return PCC_ERR_INVALID; }
     float* dmean = nullptr;
     PCC_TRY(sor_shard_means(ix, start, count, mean_k, &dmean));
@@ -341,10 +329,10 @@ int pcc_sor_sharded(pcc_index* ix, pcc_comm* c, size_t start, size_t count, int 
     // (every failure of one rank alone ends in the status exchange below, never in a peer waiting for its all-reduce)
     if (!ix) { set_error("null index"); return agree_status(c, PCC_ERR_INVALID); }
     if (ix->device != c->device) { set_error("index on device %d, communicator on device %d", ix->device, c->device); return agree_status(c, PCC_ERR_INVALID); }
-    if (mem != PCC_MEM_HOST && mem != PCC_MEM_DEVICE) { set_error("bad mem space"); return agree_status(c, PCC_ERR_INVALID); }
+    if (check_mem(mem) != PCC_OK) return agree_status(c, PCC_ERR_INVALID);
     std::lock_guard<std::mutex> lock(ix->mu);
     pcc::entered(ix);
-    SetDevice g(ix->device);
+    DeviceGuard g(ix->device);
     hipStream_t s = ix->stream;
     const int K = mean_k + 1;
     float* dmean = nullptr;

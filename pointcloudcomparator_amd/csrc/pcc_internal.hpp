@@ -55,6 +55,20 @@ struct HostBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// selects `dev` for the scope and restores the caller's device at its end; ok = false when the device could not be selected
+struct DeviceGuard {
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) { ok = false; return; }
+        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
+    }
+    ~DeviceGuard() {
+        int cur;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
 // Uniform-grid parameters (device + host copy).  Cell of a point along GRID axis a (0: the cells of a row, fastest in the
 // linear id (c2 * dim1 + c1) * dim0 + c0; 1: the rows of a layer; 2: the layers):
 //   c_a = clamp(int((p[ax_a] - org_a) * inv_h), 0, dim_a - 1)
@@ -542,6 +556,7 @@ struct IcpHooks {
 int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
                    float T[16], double* fitness, int* iterations, int* converged);
 // ---- api.hip internals comm.hip builds on -------------------------------------------------------------------------
+int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem);
 int nn1_packed(pcc_index* ix, size_t nq);
