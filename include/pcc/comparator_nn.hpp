@@ -44,6 +44,40 @@ inline std::vector<int> matchRIFTFeaturesKnn(const PointCloud<RIFT32>::Ptr& desc
     return out;
 }
 
+// ---- every matchRIFTFeaturesKnn call of the cluster-matching loop at once (src/comparator.cpp:1296-1365, call at :1322) ----
+// pairs[p] = (descriptors1, descriptors2) of one call; element p of the result is what matchRIFTFeaturesKnn(pairs[p]) returns
+// (PCC_TIES_FLANN as there; a null or empty cloud on either side gives the dummy alone).  One pcc_match_knn_batch: one
+// upload, one search launch and one wait for all pairs.  No pair at all makes no library call.
+inline std::vector<std::vector<int> > matchRIFTFeaturesKnnBatch(
+    const std::vector<std::pair<PointCloud<RIFT32>::Ptr, PointCloud<RIFT32>::Ptr> >& pairs) {
+    std::vector<std::vector<int> > result(pairs.size(), std::vector<int>(1));
+    if (pairs.empty()) return result;
+    static thread_local KdTreeFLANN<RIFT32> context;  // lends device, stream and scratch; the cloud it indexes is never asked
+    if (!context.handle()) {
+        PointCloud<RIFT32>::Ptr one(new PointCloud<RIFT32>);
+        one->push_back(RIFT32());
+        for (float& v : one->points[0].histogram) v = 0.f;
+        context.setInputCloud(one);
+    }
+    context.setTieOrder(PCC_TIES_FLANN);
+    std::vector<const void*> d1(pairs.size(), nullptr), d2(pairs.size(), nullptr);
+    std::vector<size_t> n1(pairs.size(), 0), n2(pairs.size(), 0), offsets(pairs.size() + 1);
+    size_t total = pairs.size();
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        if (!pairs[p].first || !pairs[p].second || pairs[p].first->empty() || pairs[p].second->empty()) continue;
+        d1[p] = pairs[p].first->points.data();
+        n1[p] = pairs[p].first->size();
+        d2[p] = pairs[p].second->points.data();
+        n2[p] = pairs[p].second->size();
+        total += n2[p];
+    }
+    std::vector<int32_t> out(total);
+    check(pcc_match_knn_batch(context.handle(), pairs.size(), d1.data(), n1.data(), d2.data(), n2.data(), sizeof(RIFT32), PCC_MEM_HOST,
+                              0.05f, out.data(), offsets.data()));
+    for (size_t p = 0; p < pairs.size(); ++p) result[p].assign(out.begin() + offsets[p], out.begin() + offsets[p + 1]);
+    return result;
+}
+
 // ---- pcl::VoxelGrid (src/segmentation.cpp:69-74, 224-229) -------------------------------------------
 template <class PointT>
 class VoxelGrid {

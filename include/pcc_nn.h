@@ -314,6 +314,26 @@ int pcc_icp_align(pcc_index *target, const void *src, size_t n, size_t stride_by
 int pcc_match_knn(pcc_index *index_des1, const void *des2, size_t n2,
                   size_t stride_bytes, int mem, float threshold, int32_t *out,
                   int32_t *out_size);
+/* The same for EVERY cluster pair of a comparison at once -- replaces the calls of the cluster-matching loop
+ *   (src/comparator.cpp:1296-1365, call at :1322): per cluster of cloud 1 the three nearest clusters of cloud 2 behind
+ *   two size gates, none depending on an earlier result.  One upload, one search launch, one wait for all pairs (one
+ *   more of each when PCC_TIES_FLANN meets a tied query), whatever n_pairs is.
+ *   ctx: any index handle; it supplies device, stream, scratch, the tie order (pcc_index_set_tie_order) and
+ *     PCC_OPT_FLANN_SPLIT, as for pcc_voxel_grid.  The cloud it indexes is neither read nor changed.  pcc_index_stats
+ *     afterwards reports the batch's totals in [1] (queries), [5] (tied) and [6] (indices the FLANN walk changed).
+ *   Pair p searches the n2[p] records of des2[p] against the n1[p] records of des1[p]; per pair the result is what
+ *     pcc_index_create(des1[p], ..., PCC_ENGINE_AUTO) + pcc_match_knn(des2[p]) returns under the same tie order, bit
+ *     for bit.  Its row is out[out_offsets[p] .. out_offsets[p + 1]): the dummy 0 of :568, then one index into des1[p]
+ *     per query with d2 < threshold, in query order.  A pair with n1 == 0, n2 == 0 or no finite record in des1[p]
+ *     yields the dummy alone (the single path answers PCC_ERR_EMPTY there); n_pairs == 0 touches no device.
+ *   out: HOST array of at least sum(n2) + n_pairs ints; out_offsets: n_pairs + 1 entries.  mem must be PCC_MEM_HOST
+ *     (PCC_MEM_DEVICE: PCC_ERR_UNSUPPORTED).  The arrays, the stride and the totals (below 2^31) are checked before
+ *     the handle is looked at. */
+int pcc_match_knn_batch(pcc_index *ctx, size_t n_pairs,
+                        const void *const *des1, const size_t *n1,
+                        const void *const *des2, const size_t *n2,
+                        size_t stride_bytes, int mem, float threshold,
+                        int32_t *out, size_t *out_offsets);
 
 /* ---- voxel-grid down-sampling -----------------------------------------------------------------------
  * replaces: pcl::VoxelGrid<PointXYZRGB> with setLeafSize(l, l, l) + filter, the first step of both

@@ -31,7 +31,7 @@ SYMBOLS = [
     "pcc_index_sync", "pcc_index_engine", "pcc_index_set_engine",
     "pcc_nn1", "pcc_knn", "pcc_radius_count", "pcc_radius_fill", "pcc_radius_count_max", "pcc_radius_fill_max",
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
-    "pcc_match_knn", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
+    "pcc_match_knn", "pcc_match_knn_batch", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
@@ -114,6 +114,7 @@ def _load() -> C.CDLL:
     lib.pcc_icp_align.argtypes = [vp, vp, sz, sz, i32, i32, i32, C.POINTER(C.c_float),
                                   C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32)]
     lib.pcc_match_knn.argtypes = [vp, vp, sz, sz, i32, C.c_float, vp, C.POINTER(C.c_int32)]
+    lib.pcc_match_knn_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, C.c_float, vp, vp]
     lib.pcc_comm_unique_id.argtypes = [vp, sz]
     lib.pcc_comm_create_rank.argtypes = [vp, sz, i32, i32, i32, C.POINTER(vp)]
     lib.pcc_comm_create_local.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
@@ -257,6 +258,8 @@ class Index:
     only serial.  Callers that time or pipeline (bench.py) pass auto_sync=False and order the streams themselves (sync(),
     wait_stream(), stream_wait())."""
 
+    _ties = TIES_LOWEST_INDEX  # what set_tie_order last set (a new handle starts with the lowest index)
+
     @classmethod
     def broadcast(cls, comm: "Comm", root: int, points=None, engine: int = ENGINE_AUTO, auto_sync: bool = True):
         """the reference cloud of rank `root` indexed on every rank of `comm` (pcc_index_create_broadcast; collective).
@@ -394,6 +397,7 @@ class Index:
     def set_tie_order(self, ties: int):
         """TIES_LOWEST_INDEX (default) or TIES_FLANN: which of several equally near references nn1 / match_knn name"""
         _check(LIB.pcc_index_set_tie_order(self._h, ties))
+        self._ties = ties
 
     def set_stream(self, stream_ptr: int):
         _check(LIB.pcc_index_set_stream(self._h, C.c_void_p(stream_ptr)))
@@ -695,3 +699,41 @@ class Index:
         _check(LIB.pcc_match_knn(self._h, ptr, n, stride, mem, np.float32(threshold), out.ctypes.data,
                                  C.byref(sz)))
         return out[:sz.value]
+
+    def match_knn_batch(self, pairs, threshold: float = 0.05, ties=None):
+        """pcc_match_knn_batch with this handle as the context: `pairs` is a sequence of (des1, des2) float32 numpy arrays of
+        one row stride; returns one int32 array per pair, each what Index(des1).match_knn(des2) returns.  The cloud the
+        handle indexes is neither read nor changed.  ties: None = the handle's own tie order, else that order for this call."""
+        pairs = list(pairs)
+        n = len(pairs)
+        args = [(_points(a), _points(b)) for a, b in pairs]
+        strides = {x[2] for ab in args for x in ab}
+        assert len(strides) <= 1, "every descriptor array of a batch must have the same row stride"
+        assert all(x[3] == MEM_HOST for ab in args for x in ab), "pcc_match_knn_batch takes host arrays"
+        stride = strides.pop() if strides else 12
+        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+        d1 = vps(*[a[0] if a[1] else None for a, _ in args])
+        d2 = vps(*[b[0] if b[1] else None for _, b in args])
+        n1 = szs(*[a[1] for a, _ in args])
+        n2 = szs(*[b[1] for _, b in args])
+        out = np.empty(sum(b[1] for _, b in args) + n, dtype=np.int32)
+        off = np.zeros(n + 1, dtype=np.uintp)
+        own = self._ties
+        if ties is not None and ties != own:
+            self.set_tie_order(ties)
+        try:
+            _check(LIB.pcc_match_knn_batch(self._h, n, d1, n1, d2, n2, stride, MEM_HOST, np.float32(threshold),
+                                           out.ctypes.data, off.ctypes.data))
+        finally:
+            if self._ties != own:
+                self.set_tie_order(own)
+        return [out[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
+
+
+def match_knn_batch(pairs, threshold: float = 0.05, ties: int = TIES_LOWEST_INDEX, ctx=None):
+    """Descriptor matching for every (des1, des2) pair at once (pcc_match_knn_batch).  ctx: an Index that lends its device,
+    stream and scratch (its own cloud and tie order are left as they are); None makes a one-point handle for the call."""
+    if ctx is not None:
+        return ctx.match_knn_batch(pairs, threshold, ties)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.match_knn_batch(pairs, threshold, ties)

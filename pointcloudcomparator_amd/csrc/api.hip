@@ -555,6 +555,7 @@ int pcc_index_destroy(pcc_index* ix) {
     ix->host_b.release();
     ix->host_c.release();
     if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
+    match_batch_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
     if (ix->h_grid) (void)hipHostFree(ix->h_grid);
     if (ix->edge_ev) (void)hipEventDestroy(ix->edge_ev);

@@ -251,6 +251,7 @@ static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) 
 
 }  // namespace pcc
 
+namespace pcc { struct MatchBatchScratch; }  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
 namespace pcc { struct HostPipe; }  // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 #define PCC_EV_SLOTS 64
 #define PCC_EV_KINDS 10
@@ -342,6 +343,7 @@ struct pcc_index {
     pcc::HostBuf host_a, host_b;  // large pinned read-back buffers
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
+    pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
     // ring of PCC_EV_SLOTS calls so a timed region of many steps is covered without syncing
@@ -556,6 +558,7 @@ struct IcpHooks {
 int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
                    float T[16], double* fitness, int* iterations, int* converged);
 // ---- api.hip internals comm.hip builds on -------------------------------------------------------------------------
+void match_batch_release(pcc_index* ix);  // match_batch.hip: frees ix->mb
 int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem);

@@ -5,13 +5,14 @@
 // :1570-1615 scores and ratios, :1617-1635 verdict).
 //
 // What feeds it is the nearest-neighbour path of this repository: cluster sizes from the segmentation,
-// matchRIFTFeaturesKnn() (one pcc_match_knn per candidate pair) for the correspondences.  The descriptors
+// matchRIFTFeaturesKnnBatch() (one pcc_match_knn_batch for all candidate pairs of a comparison) for the correspondences.  The descriptors
 // themselves (SIFT keypoints + RIFT histograms) are NOT computed here -- SURVEY.md section 2 keeps that pipeline
 // out of scope -- they are read from files a caller provides (descriptors_io below); without them every
 // cluster has 0 descriptors, nothing can match and no verdict is given.  The colour-based element count of a match
 // (color_growing_segmentation on both clusters, :1466-1500) runs pcl::RegionGrowingRGB's 100-neighbour search on the GPU
 // (include/pcc/region_growing_rgb.hpp) and writes the reference's three lines.
 #pragma once
+#include <array>
 #include <cmath>
 #include <fstream>
 #include <iostream>
@@ -138,32 +139,50 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
         w.clusterEnd(des2[j]->points.size(), c);
         centroids2.push_back(std::vector<float>(c, c + 3));
     }
-    w.sectionTitle("Information of clusters of PCL 1:");
-    matches.assign(clusters1.size(), -1);
+    // first pass, nothing printed: per cluster of PCL 1 the three nearest clusters of PCL 2 (by centroid, in order of
+    // distance) and the two gates in front of matchRIFTFeaturesKnn.  No call depends on an earlier one's result
+    // (reference :1296-1365), so every gated pair goes to the library in ONE call
+    std::vector<std::array<float, 3> > centroids1(clusters1.size());
+    std::vector<std::array<int, 3> > candidates(clusters1.size());
+    std::vector<std::array<int, 3> > call_of(clusters1.size());  // position of (i, candidate k) among the gated pairs, -1: gated out
+    std::vector<std::pair<DescPtr, DescPtr> > gated;
     for (size_t i = 0; i < clusters1.size(); ++i) {
-        float c[3];
-        centroidOf(*clusters1[i], c);
-        w.clusterBegin(1, i, clusters1[i]->points.size());
-        w.clusterEnd(des1[i]->points.size(), c);
-        // the three nearest clusters of PCL 2 (by centroid) are tried in order of distance
+        centroidOf(*clusters1[i], centroids1[i].data());
         std::set<int> taken;
-        int candidate[3];
         for (int k = 0; k < 3; ++k) {
-            candidate[k] = nearestFreeCentroid(c, centroids2, taken);
-            if (k < 2) taken.insert(candidate[k]);
+            candidates[i][k] = nearestFreeCentroid(centroids1[i].data(), centroids2, taken);
+            if (k < 2) taken.insert(candidates[i][k]);
         }
-        size_t best_corr = 0;
         const size_t n1 = des1[i]->points.size();
         for (int k = 0; k < 3; ++k) {
-            const int j = candidate[k];
-            if (j == -1) { std::cout << "No closer centroid found" << std::endl; continue; }
+            const int j = candidates[i][k];
+            call_of[i][k] = -1;
+            if (j == -1) continue;
             const size_t n2 = des2[j]->points.size();
             if (n1 <= 3 || n2 <= 3) continue;  // "!empty() and size() > 3" on both sides
             // size ratio: size_t / size_t, kept only when it is exactly 1 (0.5 < coef < 2 on an integer quotient)
             const size_t coef = clusters2[j]->points.size() / clusters1[i]->points.size();
             if (coef != 1) continue;
+            call_of[i][k] = (int)gated.size();
+            gated.push_back(std::make_pair(des1[i], des2[j]));
+        }
+    }
+    // (without descriptors nothing passes the gates and the library is not called: the report then needs no device)
+    const std::vector<std::vector<int> > correspondences = matchRIFTFeaturesKnnBatch(gated);
+    w.sectionTitle("Information of clusters of PCL 1:");
+    matches.assign(clusters1.size(), -1);
+    for (size_t i = 0; i < clusters1.size(); ++i) {
+        w.clusterBegin(1, i, clusters1[i]->points.size());
+        w.clusterEnd(des1[i]->points.size(), centroids1[i].data());
+        size_t best_corr = 0;
+        const size_t n1 = des1[i]->points.size();
+        for (int k = 0; k < 3; ++k) {
+            const int j = candidates[i][k];
+            if (j == -1) { std::cout << "No closer centroid found" << std::endl; continue; }
+            if (call_of[i][k] < 0) continue;  // gated out above
+            const size_t n2 = des2[j]->points.size();
             std::cout << "Des pcl 1: " << n1 << std::endl << "Des pcl 2: " << n2 << std::endl;
-            const size_t corr = matchRIFTFeaturesKnn(des1[i], des2[j]).size();  // matches + the dummy first element
+            const size_t corr = correspondences[call_of[i][k]].size();  // matches + the dummy first element
             // percentage and acceptance use integer division by the LARGER descriptor count
             const bool first_larger = n1 > n2;
             const size_t denom = first_larger ? n1 : n2;

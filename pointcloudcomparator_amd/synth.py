@@ -142,3 +142,44 @@ def with_rgb_stride(points: np.ndarray) -> np.ndarray:
     rgb = (splitmix64(0xC0104, np.arange(n, dtype=np.uint64)) & np.uint64(0xFFFFFF)).astype(np.uint32)
     out[:, 4] = rgb.view(np.float32)
     return out
+
+
+# ---- descriptor clouds for matchRIFTFeaturesKnn's call pattern (reference src/comparator.cpp:560-588) ----------------------
+DESCRIPTOR_FAMILIES = ("uniform", "quantised")
+
+
+def descriptor_cloud(n: int, family: str, seed: int) -> np.ndarray:
+    """n records of 32 floats.  "uniform": every bin uniform in [0, 1) -- exact float ties are rare.  "quantised": every bin a
+    multiple of 1/64 in [0, 1/4] -- 17^3 distinct values in the three bins the search reads, so clouds are full of duplicates."""
+    rng = np.random.default_rng([0xDE5C, seed])
+    if family == "uniform":
+        return rng.random((n, 32), dtype=np.float32)
+    assert family == "quantised"
+    return np.round(rng.random((n, 32), dtype=np.float32) * 16) / np.float32(64)
+
+
+def descriptor_queries(des1: np.ndarray, n: int, family: str, seed: int) -> np.ndarray:
+    """n query records made from des1: randomly chosen records of it, perturbed -- "uniform": by up to +-0.15 a bin (matches on
+    both sides of the 0.05 threshold in small clouds), "quantised": by one step of 1/64 in 30 % of the bins (still on the
+    lattice: most queries have several references at exactly the same distance)."""
+    rng = np.random.default_rng([0xDE5D, seed])
+    if len(des1) == 0:
+        return descriptor_cloud(n, family, seed + 1)
+    base = des1[rng.integers(0, len(des1), n)]
+    if family == "uniform":
+        noise = (rng.random((n, 32), dtype=np.float32) - np.float32(0.5)) * np.float32(0.3)
+    else:
+        noise = (rng.random((n, 32), dtype=np.float32) < 0.3) * np.float32(1.0 / 64)
+    return np.ascontiguousarray(base + noise, dtype=np.float32)
+
+
+def descriptor_pairs(sizes, family: str, seed: int):
+    """[(des1, des2)] for sizes = [(cluster1, cluster2, n1, n2)]: one des1 array per distinct cluster1 (pairs of the same
+    cluster share the array, as the clusters of a comparison do), one des2 array per pair."""
+    firsts, pairs = {}, []
+    for p, (c1, _c2, n1, n2) in enumerate(sizes):
+        if c1 not in firsts:
+            firsts[c1] = descriptor_cloud(n1, family, seed * 100003 + 2 * c1)
+        assert len(firsts[c1]) == n1
+        pairs.append((firsts[c1], descriptor_queries(firsts[c1], n2, family, seed * 100003 + 2 * p + 1)))
+    return pairs
