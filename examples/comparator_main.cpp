@@ -11,8 +11,9 @@
 //   when it does not converge) -> [-e] Euclidean clustering (src/segmentation.cpp:119-156) -> point /
 //   cluster counts (:1199-1205) -> [-n] noise pass (:1520-1568) -> results file.
 // Same flags, banner lines, section strings and exit code (always 1, :1704).  NOT part of this build
-// (out of scope): descriptor pipelines (SIFT/RIFT) and the per-cluster matching /
-// scoring that needs them, and the viewer (-v is accepted and ignored).  Both segmentation paths run: region growing (default, src/segmentation.cpp:218-327) and
+// (out of scope): the SIFT keypoint pipeline and the viewer (-v is accepted and ignored).  The RIFT
+// descriptors of the clusters come from files (--descriptors1/2) or, with --rift, from pcc::processRIFT (:590-684), dense
+// for every cluster (the reference sends clusters above 700 points through SIFT keypoints first, :1228-1231).  Both segmentation paths run: region growing (default, src/segmentation.cpp:218-327) and
 // Euclidean clustering (-e, :64-156), each behind the VoxelGrid the reference applies first.
 #include <cmath>
 #include <cstdio>
@@ -25,6 +26,7 @@
 #include <vector>
 #include "pcc/comparator_nn.hpp"
 #include "pcc/multi_device.hpp"
+#include "pcc/rift.hpp"
 #include "ply_io.hpp"
 #include "report.hpp"
 
@@ -33,9 +35,12 @@ using namespace pcc;
 static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // not in the reference: --gpus N (the two clouds are segmented / filtered as replicas on two devices),
 // --descriptors1/2 FILE (precomputed RIFT32 descriptors per cluster: the descriptor pipeline itself is out of scope),
-// --dump-clusters PREFIX (the clusters as PLY files, so that descriptors can be computed for them elsewhere)
+// --dump-clusters PREFIX (the clusters as PLY files, so that descriptors can be computed for them elsewhere),
+// --rift (clusters of a scene without a descriptor file get their descriptors from pcc::processRIFT),
+// --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read)
 static int n_gpus = 1;
-static std::string descriptors_path[2], dump_prefix;
+static bool rift = false;
+static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
 static void printUsage() {
     std::cout << "\n\nUsage: [options] </pathToScene1.ply> </pathToScene2.ply>\n\n"
@@ -49,6 +54,10 @@ static void printUsage() {
               << "--descriptors1 F   (this build) precomputed RIFT32 descriptors of the clusters of scene 1\n"
               << "--descriptors2 F   (this build) ... of scene 2\n"
               << "--dump-clusters P  (this build) write the clusters as P_<scene>_<cluster>.ply\n"
+              << "--rift             (this build) RIFT descriptors of every cluster of a scene without a descriptor file are computed\n"
+              << "                   (processRIFT: normals 0.03, intensity gradient 0.03, RIFT 0.05, 4 x 8 bins), DENSE for every\n"
+              << "                   cluster: the reference's SIFT keypoint stage for clusters above 700 points is not part of this build\n"
+              << "--dump-descriptors P  (this build) write the descriptors in use as P_<scene>.txt (the format of --descriptors1/2)\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
@@ -220,11 +229,13 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
                 io::savePLYFileBinary(name.str(), *clusters[k][j]);
             }
 
-    // descriptors per cluster: from files, or none (the SIFT / RIFT pipeline is not part of this build)
+    // descriptors per cluster: from files, computed (--rift), or none
     std::vector<report::DescPtr> des[2];
     bool have_descriptors = true;
     for (int k = 0; k < 2; ++k) {
-        if (descriptors_path[k].empty()) {
+        if (descriptors_path[k].empty() && rift) {
+            for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) des[k].push_back(processRIFT(c));
+        } else if (descriptors_path[k].empty()) {
             have_descriptors = false;
             des[k].assign(clusters[k].size(), report::DescPtr());
             for (report::DescPtr& d : des[k]) d.reset(new PointCloud<RIFT32>);
@@ -233,6 +244,21 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
             return -2;
         }
     }
+    if (!dump_descriptors_prefix.empty())
+        for (int k = 0; k < 2; ++k) {
+            std::ostringstream name;
+            name << dump_descriptors_prefix << "_" << k + 1 << ".txt";
+            std::ofstream df(name.str().c_str());
+            df.precision(9);
+            df << "pcc_descriptors 1\n";
+            for (size_t j = 0; j < des[k].size(); ++j) {
+                df << "cluster " << j << " " << des[k][j]->size() << "\n";
+                for (const RIFT32& d : des[k][j]->points) {
+                    for (int b = 0; b < 32; ++b) df << (b ? " " : "") << d.histogram[b];
+                    df << "\n";
+                }
+            }
+        }
     std::vector<int> matches;
     const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches);
 
@@ -289,6 +315,8 @@ int main(int argc, char** argv) {
         else if (a == "--descriptors1" && i + 1 < argc) descriptors_path[0] = argv[++i];
         else if (a == "--descriptors2" && i + 1 < argc) descriptors_path[1] = argv[++i];
         else if (a == "--dump-clusters" && i + 1 < argc) dump_prefix = argv[++i];
+        else if (a == "--rift") rift = true;
+        else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }

@@ -193,10 +193,13 @@ enum pcc_option {
     PCC_OPT_SCAN_CHAINED = 22,   /* exclusive scans inside the sorts: 1 = one launch, workgroups hand their totals forward through tagged
                                     64-bit atomics (default); 0 = two launches (totals, then apply) that wait for nothing -- for
                                     environments where workgroups are not dispatched in order (preemption, shared devices) */
-    PCC_OPT_KNN_RUN = 23         /* k-NN selection (k <= 512): a wave takes this many consecutive queries of the cell-sorted order in a
+    PCC_OPT_KNN_RUN = 23,        /* k-NN selection (k <= 512): a wave takes this many consecutive queries of the cell-sorted order in a
                                     row; every query after the first of its run starts from a bound -- its predecessor's K-th distance
                                     plus their separation (the K-th neighbour distance is 1-Lipschitz) -- and skips the cube sizing,
                                     the bucket histogram and the compaction (default 16; 1 = every query on its own, round 5) */
+    PCC_OPT_RIFT_LAYOUT = 24     /* pcc_rift_descriptors, the histogram kernel: 1 = 32 lanes per row -- every lane computes one row entry's
+                                    vote, then every lane adds, in row order, the shares of the bin it owns (default); 0 = one lane per row
+                                    (PCL's loop as it stands).  Same bits either way. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -392,6 +395,32 @@ int pcc_normals(pcc_index *index, int k, const float viewpoint[3], int mem, floa
  * src/comparator.cpp:628-635, radius 0.03): the neighbourhood is the sorted radiusSearch result
  * (d2 < float(radius^2), ascending (d2, index)); NaN where it holds fewer than 3 points. */
 int pcc_normals_radius(pcc_index *index, double radius, const float viewpoint[3], int mem, float *out);
+/* ---- RIFT descriptors of the indexed cloud ---------------------------------------------------------
+ * replaces: processRIFT (src/comparator.cpp:590-684) for one cloud: pcl::PointCloudXYZRGBtoXYZI, pcl::NormalEstimation
+ *   (setRadiusSearch 0.03, :628-635), removeNaNNormalsFromPointCloud (:637-646), pcl::IntensityGradientEstimation
+ *   (setRadiusSearch 0.03), pcl::RIFTEstimation (setRadiusSearch 0.05, 4 distance x 8 gradient bins) and the removal of
+ *   descriptors whose first bin is not finite (:676-682).  The PCL stages are restated from the published algorithms
+ *   ([recalled]): parity with PCL 1.7 itself is unpinned.
+ * Every neighbourhood is the sorted radius row of the library (d2 < float(r^2), ascending (d2, index), the point itself
+ * included), taken among the points that are still in the cloud at that stage:
+ *   intensity  0.299f r + 0.587f g + 0.114f b of the bytes, left to right;
+ *   normals    pcc_normals_radius at normal_radius, viewpoint origin; points without a finite normal leave (cloud2);
+ *   gradient   per point of cloud2, rows of cloud2 at gradient_radius: fewer than 3 entries -> NaN, else the least-squares
+ *              slope of the intensity about the row's centroid (3 x 3 normal equations, column-pivoted Householder QR)
+ *              projected onto the tangent plane of the point's normal;
+ *   RIFT       per point of cloud2, rows of cloud2 at rift_radius: every entry votes its gradient magnitude into the
+ *              (distance, angle) bins bilinearly, in row order; the histogram is divided by its 2-norm; a NaN gradient
+ *              anywhere in the row makes the histogram NaN (PCL's behaviour); those leave.
+ * rgb: PCL's packed colour word of point i (bytes b, g, r, a from the low byte: offset 16 of pcl::PointXYZRGB) at
+ *   rgb + i * rgb_stride_bytes, memory space `mem`, 4-byte aligned, one per point of the indexed cloud.
+ * out_histograms[n][32] (word g_bin * 4 + d_bin, as pcl::Histogram<32> holds it) and out_point_index[n] (the ORIGINAL index
+ *   of every kept descriptor, ascending -- PCL does not return it), memory space `mem`, sized by the caller for all n points
+ *   of the indexed cloud; the first *n_out (host) rows are written.
+ * Only nr_distance_bins = 4, nr_gradient_bins = 8 is built: anything else is PCC_ERR_UNSUPPORTED.  Null arguments, radii
+ * that are not positive and finite, a bad stride or memory space are refused before any device is touched. */
+int pcc_rift_descriptors(pcc_index *index, const void *rgb, size_t rgb_stride_bytes, int mem, double normal_radius,
+                         double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins,
+                         float *out_histograms, int32_t *out_point_index, size_t *n_out);
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);

@@ -3,6 +3,7 @@
 // no CPU compute fallback: without a HIP device every entry point fails with
 // PCC_ERR_DEVICE.
 #include "pcc_internal.hpp"
+#include "rift_math.hpp"
 #include <atomic>
 #include "rigid_solve.hpp"
 #include "host_pipe.hpp"
@@ -52,6 +53,7 @@ static bool option_in_range(int option, double value) {
         case PCC_OPT_XCD_RUN: return value >= 1 && value <= 4096;
         case PCC_OPT_FUSE_PARAMS: return value >= 0 && value <= 3;
         case PCC_OPT_KNN_RUN: return value >= 1 && value <= 64;
+        case PCC_OPT_RIFT_LAYOUT: return value == 0 || value == 1;
         case PCC_OPT_HOST_PIPE: case PCC_OPT_SCAN_CHAINED: return value == 0 || value == 1;
         default: return value == 0 || value == 1;
     }
@@ -82,6 +84,7 @@ static double* option_slot(Options& o, int option, int** as_int) {
         case PCC_OPT_HOST_PIPE: *as_int = &o.host_pipe; return nullptr;
         case PCC_OPT_SCAN_CHAINED: *as_int = &o.scan_chained; return nullptr;
         case PCC_OPT_KNN_RUN: *as_int = &o.knn_run; return nullptr;
+        case PCC_OPT_RIFT_LAYOUT: *as_int = &o.rift_layout; return nullptr;
         default: return nullptr;
     }
 }
@@ -98,7 +101,8 @@ void Options::from_env() {
         {"PCC_ICP_SORTED", PCC_OPT_ICP_SORTED}, {"PCC_OVERLAP_PREP", PCC_OPT_OVERLAP_PREP},
         {"PCC_GRID_AXES", PCC_OPT_GRID_AXES}, {"PCC_XCD_RUN", PCC_OPT_XCD_RUN},
         {"PCC_FUSE_PARAMS", PCC_OPT_FUSE_PARAMS}, {"PCC_HOST_PIPE", PCC_OPT_HOST_PIPE},
-        {"PCC_SCAN_CHAINED", PCC_OPT_SCAN_CHAINED}, {"PCC_KNN_RUN", PCC_OPT_KNN_RUN}};
+        {"PCC_SCAN_CHAINED", PCC_OPT_SCAN_CHAINED}, {"PCC_KNN_RUN", PCC_OPT_KNN_RUN},
+        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}};
     for (const auto& v : vars) {
         const char* txt = getenv(v.name);
         if (!txt || !*txt) continue;
@@ -556,6 +560,7 @@ int pcc_index_destroy(pcc_index* ix) {
     ix->host_c.release();
     if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
     match_batch_release(ix);
+    rift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
     if (ix->h_grid) (void)hipHostFree(ix->h_grid);
     if (ix->edge_ev) (void)hipEventDestroy(ix->edge_ev);
@@ -1195,6 +1200,41 @@ int pcc_normals_radius(pcc_index* ix, double radius, const float viewpoint[3], i
     PCC_TRY(normals_radius(ix, radius, viewpoint ? viewpoint : origin, rn.dev));
     ev_mark(ix, EV_CALL1);
     return finish(ix, mem, rn);
+}
+
+int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int mem, double normal_radius, double gradient_radius,
+                         double rift_radius, int nr_distance_bins, int nr_gradient_bins, float* out_hist, int32_t* out_index,
+                         size_t* n_out) {
+    // the arguments first: host arithmetic, refused before any device is looked at
+    PCC_TRY(check_mem(mem));
+    if (!rgb || !out_hist || !out_index || !n_out) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (rgb_stride < 4 || rgb_stride % 4 || reinterpret_cast<uintptr_t>(rgb) % 4) {
+        set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
+        return PCC_ERR_INVALID;
+    }
+    for (double r : {normal_radius, gradient_radius, rift_radius})
+        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
+    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
+        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    PCC_ENTER(ix);
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const size_t n = ix->n_orig;
+    if (!ix->rift) ix->rift = new RiftScratch();
+    const unsigned char* drgb = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->rift->rgb, &drgb));
+    Out<float> rh;
+    Out<int32_t> ri;
+    PCC_TRY(rh.stage(out_hist, n * RIFT_BINS, mem, ix->rift->out_hist));
+    PCC_TRY(ri.stage(out_index, n, mem, ix->rift->out_index));
+    PCC_TRY(rift_descriptors(ix, drgb, rgb_stride, normal_radius, gradient_radius, rift_radius, rh.dev, ri.dev, n_out));
+    rh.count = *n_out * RIFT_BINS;  // (only the rows that were written travel)
+    ri.count = *n_out;
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rh, ri);
 }
 
 int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, float smoothness,

@@ -1,4 +1,4 @@
-// libm_f32.hpp -- glibc 2.35's sinf / cosf / atan2f, restated so that the device evaluates what the host's libm does.
+// libm_f32.hpp -- glibc 2.35's sinf / cosf / atan2f (and acosf, for the RIFT histogram: see lm_acosf), restated so that the device evaluates what the host's libm does.
 //
 // pcl::eigen33 (NormalEstimation, the RANSAC refit; reference src/segmentation.cpp:232-241, 79-117) takes the roots of the
 // characteristic cubic in closed form: theta = atan2f(sqrtf(-q), half_b) / 3, then cosf(theta), sinf(theta).  The smallest
@@ -195,6 +195,47 @@ __host__ __device__ inline float lm_atan2f(float y, float x) {
     if (m == 0) return z;
     if (m == 1) return lm_float(lm_bits(z) ^ 0x80000000u);
     return m == 2 ? pi - (z - pi_lo) : (z - pi_lo) - pi;
+}
+
+// ---- acosf (fdlibm, float arithmetic) ---------------------------------------------------------------------------------
+// sysdeps/ieee754/flt-32/e_acosf.c: three intervals (|x| < 0.5, x <= -0.5, x >= 0.5), one rational approximation
+// R(z) = z P(z) / Q(z) of (asin(x) - x) / x^3, a correctly rounded sqrtf and float arithmetic in the source's order; one
+// build for all CPUs.  The caller is the RIFT histogram (rift_math.hpp): the angle between a gradient and the direction to
+// a neighbour, where one ulp moves a share of a vote from one angular bin to the next.
+__host__ __device__ inline float lm_acosf(float x) {
+    const float one = 1.0f, pi = lm_float(0x40490fdau), pio2_hi = lm_float(0x3fc90fdau), pio2_lo = lm_float(0x33a22168u),
+                pS0 = lm_float(0x3e2aaaabu), pS1 = lm_float(0xbea6b090u), pS2 = lm_float(0x3e4e0aa8u), pS3 = lm_float(0xbd241146u),
+                pS4 = lm_float(0x3a4f7f04u), pS5 = lm_float(0x3811ef08u), qS1 = lm_float(0xc019d139u), qS2 = lm_float(0x4001572du),
+                qS3 = lm_float(0xbf303361u), qS4 = lm_float(0x3d9dc62eu);
+    const int32_t hx = (int32_t)lm_bits(x), ix = hx & 0x7fffffff;
+    if (ix == 0x3f800000) return hx > 0 ? 0.0f : pi + 2.0f * pio2_lo;  // |x| = 1
+    if (ix > 0x3f800000) return (x - x) / (x - x);                      // |x| > 1 or NaN
+    if (ix < 0x3f000000) {                                              // |x| < 0.5
+        if (ix <= 0x32800000) return pio2_hi + pio2_lo;                // |x| <= 2^-26
+        const float z = x * x;
+        const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const float r = p / q;
+        return pio2_hi - (x - (pio2_lo - x * r));
+    }
+    if (hx < 0) {  // x <= -0.5
+        const float z = (one + x) * 0.5f;
+        const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+        const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+        const float s = sqrtf(z);
+        const float r = p / q;
+        const float w = r * s - pio2_lo;
+        return pi - 2.0f * (s + w);
+    }
+    const float z = (one - x) * 0.5f;  // x >= 0.5
+    const float s = sqrtf(z);
+    const float df = lm_float(lm_bits(s) & 0xfffff000u);
+    const float c = (z - df * df) / (s + df);
+    const float p = z * (pS0 + z * (pS1 + z * (pS2 + z * (pS3 + z * (pS4 + z * pS5)))));
+    const float q = one + z * (qS1 + z * (qS2 + z * (qS3 + z * qS4)));
+    const float r = p / q;
+    const float w = r * s + c;
+    return 2.0f * (df + w);
 }
 
 }  // namespace pcc

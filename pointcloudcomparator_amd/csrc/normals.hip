@@ -146,8 +146,8 @@ k_widen_offsets(const unsigned int* __restrict__ off32, unsigned int n_plus_1, i
 
 }  // namespace
 
-// NormalEstimation with setRadiusSearch: self radius search (sorted rows, CSR) + the plane fit per row
-int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out) {
+// the sorted self radius rows of the indexed cloud as a CSR: counts, exclusive scan, sorted fill
+int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) {
     hipStream_t s = ix->stream;
     const size_t n = ix->n_orig;
     const float r2 = (float)(radius * radius);
@@ -172,11 +172,28 @@ int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out)
     PCC_TRY(ix->out_packed.reserve((size_t)(total ? total : 1) * sizeof(unsigned long long)));
     auto* keys = ix->out_packed.as<unsigned long long>();
     if (total) PCC_TRY(grid_radius(ix, self, n, (float)radius, r2, nullptr, off64, keys, 1, (size_t)total));
+    *keys_out = keys;
+    *offsets_out = off32;
+    return PCC_OK;
+}
+
+int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out) {
+    hipStream_t s = ix->stream;
+    const size_t n = ix->n_orig;
+    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     PCC_HIP(hipMemsetAsync(out, 0xff, n * sizeof(float4), s));
-    hipLaunchKernelGGL(k_normals_csr, dim3(blocks), dim3(256), 0, s, keys, off32, self, ix->cell_refs.as<float4>(),
+    hipLaunchKernelGGL(k_normals_csr, dim3(blocks), dim3(256), 0, s, keys, offsets, ix->refs.as<float4>(), ix->cell_refs.as<float4>(),
                        ix->d_grid.as<GridDev>(), vp[0], vp[1], vp[2], out);
     PCC_HIP(hipGetLastError());
     return PCC_OK;
+}
+
+// NormalEstimation with setRadiusSearch: self radius search (sorted rows, CSR) + the plane fit per row
+int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out) {
+    const unsigned long long* keys = nullptr;
+    const unsigned int* off32 = nullptr;
+    PCC_TRY(radius_csr(ix, radius, &keys, &off32));
+    return launch_normals_csr(ix, keys, off32, vp, out);
 }
 
 int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs,

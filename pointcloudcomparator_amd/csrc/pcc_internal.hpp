@@ -164,6 +164,7 @@ struct Options {
     int scan_chained = 1;           // PCC_OPT_SCAN_CHAINED: exclusive scans of up to 512 x 2048 counters in ONE launch (workgroups pass their totals on as
                                     // tagged 64-bit atomics and wait for the workgroups in front of them: relies on in-order dispatch); 0 = the two-launch
                                     // form (block totals, then apply), which waits for nothing
+    int rift_layout = 1;            // PCC_OPT_RIFT_LAYOUT: RIFT histogram kernel, 1 = 32 lanes per row (votes by all lanes, bins by owner lanes), 0 = one lane per row
     int host_pipe = 1;              // PCC_OPT_HOST_PIPE: clouds / results of 8 MB and more in pageable HOST memory cross PCIe through the library's own pinned
                                     // chunk buffers, staged by a few host threads (x, y, z only when the stride is 24 bytes or more); 0 = one
                                     // hipMemcpyAsync of the raw array (rounds 1-5)
@@ -251,6 +252,17 @@ static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) 
 
 }  // namespace pcc
 
+namespace pcc {
+// rift.hip: what pcc_rift_descriptors keeps between its stages (made at the first call on a handle).  Buffers of their own:
+// the radius searches in between use the handle's shared scratch.
+struct RiftScratch {
+    DevBuf rgb;                  // the caller's colour words, staged (host memory)
+    DevBuf normals, inten;       // float4[n] plane fit; float[n] intensity, NaN outside cloud2
+    DevBuf grad;                 // float4[n]: intensity gradient, w = 1 for the points of cloud2
+    DevBuf hist, keep, scan_tmp; // float[n][32] before the last compaction; its flags / positions
+    DevBuf out_hist, out_index;  // results staged for a caller in host memory
+};
+}  // namespace pcc
 namespace pcc { struct MatchBatchScratch; }  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
 namespace pcc { struct HostPipe; }  // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 #define PCC_EV_SLOTS 64
@@ -343,6 +355,7 @@ struct pcc_index {
     pcc::HostBuf host_a, host_b;  // large pinned read-back buffers
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
+    pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -502,6 +515,14 @@ int sac_plane(pcc_index* ix, const float4* pts_dev, size_t n, const char* host_b
 int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs,
                    const GridDev* gd, size_t n, int K, const float vp[3], float4* out);
 int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out);
+// the two halves of normals_radius: the sorted self radius rows of the indexed cloud as a CSR (keys: d2 bits << 32 | point
+// index; offsets[n + 1]; both stay valid until the next radius search on the handle), and the plane fit over such rows
+int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys, const unsigned int** offsets);
+int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out);
+// rift.hip: the RIFT descriptor pipeline on device arrays (ix->rift made by the caller); *n_out on the host
+int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
+                     double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out);
+void rift_release(pcc_index* ix);  // frees ix->rift
 int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const float4* normals, int K, float smoothness,
                         float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels_dev,
                         int32_t* n_clusters);

@@ -183,3 +183,42 @@ def descriptor_pairs(sizes, family: str, seed: int):
         assert len(firsts[c1]) == n1
         pairs.append((firsts[c1], descriptor_queries(firsts[c1], n2, family, seed * 100003 + 2 * p + 1)))
     return pairs
+
+
+# ---- coloured patches for the RIFT descriptor pipeline (reference src/comparator.cpp:590-684) -------------------------------
+def _normal24(seed: int, ctr: np.ndarray) -> np.ndarray:
+    """standard normal deviates from two counter-based uniforms (Box-Muller)"""
+    u1 = np.maximum(uniform24(seed, ctr * np.uint64(2)), 2.0 ** -24)
+    u2 = uniform24(seed, ctr * np.uint64(2) + np.uint64(1))
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def rift_cloud(n: int, seed: int, flat: float = 0.0, extent: float = 0.12):
+    """A cluster-sized coloured patch dense enough for 3 cm neighbourhoods: (points (n, 3) float32, rgb (n, 3) uint8).
+    Points are uniform in a cube of side `extent` (metres); flat > 0 squeezes z to extent / 2 + flat * N(0, 1) (a slab, or
+    with flat ~ 1e-5 a near-plane).  The colour is a smooth function of position plus per-channel noise (sigma 8 levels), so
+    that the intensity gradient is neither zero nor noise alone."""
+    i = np.arange(n, dtype=np.uint64)
+    p = np.stack([uniform24(seed, i * np.uint64(8) + np.uint64(j)) for j in range(3)], -1) * extent
+    if flat:
+        p[:, 2] = 0.5 * extent + flat * _normal24(seed ^ 0xF1A7, i)
+    p = np.ascontiguousarray(p.astype(np.float32))
+    f = 128.0 + 100.0 * np.sin(40.0 * p[:, 0].astype(np.float64)) * np.cos(30.0 * p[:, 1] + 20.0 * p[:, 2].astype(np.float64))
+    noise = [8.0 * _normal24(seed ^ (0xC010 + c), i) for c in range(3)]
+    rgb = np.stack([f + noise[0], 0.8 * f + noise[1], 255.0 - f + noise[2]], -1)
+    return p, np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+def pack_rgb(rgb: np.ndarray) -> np.ndarray:
+    """(n, 3) uint8 r, g, b -> (n,) uint32 in PCL's packed layout (bytes b, g, r, a from the low byte)"""
+    c = rgb.astype(np.uint32)
+    return c[:, 2] | (c[:, 1] << np.uint32(8)) | (c[:, 0] << np.uint32(16))
+
+
+def xyzrgb_records(points: np.ndarray, rgb: np.ndarray) -> np.ndarray:
+    """(n, 8) float32 laid out as pcl::PointXYZRGB (32 B: x, y, z, 1, colour word, padding) with the given colours"""
+    out = np.zeros((len(points), 8), dtype=np.float32)
+    out[:, :3] = points
+    out[:, 3] = 1.0
+    out[:, 4] = pack_rgb(rgb).view(np.float32)
+    return out
