@@ -179,9 +179,7 @@ void HostBuf::release() {
 // Stage a caller cloud (host or device AoS) as packed float4 on the device.
 // host: the raw array (or, for large pageable clouds, its x / y / z alone: host_pipe.hpp) to the device, then the pack kernel.
 static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
-                        DevBuf& raw, float4* packed, float* blk_stats = nullptr, int* n_blocks = nullptr,
-                        unsigned int* zero_word = nullptr, float4* seeds = nullptr, unsigned long long* invalid_keys = nullptr,
-                        unsigned int* cells = nullptr, const GridDev* gd = nullptr, const PackGrid* grid = nullptr) {
+                        DevBuf& raw, float4* packed, const PackExtras& px) {
     const void* src = pts;
     if (mem == PCC_MEM_HOST && n > 0) {
         const size_t bytes = (n - 1) * stride + 12;
@@ -201,12 +199,12 @@ static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride,
             // 8 MB the runtime's own staging is as good: 18 381 descriptors 244 us a call against 277 through the pinned buffer.)
             if (!ix->pipe) ix->pipe = new HostPipe();
             PCC_TRY(ix->pipe->init());
-            const int slot = blk_stats ? 0 : 1;
+            const int slot = px.indexed_cloud ? 0 : 1;
             PCC_HIP(hipEventSynchronize(ix->pipe->ev[slot]));  // (whoever read this buffer last has finished: nearly always true already)
             memcpy(ix->pipe->buf[slot].p, pts, bytes);
             src = ix->pipe->buf[slot].p;
             if (slot == 0) { ix->small_raw_n = n; ix->small_raw_stride = stride; }  // (the indexed cloud's records stay there: small_tie_replay)
-            PCC_TRY(launch_pack(ix->stream, src, n, stride, packed, blk_stats, n_blocks, zero_word, seeds, invalid_keys, cells, gd, grid));
+            PCC_TRY(launch_pack(ix->stream, src, n, stride, packed, px));
             PCC_HIP(hipEventRecord(ix->pipe->ev[slot], ix->stream));
             return PCC_OK;
         } else {
@@ -215,7 +213,7 @@ static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride,
         }
         src = raw.p;
     }
-    return launch_pack(ix->stream, src, n, stride, packed, blk_stats, n_blocks, zero_word, seeds, invalid_keys, cells, gd, grid);
+    return launch_pack(ix->stream, src, n, stride, packed, px);
 }
 
 int check_mem(int mem) {
@@ -231,25 +229,27 @@ int check_points(const void* pts, size_t n, size_t stride, int mem) {
     return PCC_OK;
 }
 
-// queries -> ix->q_packed (float4, w < 0 marks a non-finite query)
-int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem) {
+// queries -> ix->q_packed (float4, w < 0 marks a non-finite query).  search: the k = 1 search the caller runs next, if it does
+int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, Nn1Call* search) {
     PCC_TRY(ix->q_packed.reserve(nq * sizeof(float4)));
     PCC_TRY(ix->out_packed.reserve(nq * sizeof(unsigned long long)));
     // the pack kernel also zeroes the GRID engine's search counters (clear_search_counters) and presets the result key of
     // every non-finite query to "nothing found"
-    ix->fb_zeroed = true;
+    PackExtras px;
+    px.zero_word = &ix->words()->fb_count;
+    px.invalid_keys = ix->out_packed.as<unsigned long long>();
     // clouds that will take the three-level sort: the pack kernel also writes every query's grid cell (4 B), which level 1 of
     // the sort then reads instead of the points (pcc_index::q_cells; valid until the sort has used it)
-    unsigned int* cells = nullptr;
     ix->q_cells_n = 0;
     if (ix->engine == PCC_ENGINE_GRID && ix->has_grid && nq >= (size_t)ix->opt.sort_mp_min_q) {
         PCC_TRY(ix->q_cells.reserve(nq * sizeof(unsigned int) + 64));
-        cells = ix->q_cells.as<unsigned int>();
+        px.cells = ix->q_cells.as<unsigned int>();
+        px.gd = ix->d_grid.as<GridDev>();
         ix->q_cells_n = nq;
     }
-    return stage_points(ix, q, nq, stride, mem, ix->q_raw, ix->q_packed.as<float4>(), nullptr, nullptr,
-                        &ix->words()->fb_count, nullptr, ix->out_packed.as<unsigned long long>(), cells,
-                        cells ? ix->d_grid.as<GridDev>() : nullptr);
+    PCC_TRY(stage_points(ix, q, nq, stride, mem, ix->q_raw, ix->q_packed.as<float4>(), px));
+    if (search && nq > 0) search->counters_cleared = true;  // (px.zero_word; callers that run no k = 1 search pass none)
+    return PCC_OK;
 }
 
 // ---- caller arrays that are not point clouds (PCC_MEM_HOST or PCC_MEM_DEVICE) -----------------------------------------------
@@ -340,7 +340,6 @@ static int small_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, boo
     PCC_TRY(ix->pipe->init());
     PCC_HIP(hipEventSynchronize(ix->pipe->ev[1]));  // (whoever read the query buffer last has finished)
     memcpy(ix->pipe->buf[1].p, q, (nq - 1) * stride + 12);
-    ix->fb_zeroed = false;
     ix->q_cells_n = 0;
     ix->stats[0] = 0;
     ix->stats[1] = nq;
@@ -396,11 +395,11 @@ static int unpack_pinned(pcc_index* ix, size_t nq, bool want_idx, bool want_d2, 
     return PCC_OK;
 }
 
-int nn1_packed(pcc_index* ix, size_t nq) {
+int nn1_packed(pcc_index* ix, size_t nq, Nn1Call& call) {
     PCC_TRY(ix->out_packed.reserve(nq * sizeof(unsigned long long)));
     auto* out = ix->out_packed.as<unsigned long long>();
     // GRID: every valid query's key is written by the search kernel itself (no 8 MB memset)
-    if (ix->engine == PCC_ENGINE_GRID) return grid_nn1(ix, ix->q_packed.as<float4>(), nq, out);
+    if (ix->engine == PCC_ENGINE_GRID) return grid_nn1(ix, ix->q_packed.as<float4>(), nq, out, call);
     PCC_HIP(hipMemsetAsync(out, 0xff, nq * sizeof(unsigned long long), ix->stream));
     ix->stats[0] = 0;
     ix->stats[1] = nq;
@@ -429,12 +428,15 @@ static int set_input_impl(pcc_index* ix, const void* pts, size_t n, size_t strid
     PCC_TRY(ix->refs.reserve(n * sizeof(float4)));
     int nblk = 0;
     PCC_TRY(ix->seeds.reserve(((n + PCC_SEED_STRIDE - 1) / PCC_SEED_STRIDE) * sizeof(float4)));  // the pack kernel also emits the seed subset
-    PackGrid pg{};
+    PackExtras px;  // the indexed cloud: statistics for the grid, the seed subset
+    px.indexed_cloud = true;
+    px.blk_stats = ix->blk_stats.as<float>();
+    px.n_blocks = &nblk;
+    px.seeds = ix->seeds.as<float4>();
     // (small clouds: a launch is what a call costs there, and the fence the fused form pays is nothing over a handful of rows)
     const bool fused = (ix->opt.fuse_params & 1) != 0 || (ix->opt.host_pipe && n <= SMALL_FUSED_POINTS);
-    if (fused) PCC_TRY(grid_params_fused(ix, &pg));
-    PCC_TRY(stage_points(ix, pts, n, stride, mem, ix->q_raw, ix->refs.as<float4>(), ix->blk_stats.as<float>(), &nblk,
-                         nullptr, ix->seeds.as<float4>(), nullptr, nullptr, nullptr, fused ? &pg : nullptr));
+    if (fused) PCC_TRY(grid_params_fused(ix, &px.grid));
+    PCC_TRY(stage_points(ix, pts, n, stride, mem, ix->q_raw, ix->refs.as<float4>(), px));
     if (!fused) PCC_TRY(grid_params(ix, ix->blk_stats.as<float>(), nblk));
     ix->engine = resolve_engine(ix->engine_requested, n);
     // everything a query needs to be packed and sorted exists from here on (PrepOverlap below)
@@ -452,7 +454,6 @@ static int set_input_impl(pcc_index* ix, const void* pts, size_t n, size_t strid
 int set_input(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem) {
     ix->n_valid = 0;
     ix->has_grid = false;
-    ix->order_valid = false;
     ix->flann_valid = false;
     ix->small_raw_n = 0;
     ix->occ_valid = false;
@@ -488,7 +489,7 @@ struct PrepOverlap {
     // ordering pcc_nn.h promises -- and the side stream, which waits for the build's k_grid_params only, would read them early.
     static bool wanted(const pcc_index* ix, size_t nq) {
         return ix->opt.overlap_prep && ix->stream == ix->own_stream && ix->after_build && ix->params_ev_set && ix->engine == PCC_ENGINE_GRID && ix->has_grid &&
-               !ix->keep_order && (nq >= min_queries || ix->opt.overlap_prep == 2);  // (2: whatever the size -- tests, fuzz)
+               (nq >= min_queries || ix->opt.overlap_prep == 2);  // (2: whatever the size -- tests, fuzz)
     }
     explicit PrepOverlap(pcc_index* i) : ix(i) {}
     void swap_scratch() {
@@ -889,17 +890,18 @@ int pcc_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
     if (small_call(ix, nq, stride, mem)) {
         PCC_TRY(small_nn1(ix, q, nq, stride, idx != nullptr, d2 != nullptr));
     } else {
+        Nn1Call call;
         {
             PrepOverlap beside(ix);
             if (PrepOverlap::wanted(ix, nq)) PCC_TRY(beside.begin());
-            PCC_TRY(stage_queries(ix, q, nq, stride, mem));
-            if (beside.on) {
-                PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), nq, &ix->pre_order, &ix->pre_nsorted));
-                ix->pre_order_nq = nq;
+            PCC_TRY(stage_queries(ix, q, nq, stride, mem, &call));
+            if (beside.on) {  // (the search is given the order sorted here, beside the build)
+                PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), nq, &call.order, &call.n_sorted));
+                call.order_given = true; call.order_nq = nq;
                 PCC_TRY(beside.end());
             }
         }
-        PCC_TRY(nn1_packed(ix, nq));
+        PCC_TRY(nn1_packed(ix, nq, call));
         if (ix->tie_mode == PCC_TIES_FLANN)
             PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), nq, mem == PCC_MEM_HOST));
         // small host results: straight into pinned memory (unpack_pinned)
@@ -1425,8 +1427,9 @@ int pcc_icp_step_about(pcc_index* ix, const void* src, size_t n, size_t stride, 
     if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    PCC_TRY(stage_queries(ix, src, n, stride, mem));
-    PCC_TRY(nn1_packed(ix, n));
+    Nn1Call call;
+    PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
+    PCC_TRY(nn1_packed(ix, n, call));
     const double* center_dev = nullptr;
     if (center) {  // the sums are taken about it (device copy behind the ICP loop state)
         PCC_TRY(ix->icp_state.reserve(sizeof(IcpState) + (3 + 17) * sizeof(double)));
@@ -1496,6 +1499,8 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
     double prev_mse = 1.79769313486231570e308;
     double* center_dev = nullptr;
     bool sorted = false;
+    Nn1Call call;  // every search below is an ICP pass: they share the first pass's lane order (Nn1Call::order_given)
+    call.icp_pass = true;
     // Everything that can fail on ONE rank alone -- argument checks, staging, allocations -- comes before the first
     // collective and ends in a status the ranks agree on (hooks->agree: all-reduce MIN of one word), so a rank that
     // cannot go on takes the others out with it instead of leaving them in the broadcast below (comm.hip).
@@ -1510,7 +1515,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
         if (n == 0 && hooks) { set_error("sharded ICP: every rank needs a non-empty shard"); return PCC_ERR_INVALID; }
         if (n == 0) return PCC_OK;
         // the source stays resident: q_packed is the moving cloud, icp_src keeps the input
-        PCC_TRY(stage_queries(ix, src, n, stride, mem));
+        PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
         PCC_TRY(ix->icp_src.reserve(n * sizeof(float4)));
         // Round 5: the loop's working set in the target grid's CELL order.  Nothing of the loop leaves per point -- T, fitness,
         // counts -- so the permutation that a search pays per call (queries gathered through the sort order, keys scattered
@@ -1544,17 +1549,10 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
     const int warm_env = ix->opt.icp_warm;         // 0: every pass from scratch (measurements)
     const int loop_env = hooks ? 1 : ix->opt.icp_device_loop;  // 0: the host-driven loop (kept for comparison: same bits)
     double* sums_dev = center_dev + 3;  // (sharded: the 17 sums of a pass, all-reduced in place)
-    struct KeepOrder {  // the passes below share the first pass's lane order (see pcc_index::keep_order)
-        pcc_index* ix;
-        explicit KeepOrder(pcc_index* i) : ix(i) { ix->keep_order = true; ix->order_valid = false; ix->warm_start = false; }
-        ~KeepOrder() { ix->keep_order = false; ix->order_valid = false; ix->warm_start = false; ix->pre_transform = nullptr; }
-    } keep_order_guard(ix);
     const bool fold = sorted && loop_env && grid_nn1_takes_transform(ix);  // the pass's transform applied by the next pass's search
     if (sorted) {  // (the passes take the identity as their order; the count of valid points sits in a word of its own)
-        ix->order_valid = true;
-        ix->order_nq = n;
-        ix->order_ptr = nullptr;
-        ix->order_nsorted = &ix->words()->icp_nsorted;
+        call.order_given = true; call.order_nq = n;
+        call.order = nullptr; call.n_sorted = &ix->words()->icp_nsorted;
     }
     if (loop_env) {
         // The loop lives on the device: every pass is NN -> sums -> k_icp_solve (one workgroup: the transform, the running
@@ -1581,10 +1579,10 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
                 ev_mark(ix, EV_CALL0);
                 // (cell-ordered loop: the search applies the previous pass's matrix -- the identity before the first -- to the
                 // queries it reads and writes them back; no transform kernel, grid.hip k_grid_nn1_flat2)
-                ix->pre_transform = fold ? st->Ti : nullptr;
-                PCC_TRY(nn1_packed(ix, n));  // determineCorrespondences: one NN per source point
-                ix->pre_transform = nullptr;
-                ix->warm_start = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
+                call.pre_transform = fold ? st->Ti : nullptr;
+                PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
+                call.pre_transform = nullptr;
+                call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
                 int nb = 0;
                 unsigned int* zw = ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr;
                 // (one GPU: the sums kernel's last workgroup solves the pass itself -- DevWords::icp_ticket is its ticket word;
@@ -1604,7 +1602,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
                 // (the transform -- or, when the next search applies it itself, the solver -- also zeroes the counters of the next
                 // pass's search)
                 if (!fold) PCC_TRY(launch_transform(ix->stream, st->Ti, nullptr, ix->q_packed.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4), zw));
-                if (zw && n > 0) ix->fb_zeroed = true;
+                call.counters_cleared = zw != nullptr;
                 ev_mark(ix, EV_CALL1);
             }
             PCC_HIP(hipMemcpyAsync(&h1, ix->icp_state.p, sizeof(h1), hipMemcpyDeviceToHost, ix->stream));
@@ -1619,8 +1617,8 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
     while (it < max_iter) {
         ev_next(ix);  // instrumentation: every pass is one "call" (NN kernel, far/fallback, whole pass)
         ev_mark(ix, EV_CALL0);
-        PCC_TRY(nn1_packed(ix, n));  // determineCorrespondences: one NN per source point
-        ix->warm_start = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
+        PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
+        call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
         double sums[17];
         PCC_TRY(icp_reduce(ix, n, sums, center_dev));
         if (!have_center) {
@@ -1649,7 +1647,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
         PCC_TRY(launch_copy_w(ix->stream, ix->icp_src.as<float4>(), ix->q_packed.as<float4>(), n));
         ev_next(ix);
         ev_mark(ix, EV_CALL0);
-        PCC_TRY(nn1_packed(ix, n));
+        PCC_TRY(nn1_packed(ix, n, call));
         double sums[17];
         if (hooks) {  // sum of d2 and count over ALL shards
             int nb = 0;
@@ -1683,8 +1681,9 @@ int pcc_match_knn(pcc_index* ix, const void* des2, size_t n2, size_t stride, int
     if (small_call(ix, n2, stride, mem)) {
         PCC_TRY(small_nn1(ix, des2, n2, stride, true, true));
     } else {
-        PCC_TRY(stage_queries(ix, des2, n2, stride, mem));
-        PCC_TRY(nn1_packed(ix, n2));
+        Nn1Call call;
+        PCC_TRY(stage_queries(ix, des2, n2, stride, mem, &call));
+        PCC_TRY(nn1_packed(ix, n2, call));
         if (ix->tie_mode == PCC_TIES_FLANN) PCC_TRY(resolve_ties_flann(ix, ix->q_packed.as<float4>(), ix->out_packed.as<unsigned long long>(), n2, true));
         PCC_TRY(unpack_pinned(ix, n2, true, true, false));
     }

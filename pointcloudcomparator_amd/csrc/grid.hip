@@ -564,7 +564,7 @@ k_grid_nn1_flat2(const float4* __restrict__ cell_refs, const unsigned int* __res
         qv = q[qi];
     }
     const bool active = __float_as_int(qv.w) >= 0;
-    // ICP passes in cell order (pcc_index::pre_transform): the previous pass's rigid motion is applied HERE, to the query the lane
+    // ICP passes in cell order (Nn1Call::pre_transform): the previous pass's rigid motion is applied HERE, to the query the lane
     // has just read, and written back for the kernels that follow (open lanes, far walk, sums) -- pcl::transformPointCloud's
     // rounding, ((m0 x + m1 y) + m2 z) + m3, exactly as k_transform does it; the pass then has no transform kernel of its own
     if (pre_T && active) {
@@ -994,34 +994,25 @@ int grid_sort_queries(pcc_index* ix, const float4* q, size_t nq, unsigned int** 
 // can the k = 1 search of this handle apply the ICP loop's transform itself (flat kernel form)?
 bool grid_nn1_takes_transform(const pcc_index* ix) { return ix->opt.nn1_kernel != 0 && ix->n_orig <= F2_MAX_REFS; }
 
-int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out) {
+int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out, Nn1Call& call) {
     hipStream_t s = ix->stream;
     const unsigned int n = (unsigned int)nq;
     PCC_TRY(ix->scratch_d.reserve(((size_t)n * 2 + 128) * sizeof(unsigned int) + 256));
     unsigned int* fb_list = ix->scratch_d.as<unsigned int>();
     unsigned int* fb_count = &ix->words()->fb_count;
-    // zeroed by the query pack kernel of this call; searches that re-use packed queries (the ICP
-    // loop transforms them in place) have no pack and zero it here
-    if (!ix->fb_zeroed) {  // fallback and far counters, the sharded open-lane counters
+    // (no kernel in front has cleared them -- Nn1Call::counters_cleared: the later passes of the host-driven ICP loop)
+    if (!call.counters_cleared) {  // fallback and far counters, the sharded open-lane counters
         PCC_HIP(hipMemsetAsync(fb_count, 0, sizeof(DevWords::fb_count) + sizeof(DevWords::far_count), s));
         PCC_HIP(hipMemsetAsync(ix->words()->open, 0, sizeof(DevWords::open), s));
     }
-    ix->fb_zeroed = false;
-    unsigned int *order = nullptr, *n_sorted = nullptr;
-    if (ix->pre_order && ix->pre_order_nq == nq && !ix->keep_order) {
-        order = ix->pre_order;  // sorted beside the index build by the caller (api.hip: PrepOverlap), for this search only
-        n_sorted = ix->pre_nsorted;
-        ix->pre_order = nullptr;
-    } else if (ix->keep_order && ix->order_valid && ix->order_nq == nq) {
-        order = ix->order_ptr;  // (any permutation of the valid queries is correct; this one is still coherent)
-        n_sorted = ix->order_nsorted;
-    } else {
-        PCC_TRY(grid_sort_queries(ix, q, nq, &order, &n_sorted));
-        ix->order_valid = ix->keep_order;
-        ix->order_nq = nq;
-        ix->order_ptr = order;
-        ix->order_nsorted = n_sorted;
+    call.counters_cleared = false;
+    // (a given order: sorted beside the index build -- api.hip: PrepOverlap -- or an ICP loop's, see Nn1Call)
+    if (!(call.order_given && call.order_nq == nq)) {
+        PCC_TRY(grid_sort_queries(ix, q, nq, &call.order, &call.n_sorted));
+        call.order_given = call.icp_pass;  // (reused by the later passes of an ICP loop only)
+        call.order_nq = nq;
     }
+    unsigned int *const order = call.order, *const n_sorted = call.n_sorted;
     ev_mark(ix, EV_MAIN0);
     const int BS = 256;  // 128 and 512 measured 9-12 % slower (fewer lanes to pack / longer wait at the barrier)
     // consecutive workgroups per XCD (see k_grid_nn1; PCC_OPT_XCD_RUN) -- at most a sixteenth of the launch, so that every XCD gets
@@ -1033,8 +1024,8 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
     // balls are several cells wide and the per-row chord arithmetic costs more than the rows it drops
     // (2M x 2M, 50 passes: 26.5 ms with the plain box, 29.1 ms with the ball; 10M x 10M sorted: 1047 vs 1030 us; again with the
     // open lanes in their own kernel, round 3: 19.5 vs 21.1 ms)
-    const bool ball_walk = !ix->keep_order;
-    const bool warm = ix->warm_start && ix->keep_order;  // out[] holds the previous pass's keys of the SAME queries (pcc_icp_align)
+    const bool ball_walk = !call.icp_pass;
+    const bool warm = call.warm && call.icp_pass;  // out[] holds the previous pass's keys of the SAME queries (pcc_icp_align)
     // PCC_OPT_NN1_KERNEL: 0 one lane per query (k_grid_nn1); 1 rows drained flat (k_grid_nn1_flat2), the lanes it leaves open
     // finished by k_nn1_open from 2M queries on and in place below (a compacted list of 100k queries is a few hundred
     // waves whose dependent loads nothing hides: 116 vs 99 us at 1M x 1M; 688 vs 792 us at 10M x 10M); 2 / 3 force the
@@ -1042,8 +1033,8 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
     int form = ix->opt.nn1_kernel;
     if (form != 0 && ix->n_orig > F2_MAX_REFS) form = 0;  // (the packed span record holds 26 bits of reference position)
     // (the folded transform needs the flat kernel and the identity order; the caller checks with grid_nn1_takes_transform)
-    const float* pre_T = form != 0 && order == nullptr ? ix->pre_transform : nullptr;
-    if (ix->pre_transform && !pre_T) { set_error("internal: pre_transform without the flat kernel / identity order"); return PCC_ERR_INVALID; }
+    const float* pre_T = form != 0 && order == nullptr ? call.pre_transform : nullptr;
+    if (call.pre_transform && !pre_T) { set_error("internal: Nn1Call::pre_transform without the flat kernel / identity order"); return PCC_ERR_INVALID; }
     if (form != 0) {
         const bool listed = form == 2 || (form == 1 && nq >= 2000000);
         const unsigned int dm = (unsigned int)ix->opt.nn1_dense_min;
@@ -1096,7 +1087,7 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out)
     if (seen > ix->last_fallback_seen) ix->last_fallback_seen = seen;
     const int far_mode = ix->opt.far_mode;  // -1 auto, 0 off, 1 on
     // (ICP passes always take it: their loop may be enqueued as a whole before the first count comes back)
-    const bool far = far_mode == 1 || (far_mode == -1 && (ix->last_fallback_seen >= 64 || ix->keep_order));
+    const bool far = far_mode == 1 || (far_mode == -1 && (ix->last_fallback_seen >= 64 || call.icp_pass));
     if (far) {
         unsigned int* fb2_list = fb_list + n + 64;
         unsigned int* fb2_count = &ix->words()->far_count;

@@ -122,26 +122,26 @@ k_pack(const char* __restrict__ aos, size_t n, size_t stride, float4* __restrict
     }
 }
 
-int launch_pack(hipStream_t s, const void* aos, size_t n, size_t stride, float4* out,
-                float* blk_stats, int* n_blocks, unsigned int* zero_word, float4* seeds, unsigned long long* invalid_keys,
-                unsigned int* cells, const GridDev* gd, const PackGrid* grid) {
-    if (n_blocks) *n_blocks = 0;
+int launch_pack(hipStream_t s, const void* aos, size_t n, size_t stride, float4* out, const PackExtras& x) {
+    if (x.n_blocks) *x.n_blocks = 0;
     if (n == 0) return PCC_OK;
     bool vec = (stride % 16 == 0) && ((reinterpret_cast<uintptr_t>(aos) & 15) == 0);
     int g = grid_for(n, 256, 2);
     if (g > PACK_MAX_BLOCKS) g = PACK_MAX_BLOCKS;
-    if (n_blocks) *n_blocks = g;
+    if (x.n_blocks) *x.n_blocks = g;
     const char* a = (const char*)aos;
-    bool st = blk_stats != nullptr;
+    bool st = x.blk_stats != nullptr;
     PackGrid pg{};
-    if (grid && st) {
-        pg = *grid;
+    if (x.grid.out && st) {
+        pg = x.grid;
         if (g < 128) pg.trim_k = 0;  // (trimming needs enough rows to tell an outlier from the scene: 128 pack workgroups = 64k points)
     }
-    if (vec && st) hipLaunchKernelGGL((k_pack<true, true>), dim3(g), dim3(256), 0, s, a, n, stride, out, blk_stats, zero_word, seeds, invalid_keys, cells, gd, pg);
-    else if (vec) hipLaunchKernelGGL((k_pack<true, false>), dim3(g), dim3(256), 0, s, a, n, stride, out, blk_stats, zero_word, seeds, invalid_keys, cells, gd, pg);
-    else if (st) hipLaunchKernelGGL((k_pack<false, true>), dim3(g), dim3(256), 0, s, a, n, stride, out, blk_stats, zero_word, seeds, invalid_keys, cells, gd, pg);
-    else hipLaunchKernelGGL((k_pack<false, false>), dim3(g), dim3(256), 0, s, a, n, stride, out, blk_stats, zero_word, seeds, invalid_keys, cells, gd, pg);
+#define PCC_PACK_ARGS a, n, stride, out, x.blk_stats, x.zero_word, x.seeds, x.invalid_keys, x.cells, x.gd, pg
+    if (vec && st) hipLaunchKernelGGL((k_pack<true, true>), dim3(g), dim3(256), 0, s, PCC_PACK_ARGS);
+    else if (vec) hipLaunchKernelGGL((k_pack<true, false>), dim3(g), dim3(256), 0, s, PCC_PACK_ARGS);
+    else if (st) hipLaunchKernelGGL((k_pack<false, true>), dim3(g), dim3(256), 0, s, PCC_PACK_ARGS);
+    else hipLaunchKernelGGL((k_pack<false, false>), dim3(g), dim3(256), 0, s, PCC_PACK_ARGS);
+#undef PCC_PACK_ARGS
     PCC_HIP(hipGetLastError());
     return PCC_OK;
 }

@@ -250,9 +250,6 @@ static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) 
                   offsetof(PinnedWords, vox_rows) >= offsetof(PinnedWords, vox_count) + 4,
               "PinnedWords: the asynchronously written words overlap");
 
-}  // namespace pcc
-
-namespace pcc {
 // rift.hip: what pcc_rift_descriptors keeps between its stages (made at the first call on a handle).  Buffers of their own:
 // the radius searches in between use the handle's shared scratch.
 struct RiftScratch {
@@ -262,9 +259,9 @@ struct RiftScratch {
     DevBuf hist, keep, scan_tmp; // float[n][32] before the last compaction; its flags / positions
     DevBuf out_hist, out_index;  // results staged for a caller in host memory
 };
+struct MatchBatchScratch;  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
+struct HostPipe;           // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 }  // namespace pcc
-namespace pcc { struct MatchBatchScratch; }  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
-namespace pcc { struct HostPipe; }  // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 #define PCC_EV_SLOTS 64
 #define PCC_EV_KINDS 10
 // The opaque handle of the C-ABI.
@@ -289,9 +286,6 @@ struct pcc_index {
         pcc::DevBuf a, b, c, e, mp_a, mp_b, mp_c, scan_flags;
         unsigned int scan_epoch = 0;
     } side;
-    unsigned int* pre_order = nullptr;    // a query order prepared ahead of grid_nn1 (this call only): order, count word, queries
-    unsigned int* pre_nsorted = nullptr;
-    size_t pre_order_nq = 0;
     size_t n_orig = 0;                 // points handed to pcc_index_create / set_input
     size_t n_valid = 0;                // finite points (PCL total_nr_points_); valid after sync_info()
     unsigned int nc_cap = 0;           // upper bound of the grid's cell count the host sizes launches with
@@ -312,16 +306,6 @@ struct pcc_index {
     pcc::DevBuf cell_refs;   // float4[n_valid], cell-sorted, .w = orig index
     pcc::DevBuf cell_start;  // uint32[ncells + 1]
     pcc::DevBuf seeds;       // float4[ceil(n / PCC_SEED_STRIDE)]: every 64th reference (w = its position; strides 32 / 128 / 256 measured 38.3 / 40.0 / 44.2 ms vs 38.0 on the ICP config) -- upper bounds for far queries
-    bool fb_zeroed = false;  // the query pack kernel of this call already zeroed the fallback counter
-    // ICP moves the same source cloud rigidly from pass to pass: the lane order of its first pass keeps
-    // neighbouring lanes on neighbouring points, so later passes skip the query sort
-    bool keep_order = false, order_valid = false;
-    const float* pre_transform = nullptr;  // ICP loop in cell order: the 3 x 4 matrix (device memory) the next k = 1 search applies to its
-                                           // queries, and writes back, before it looks -- the pass's k_transform folded into the search
-    bool warm_start = false;  // ICP passes after the first: out_packed holds the previous pass's keys (grid_nn1 starts from them)
-    size_t order_nq = 0;
-    unsigned int* order_ptr = nullptr;
-    unsigned int* order_nsorted = nullptr;
     unsigned int last_fallback_seen = 0;  // fallback count of an earlier search (heuristic only, may be stale)
     // scratch (grow-only, reused across calls on the index's stream)
     pcc::DevBuf q_raw, q_packed, out_packed, out_idx, out_d2, scratch_a, scratch_b,
@@ -382,7 +366,6 @@ enum { EV_MAIN0 = 0, EV_MAIN1, EV_FB0, EV_FB1, EV_CALL0, EV_CALL1, EV_BUILD0, EV
 inline void entered(pcc_index* ix) {
     ix->after_build = ix->build_fresh;
     ix->build_fresh = false;
-    ix->pre_order = nullptr;  // (an order prepared by a call that failed before using it)
 }
 inline void ev_mark(pcc_index* ix, int id) {
     if (!ix->timing || (ix->timing == 1 && id > EV_MAIN1)) return;
@@ -409,9 +392,8 @@ int read_back(pcc_index* ix, const T* dev, T* out) {
 
 // ---- kernels / launchers (pack.hip) -------------------------------------------
 // AoS (stride bytes, 3 floats at offset 0) -> float4(x,y,z,bits(i)); non-finite points are
-// written with w = -1.  With blk_stats != nullptr every workgroup b also writes 8 floats:
-// [0] bits(invalid count), [1..3] min xyz, [4..6] max xyz of its valid points; *n_blocks rows.
-// grid (index builds, with blk_stats): the pack kernel's last workgroup also derives the index's grid (what k_grid_params does in
+// written with w = -1.
+// PackGrid (index builds): the pack kernel's last workgroup also derives the index's grid (what k_grid_params does in
 // a launch of its own): ticket = a zeroed device word, the rest are k_grid_params' arguments
 struct PackGrid {
     unsigned int* ticket;
@@ -421,10 +403,19 @@ struct PackGrid {
     GridDev* out;
     GridDev* host_mirror;
 };
-int launch_pack(hipStream_t s, const void* aos, size_t n, size_t stride, float4* out,
-                float* blk_stats = nullptr, int* n_blocks = nullptr, unsigned int* zero_word = nullptr, float4* seeds = nullptr,
-                unsigned long long* invalid_keys = nullptr, unsigned int* cells = nullptr, const GridDev* gd = nullptr,
-                const PackGrid* grid = nullptr);
+// What a pack launch writes besides the packed points; what is left empty is not written.
+struct PackExtras {
+    float* blk_stats = nullptr;  // 8 floats per workgroup: [0] bits(invalid count), [1..3] min xyz, [4..6] max xyz of its valid points
+    int* n_blocks = nullptr;     // host word: the number of workgroups launched (rows of blk_stats)
+    unsigned int* zero_word = nullptr;           // &DevWords::fb_count: clears the counters of a k = 1 search (clear_search_counters)
+    float4* seeds = nullptr;                     // (with blk_stats) every PCC_SEED_STRIDE-th point
+    unsigned long long* invalid_keys = nullptr;  // result key of every non-finite point preset to "nothing found"
+    unsigned int* cells = nullptr;               // (without blk_stats) the cell of every point in the grid *gd describes
+    const GridDev* gd = nullptr;
+    PackGrid grid{};             // (with blk_stats) used when grid.out is set
+    bool indexed_cloud = false;  // read by stage_points alone: a small cloud goes to pinned slot 0 and its raw records stay (small_tie_replay)
+};
+int launch_pack(hipStream_t s, const void* aos, size_t n, size_t stride, float4* out, const PackExtras& x);
 // exclusive scan of uint32 data[n] in place; data[n] receives the total when
 // write_total.  tmp is grown as needed.
 int launch_exclusive_scan(pcc_index* ix, hipStream_t s, unsigned int* data, size_t n, DevBuf& tmp);
@@ -480,9 +471,25 @@ int grid_params_fused(pcc_index* ix, PackGrid* pg);                        // th
 int grid_build(pcc_index* ix);                                             // async: cell sort of the references
 int sync_info(pcc_index* ix);                                              // wait for the pinned mirror, refresh host fields
 unsigned int grid_nc_cap(size_t n, double ppc);
-int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out);
-// sort queries by reference-grid cell: order[0..*n_sorted) (device) lists the valid queries
+// What ONE k = 1 search is told by its caller, on the caller's stack (nn1_packed -> grid_nn1; the exhaustive engine needs none of
+// it).  Default-constructed: a plain search that sorts its queries itself.
+struct Nn1Call {
+    // order_given: the lane order is given for order_nq queries (order == nullptr: the identity).  An ICP pass (icp_pass) that sorts
+    // leaves its order here as given: the loop keeps one struct, a rigid motion keeps neighbouring points neighbours, and any
+    // permutation of the valid queries is correct, so its later passes skip the sort.  No other search's order is reused
+    bool order_given = false;
+    unsigned int *order = nullptr, *n_sorted = nullptr;  // (n_sorted: device word, the number of valid queries)
+    size_t order_nq = 0;
+    bool counters_cleared = false;  // the pack / transform / solve kernel in front has cleared fb_count, far_count and the open-lane
+                                    // shards (clear_search_counters); the search uses them up
+    bool icp_pass = false;          // a pass of pcc_icp_align: plain box instead of the ball walk, far route in auto mode
+    bool warm = false;              // (ICP passes) out[] holds the previous pass's keys of the same queries: the search starts from them
+    const float* pre_transform = nullptr;  // cell-ordered ICP loop: the 3 x 4 matrix (device memory) the search applies to its queries, and writes
+                                           // back, before it looks -- the pass's k_transform; needs grid_nn1_takes_transform, identity order
+};
+int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out, Nn1Call& call);
 bool grid_nn1_takes_transform(const pcc_index* ix);
+// sort queries by reference-grid cell: order[0..*n_sorted) (device) lists the valid queries
 int grid_sort_queries(pcc_index* ix, const float4* q, size_t nq, unsigned int** order_dev,
                       unsigned int** n_sorted_dev);
 float grid_slack(const GridParams& g);
@@ -582,8 +589,8 @@ int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t
 void match_batch_release(pcc_index* ix);  // match_batch.hip: frees ix->mb
 int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
-int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem);
-int nn1_packed(pcc_index* ix, size_t nq);
+int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, Nn1Call* search = nullptr);
+int nn1_packed(pcc_index* ix, size_t nq, Nn1Call& call);
 int set_input(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem);
 int need_grid(pcc_index* ix);                              // (the GRID engine's index, built on demand)
 int make_handle(int device, int engine, pcc_index** out);  // an empty handle on `device`

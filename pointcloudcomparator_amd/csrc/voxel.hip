@@ -82,7 +82,10 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
         src = ix->q_raw.p;
     }
     int nblk = 0;
-    PCC_TRY(launch_pack(s, src, n, stride, ix->vox_a.as<float4>(), ix->blk_stats.as<float>(), &nblk));
+    PackExtras px;
+    px.blk_stats = ix->blk_stats.as<float>();
+    px.n_blocks = &nblk;
+    PCC_TRY(launch_pack(s, src, n, stride, ix->vox_a.as<float4>(), px));
     float* h_blk = ix->pinned->vox_rows;
     PCC_HIP(hipMemcpyAsync(h_blk, ix->blk_stats.p, (size_t)nblk * 8 * sizeof(float), hipMemcpyDeviceToHost, s));
     PCC_HIP(hipStreamSynchronize(s));
