@@ -11,9 +11,10 @@
 //   when it does not converge) -> [-e] Euclidean clustering (src/segmentation.cpp:119-156) -> point /
 //   cluster counts (:1199-1205) -> [-n] noise pass (:1520-1568) -> results file.
 // Same flags, banner lines, section strings and exit code (always 1, :1704).  NOT part of this build
-// (out of scope): the SIFT keypoint pipeline and the viewer (-v is accepted and ignored).  The RIFT
+// (out of scope): the viewer (-v is accepted and ignored).  The RIFT
 // descriptors of the clusters come from files (--descriptors1/2) or, with --rift, from pcc::processRIFT (:590-684), dense
-// for every cluster (the reference sends clusters above 700 points through SIFT keypoints first, :1228-1231).  Both segmentation paths run: region growing (default, src/segmentation.cpp:218-327) and
+// for every cluster; with --sift as well, clusters above 700 points go through SIFT keypoints first as in the reference
+// (pcc::processRIFTwithSIFT, :686-822, chosen at :1228-1231 and :1264-1265).  Both segmentation paths run: region growing (default, src/segmentation.cpp:218-327) and
 // Euclidean clustering (-e, :64-156), each behind the VoxelGrid the reference applies first.
 #include <cmath>
 #include <cstdio>
@@ -27,6 +28,7 @@
 #include "pcc/comparator_nn.hpp"
 #include "pcc/multi_device.hpp"
 #include "pcc/rift.hpp"
+#include "pcc/sift.hpp"
 #include "ply_io.hpp"
 #include "report.hpp"
 
@@ -37,9 +39,10 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --descriptors1/2 FILE (precomputed RIFT32 descriptors per cluster: the descriptor pipeline itself is out of scope),
 // --dump-clusters PREFIX (the clusters as PLY files, so that descriptors can be computed for them elsewhere),
 // --rift (clusters of a scene without a descriptor file get their descriptors from pcc::processRIFT),
+// --sift (with --rift: clusters above 700 points take pcc::processRIFTwithSIFT, the reference's own choice),
 // --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read)
 static int n_gpus = 1;
-static bool rift = false;
+static bool rift = false, sift = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
 static void printUsage() {
@@ -56,7 +59,10 @@ static void printUsage() {
               << "--dump-clusters P  (this build) write the clusters as P_<scene>_<cluster>.ply\n"
               << "--rift             (this build) RIFT descriptors of every cluster of a scene without a descriptor file are computed\n"
               << "                   (processRIFT: normals 0.03, intensity gradient 0.03, RIFT 0.05, 4 x 8 bins), DENSE for every\n"
-              << "                   cluster: the reference's SIFT keypoint stage for clusters above 700 points is not part of this build\n"
+              << "                   cluster: the reference's SIFT keypoint stage for clusters above 700 points is not part of --rift alone\n"
+              << "--sift             (this build, with --rift) clusters above 700 points take the reference's processRIFTwithSIFT instead:\n"
+              << "                   SIFT keypoints (scales 0.005, 5, 5; minimum contrast 0.001), each snapped to the first cluster point\n"
+              << "                   within 0.05, RIFT descriptors of the snapped cloud\n"
               << "--dump-descriptors P  (this build) write the descriptors in use as P_<scene>.txt (the format of --descriptors1/2)\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
@@ -234,7 +240,15 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
     bool have_descriptors = true;
     for (int k = 0; k < 2; ++k) {
         if (descriptors_path[k].empty() && rift) {
-            for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) des[k].push_back(processRIFT(c));
+            for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
+                if (sift && c->points.size() > 700) {  // reference :1228-1231, :1264-1265
+                    size_t n_keypoints = 0;
+                    des[k].push_back(processRIFTwithSIFT(c, nullptr, &n_keypoints));
+                    std::cout << "Computed " << n_keypoints << " SIFT Keypoints\n";  // reference :467
+                } else {
+                    des[k].push_back(processRIFT(c));
+                }
+            }
         } else if (descriptors_path[k].empty()) {
             have_descriptors = false;
             des[k].assign(clusters[k].size(), report::DescPtr());
@@ -316,10 +330,12 @@ int main(int argc, char** argv) {
         else if (a == "--descriptors2" && i + 1 < argc) descriptors_path[1] = argv[++i];
         else if (a == "--dump-clusters" && i + 1 < argc) dump_prefix = argv[++i];
         else if (a == "--rift") rift = true;
+        else if (a == "--sift") sift = true;
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }
+    if (sift && !rift) { std::cerr << "--sift needs --rift\n"; printUsage(); return 1; }
     std::cout << (seeClusters ? "Visualization of clusters is on." : "Visualization of clusters is off.") << std::endl;
     std::cout << (noise ? "Noise analysis is on." : "Noise analysis is off.") << std::endl;
     std::cout << (icp ? "ICP matching pre-comparison is on." : "ICP matching pre-comparison is off.") << std::endl;

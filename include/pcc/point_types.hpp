@@ -1,6 +1,6 @@
 // point_types.hpp -- POD point types and containers with the layouts the reference's PCL types
 // have at the search boundary: pcl::PointXYZ (16 B), pcl::PointXYZRGB
-// (32 B, 16-byte aligned, x y z at 0/4/8, rgb at 16), pcl::Histogram<N> (RIFT32 =
+// (32 B, 16-byte aligned, x y z at 0/4/8, rgb at 16), pcl::PointWithScale (32 B), pcl::Histogram<N> (RIFT32 =
 // pcl::Histogram<32>, reference src/comparator.cpp:9), pcl::PointIndices, pcl::Correspondence.
 // Only what the hot path touches; no PCL dependency.
 #pragma once
@@ -34,7 +34,15 @@ struct alignas(16) Normal {
     float curvature = 0;
     float pad2_[3] = {0, 0, 0};
 };
-static_assert(sizeof(Normal) == 32, "PCL layout");
+// pcl::PointWithScale: x y z + pad, scale, angle, response, octave (32 bytes): what pcl::SIFTKeypoint returns
+struct alignas(16) PointWithScale {
+    float x = 0, y = 0, z = 0, pad_ = 1.0f;
+    float scale = 1.0f;
+    float angle = -1.0f;
+    float response = 0;
+    int octave = 0;
+};
+static_assert(sizeof(Normal) == 32 && sizeof(PointWithScale) == 32, "PCL layout");
 static_assert(sizeof(PointXYZ) == 16 && sizeof(PointXYZRGB) == 32 && sizeof(Histogram<32>) == 128, "PCL layouts");
 
 struct PointIndices {

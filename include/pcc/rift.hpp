@@ -2,8 +2,8 @@
 // Same signature, radii (normals 0.03, intensity gradient 0.03, RIFT 0.05) and bins (4 distance x 8 gradient) as the
 // reference; the whole pipeline -- intensity, normals, removal of NaN normals, intensity gradient, RIFT, removal of
 // non-finite descriptors -- is one pcc_rift_descriptors call on a tree over the cloud.  The reference sends clusters
-// above 700 points through SIFT keypoints first (processRIFTwithSIFT, :1228-1231); SIFT is not part of this library, a
-// caller that wants descriptors for such a cluster calls this dense form.
+// above 700 points through SIFT keypoints first (processRIFTwithSIFT, :1228-1231): that route is pcc::processRIFTwithSIFT
+// in pcc/sift.hpp, which ends in this function on the snapped keypoint cloud.
 #pragma once
 #include <vector>
 #include "pcc/search.hpp"

@@ -197,9 +197,12 @@ enum pcc_option {
                                     row; every query after the first of its run starts from a bound -- its predecessor's K-th distance
                                     plus their separation (the K-th neighbour distance is 1-Lipschitz) -- and skips the cube sizing,
                                     the bucket histogram and the compaction (default 16; 1 = every query on its own, round 5) */
-    PCC_OPT_RIFT_LAYOUT = 24     /* pcc_rift_descriptors, the histogram kernel: 1 = 32 lanes per row -- every lane computes one row entry's
+    PCC_OPT_RIFT_LAYOUT = 24,    /* pcc_rift_descriptors, the histogram kernel: 1 = 32 lanes per row -- every lane computes one row entry's
                                     vote, then every lane adds, in row order, the shares of the bin it owns (default); 0 = one lane per row
                                     (PCL's loop as it stands).  Same bits either way. */
+    PCC_OPT_SIFT_LAYOUT = 25     /* pcc_sift_keypoints, the scale-space kernel: 1 = a wave per point -- every lane computes one row entry's
+                                    Gaussian weights for all scales, then one lane per scale adds its shares in row order (default);
+                                    0 = one lane per (point, scale) walking its row prefix.  Same bits either way. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -421,6 +424,43 @@ int pcc_normals_radius(pcc_index *index, double radius, const float viewpoint[3]
 int pcc_rift_descriptors(pcc_index *index, const void *rgb, size_t rgb_stride_bytes, int mem, double normal_radius,
                          double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins,
                          float *out_histograms, int32_t *out_point_index, size_t *n_out);
+/* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
+ * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
+ *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)
+ *   and of the RIFT stage (pcc_rift_descriptors) in processRIFTwithSIFT (:686-822).  The PCL stage is restated from the
+ *   published algorithm ([recalled]): parity with PCL 1.7 itself is unpinned.
+ * ctx: any index handle, as for pcc_voxel_grid: it supplies device, stream and scratch; the cloud it indexes is neither read
+ *   nor changed.  The octave clouds are indexed on a work handle the library keeps inside ctx (reused across calls, freed
+ *   with ctx).
+ * pts / rgb: n points (x, y, z at pts + i * stride_bytes) and PCL's packed colour word of each (bytes b, g, r, a from the
+ *   low byte) at rgb + i * rgb_stride_bytes, memory space `mem`; for 32-byte pcl::PointXYZRGB records rgb = pts + 16 with the
+ *   same stride.
+ * PCL 1.7 SIFTKeypoint::detectKeypoints, float32 throughout, every operation rounded on its own, sums in row order.  Per
+ * octave o, scale = min_scale * 2^o (a float, doubled per octave):
+ *   1. the current cloud (the input for the first octave) through pcc_voxel_grid with leaf = scale, colour averaged per
+ *      channel and truncated; the octave cloud is in ascending voxel-index order, non-finite points drop out here;
+ *   2. fewer than 25 points end the loop (PCL's min_nr_points);
+ *   3. scales[i] = scale * powf(2.0f, (float(i) - 1.0f) / float(nr_scales_per_octave)), i = 0 .. nr_scales_per_octave + 2;
+ *   4. intensity float(299 r + 587 g + 114 b) / 1000.0f of the averaged bytes;
+ *   5. scale space, per point: the sorted radius row over the octave cloud at 3.0f * scales.back() (d2 < float(r^2),
+ *      ascending (d2, index), the point itself first); per scale sigma2 = powf(s, 2.0f); the row is walked while
+ *      d2 <= 9 * sigma2: w = expf(-0.5f * d2 / sigma2), num += value * w, den += w; response = num / den;
+ *      dog(point, i - 1) = response_i - response_{i-1};
+ *   6. extrema, per point: min_val / max_val of every DoG column over its min(25, n) nearest neighbours (self included);
+ *      for the columns s = 1 .. nr_columns - 2 with v = dog(point, s) and fabs(v) >= min_contrast, a keypoint when
+ *      v == min_val[s] && v < min_val[s-1] && v < min_val[s+1], or the mirrored maximum test holds:
+ *      (x, y, z of the octave cloud's point, scales[s]);
+ *   7. keypoints in order of octave, then point index within the octave cloud, then s (PCL's loop order).
+ * out_keypoints[capacity][4] (x, y, z, scale) in memory space `mem`; *n_out (host) = the number of keypoints.  More than
+ *   capacity: PCC_ERR_OVERFLOW, nothing written, *n_out = the number needed.  n == 0 or no finite point: *n_out = 0, PCC_OK.
+ * Null arguments, a bad stride, alignment or memory space, a min_scale that is not positive and finite, a negative or NaN
+ * min_contrast and nr_octaves < 1 are refused before any device is touched; so is nr_scales_per_octave outside 1 .. 13
+ * (PCC_ERR_UNSUPPORTED: the kernels are built for up to 16 scales).  A first-octave lattice of more than 2^26 voxels is
+ * pcc_voxel_grid's PCC_ERR_UNSUPPORTED (min_scale too small for the cloud's extent). */
+int pcc_sift_keypoints(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, const void *rgb,
+                       size_t rgb_stride_bytes, int mem, float min_scale, int nr_octaves, int nr_scales_per_octave,
+                       float min_contrast, float *out_keypoints /* [capacity][4]: x, y, z, scale */, size_t capacity,
+                       size_t *n_out);
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);

@@ -20,7 +20,7 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT) = range(1, 25)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT) = range(1, 26)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -36,7 +36,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_sift_keypoints", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -103,6 +103,7 @@ def _load() -> C.CDLL:
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_voxel_grid.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, vp, sz, C.POINTER(sz)]
     lib.pcc_radius_fill.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, vp, vp, vp]
@@ -178,6 +179,31 @@ def _out(like, shape, dtype):
         return t, t.data_ptr()
     a = np.empty(shape, dtype=dtype)
     return a, a.ctypes.data
+
+
+def _colour_words(rgb):
+    """(keep-alive, pointer, stride_bytes, mem) of one colour per point, numpy array or torch tensor:
+    (n, 3) uint8 r, g, b;  (n,) uint32 / int32 packed colour words (bytes b, g, r, a from the low byte);  or the (n, >= 5)
+    float32 records of pcl::PointXYZRGB (colour word in column 4), read in place with their stride."""
+    torch_in = _is_torch(rgb)
+    if torch_in:
+        import torch
+    if rgb.ndim == 2 and rgb.shape[1] == 3 and rgb.dtype == (torch.uint8 if torch_in else np.uint8):
+        c = rgb.to(torch.int32) if torch_in else rgb.astype(np.uint32)
+        words = c[:, 2] | (c[:, 1] << 8) | (c[:, 0] << 16)
+        words = words.contiguous() if torch_in else np.ascontiguousarray(words)
+        ptr, stride = (words.data_ptr() if torch_in else words.ctypes.data), 4
+    elif rgb.ndim == 1:
+        words = rgb.contiguous() if torch_in else np.ascontiguousarray(rgb)
+        assert (words.element_size() if torch_in else words.itemsize) == 4, "packed colour words are 32-bit"
+        ptr, stride = (words.data_ptr() if torch_in else words.ctypes.data), 4
+    else:
+        words = rgb  # pcl::PointXYZRGB records: the colour word sits 16 bytes into each
+        base, _, stride, _ = _points(rgb)
+        assert rgb.shape[1] >= 5, "PointXYZRGB records have their colour word in column 4"
+        ptr = base + 16
+    mem = MEM_DEVICE if torch_in and words.is_cuda else MEM_HOST
+    return words, ptr, stride, mem
 
 
 def rigid_from_sums(sums, center=None):
@@ -629,25 +655,8 @@ class Index:
         Returns (histograms (n_out, 32) float32, point index (n_out,) int32): the descriptors that survive both
         compactions and the original index of the point each belongs to."""
         n = self.n_original
-        torch_in = _is_torch(rgb)
-        if torch_in:
-            import torch
         assert len(rgb) == n, "one colour per point of the indexed cloud"
-        if rgb.ndim == 2 and rgb.shape[1] == 3 and rgb.dtype == (torch.uint8 if torch_in else np.uint8):
-            c = rgb.to(torch.int32) if torch_in else rgb.astype(np.uint32)
-            words = c[:, 2] | (c[:, 1] << 8) | (c[:, 0] << 16)
-            words = words.contiguous() if torch_in else np.ascontiguousarray(words)
-            ptr, stride = (words.data_ptr() if torch_in else words.ctypes.data), 4
-        elif rgb.ndim == 1:
-            words = rgb.contiguous() if torch_in else np.ascontiguousarray(rgb)
-            assert (words.element_size() if torch_in else words.itemsize) == 4, "packed colour words are 32-bit"
-            ptr, stride = (words.data_ptr() if torch_in else words.ctypes.data), 4
-        else:
-            words = rgb  # pcl::PointXYZRGB records: the colour word sits 16 bytes into each
-            base, _, stride, _ = _points(rgb)
-            assert rgb.shape[1] >= 5, "PointXYZRGB records have their colour word in column 4"
-            ptr = base + 16
-        mem = MEM_DEVICE if torch_in and words.is_cuda else MEM_HOST
+        words, ptr, stride, mem = _colour_words(rgb)
         hist, ph = _out(words, (max(n, 1), 32), np.float32)
         index, pi = _out(words, (max(n, 1),), np.int32)
         n_out = C.c_size_t(0)
@@ -656,6 +665,32 @@ class Index:
                                         int(nr_distance_bins), int(nr_gradient_bins), ph, pi, C.byref(n_out)))
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
+
+    def sift_keypoints(self, points, rgb, min_scale: float = 0.005, nr_octaves: int = 5, nr_scales_per_octave: int = 5,
+                       min_contrast: float = 0.001):
+        """pcc_sift_keypoints: the reference's processSift (src/comparator.cpp:435-469, pcl::SIFTKeypoint) for `points`, an
+        (n, >= 3) float32 numpy array or torch tensor; this handle is the context only (device, stream, scratch), the cloud it
+        indexes is not read.  rgb: one colour per point in any of rift_descriptors' three forms, in the memory space of
+        `points` (the records themselves may be passed for both).  Returns (m, 4) float32 x, y, z, scale in the detector's
+        order (octave, point of the octave cloud, scale) -- a CUDA tensor for CUDA input."""
+        ptr, n, stride, mem = _points(points)
+        assert len(rgb) == n, "one colour per point"
+        words, cptr, cstride, cmem = _colour_words(rgb)
+        assert cmem == mem, "points and colours live in the same memory space"
+        found = C.c_size_t(0)
+        capacity = 256
+        for attempt in range(2):
+            out, po = _out(points, (capacity, 4), np.float32)
+            st = self._before(points, words, out)
+            status = LIB.pcc_sift_keypoints(self._h, ptr, n, stride, cptr, cstride, mem, float(min_scale), int(nr_octaves),
+                                            int(nr_scales_per_octave), float(min_contrast), po, capacity, C.byref(found))
+            self._after(st)
+            if status == -6 and attempt == 0:  # PCC_ERR_OVERFLOW: once more with the room it asks for
+                capacity = found.value
+                continue
+            _check(status)
+            break
+        return out[:found.value]
 
     def region_growing(self, normals, k: int = 100, smoothness: float = 3.0 / 180.0 * np.pi,
                        curvature_threshold: float = 1.0, min_size: int = 50, max_size: int = 1000000):

@@ -4,6 +4,7 @@
 // PCC_ERR_DEVICE.
 #include "pcc_internal.hpp"
 #include "rift_math.hpp"
+#include "sift_math.hpp"
 #include <atomic>
 #include "rigid_solve.hpp"
 #include "host_pipe.hpp"
@@ -53,7 +54,7 @@ static bool option_in_range(int option, double value) {
         case PCC_OPT_XCD_RUN: return value >= 1 && value <= 4096;
         case PCC_OPT_FUSE_PARAMS: return value >= 0 && value <= 3;
         case PCC_OPT_KNN_RUN: return value >= 1 && value <= 64;
-        case PCC_OPT_RIFT_LAYOUT: return value == 0 || value == 1;
+        case PCC_OPT_RIFT_LAYOUT: case PCC_OPT_SIFT_LAYOUT: return value == 0 || value == 1;
         case PCC_OPT_HOST_PIPE: case PCC_OPT_SCAN_CHAINED: return value == 0 || value == 1;
         default: return value == 0 || value == 1;
     }
@@ -85,6 +86,7 @@ static double* option_slot(Options& o, int option, int** as_int) {
         case PCC_OPT_SCAN_CHAINED: *as_int = &o.scan_chained; return nullptr;
         case PCC_OPT_KNN_RUN: *as_int = &o.knn_run; return nullptr;
         case PCC_OPT_RIFT_LAYOUT: *as_int = &o.rift_layout; return nullptr;
+        case PCC_OPT_SIFT_LAYOUT: *as_int = &o.sift_layout; return nullptr;
         default: return nullptr;
     }
 }
@@ -102,7 +104,7 @@ void Options::from_env() {
         {"PCC_GRID_AXES", PCC_OPT_GRID_AXES}, {"PCC_XCD_RUN", PCC_OPT_XCD_RUN},
         {"PCC_FUSE_PARAMS", PCC_OPT_FUSE_PARAMS}, {"PCC_HOST_PIPE", PCC_OPT_HOST_PIPE},
         {"PCC_SCAN_CHAINED", PCC_OPT_SCAN_CHAINED}, {"PCC_KNN_RUN", PCC_OPT_KNN_RUN},
-        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}};
+        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}, {"PCC_SIFT_LAYOUT", PCC_OPT_SIFT_LAYOUT}};
     for (const auto& v : vars) {
         const char* txt = getenv(v.name);
         if (!txt || !*txt) continue;
@@ -562,6 +564,7 @@ int pcc_index_destroy(pcc_index* ix) {
     if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
     match_batch_release(ix);
     rift_release(ix);
+    sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
     if (ix->h_grid) (void)hipHostFree(ix->h_grid);
     if (ix->edge_ev) (void)hipEventDestroy(ix->edge_ev);
@@ -1237,6 +1240,48 @@ int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int 
     ri.count = *n_out;
     ev_mark(ix, EV_CALL1);
     return finish(ix, mem, rh, ri);
+}
+
+int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, const void* rgb, size_t rgb_stride, int mem, float min_scale,
+                       int nr_octaves, int nr_scales_per_octave, float min_contrast, float* out_keypoints, size_t capacity, size_t* n_out) {
+    // the arguments first: host arithmetic, refused before any device is looked at
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (!n_out || (n && !rgb) || (capacity && !out_keypoints)) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (rgb_stride < 4 || rgb_stride % 4 || (n && (reinterpret_cast<uintptr_t>(rgb) % 4 || reinterpret_cast<uintptr_t>(pts) % 4)) ||
+        (capacity && reinterpret_cast<uintptr_t>(out_keypoints) % 4)) {
+        set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
+        return PCC_ERR_INVALID;
+    }
+    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
+    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
+    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
+    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
+        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
+                  SIFT_MAX_SCALES_PER_OCTAVE);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    PCC_ENTER(ix);
+    *n_out = 0;
+    if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    if (!ix->sift) ix->sift = new SiftScratch();
+    const unsigned char *dpts = nullptr, *drgb = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(pts), (n - 1) * stride + 12, mem, ix->sift->pts, &dpts));
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->sift->rgb, &drgb));
+    size_t found = 0;
+    PCC_TRY(sift_keypoints(ix, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
+    ev_mark(ix, EV_CALL1);
+    *n_out = found;
+    if (found > capacity) {
+        set_error("%zu keypoints, room for %zu", found, capacity);
+        return PCC_ERR_OVERFLOW;
+    }
+    if (found == 0) return PCC_OK;
+    PCC_HIP(hipMemcpyAsync(out_keypoints, ix->sift->kp.p, found * 4 * sizeof(float), mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                           ix->stream));
+    if (mem == PCC_MEM_HOST) PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
 }
 
 int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, float smoothness,

@@ -1,4 +1,4 @@
-// libm_f32.hpp -- glibc 2.35's sinf / cosf / atan2f (and acosf, for the RIFT histogram: see lm_acosf), restated so that the device evaluates what the host's libm does.
+// libm_f32.hpp -- glibc 2.35's sinf / cosf / atan2f (and acosf, for the RIFT histogram: see lm_acosf; expf, for the SIFT scale space: see lm_expf), restated so that the device evaluates what the host's libm does.
 //
 // pcl::eigen33 (NormalEstimation, the RANSAC refit; reference src/segmentation.cpp:232-241, 79-117) takes the roots of the
 // characteristic cubic in closed form: theta = atan2f(sqrtf(-q), half_b) / 3, then cosf(theta), sinf(theta).  The smallest
@@ -236,6 +236,74 @@ __host__ __device__ inline float lm_acosf(float x) {
     const float r = p / q;
     const float w = r * s + c;
     return 2.0f * (df + w);
+}
+
+// ---- expf (double-precision table form) ---------------------------------------------------------------------------------
+// sysdeps/ieee754/flt-32/e_expf.c + e_exp2f_data.c (Szabolcs Nagy): x * 32 / ln 2 = k + r with k an integer (the 0x1.8p52
+// shift) and r in [-1/2, 1/2]; exp(x) = 2^(k / 32) * 2^(r / 32), the first factor from a 32-entry table whose entries have
+// the exponent bits of k folded in by an integer add, the second a degree-3 polynomial; everything in double, rounded to
+// float once.  As for sinf / cosf the host runs the build for CPUs with FMA (__expf_fma), which contracts every
+// multiply-add -- the scaling product included: it feeds only the shift's addition and the subtraction that yields r, and
+// both were fused.  The table is 2^(i / 32) correctly rounded (generated with 80-digit decimal arithmetic), stored as
+// bits(2^(i / 32)) - (i << 47).  The caller is the SIFT detector's Gaussian weight (sift_math.hpp), arguments in [-4.5, 0];
+// tests/cpp/test_expf.cpp compares every float of that interval, a stride sample of [-104, 89] and the special cases with
+// the host's expf.
+__host__ __device__ inline double lm_double(uint64_t u) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __longlong_as_double((long long)u);
+#else
+    double d;
+    memcpy(&d, &u, 8);
+    return d;
+#endif
+}
+__host__ __device__ inline uint64_t lm_bits64(double d) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint64_t)__double_as_longlong(d);
+#else
+    uint64_t u;
+    memcpy(&u, &d, 8);
+    return u;
+#endif
+}
+__host__ __device__ inline uint64_t lm_exp2f_tab(unsigned int i) {
+    switch (i & 31u) {
+#define LM_T(I, V) case I: return V
+        LM_T(0, 0x3ff0000000000000ull); LM_T(1, 0x3fefd9b0d3158574ull); LM_T(2, 0x3fefb5586cf9890full); LM_T(3, 0x3fef9301d0125b51ull);
+        LM_T(4, 0x3fef72b83c7d517bull); LM_T(5, 0x3fef54873168b9aaull); LM_T(6, 0x3fef387a6e756238ull); LM_T(7, 0x3fef1e9df51fdee1ull);
+        LM_T(8, 0x3fef06fe0a31b715ull); LM_T(9, 0x3feef1a7373aa9cbull); LM_T(10, 0x3feedea64c123422ull); LM_T(11, 0x3feece086061892dull);
+        LM_T(12, 0x3feebfdad5362a27ull); LM_T(13, 0x3feeb42b569d4f82ull); LM_T(14, 0x3feeab07dd485429ull); LM_T(15, 0x3feea47eb03a5585ull);
+        LM_T(16, 0x3feea09e667f3bcdull); LM_T(17, 0x3fee9f75e8ec5f74ull); LM_T(18, 0x3feea11473eb0187ull); LM_T(19, 0x3feea589994cce13ull);
+        LM_T(20, 0x3feeace5422aa0dbull); LM_T(21, 0x3feeb737b0cdc5e5ull); LM_T(22, 0x3feec49182a3f090ull); LM_T(23, 0x3feed503b23e255dull);
+        LM_T(24, 0x3feee89f995ad3adull); LM_T(25, 0x3feeff76f2fb5e47ull); LM_T(26, 0x3fef199bdd85529cull); LM_T(27, 0x3fef3720dcef9069ull);
+        LM_T(28, 0x3fef5818dcfba487ull); LM_T(29, 0x3fef7c97337b9b5full); LM_T(30, 0x3fefa4afa2a490daull);
+#undef LM_T
+        default: return 0x3fefd0765b6e4540ull;
+    }
+}
+__host__ __device__ inline float lm_expf(float x) {
+    const double inv_ln2_n = 0x1.71547652b82fep+0 * 32.0, shift = 0x1.8p+52;
+    const double c0 = 0x1.c6af84b912394p-5 / 32.0 / 32.0 / 32.0, c1 = 0x1.ebfce50fac4f3p-3 / 32.0 / 32.0, c2 = 0x1.62e42ff0c52d6p-1 / 32.0;
+    const uint32_t abstop = (lm_bits(x) >> 20) & 0x7ffu;
+    if (abstop >= ((lm_bits(88.0f) >> 20) & 0x7ffu)) {  // |x| >= 88 or NaN
+        if (lm_bits(x) == 0xff800000u) return 0.0f;
+        if (abstop >= 0x7f8u) return x + x;
+        if (x > 0x1.62e42ep6f) return lm_float(0x7f800000u);  // overflow
+        if (x < -0x1.9fe368p6f) return 0.0f;                  // underflow
+    }
+    const double xd = (double)x;
+    double kd = LM_MADD(inv_ln2_n, xd, shift);
+    const uint64_t ki = lm_bits64(kd);
+    kd -= shift;
+    const double r = LM_MADD(inv_ln2_n, xd, -kd);
+    const uint64_t t = lm_exp2f_tab((unsigned int)ki) + (ki << 47);
+    const double s = lm_double(t);
+    const double z = LM_MADD(c0, r, c1);
+    const double r2 = r * r;
+    double y = LM_MADD(c2, r, 1.0);
+    y = LM_MADD(z, r2, y);
+    y = y * s;
+    return (float)y;
 }
 
 }  // namespace pcc

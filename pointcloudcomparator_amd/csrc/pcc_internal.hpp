@@ -165,6 +165,8 @@ struct Options {
                                     // tagged 64-bit atomics and wait for the workgroups in front of them: relies on in-order dispatch); 0 = the two-launch
                                     // form (block totals, then apply), which waits for nothing
     int rift_layout = 1;            // PCC_OPT_RIFT_LAYOUT: RIFT histogram kernel, 1 = 32 lanes per row (votes by all lanes, bins by owner lanes), 0 = one lane per row
+    int sift_layout = 1;            // PCC_OPT_SIFT_LAYOUT: SIFT scale-space kernel, 1 = a wave per point (weights by all lanes, sums by one owner lane per
+                                    // scale), 0 = one lane per (point, scale)
     int host_pipe = 1;              // PCC_OPT_HOST_PIPE: clouds / results of 8 MB and more in pageable HOST memory cross PCIe through the library's own pinned
                                     // chunk buffers, staged by a few host threads (x, y, z only when the stride is 24 bytes or more); 0 = one
                                     // hipMemcpyAsync of the raw array (rounds 1-5)
@@ -259,6 +261,17 @@ struct RiftScratch {
     DevBuf hist, keep, scan_tmp; // float[n][32] before the last compaction; its flags / positions
     DevBuf out_hist, out_index;  // results staged for a caller in host memory
 };
+// sift.hip: what pcc_sift_keypoints keeps between its octaves and calls (made at the first call on a handle)
+struct SiftScratch {
+    pcc_index* work = nullptr;   // the handle the octave clouds are indexed on (the caller's stream, scratch of its own)
+    DevBuf pts, rgb;             // the caller's points / colour words, staged (host memory)
+    DevBuf cloud[2];             // octave clouds, 32-byte records: the voxel grid reads one and writes the other
+    DevBuf inten, resp;          // float[n] intensity; float[n][scales] Gaussian responses
+    DevBuf nbr, nbr_d2;          // the k-NN rows of the extremum test
+    DevBuf mask, count, scan_tmp;  // keypoint columns per point (bits), their number / positions
+    DevBuf octaves;              // SiftOctave per octave
+    DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
+};
 struct MatchBatchScratch;  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
 struct HostPipe;           // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 }  // namespace pcc
@@ -340,6 +353,7 @@ struct pcc_index {
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
     pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
+    pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -530,6 +544,10 @@ int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsi
 int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
                      double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out);
 void rift_release(pcc_index* ix);  // frees ix->rift
+// sift.hip: the SIFT keypoint detector on device arrays (ix->sift made by the caller); the keypoints stay in ix->sift->kp
+int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
+                   float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
+void sift_release(pcc_index* ix);  // frees ix->sift and its work handle
 int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const float4* normals, int K, float smoothness,
                         float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels_dev,
                         int32_t* n_clusters);
