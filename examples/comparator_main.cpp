@@ -40,9 +40,10 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --dump-clusters PREFIX (the clusters as PLY files, so that descriptors can be computed for them elsewhere),
 // --rift (clusters of a scene without a descriptor file get their descriptors from pcc::processRIFT),
 // --sift (with --rift: clusters above 700 points take pcc::processRIFTwithSIFT, the reference's own choice),
+// --rift-loop (with --rift: one call per cluster as in the reference, :1224-1272, instead of one pcc::processRIFTBatch for all),
 // --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read)
 static int n_gpus = 1;
-static bool rift = false, sift = false;
+static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
 static void printUsage() {
@@ -63,6 +64,8 @@ static void printUsage() {
               << "--sift             (this build, with --rift) clusters above 700 points take the reference's processRIFTwithSIFT instead:\n"
               << "                   SIFT keypoints (scales 0.005, 5, 5; minimum contrast 0.001), each snapped to the first cluster point\n"
               << "                   within 0.05, RIFT descriptors of the snapped cloud\n"
+              << "--rift-loop        (this build, with --rift) one library call per cluster, as the reference's loop does; without it\n"
+              << "                   every cluster of both scenes goes through ONE processRIFTBatch call (same descriptors)\n"
               << "--dump-descriptors P  (this build) write the descriptors in use as P_<scene>.txt (the format of --descriptors1/2)\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
@@ -238,8 +241,22 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
     // descriptors per cluster: from files, computed (--rift), or none
     std::vector<report::DescPtr> des[2];
     bool have_descriptors = true;
+    std::vector<PointCloud<PointXYZRGB>::Ptr> batch_clouds;  // --rift without --rift-loop: every cluster of both scenes that needs descriptors
+    bool batch_scene[2] = {false, false};
     for (int k = 0; k < 2; ++k) {
-        if (descriptors_path[k].empty() && rift) {
+        if (descriptors_path[k].empty() && rift && !rift_loop) {
+            // the clouds the RIFT pipeline runs over, in cluster order; one processRIFTBatch call for both scenes below
+            for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
+                if (sift && c->points.size() > 700) {  // reference :1228-1231, :1264-1265
+                    size_t n_keypoints = 0;
+                    batch_clouds.push_back(siftSnappedCloud(c, &n_keypoints));
+                    std::cout << "Computed " << n_keypoints << " SIFT Keypoints\n";  // reference :467
+                } else {
+                    batch_clouds.push_back(c);
+                }
+            }
+            batch_scene[k] = true;
+        } else if (descriptors_path[k].empty() && rift) {
             for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
                 if (sift && c->points.size() > 700) {  // reference :1228-1231, :1264-1265
                     size_t n_keypoints = 0;
@@ -257,6 +274,13 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
             std::cerr << "Was not able to read descriptors \"" << descriptors_path[k] << "\".\n";
             return -2;
         }
+    }
+    if (!batch_clouds.empty()) {
+        const std::vector<PointCloud<RIFT32>::Ptr> batch = processRIFTBatch(batch_clouds);
+        size_t at = 0;
+        for (int k = 0; k < 2; ++k)
+            if (batch_scene[k])
+                for (size_t j = 0; j < clusters[k].size(); ++j) des[k].push_back(batch[at++]);
     }
     if (!dump_descriptors_prefix.empty())
         for (int k = 0; k < 2; ++k) {
@@ -331,6 +355,7 @@ int main(int argc, char** argv) {
         else if (a == "--dump-clusters" && i + 1 < argc) dump_prefix = argv[++i];
         else if (a == "--rift") rift = true;
         else if (a == "--sift") sift = true;
+        else if (a == "--rift-loop") rift_loop = true;
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }

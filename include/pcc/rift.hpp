@@ -4,6 +4,8 @@
 // non-finite descriptors -- is one pcc_rift_descriptors call on a tree over the cloud.  The reference sends clusters
 // above 700 points through SIFT keypoints first (processRIFTwithSIFT, :1228-1231): that route is pcc::processRIFTwithSIFT
 // in pcc/sift.hpp, which ends in this function on the snapped keypoint cloud.
+// pcc::processRIFTBatch is the same for every cluster of a comparison at once (the reference's per-cluster loop,
+// src/comparator.cpp:1224-1272): one pcc_rift_descriptors_batch call.
 #pragma once
 #include <vector>
 #include "pcc/search.hpp"
@@ -33,6 +35,57 @@ inline PointCloud<RIFT32>::Ptr processRIFT(const PointCloud<PointXYZRGB>::Ptr& c
     descriptors->is_dense = true;
     if (point_indices) point_indices->assign(index.begin(), index.begin() + n_out);
     return descriptors;
+}
+
+// processRIFT for every cloud of `clouds` in ONE library call: element c of the result is what processRIFT(clouds[c])
+// returns, bit for bit (a null or empty cloud, or one without a finite point, gives empty descriptors).
+// point_indices (nullable): per cloud, the index in that cloud of the point every returned descriptor belongs to.
+// ctx (nullable): any tree whose handle may serve as the call's context; the cloud it indexes is not read.
+inline std::vector<PointCloud<RIFT32>::Ptr> processRIFTBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds,
+                                                             std::vector<std::vector<int>>* point_indices = nullptr,
+                                                             search::KdTree<PointXYZRGB>* ctx = nullptr) {
+    std::vector<PointCloud<RIFT32>::Ptr> result(clouds.size());
+    for (PointCloud<RIFT32>::Ptr& d : result) d.reset(new PointCloud<RIFT32>);
+    if (point_indices) point_indices->assign(clouds.size(), std::vector<int>());
+    std::vector<const void*> pts(clouds.size(), nullptr), rgb(clouds.size(), nullptr);
+    std::vector<size_t> n(clouds.size(), 0), offsets(clouds.size() + 1, 0);
+    size_t total = 0;
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        if (!clouds[c] || clouds[c]->empty()) continue;
+        pts[c] = &clouds[c]->points[0].x;
+        rgb[c] = &clouds[c]->points[0].rgba;
+        n[c] = clouds[c]->size();
+        total += n[c];
+    }
+    if (total == 0) return result;  // (no library call)
+    static thread_local search::KdTree<PointXYZRGB> context;  // lends device, stream and scratch; the cloud it indexes is never asked
+    if (!ctx || !ctx->handle()) {
+        if (!context.handle()) {
+            PointCloud<PointXYZRGB>::Ptr one(new PointCloud<PointXYZRGB>);
+            PointXYZRGB p;
+            p.x = p.y = p.z = 0.f;
+            p.rgba = 0;
+            one->push_back(p);
+            context.setInputCloud(one);
+        }
+        ctx = &context;
+    }
+    std::vector<float> hist(total * 32);
+    std::vector<int32_t> index(total);
+    check(pcc_rift_descriptors_batch(ctx->handle(), clouds.size(), pts.data(), n.data(), sizeof(PointXYZRGB), rgb.data(), sizeof(PointXYZRGB),
+                                     PCC_MEM_HOST, 0.03, 0.03, 0.05, 4, 8, hist.data(), index.data(), offsets.data()));
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        const size_t m = offsets[c + 1] - offsets[c];
+        PointCloud<RIFT32>& d = *result[c];
+        d.points.resize(m);
+        for (size_t i = 0; i < m; ++i)
+            for (int b = 0; b < 32; ++b) d.points[i].histogram[b] = hist[(offsets[c] + i) * 32 + b];
+        d.width = (std::uint32_t)m;
+        d.height = 1;
+        d.is_dense = true;
+        if (point_indices) (*point_indices)[c].assign(index.begin() + offsets[c], index.begin() + offsets[c + 1]);
+    }
+    return result;
 }
 
 }  // namespace pcc

@@ -7,6 +7,8 @@
 //                        one pcc_sift_keypoints call
 //   processRIFTwithSIFT  processSift -> snapKeypointsToCloud (pcc_first_within; keypoints without a point within 0.05 are
 //                        skipped, duplicates are kept) -> a tree over the snapped cloud -> processRIFT on it
+//   siftSnappedCloud     the part of processRIFTwithSIFT in front of processRIFT: the snapped keypoint cloud, for callers
+//                        that hand it to pcc::processRIFTBatch with other clouds
 #pragma once
 #include <vector>
 #include "pcc/comparator_nn.hpp"
@@ -48,6 +50,19 @@ inline PointCloud<PointWithScale>::Ptr processSift(const PointCloud<PointXYZRGB>
     return keypoints;
 }
 
+// the front of processRIFTwithSIFT: processSift, then every keypoint snapped to the first point of `cloud` within 0.05 (:696-713).
+// The snapped cloud is what the RIFT pipeline runs over (processRIFT, or one entry of processRIFTBatch).
+// n_keypoints (nullable): what processSift found (the reference prints it)
+inline PointCloud<PointXYZRGB>::Ptr siftSnappedCloud(const PointCloud<PointXYZRGB>::Ptr& cloud, size_t* n_keypoints = nullptr) {
+    if (n_keypoints) *n_keypoints = 0;
+    if (!cloud || cloud->empty()) return PointCloud<PointXYZRGB>::Ptr(new PointCloud<PointXYZRGB>);
+    search::KdTree<PointXYZRGB> tree;
+    tree.setInputCloud(cloud);
+    const PointCloud<PointWithScale>::Ptr keypoints = processSift(cloud, &tree);
+    if (n_keypoints) *n_keypoints = keypoints->size();
+    return snapKeypointsToCloud(cloud, *keypoints, 0.05, &tree);
+}
+
 // point_indices (nullable): the index in the SNAPPED cloud of the point every returned descriptor belongs to;
 // n_keypoints (nullable): what processSift found (the reference prints it)
 inline PointCloud<RIFT32>::Ptr processRIFTwithSIFT(const PointCloud<PointXYZRGB>::Ptr& cloud, std::vector<int>* point_indices = nullptr,
@@ -55,12 +70,7 @@ inline PointCloud<RIFT32>::Ptr processRIFTwithSIFT(const PointCloud<PointXYZRGB>
     if (point_indices) point_indices->clear();
     if (n_keypoints) *n_keypoints = 0;
     if (!cloud || cloud->empty()) return PointCloud<RIFT32>::Ptr(new PointCloud<RIFT32>);
-    search::KdTree<PointXYZRGB> tree;
-    tree.setInputCloud(cloud);
-    const PointCloud<PointWithScale>::Ptr keypoints = processSift(cloud, &tree);
-    if (n_keypoints) *n_keypoints = keypoints->size();
-    const PointCloud<PointXYZRGB>::Ptr snapped = snapKeypointsToCloud(cloud, *keypoints, 0.05, &tree);
-    return processRIFT(snapped, point_indices);
+    return processRIFT(siftSnappedCloud(cloud, n_keypoints), point_indices);
 }
 
 }  // namespace pcc

@@ -200,9 +200,14 @@ enum pcc_option {
     PCC_OPT_RIFT_LAYOUT = 24,    /* pcc_rift_descriptors, the histogram kernel: 1 = 32 lanes per row -- every lane computes one row entry's
                                     vote, then every lane adds, in row order, the shares of the bin it owns (default); 0 = one lane per row
                                     (PCL's loop as it stands).  Same bits either way. */
-    PCC_OPT_SIFT_LAYOUT = 25     /* pcc_sift_keypoints, the scale-space kernel: 1 = a wave per point -- every lane computes one row entry's
+    PCC_OPT_SIFT_LAYOUT = 25,    /* pcc_sift_keypoints, the scale-space kernel: 1 = a wave per point -- every lane computes one row entry's
                                     Gaussian weights for all scales, then one lane per scale adds its shares in row order (default);
                                     0 = one lane per (point, scale) walking its row prefix.  Same bits either way. */
+    PCC_OPT_RIFT_BATCH_BRUTE_MAX = 26  /* pcc_rift_descriptors_batch: clouds of up to this many points get their radius rows from the
+                                    exhaustive builder that serves the whole batch at once (n^2 distance tests per cloud); larger
+                                    clouds take the single path inside the same call, one by one, on a work handle kept in ctx
+                                    (default 8192; PCC_RIFT_BATCH_BRUTE_MAX in the environment of a new handle).  No result bit
+                                    depends on it. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -424,6 +429,36 @@ int pcc_normals_radius(pcc_index *index, double radius, const float viewpoint[3]
 int pcc_rift_descriptors(pcc_index *index, const void *rgb, size_t rgb_stride_bytes, int mem, double normal_radius,
                          double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins,
                          float *out_histograms, int32_t *out_point_index, size_t *n_out);
+/* The same for EVERY cluster of a comparison at once -- replaces the per-cluster descriptor loop of the comparison
+ *   (src/comparator.cpp:1224-1272: processRIFT, :590-684, or processRIFTwithSIFT ending in it, once per cluster of both
+ *   scenes; no call depends on an earlier one).  The clouds of a call are concatenated on the device and every stage runs
+ *   once over all of them: one upload, one CSR build per radius, one pass of each stage.  Launches and host waits do not
+ *   depend on n_clouds: one wait per CSR (two; three when gradient_radius != normal_radius), one for the slice bounds and
+ *   one for the rows coming back.
+ *   ctx: any index handle, as for pcc_match_knn_batch and pcc_voxel_grid: it supplies device, stream and scratch; the cloud
+ *     it indexes is neither read nor changed.
+ *   Cloud c is the n[c] points at pts[c] + i * stride_bytes (x, y, z) with PCL's packed colour word of each at
+ *     rgb[c] + i * rgb_stride_bytes; for 32-byte pcl::PointXYZRGB records rgb[c] = pts[c] + 16 with the same stride.  Its
+ *     result is, bit for bit and in order, what pcc_index_create(pts[c], ...) + pcc_rift_descriptors(...) returns for that
+ *     cloud alone: its histograms are rows out_offsets[c] .. out_offsets[c + 1] of out_histograms, its point indices --
+ *     LOCAL to the cloud, ascending -- the same rows of out_point_index.  No point of another cloud enters a neighbourhood,
+ *     however the clouds overlap in space.  A cloud with n[c] == 0 or without a finite point yields an empty slice (the
+ *     single path answers PCC_ERR_EMPTY there).
+ *   out_histograms[sum(n)][32], out_point_index[sum(n)], out_offsets[n_clouds + 1]: HOST arrays.  mem must be PCC_MEM_HOST
+ *     (PCC_MEM_DEVICE: PCC_ERR_UNSUPPORTED).  n_clouds == 0: PCC_OK, out_offsets[0] = 0, no device is touched.
+ *   Clouds above PCC_OPT_RIFT_BATCH_BRUTE_MAX points take the single path inside the call (same bits).  pcc_index_stats
+ *     afterwards reports in [0] the points whose rows the batch kernels built and in [1] the points of the clouds sent
+ *     through the work handle.
+ *   Refused before the handle is looked at, with pcc_rift_descriptors' messages where it has one: null arrays, a null
+ *     pts[c] or rgb[c] with n[c] > 0, a bad stride or alignment, radii that are not positive and finite, bins other than
+ *     4 x 8 (PCC_ERR_UNSUPPORTED), sum(n) >= 2^31 (PCC_ERR_UNSUPPORTED).  A CSR of 2^32 entries or more over the whole batch
+ *     is PCC_ERR_OVERFLOW. */
+int pcc_rift_descriptors_batch(pcc_index *ctx, size_t n_clouds,
+                               const void *const *pts, const size_t *n, size_t stride_bytes,
+                               const void *const *rgb, size_t rgb_stride_bytes, int mem,
+                               double normal_radius, double gradient_radius, double rift_radius,
+                               int nr_distance_bins, int nr_gradient_bins,
+                               float *out_histograms, int32_t *out_point_index, size_t *out_offsets);
 /* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
  * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
  *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)
@@ -532,7 +567,9 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  radius, clustering, tie flags) since the previous pcc_index_stats call, process-wide -- counted by the PROFILING build
  *  only (libpcc_nn_prof.so, `make prof`; pcc_counts_pairs() == 1), 0 in libpcc_nn.so, [5] queries flagged as tied and [6] indices changed by
  *  the FLANN walk (PCC_TIES_FLANN, last search), [7] queries the 3x3x3 cube of the pruned k = 1 kernel left open
- *  (last search that listed them: from 2M queries on, or PCC_OPT_NN1_KERNEL = 2). */
+ *  (last search that listed them: from 2M queries on, or PCC_OPT_NN1_KERNEL = 2).
+ *  After pcc_rift_descriptors_batch on the handle: [0] points whose radius rows the batch kernels built, [1] points of the
+ *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX). */
 int pcc_index_stats(const pcc_index *index, uint64_t stats[8]);
 /* 1 when this library was built with the pair counter (-DPCC_COUNT_PAIRS: the profiling build), else 0 */
 int pcc_counts_pairs(void);

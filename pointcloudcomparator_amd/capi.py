@@ -20,7 +20,7 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT) = range(1, 26)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX) = range(1, 27)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -36,7 +36,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_sift_keypoints", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -103,6 +103,7 @@ def _load() -> C.CDLL:
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_voxel_grid.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, vp, sz, C.POINTER(sz)]
@@ -666,6 +667,41 @@ class Index:
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
 
+    def rift_descriptors_batch(self, clouds, rgbs=None, normal_radius: float = 0.03, gradient_radius: float = 0.03,
+                               rift_radius: float = 0.05, nr_distance_bins: int = 4, nr_gradient_bins: int = 8):
+        """pcc_rift_descriptors_batch with this handle as the context: the descriptors of every cloud in one call (the
+        reference's per-cluster loop, src/comparator.cpp:1224-1272).  clouds[c]: (n, >= 3) float32 numpy array with rgbs[c]
+        in any of rift_descriptors' three forms, or (n, >= 5) pcl::PointXYZRGB records with rgbs omitted (the colour word is
+        read in place).  Returns one (histograms (m, 32) float32, point index (m,) int32) per cloud, each what
+        Index(clouds[c]).rift_descriptors(rgbs[c]) returns; an empty cloud or one without a finite point gives m = 0.  The
+        cloud the handle indexes is neither read nor changed."""
+        clouds = list(clouds)
+        rgbs = list(clouds if rgbs is None else rgbs)
+        n = len(clouds)
+        assert len(rgbs) == n, "one colour array per cloud"
+        args = [_points(a) for a in clouds]
+        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
+        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
+        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_rift_descriptors_batch takes host arrays"
+        strides = {a[2] for a in args if a[1] > 1}
+        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
+        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
+        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
+        stride = strides.pop() if strides else (single[0][0] if single else 12)
+        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
+        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+        pp = vps(*[a[0] if a[1] else None for a in args])
+        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
+        nn = szs(*[a[1] for a in args])
+        total = sum(a[1] for a in args)
+        hist = np.empty((max(total, 1), 32), dtype=np.float32)
+        index = np.empty(max(total, 1), dtype=np.int32)
+        off = np.zeros(n + 1, dtype=np.uintp)
+        _check(LIB.pcc_rift_descriptors_batch(self._h, n, pp, nn, stride, cp, cstride, MEM_HOST, float(normal_radius), float(gradient_radius),
+                                              float(rift_radius), int(nr_distance_bins), int(nr_gradient_bins), hist.ctypes.data,
+                                              index.ctypes.data, off.ctypes.data))
+        return [(hist[int(off[c]):int(off[c + 1])].copy(), index[int(off[c]):int(off[c + 1])].copy()) for c in range(n)]
+
     def sift_keypoints(self, points, rgb, min_scale: float = 0.005, nr_octaves: int = 5, nr_scales_per_octave: int = 5,
                        min_contrast: float = 0.001):
         """pcc_sift_keypoints: the reference's processSift (src/comparator.cpp:435-469, pcl::SIFTKeypoint) for `points`, an
@@ -811,3 +847,14 @@ def match_knn_batch(pairs, threshold: float = 0.05, ties: int = TIES_LOWEST_INDE
         return ctx.match_knn_batch(pairs, threshold, ties)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
         return own.match_knn_batch(pairs, threshold, ties)
+
+
+def rift_descriptors_batch(clouds, rgbs=None, normal_radius: float = 0.03, gradient_radius: float = 0.03, rift_radius: float = 0.05,
+                           nr_distance_bins: int = 4, nr_gradient_bins: int = 8, ctx=None):
+    """RIFT descriptors of every cloud at once (pcc_rift_descriptors_batch): a list of (histograms, point index) per cloud.
+    ctx: an Index that lends its device, stream and scratch (its own cloud is left as it is); None makes a one-point handle
+    for the call."""
+    if ctx is not None:
+        return ctx.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)

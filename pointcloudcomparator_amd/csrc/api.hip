@@ -23,6 +23,7 @@ unsigned long long pairs_take_grid();
 unsigned long long pairs_take_knn();
 unsigned long long pairs_take_cluster();
 unsigned long long pairs_take_flann();
+unsigned long long pairs_take_rift_batch();
 #endif
 
 static thread_local std::string g_err;
@@ -55,6 +56,7 @@ static bool option_in_range(int option, double value) {
         case PCC_OPT_FUSE_PARAMS: return value >= 0 && value <= 3;
         case PCC_OPT_KNN_RUN: return value >= 1 && value <= 64;
         case PCC_OPT_RIFT_LAYOUT: case PCC_OPT_SIFT_LAYOUT: return value == 0 || value == 1;
+        case PCC_OPT_RIFT_BATCH_BRUTE_MAX: return value >= 0 && value <= 1073741824;
         case PCC_OPT_HOST_PIPE: case PCC_OPT_SCAN_CHAINED: return value == 0 || value == 1;
         default: return value == 0 || value == 1;
     }
@@ -87,6 +89,7 @@ static double* option_slot(Options& o, int option, int** as_int) {
         case PCC_OPT_KNN_RUN: *as_int = &o.knn_run; return nullptr;
         case PCC_OPT_RIFT_LAYOUT: *as_int = &o.rift_layout; return nullptr;
         case PCC_OPT_SIFT_LAYOUT: *as_int = &o.sift_layout; return nullptr;
+        case PCC_OPT_RIFT_BATCH_BRUTE_MAX: *as_int = &o.rift_batch_brute_max; return nullptr;
         default: return nullptr;
     }
 }
@@ -104,7 +107,8 @@ void Options::from_env() {
         {"PCC_GRID_AXES", PCC_OPT_GRID_AXES}, {"PCC_XCD_RUN", PCC_OPT_XCD_RUN},
         {"PCC_FUSE_PARAMS", PCC_OPT_FUSE_PARAMS}, {"PCC_HOST_PIPE", PCC_OPT_HOST_PIPE},
         {"PCC_SCAN_CHAINED", PCC_OPT_SCAN_CHAINED}, {"PCC_KNN_RUN", PCC_OPT_KNN_RUN},
-        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}, {"PCC_SIFT_LAYOUT", PCC_OPT_SIFT_LAYOUT}};
+        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}, {"PCC_SIFT_LAYOUT", PCC_OPT_SIFT_LAYOUT},
+        {"PCC_RIFT_BATCH_BRUTE_MAX", PCC_OPT_RIFT_BATCH_BRUTE_MAX}};
     for (const auto& v : vars) {
         const char* txt = getenv(v.name);
         if (!txt || !*txt) continue;
@@ -563,6 +567,7 @@ int pcc_index_destroy(pcc_index* ix) {
     ix->host_c.release();
     if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
     match_batch_release(ix);
+    rift_batch_release(ix);
     rift_release(ix);
     sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
@@ -850,7 +855,7 @@ int pcc_index_stats(const pcc_index* cix, uint64_t stats[8]) {
 #ifdef PCC_COUNT_PAIRS
     // profiling build: distances evaluated by the pruned kernels (process-wide, every handle) since the previous call
     PCC_HIP(hipStreamSynchronize(ix->stream));
-    ix->stats[4] = pairs_take_grid() + pairs_take_knn() + pairs_take_cluster() + pairs_take_flann();
+    ix->stats[4] = pairs_take_grid() + pairs_take_knn() + pairs_take_cluster() + pairs_take_flann() + pairs_take_rift_batch();
 #endif
     if (ix->stats_pending) {
         PCC_HIP(hipStreamSynchronize(ix->stream));

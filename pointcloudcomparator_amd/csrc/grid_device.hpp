@@ -84,6 +84,15 @@ __device__ __forceinline__ float dist2(float qx, float qy, float qz, const float
     return dist2_nc(qx, qy, qz, r);
 }
 
+// the search key of a candidate: d2 bits << 32 | the index its record carries in w
+__device__ __forceinline__ unsigned long long make_key(float d, const float4& r) {
+    return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned int)__float_as_int(r.w);
+}
+// base + the number of lanes below this one whose bit is set in `mask` (v_mbcnt: two instructions, the base folded in)
+__device__ __forceinline__ unsigned int lanes_below(unsigned long long mask, unsigned int base) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, base));
+}
+
 // lower bound (squared, shrunk) of the distance from q to any point outside the cell cube
 // [x0..x1] x [y0..y1] x [z0..z1]; +inf when the cube covers the whole grid.  (qx, qy, qz): the query in the GRID's frame
 __device__ __forceinline__ float outside_bound2(float qx, float qy, float qz, int x0, int x1, int y0,

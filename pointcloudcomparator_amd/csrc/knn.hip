@@ -14,20 +14,12 @@
 #include "pcc_internal.hpp"
 #include "grid_device.hpp"
 #include "lane_ops.hpp"
+#include <algorithm>
 #include <type_traits>
 #include <cmath>
 #include <cstring>
 
 namespace pcc {
-// base + the number of lanes below this one whose bit is set in `mask` (v_mbcnt: two instructions, the base folded in)
-__device__ __forceinline__ unsigned int lanes_below(unsigned long long mask, unsigned int base) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, base));
-}
-
-__device__ __forceinline__ unsigned long long make_key(float d, const float4& r) {
-    return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned int)__float_as_int(r.w);
-}
-
 // insert key into the ascending list[0..K) (unused slots hold ~0)
 __device__ __forceinline__ void knn_insert(unsigned long long* __restrict__ list, int K, unsigned long long key,
                                            unsigned long long& worst) {
@@ -1570,6 +1562,16 @@ int grid_radius(pcc_index* ix, const float4* q, size_t nq, float r, float r2, in
         PCC_HIP(hipGetLastError());
     }
     ev_mark(ix, EV_MAIN1);
+    return PCC_OK;
+}
+
+// every row of a CSR that another builder filled (rift_batch.hip), sorted ascending in place: k_sort_rows as the grid fill uses it
+int sort_csr_rows(hipStream_t s, const int64_t* offsets, size_t n, unsigned long long* keys) {
+    if (n == 0) return PCC_OK;
+    unsigned int gw = (unsigned int)std::min<size_t>((n + 3) / 4, 8192);  // 4 waves per workgroup, waves loop
+    hipLaunchKernelGGL(k_sort_rows, dim3(gw), dim3(256), 0, s, offsets, (unsigned int)n, keys, 0u, 1, (int32_t*)nullptr, (float*)nullptr,
+                       (const unsigned int*)nullptr, (const unsigned int*)nullptr);
+    PCC_HIP(hipGetLastError());
     return PCC_OK;
 }
 

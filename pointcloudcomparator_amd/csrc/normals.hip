@@ -146,6 +146,24 @@ k_widen_offsets(const unsigned int* __restrict__ off32, unsigned int n_plus_1, i
 
 }  // namespace
 
+// counts off32[n] (off32[n] = 0) -> exclusive offsets in place, off32[n] = the total, and the same widened into off64; the
+// total comes back to the host, which is the one wait of a CSR build
+int csr_offsets(pcc_index* ix, unsigned int* off32, int64_t* off64, size_t n, unsigned long long* total_out) {
+    hipStream_t s = ix->stream;
+    unsigned long long* d_total = &ix->words()->radius_total;
+    PCC_HIP(hipMemsetAsync(d_total, 0, 8, s));
+    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_sum_counts, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const int32_t*>(off32), (unsigned int)n, d_total);
+    unsigned long long total;
+    PCC_TRY(read_back(ix, d_total, &total));
+    if (total >= (1ull << 32)) { set_error("radius neighbourhoods hold %llu entries: more than a 32-bit CSR takes", total); return PCC_ERR_OVERFLOW; }
+    PCC_TRY(launch_exclusive_scan(ix, s, off32, n + 1, ix->vox_b));
+    hipLaunchKernelGGL(k_widen_offsets, dim3(blocks), dim3(256), 0, s, off32, (unsigned int)(n + 1), off64);
+    PCC_HIP(hipGetLastError());
+    *total_out = total;
+    return PCC_OK;
+}
+
 // the sorted self radius rows of the indexed cloud as a CSR: counts, exclusive scan, sorted fill
 int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) {
     hipStream_t s = ix->stream;
@@ -158,16 +176,8 @@ int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys_out
     int64_t* off64 = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(ix->vox_a.p) + (((n + 1) * sizeof(unsigned int) + 15) & ~(size_t)15));
     PCC_HIP(hipMemsetAsync(off32, 0, (n + 1) * sizeof(unsigned int), s));
     PCC_TRY(grid_radius(ix, self, n, (float)radius, r2, reinterpret_cast<int32_t*>(off32), nullptr, nullptr, 0));
-    unsigned long long* d_total = &ix->words()->radius_total;
-    PCC_HIP(hipMemsetAsync(d_total, 0, 8, s));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_sum_counts, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const int32_t*>(off32), (unsigned int)n, d_total);
     unsigned long long total;
-    PCC_TRY(read_back(ix, d_total, &total));
-    if (total >= (1ull << 32)) { set_error("radius neighbourhoods hold %llu entries: more than a 32-bit CSR takes", total); return PCC_ERR_OVERFLOW; }
-    PCC_TRY(launch_exclusive_scan(ix, s, off32, n + 1, ix->vox_b));
-    hipLaunchKernelGGL(k_widen_offsets, dim3(blocks), dim3(256), 0, s, off32, (unsigned int)(n + 1), off64);
-    PCC_HIP(hipGetLastError());
+    PCC_TRY(csr_offsets(ix, off32, off64, n, &total));
     // sorted fill
     PCC_TRY(ix->out_packed.reserve((size_t)(total ? total : 1) * sizeof(unsigned long long)));
     auto* keys = ix->out_packed.as<unsigned long long>();
@@ -177,15 +187,16 @@ int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys_out
     return PCC_OK;
 }
 
-int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out) {
-    hipStream_t s = ix->stream;
-    const size_t n = ix->n_orig;
+int launch_normals_csr(hipStream_t s, const float4* refs, const float4* order, const GridDev* gd, size_t n, const unsigned long long* keys,
+                       const unsigned int* offsets, const float vp[3], float4* out) {
     const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     PCC_HIP(hipMemsetAsync(out, 0xff, n * sizeof(float4), s));
-    hipLaunchKernelGGL(k_normals_csr, dim3(blocks), dim3(256), 0, s, keys, offsets, ix->refs.as<float4>(), ix->cell_refs.as<float4>(),
-                       ix->d_grid.as<GridDev>(), vp[0], vp[1], vp[2], out);
+    hipLaunchKernelGGL(k_normals_csr, dim3(blocks), dim3(256), 0, s, keys, offsets, refs, order, gd, vp[0], vp[1], vp[2], out);
     PCC_HIP(hipGetLastError());
     return PCC_OK;
+}
+int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out) {
+    return launch_normals_csr(ix->stream, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), ix->n_orig, keys, offsets, vp, out);
 }
 
 // NormalEstimation with setRadiusSearch: self radius search (sorted rows, CSR) + the plane fit per row

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
+#include <functional>
 #include <mutex>
 #include <string>
 #include "pcc_nn.h"
@@ -179,6 +180,9 @@ struct Options {
                                     // with the layers of the grid a few rows apart (grid_axes) a run should hold several LAYERS, so that the rows of
                                     // the layer behind are re-read from the same L2: C3 fabric traffic of the search 2.95 -> 2.42 GB per call.  Time,
                                     // on one handle: C3 step 1.3517 (by extent, 32) -> 1.3334 (by extent, 256); x / y / z layout 1.3333 / 1.3316
+    int rift_batch_brute_max = 8192;   // PCC_OPT_RIFT_BATCH_BRUTE_MAX: clouds of a pcc_rift_descriptors_batch call up to this many points get their radius
+                                    // rows from the exhaustive builder over the whole batch (rift_batch.hip); larger ones take the single path, one by
+                                    // one, on a work handle.  Measured (EXPERIMENTS.md, "Batched RIFT descriptors"): a cloud alone is cheaper there from ~4500 points, beside others from ~11 000
     int overlap_prep = 1;           // PCC_OPT_OVERLAP_PREP: a k = 1 search that follows setInputCloud directly packs and sorts its queries on a
                                     // second stream while the build's cell sort is still running (they share nothing but the grid parameters);
                                     // from 2M queries on, 2 = at every size
@@ -272,6 +276,7 @@ struct SiftScratch {
     DevBuf octaves;              // SiftOctave per octave
     DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
 };
+struct RiftBatchScratch;   // rift_batch.hip: the staging buffers, CSR and work handle of pcc_rift_descriptors_batch
 struct MatchBatchScratch;  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
 struct HostPipe;           // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 }  // namespace pcc
@@ -354,6 +359,7 @@ struct pcc_index {
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
     pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
     pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
+    pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -540,10 +546,29 @@ int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out)
 // index; offsets[n + 1]; both stay valid until the next radius search on the handle), and the plane fit over such rows
 int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys, const unsigned int** offsets);
 int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out);
+// the plane fit over the rows of any packed cloud: refs[n], `order` a cell_refs-shaped array whose first gd->n_valid entries name
+// the points to take (their w)
+int launch_normals_csr(hipStream_t s, const float4* refs, const float4* order, const GridDev* gd, size_t n, const unsigned long long* keys,
+                       const unsigned int* offsets, const float vp[3], float4* out);
+// the middle of a CSR build (normals.hip): counts off32[n] (off32[n] = 0) -> exclusive offsets in place (off32[n] = the total) and
+// widened into off64[n + 1]; *total on the host (the build's one wait); 2^32 entries and more are PCC_ERR_OVERFLOW
+int csr_offsets(pcc_index* ix, unsigned int* off32, int64_t* off64, size_t n, unsigned long long* total);
+// knn.hip: every row of a CSR somebody else filled, sorted ascending in place (k_sort_rows)
+int sort_csr_rows(hipStream_t s, const int64_t* offsets, size_t n, unsigned long long* keys);
 // rift.hip: the RIFT descriptor pipeline on device arrays (ix->rift made by the caller); *n_out on the host
 int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
                      double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out);
 void rift_release(pcc_index* ix);  // frees ix->rift
+// the same stages over any packed cloud (rift_batch.hip: the concatenation of a batch): see rift.hip
+typedef std::function<int(double radius, const unsigned long long** keys, const unsigned int** offsets)> RiftRows;
+int rift_stages(pcc_index* ix, const float4* refs, const float4* order, const GridDev* gd, size_t n, const RiftRows& rows,
+                const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius,
+                float* out_hist, int32_t* out_index);
+// rift_batch.hip: pcc_rift_descriptors_batch behind its argument checks (ix->rift made by the caller)
+int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
+                           size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
+                           int32_t* out_index, size_t* out_offsets);
+void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work handle
 // sift.hip: the SIFT keypoint detector on device arrays (ix->sift made by the caller); the keypoints stay in ix->sift->kp
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);

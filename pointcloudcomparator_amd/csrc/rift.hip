@@ -214,16 +214,17 @@ void rift_release(pcc_index* ix) {
     ix->rift = nullptr;
 }
 
-// rgb: the colour words on the device (stride bytes apart); out_hist[n * 32], out_index[n] on the device; *n_out on the host
-int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
-                     double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out) {
+// The stages over ANY packed cloud with sorted radius rows: refs[n] (w = the point's index), `order` a cell_refs-shaped
+// array whose first gd->n_valid entries name the points to take (their w), `rows` the source of the CSR at a radius
+// (keys: d2 bits << 32 | point index, ascending per row; valid until the next call of `rows`).  rgb: the colour words on
+// the device (stride bytes apart); out_hist[n * 32], out_index[n] on the device.  Leaves the exclusive scan of the keep
+// flags in ix->rift->keep: keep[i] = kept descriptors in front of point i, keep[n] = their number.
+int rift_stages(pcc_index* ix, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n, const RiftRows& rows,
+                const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius,
+                float* out_hist, int32_t* out_index) {
     hipStream_t s = ix->stream;
     RiftScratch* r = ix->rift;
-    const size_t n = ix->n_orig;
     const unsigned int un = (unsigned int)n;
-    const float4* refs = ix->refs.as<float4>();
-    const float4* cell_refs = ix->cell_refs.as<float4>();
-    const GridDev* gd = ix->d_grid.as<GridDev>();
     const float origin[3] = {0.f, 0.f, 0.f};
     PCC_TRY(r->normals.reserve(n * sizeof(float4)));
     PCC_TRY(r->inten.reserve(n * sizeof(float)));
@@ -234,17 +235,17 @@ int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride,
     // rows at normal_radius: the plane fit, then (same radius: same rows) the intensity gradient
     const unsigned long long* keys = nullptr;
     const unsigned int* off32 = nullptr;
-    PCC_TRY(radius_csr(ix, normal_radius, &keys, &off32));
-    PCC_TRY(launch_normals_csr(ix, keys, off32, origin, r->normals.as<float4>()));
+    PCC_TRY(rows(normal_radius, &keys, &off32));
+    PCC_TRY(launch_normals_csr(s, refs, cell_refs, gd, n, keys, off32, origin, r->normals.as<float4>()));
     hipLaunchKernelGGL(k_rift_intensity, dim3(blocks), dim3(256), 0, s, rgb, rgb_stride, r->normals.as<float4>(), un, r->inten.as<float>());
     PCC_HIP(hipGetLastError());
-    if (gradient_radius != normal_radius) PCC_TRY(radius_csr(ix, gradient_radius, &keys, &off32));
+    if (gradient_radius != normal_radius) PCC_TRY(rows(gradient_radius, &keys, &off32));
     PCC_HIP(hipMemsetAsync(r->grad.p, 0, n * sizeof(float4), s));
     hipLaunchKernelGGL(k_rift_gradient, dim3(blocks), dim3(256), 0, s, keys, off32, refs, r->inten.as<float>(), r->normals.as<float4>(),
                        cell_refs, gd, r->grad.as<float4>());
     PCC_HIP(hipGetLastError());
     // rows at rift_radius: the histograms
-    PCC_TRY(radius_csr(ix, rift_radius, &keys, &off32));
+    PCC_TRY(rows(rift_radius, &keys, &off32));
     PCC_HIP(hipMemsetAsync(r->keep.p, 0, (n + 1) * sizeof(unsigned int), s));
     if (ix->opt.rift_layout == 1) {
         const unsigned int rb = (unsigned int)std::min<size_t>((n + 7) / 8, 8192);
@@ -260,8 +261,21 @@ int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride,
     const unsigned int cb = (unsigned int)std::min<size_t>((n + 7) / 8, 4096);
     hipLaunchKernelGGL(k_rift_compact, dim3(cb), dim3(256), 0, s, r->hist.as<float>(), r->keep.as<unsigned int>(), un, out_hist, out_index);
     PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+// the indexed cloud of ix: its grid's rows.  rgb: the colour words on the device (stride bytes apart); out_hist[n * 32],
+// out_index[n] on the device; *n_out on the host
+int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
+                     double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out) {
+    const size_t n = ix->n_orig;
+    const RiftRows rows = [ix](double radius, const unsigned long long** keys, const unsigned int** offsets) -> int {
+        return radius_csr(ix, radius, keys, offsets);
+    };
+    PCC_TRY(rift_stages(ix, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, rows, rgb, rgb_stride, normal_radius,
+                        gradient_radius, rift_radius, out_hist, out_index));
     unsigned int kept = 0;
-    PCC_TRY(read_back(ix, r->keep.as<unsigned int>() + n, &kept));
+    PCC_TRY(read_back(ix, ix->rift->keep.as<unsigned int>() + n, &kept));
     *n_out = kept;
     return PCC_OK;
 }

@@ -1,0 +1,346 @@
+// rift_batch.hip -- the RIFT descriptor pipeline for EVERY cluster of a comparison at once (gfx950): pcc_rift_descriptors_batch.
+//
+// The reference computes descriptors one cluster at a time (src/comparator.cpp:1224-1272: processRIFT, :590-684, or
+// processRIFTwithSIFT ending in it, per cluster of both scenes).  One cluster at a time is set_input + pcc_rift_descriptors on
+// a tree of its own: two CSR builds with a wait each, about 25 launches and the final count, never below 0.32 ms however small
+// the cluster (EXPERIMENTS.md, "RIFT descriptors").  Here the clouds of a call are ONE concatenated cloud -- point base[c] + i
+// is point i of cloud c -- with ONE CSR per radius whose rows hold members of the point's own cloud only, and the stages of
+// rift.hip / normals.hip run once over it.  Launches and waits do not depend on the number of clouds.
+//
+// The rows come from an exhaustive builder (k_rift_batch_rows): the reference sends only clusters of up to 700 points down this
+// route, and at that size n^2 distance tests per cloud cost less than any index build.  It is driven by a host-built table of
+// work items (rift_batch_plan.hpp: up to 64 queries of one cloud each, fewer while the table is short).  A workgroup stages its cloud in LDS, 2048 points at a time,
+// tiles in ascending order; each wave takes one query at a time with its lanes over the candidates of the tile; the test is
+// grid_device.hpp's dist2 arithmetic, d < r2 (the grid path's rounding); hits are compacted with a ballot, so a row comes out in
+// candidate (index) order, the count pass and the fill pass agreeing because they are the same code.  Non-finite points carry
+// their raw coordinates: every distance to or from one is NaN or +inf and fails the comparison, so they are in no row and
+// their own rows are empty -- as in the single path.  k_sort_rows (knn.hip) then sorts every row by (d2, index): ascending
+// concatenated index within a cloud is ascending local index, so a row is the single path's row with base[c] added.
+//
+// Clouds above PCC_OPT_RIFT_BATCH_BRUTE_MAX points would make the quadratic builder the bottleneck: they take the single path
+// inside the same call, one by one, on a work handle kept in ctx (as sift.hip keeps one), and their slices are spliced in.
+#include <algorithm>
+#include <vector>
+
+#include "pcc_internal.hpp"
+#include "lane_ops.hpp"
+#include "grid_device.hpp"
+#include "rift_math.hpp"
+#include "rift_batch_plan.hpp"
+
+namespace pcc {
+
+namespace {
+
+// FILL = false: counts[q] = the row length of every query of the item.  FILL = true: the row's keys at offsets[q], in
+// candidate order.  pts: the concatenated cloud, w = bits(concatenated index).
+template <bool FILL>
+__global__ void __launch_bounds__(256)
+k_rift_batch_rows(const RiftBatchItem* __restrict__ items, const float4* __restrict__ pts, float r2, unsigned int* __restrict__ counts,
+                  const unsigned int* __restrict__ offsets, unsigned long long* __restrict__ keys) {
+    __shared__ float4 tile[RB_TILE];
+    __shared__ unsigned int found[RB_QUERIES];  // hits of every query over the tiles so far; a query belongs to one wave
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const RiftBatchItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
+    const float4* __restrict__ cloud = pts + it.base;
+    if (threadIdx.x < RB_QUERIES) found[threadIdx.x] = 0u;
+    for (unsigned int t0 = 0; t0 < it.n; t0 += RB_TILE) {  // block-uniform
+        const unsigned int tn = min(RB_TILE, it.n - t0);
+        __syncthreads();  // (the tile before has been used up; found[] is cleared)
+        for (unsigned int i = threadIdx.x; i < tn; i += 256) tile[i] = cloud[t0 + i];
+        __syncthreads();
+        for (unsigned int qi = wave; qi < it.nq; qi += 4) {  // wave-uniform
+            const unsigned int q = it.base + it.q0 + qi;
+            const float4 qv = pts[q];
+            unsigned int written = found[qi];
+            unsigned int row_beg = 0, row_len = 0;
+            if constexpr (FILL) {
+                row_beg = offsets[q];
+                row_len = offsets[q + 1] - row_beg;
+            }
+            for (unsigned int c0 = 0; c0 < tn; c0 += 64) {
+                const unsigned int c = c0 + lane;
+                const float4 r = tile[min(c, tn - 1u)];
+                const float d = dist2_nc(qv.x, qv.y, qv.z, r);
+                PCC_PAIR(c < tn);
+                const bool hit = c < tn && d < r2;
+                const unsigned long long mask = __ballot(hit);
+                if constexpr (FILL) {
+                    // (a fill can only find what the count found -- same arithmetic --; the bound is belt and braces)
+                    const unsigned int slot = lanes_below(mask, written);
+                    if (hit && slot < row_len) keys[(size_t)row_beg + slot] = make_key(d, r);
+                }
+                written += (unsigned int)__popcll(mask);
+            }
+            if (lane == 0) found[qi] = written;
+        }
+    }
+    if constexpr (!FILL) {
+        __syncthreads();
+        if (threadIdx.x < it.nq) counts[it.base + it.q0 + threadIdx.x] = found[threadIdx.x];
+    }
+}
+
+// After the compaction (pos = the exclusive scan of the keep flags over the concatenation, pos[n] = the kept rows): the rows
+// of cloud c are slice[c] .. slice[c + 1], and every kept point index loses its cloud's base.
+__global__ void __launch_bounds__(256)
+k_rift_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __restrict__ bases, unsigned int n_clouds, unsigned int n,
+                    unsigned int* __restrict__ slice, int32_t* __restrict__ out_index) {
+    const unsigned int stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
+    for (unsigned int c = t; c <= n_clouds; c += stride) slice[c] = pos[bases[c]];
+    const unsigned int kept = pos[n];
+    for (unsigned int row = t; row < kept; row += stride) {
+        const unsigned int i = (unsigned int)out_index[row];
+        // the last cloud whose base is <= i (empty clouds share a base with the cloud behind them: never the answer)
+        unsigned int lo = 0, hi = n_clouds;
+        while (hi - lo > 1) {
+            const unsigned int mid = (lo + hi) >> 1;
+            if (bases[mid] <= i) lo = mid; else hi = mid;
+        }
+        out_index[row] = (int32_t)(i - bases[lo]);
+    }
+}
+
+size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
+
+}  // namespace
+
+struct RiftBatchScratch {
+    pcc_index* work = nullptr;  // the handle clouds above the brute limit are indexed on (the caller's stream, scratch of its own)
+    HostBuf up, down;           // pinned: order words + bases + table + points + colour words going up; the slice bounds coming down
+    DevBuf dev;                 // what `up` holds, on the device
+    DevBuf offs, keys;          // the CSR of the radius in use: uint32 offsets[n + 1] + the same as int64; u64 keys
+    DevBuf slice;               // uint32[n_clouds + 1]
+};
+
+void rift_batch_release(pcc_index* ix) {
+    if (!ix->rift_batch) return;
+    RiftBatchScratch* b = ix->rift_batch;
+    if (b->work) (void)pcc_index_destroy(b->work);
+    b->up.release(); b->down.release();
+    b->dev.release(); b->offs.release(); b->keys.release(); b->slice.release();
+    delete b;
+    ix->rift_batch = nullptr;
+}
+
+// every cloud of the call through the exhaustive builder: out_hist / out_index / offsets (n_clouds + 1) are host arrays
+static int rift_batch_brute(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
+                            size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
+                            int32_t* out_index, size_t* out_offsets) {
+    hipStream_t s = ix->stream;
+    RiftBatchScratch* b = ix->rift_batch;
+    std::vector<uint32_t> bases;
+    std::vector<RiftBatchItem> items;
+    rift_batch_plan(n, n_clouds, &bases, &items);
+    const size_t total = bases[n_clouds];
+    for (size_t c = 0; c <= n_clouds; ++c) out_offsets[c] = 0;
+    if (total == 0) return PCC_OK;
+
+    // ---- one pinned buffer, one copy: the order's n_valid word, bases, table, 16 bytes + 4 bytes a point ------------------
+    const size_t gd_bytes = align_up(sizeof(GridDev), 128), bases_bytes = align_up((n_clouds + 1) * sizeof(uint32_t), 16);
+    const size_t items_bytes = items.size() * sizeof(RiftBatchItem);
+    const size_t pts_at = gd_bytes + bases_bytes + items_bytes, rgb_at = pts_at + total * sizeof(float4);
+    const size_t up_bytes = rgb_at + total * sizeof(uint32_t);
+    PCC_TRY(b->up.reserve(up_bytes));
+    PCC_TRY(b->dev.reserve(up_bytes));
+    char* u = b->up.as<char>();
+    // (the consumers read nothing of the grid but n_valid: every point of the concatenation is taken, in its order -- the
+    // non-finite ones have empty rows and end as the points outside cloud2 do)
+    memset(u, 0, gd_bytes);
+    reinterpret_cast<GridDev*>(u)->n_valid = (unsigned int)total;
+    memcpy(u + gd_bytes, bases.data(), (n_clouds + 1) * sizeof(uint32_t));
+    memcpy(u + gd_bytes + bases_bytes, items.data(), items_bytes);
+    float* p4 = reinterpret_cast<float*>(u + pts_at);
+    uint32_t* words = reinterpret_cast<uint32_t*>(u + rgb_at);
+    for (size_t c = 0; c < n_clouds; ++c) {
+        const char* src = static_cast<const char*>(pts[c]);
+        const char* col = static_cast<const char*>(rgb[c]);
+        for (size_t i = 0; i < n[c]; ++i) {
+            const size_t at = bases[c] + i;
+            const uint32_t w = (uint32_t)at;
+            memcpy(p4 + at * 4, src + i * stride, 12);
+            memcpy(p4 + at * 4 + 3, &w, 4);
+            memcpy(words + at, col + i * rgb_stride, 4);
+        }
+    }
+    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
+    const char* d = b->dev.as<char>();
+    const GridDev* gd = reinterpret_cast<const GridDev*>(d);
+    const unsigned int* d_bases = reinterpret_cast<const unsigned int*>(d + gd_bytes);
+    const RiftBatchItem* d_items = reinterpret_cast<const RiftBatchItem*>(d + gd_bytes + bases_bytes);
+    const float4* d_pts = reinterpret_cast<const float4*>(d + pts_at);
+    const unsigned char* d_rgb = reinterpret_cast<const unsigned char*>(d + rgb_at);
+
+    // ---- the CSR at a radius: count, total (the wait), scan, fill, sort ---------------------------------------------------
+    const size_t off32_bytes = align_up((total + 1) * sizeof(unsigned int), 16);
+    PCC_TRY(b->offs.reserve(off32_bytes + (total + 1) * sizeof(int64_t)));
+    unsigned int* off32 = b->offs.as<unsigned int>();
+    int64_t* off64 = reinterpret_cast<int64_t*>(b->offs.as<char>() + off32_bytes);
+    const unsigned int n_items = (unsigned int)items.size();
+    const RiftRows rows = [&](double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) -> int {
+        const float r2 = (float)(radius * radius);
+        PCC_HIP(hipMemsetAsync(off32, 0, (total + 1) * sizeof(unsigned int), s));
+        hipLaunchKernelGGL((k_rift_batch_rows<false>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, off32, (const unsigned int*)nullptr,
+                           (unsigned long long*)nullptr);
+        PCC_HIP(hipGetLastError());
+        unsigned long long entries = 0;
+        PCC_TRY(csr_offsets(ix, off32, off64, total, &entries));
+        PCC_TRY(b->keys.reserve((size_t)(entries ? entries : 1) * sizeof(unsigned long long)));
+        unsigned long long* keys = b->keys.as<unsigned long long>();
+        if (entries) {
+            hipLaunchKernelGGL((k_rift_batch_rows<true>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, (unsigned int*)nullptr,
+                               (const unsigned int*)off32, keys);
+            PCC_HIP(hipGetLastError());
+            PCC_TRY(sort_csr_rows(s, off64, total, keys));
+        }
+        *keys_out = keys;
+        *offsets_out = off32;
+        return PCC_OK;
+    };
+
+    // ---- the stages of the single call, once over the concatenation -------------------------------------------------------
+    RiftScratch* r = ix->rift;
+    PCC_TRY(r->out_hist.reserve(total * RIFT_BINS * sizeof(float)));
+    PCC_TRY(r->out_index.reserve(total * sizeof(int32_t)));
+    PCC_TRY(rift_stages(ix, d_pts, d_pts, gd, total, rows, d_rgb, sizeof(uint32_t), normal_radius, gradient_radius, rift_radius,
+                        r->out_hist.as<float>(), r->out_index.as<int32_t>()));
+    PCC_TRY(b->slice.reserve((n_clouds + 1) * sizeof(unsigned int)));
+    PCC_TRY(b->down.reserve((n_clouds + 1) * sizeof(unsigned int)));
+    const unsigned int fb = (unsigned int)std::min<size_t>((std::max(total, n_clouds + 1) + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_rift_batch_finish, dim3(fb), dim3(256), 0, s, r->keep.as<unsigned int>(), d_bases, (unsigned int)n_clouds,
+                       (unsigned int)total, b->slice.as<unsigned int>(), r->out_index.as<int32_t>());
+    PCC_HIP(hipGetLastError());
+    // the slice bounds in one copy, then the rows that were written in one copy each
+    PCC_HIP(hipMemcpyAsync(b->down.p, b->slice.p, (n_clouds + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+    PCC_HIP(hipStreamSynchronize(s));
+    const unsigned int* h_slice = b->down.as<unsigned int>();
+    for (size_t c = 0; c <= n_clouds; ++c) out_offsets[c] = h_slice[c];
+    const size_t kept = h_slice[n_clouds];
+    if (kept) {
+        PCC_HIP(hipMemcpyAsync(out_hist, r->out_hist.p, kept * RIFT_BINS * sizeof(float), hipMemcpyDeviceToHost, s));
+        PCC_HIP(hipMemcpyAsync(out_index, r->out_index.p, kept * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        PCC_HIP(hipStreamSynchronize(s));
+    }
+    return PCC_OK;
+}
+
+static bool any_finite(const void* pts, size_t n, size_t stride) {
+    const char* p = static_cast<const char*>(pts);
+    for (size_t i = 0; i < n; ++i) {
+        float v[3];
+        memcpy(v, p + i * stride, 12);
+        if ((v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f) return true;
+    }
+    return false;
+}
+
+int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
+                           size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
+                           int32_t* out_index, size_t* out_offsets) {
+    if (!ix->rift_batch) ix->rift_batch = new RiftBatchScratch();
+    RiftBatchScratch* b = ix->rift_batch;
+    const size_t brute_max = (size_t)ix->opt.rift_batch_brute_max;
+    size_t n_brute = 0, n_large = 0;
+    for (size_t c = 0; c < n_clouds; ++c) (n[c] > brute_max ? n_large : n_brute) += n[c];
+    ix->stats[0] = n_brute;
+    ix->stats[1] = n_large;
+    ix->stats_pending = false;
+    if (n_large == 0)
+        return rift_batch_brute(ix, n_clouds, pts, n, stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius, out_hist, out_index,
+                                out_offsets);
+
+    // ---- some clouds are above the limit: the others as a batch into arrays of their own, these one by one, then the splice --
+    std::vector<size_t> small_n(n, n + n_clouds), small_off(n_clouds + 1, 0);
+    for (size_t c = 0; c < n_clouds; ++c)
+        if (n[c] > brute_max) small_n[c] = 0;  // (an empty cloud of the batch: its slice stays empty)
+    std::vector<float> small_hist(std::max<size_t>(n_brute, 1) * RIFT_BINS);
+    std::vector<int32_t> small_index(std::max<size_t>(n_brute, 1));
+    PCC_TRY(rift_batch_brute(ix, n_clouds, pts, small_n.data(), stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius,
+                             small_hist.data(), small_index.data(), small_off.data()));
+    if (!b->work) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &b->work));
+    pcc_index* w = b->work;
+    // the work handle's launches join the caller's queue for the length of this call, under the caller's options
+    struct Borrow {
+        pcc_index* w;
+        ~Borrow() { w->stream = w->own_stream; }
+    } borrow{w};
+    w->stream = ix->stream;
+    w->opt = ix->opt;
+    size_t at = 0;
+    for (size_t c = 0; c < n_clouds; ++c) {
+        out_offsets[c] = at;
+        if (n[c] <= brute_max) {
+            const size_t m = small_off[c + 1] - small_off[c];
+            if (m) {
+                memcpy(out_hist + at * RIFT_BINS, small_hist.data() + small_off[c] * RIFT_BINS, m * RIFT_BINS * sizeof(float));
+                memcpy(out_index + at, small_index.data() + small_off[c], m * sizeof(int32_t));
+            }
+            at += m;
+            continue;
+        }
+        if (!any_finite(pts[c], n[c], stride)) continue;  // (the single path answers PCC_ERR_EMPTY there)
+        size_t m = 0;
+        PCC_TRY(pcc_index_set_input(w, pts[c], n[c], stride, 3, PCC_MEM_HOST));
+        PCC_TRY(pcc_rift_descriptors(w, rgb[c], rgb_stride, PCC_MEM_HOST, normal_radius, gradient_radius, rift_radius, RIFT_D_BINS, RIFT_G_BINS,
+                                     out_hist + at * RIFT_BINS, out_index + at, &m));
+        at += m;
+    }
+    out_offsets[n_clouds] = at;
+    return PCC_OK;
+}
+
+PCC_PAIRS_TAKE(rift_batch)
+
+}  // namespace pcc
+
+extern "C" {
+
+int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
+                               size_t rgb_stride, int mem, double normal_radius, double gradient_radius, double rift_radius,
+                               int nr_distance_bins, int nr_gradient_bins, float* out_hist, int32_t* out_index, size_t* out_offsets) {
+    using namespace pcc;
+    // the arguments first: all of it host arithmetic, refused before the handle or any device is looked at
+    PCC_TRY(check_mem(mem));
+    if (mem != PCC_MEM_HOST) { set_error("pcc_rift_descriptors_batch takes host arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
+    PCC_TRY(check_points(nullptr, 0, stride, mem));  // (the stride alone)
+    if (rgb_stride < 4 || rgb_stride % 4) {
+        set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
+        return PCC_ERR_INVALID;
+    }
+    if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
+    if (n_clouds >= (1ull << 31)) { set_error("more than 2^31 clouds"); return PCC_ERR_UNSUPPORTED; }
+    if (n_clouds && (!pts || !n || !rgb || !out_hist || !out_index)) { set_error("null array argument"); return PCC_ERR_INVALID; }
+    for (double r : {normal_radius, gradient_radius, rift_radius})
+        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
+    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
+        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    size_t total = 0;
+    for (size_t c = 0; c < n_clouds; ++c) {
+        PCC_TRY(check_points(pts[c], n[c], stride, mem));
+        if (n[c] && !rgb[c]) { set_error("null colour pointer"); return PCC_ERR_INVALID; }
+        if (n[c] && (reinterpret_cast<uintptr_t>(rgb[c]) % 4 || reinterpret_cast<uintptr_t>(pts[c]) % 4)) {
+            set_error("points and colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
+            return PCC_ERR_INVALID;
+        }
+        total += n[c];
+        if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
+    }
+    if (n_clouds == 0) { out_offsets[0] = 0; return PCC_OK; }  // (no device is touched: not even the handle's)
+    if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) { set_error("hipSetDevice(%d) failed", ctx->device); return PCC_ERR_DEVICE; }
+    entered(ctx);
+    ev_next(ctx);
+    ev_mark(ctx, EV_CALL0);
+    if (!ctx->rift) ctx->rift = new RiftScratch();
+    const int st = rift_descriptors_batch(ctx, n_clouds, pts, n, stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius, out_hist,
+                                          out_index, out_offsets);
+    ev_mark(ctx, EV_CALL1);
+    return st;
+}
+
+}  // extern "C"
