@@ -1,12 +1,10 @@
-// api.hip -- the C-ABI of libpcc_nn (include/pcc_nn.h) on top of the gfx950 kernels.
+// api.hip -- the handle of libpcc_nn's C-ABI (include/pcc_nn.h) -- lifecycle, options, streams, staging of clouds -- and the point
+// searches on it; every other operation's entry points live beside its kernels.
 // Host-side glue only: argument checks, H2D/D2H staging, launch order.  There is
 // no CPU compute fallback: without a HIP device every entry point fails with
 // PCC_ERR_DEVICE.
-#include "pcc_internal.hpp"
-#include "rift_math.hpp"
-#include "sift_math.hpp"
+#include "entry.hpp"
 #include <atomic>
-#include "rigid_solve.hpp"
 #include "host_pipe.hpp"
 #include <cstdarg>
 #include <cstdio>
@@ -36,88 +34,63 @@ void set_error(const char* fmt, ...) {
     g_err = buf;
 }
 
-// the range every option value must lie in, whoever sets it (pcc_index_set_option or a PCC_* environment default)
-static bool option_in_range(int option, double value) {
-    if (!std::isfinite(value)) return false;
-    switch (option) {
-        case PCC_OPT_GRID_PPC: return value > 0 && value <= 1024;
-        case PCC_OPT_GRID_TRIM: return value >= 0 && value <= 8;
-        case PCC_OPT_FAR_MODE: return value >= -1 && value <= 1;
-        case PCC_OPT_SORT_MP_MIN: case PCC_OPT_SORT_MP_MIN_Q: return value >= 0;
-        case PCC_OPT_NN1_KERNEL: return value >= 0 && value <= 3;
-        case PCC_OPT_EC_CELLS: return value >= 0 && value <= 4;
-        case PCC_OPT_KNN_CACHE_K: return value >= 0 && value <= 512;
-        case PCC_OPT_NN1_DENSE_MIN: return value >= 1 && value <= 1000000;
-        case PCC_OPT_FLANN_SPLIT: return value >= 0 && value <= 2;
-        case PCC_OPT_SORT_STAGE1: return value >= 0 && value <= 2;
-        case PCC_OPT_OVERLAP_PREP: return value >= 0 && value <= 2;
-        case PCC_OPT_GRID_AXES: return value >= -2 && value <= 5;
-        case PCC_OPT_XCD_RUN: return value >= 1 && value <= 4096;
-        case PCC_OPT_FUSE_PARAMS: return value >= 0 && value <= 3;
-        case PCC_OPT_KNN_RUN: return value >= 1 && value <= 64;
-        case PCC_OPT_RIFT_LAYOUT: case PCC_OPT_SIFT_LAYOUT: return value == 0 || value == 1;
-        case PCC_OPT_RIFT_BATCH_BRUTE_MAX: return value >= 0 && value <= 1073741824;
-        case PCC_OPT_HOST_PIPE: case PCC_OPT_SCAN_CHAINED: return value == 0 || value == 1;
-        default: return value == 0 || value == 1;
-    }
-}
-static double* option_slot(Options& o, int option, int** as_int) {
-    *as_int = nullptr;
-    switch (option) {
-        case PCC_OPT_GRID_PPC: return &o.grid_ppc;
-        case PCC_OPT_SORT_MP_MIN: return &o.sort_mp_min;
-        case PCC_OPT_SORT_MP_MIN_Q: return &o.sort_mp_min_q;
-        case PCC_OPT_GRID_TRIM: *as_int = &o.grid_trim; return nullptr;
-        case PCC_OPT_FAR_MODE: *as_int = &o.far_mode; return nullptr;
-        case PCC_OPT_ICP_WARM: *as_int = &o.icp_warm; return nullptr;
-        case PCC_OPT_ICP_DEVICE_LOOP: *as_int = &o.icp_device_loop; return nullptr;
-        case PCC_OPT_EC_CELLS: *as_int = &o.ec_cells; return nullptr;
-        case PCC_OPT_NN1_KERNEL: *as_int = &o.nn1_kernel; return nullptr;
-        case PCC_OPT_FLANN_SPLIT: *as_int = &o.flann_split; return nullptr;
-        case PCC_OPT_NN1_DENSE_MIN: *as_int = &o.nn1_dense_min; return nullptr;
-        case PCC_OPT_KNN_KERNEL: *as_int = &o.knn_kernel; return nullptr;
-        case PCC_OPT_KNN_CACHE_K: *as_int = &o.knn_cache_k; return nullptr;
-        case PCC_OPT_NN1_OPEN_FLAT: *as_int = &o.nn1_open_flat; return nullptr;
-        case PCC_OPT_SORT_STAGE1: *as_int = &o.sort_stage1; return nullptr;
-        case PCC_OPT_ICP_SORTED: *as_int = &o.icp_sorted; return nullptr;
-        case PCC_OPT_OVERLAP_PREP: *as_int = &o.overlap_prep; return nullptr;
-        case PCC_OPT_GRID_AXES: *as_int = &o.grid_axes; return nullptr;
-        case PCC_OPT_XCD_RUN: *as_int = &o.xcd_run; return nullptr;
-        case PCC_OPT_FUSE_PARAMS: *as_int = &o.fuse_params; return nullptr;
-        case PCC_OPT_HOST_PIPE: *as_int = &o.host_pipe; return nullptr;
-        case PCC_OPT_SCAN_CHAINED: *as_int = &o.scan_chained; return nullptr;
-        case PCC_OPT_KNN_RUN: *as_int = &o.knn_run; return nullptr;
-        case PCC_OPT_RIFT_LAYOUT: *as_int = &o.rift_layout; return nullptr;
-        case PCC_OPT_SIFT_LAYOUT: *as_int = &o.sift_layout; return nullptr;
-        case PCC_OPT_RIFT_BATCH_BRUTE_MAX: *as_int = &o.rift_batch_brute_max; return nullptr;
-        default: return nullptr;
-    }
+// Every option of a handle, once: its id, the PCC_* environment variable that supplies a new handle's default, the member of
+// Options it lives in (an int or a double) and the values it takes, whoever sets it (pcc_index_set_option or the environment).
+// An int option takes any value inside its range and keeps its truncation.
+struct OptionRow {
+    enum Kind { CLOSED, ABOVE_LO, FLAG };  // lo <= v <= hi; lo < v <= hi; exactly 0 or 1
+    int id;
+    const char* env;
+    int Options::*i;
+    double Options::*d;
+    double lo, hi;  // (hi = HUGE_VAL: no upper bound)
+    Kind kind;
+    bool takes(double v) const { return std::isfinite(v) && (kind == FLAG ? v == 0 || v == 1 : (kind == ABOVE_LO ? v > lo : v >= lo) && v <= hi); }
+};
+static const OptionRow g_options[] = {
+    {PCC_OPT_GRID_PPC, "PCC_GRID_PPC", nullptr, &Options::grid_ppc, 0, 1024, OptionRow::ABOVE_LO},
+    {PCC_OPT_GRID_TRIM, "PCC_GRID_TRIM", &Options::grid_trim, nullptr, 0, 8, OptionRow::CLOSED},
+    {PCC_OPT_FAR_MODE, "PCC_GRID_FAR", &Options::far_mode, nullptr, -1, 1, OptionRow::CLOSED},
+    {PCC_OPT_ICP_WARM, "PCC_ICP_WARM", &Options::icp_warm, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_ICP_DEVICE_LOOP, "PCC_ICP_DEVICE_LOOP", &Options::icp_device_loop, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_EC_CELLS, "PCC_EC_CELLS", &Options::ec_cells, nullptr, 0, 4, OptionRow::CLOSED},
+    {PCC_OPT_SORT_MP_MIN, "PCC_SORT_MP_MIN", nullptr, &Options::sort_mp_min, 0, HUGE_VAL, OptionRow::CLOSED},
+    {PCC_OPT_SORT_MP_MIN_Q, "PCC_SORT_MP_MIN_Q", nullptr, &Options::sort_mp_min_q, 0, HUGE_VAL, OptionRow::CLOSED},
+    {PCC_OPT_NN1_KERNEL, "PCC_NN1_KERNEL", &Options::nn1_kernel, nullptr, 0, 3, OptionRow::CLOSED},
+    {PCC_OPT_FLANN_SPLIT, "PCC_FLANN_SPLIT", &Options::flann_split, nullptr, 0, 2, OptionRow::CLOSED},
+    {PCC_OPT_NN1_DENSE_MIN, "PCC_NN1_DENSE_MIN", &Options::nn1_dense_min, nullptr, 1, 1000000, OptionRow::CLOSED},
+    {PCC_OPT_KNN_KERNEL, "PCC_KNN_KERNEL", &Options::knn_kernel, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_KNN_CACHE_K, "PCC_KNN_CACHE_K", &Options::knn_cache_k, nullptr, 0, 512, OptionRow::CLOSED},
+    {PCC_OPT_NN1_OPEN_FLAT, "PCC_NN1_OPEN_FLAT", &Options::nn1_open_flat, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_SORT_STAGE1, "PCC_SORT_STAGE1", &Options::sort_stage1, nullptr, 0, 2, OptionRow::CLOSED},
+    {PCC_OPT_ICP_SORTED, "PCC_ICP_SORTED", &Options::icp_sorted, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_OVERLAP_PREP, "PCC_OVERLAP_PREP", &Options::overlap_prep, nullptr, 0, 2, OptionRow::CLOSED},
+    {PCC_OPT_GRID_AXES, "PCC_GRID_AXES", &Options::grid_axes, nullptr, -2, 5, OptionRow::CLOSED},
+    {PCC_OPT_XCD_RUN, "PCC_XCD_RUN", &Options::xcd_run, nullptr, 1, 4096, OptionRow::CLOSED},
+    {PCC_OPT_FUSE_PARAMS, "PCC_FUSE_PARAMS", &Options::fuse_params, nullptr, 0, 3, OptionRow::CLOSED},
+    {PCC_OPT_HOST_PIPE, "PCC_HOST_PIPE", &Options::host_pipe, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_SCAN_CHAINED, "PCC_SCAN_CHAINED", &Options::scan_chained, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_KNN_RUN, "PCC_KNN_RUN", &Options::knn_run, nullptr, 1, 64, OptionRow::CLOSED},
+    {PCC_OPT_RIFT_LAYOUT, "PCC_RIFT_LAYOUT", &Options::rift_layout, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_SIFT_LAYOUT, "PCC_SIFT_LAYOUT", &Options::sift_layout, nullptr, 0, 1, OptionRow::FLAG},
+    {PCC_OPT_RIFT_BATCH_BRUTE_MAX, "PCC_RIFT_BATCH_BRUTE_MAX", &Options::rift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
+};
+static const OptionRow* option_row(int option) {
+    for (const OptionRow& r : g_options)
+        if (r.id == option) return &r;
+    return nullptr;
 }
 
 // PCC_* environment variables give a new handle its defaults; a value outside the option's range is ignored (the
 // built-in default stays), exactly what pcc_index_set_option would have refused
 void Options::from_env() {
-    static const struct { const char* name; int option; } vars[] = {
-        {"PCC_GRID_PPC", PCC_OPT_GRID_PPC}, {"PCC_GRID_TRIM", PCC_OPT_GRID_TRIM}, {"PCC_GRID_FAR", PCC_OPT_FAR_MODE},
-        {"PCC_ICP_WARM", PCC_OPT_ICP_WARM}, {"PCC_ICP_DEVICE_LOOP", PCC_OPT_ICP_DEVICE_LOOP}, {"PCC_EC_CELLS", PCC_OPT_EC_CELLS},
-        {"PCC_SORT_MP_MIN", PCC_OPT_SORT_MP_MIN}, {"PCC_SORT_MP_MIN_Q", PCC_OPT_SORT_MP_MIN_Q}, {"PCC_NN1_KERNEL", PCC_OPT_NN1_KERNEL},
-        {"PCC_FLANN_SPLIT", PCC_OPT_FLANN_SPLIT}, {"PCC_NN1_DENSE_MIN", PCC_OPT_NN1_DENSE_MIN}, {"PCC_KNN_KERNEL", PCC_OPT_KNN_KERNEL},
-        {"PCC_KNN_CACHE_K", PCC_OPT_KNN_CACHE_K}, {"PCC_NN1_OPEN_FLAT", PCC_OPT_NN1_OPEN_FLAT}, {"PCC_SORT_STAGE1", PCC_OPT_SORT_STAGE1},
-        {"PCC_ICP_SORTED", PCC_OPT_ICP_SORTED}, {"PCC_OVERLAP_PREP", PCC_OPT_OVERLAP_PREP},
-        {"PCC_GRID_AXES", PCC_OPT_GRID_AXES}, {"PCC_XCD_RUN", PCC_OPT_XCD_RUN},
-        {"PCC_FUSE_PARAMS", PCC_OPT_FUSE_PARAMS}, {"PCC_HOST_PIPE", PCC_OPT_HOST_PIPE},
-        {"PCC_SCAN_CHAINED", PCC_OPT_SCAN_CHAINED}, {"PCC_KNN_RUN", PCC_OPT_KNN_RUN},
-        {"PCC_RIFT_LAYOUT", PCC_OPT_RIFT_LAYOUT}, {"PCC_SIFT_LAYOUT", PCC_OPT_SIFT_LAYOUT},
-        {"PCC_RIFT_BATCH_BRUTE_MAX", PCC_OPT_RIFT_BATCH_BRUTE_MAX}};
-    for (const auto& v : vars) {
-        const char* txt = getenv(v.name);
+    for (const OptionRow& r : g_options) {
+        const char* txt = getenv(r.env);
         if (!txt || !*txt) continue;
         char* end = nullptr;
         const double value = strtod(txt, &end);
-        int* pi = nullptr;
-        double* pd = option_slot(*this, v.option, &pi);
-        if (end == txt || !option_in_range(v.option, pi ? std::trunc(value) : value)) continue;
-        if (pd) *pd = value; else *pi = (int)value;
+        if (end == txt || !r.takes(r.i ? std::trunc(value) : value)) continue;
+        if (r.d) this->*r.d = value; else this->*r.i = (int)value;
     }
 }
 
@@ -172,15 +145,6 @@ void HostBuf::release() {
     p = nullptr;
     cap = 0;
 }
-
-#define PCC_ENTER(ix)                                                         \
-    if (!(ix)) { pcc::set_error("null index"); return PCC_ERR_INVALID; }      \
-    std::lock_guard<std::mutex> _lock((ix)->mu);                              \
-    pcc::DeviceGuard _guard((ix)->device);                                    \
-    if (!_guard.ok) { pcc::set_error("hipSetDevice(%d) failed", (ix)->device); return PCC_ERR_DEVICE; } \
-    pcc::entered(ix);
-// entry points that put nothing on the stream leave "the build was the last thing enqueued" as they found it
-#define PCC_NOTHING_ENQUEUED(ix) (ix)->build_fresh = (ix)->after_build
 
 // Stage a caller cloud (host or device AoS) as packed float4 on the device.
 // host: the raw array (or, for large pageable clouds, its x / y / z alone: host_pipe.hpp) to the device, then the pack kernel.
@@ -258,69 +222,15 @@ int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int me
     return PCC_OK;
 }
 
-// ---- caller arrays that are not point clouds (PCC_MEM_HOST or PCC_MEM_DEVICE) -----------------------------------------------
-// An input on the device: the caller's own array, or for host memory a copy in `buf`.
-template <class T>
-static int stage_in(pcc_index* ix, const T* user, size_t count, int mem, DevBuf& buf, const T** dev) {
-    *dev = user;
-    if (mem != PCC_MEM_HOST) return PCC_OK;
-    PCC_TRY(buf.reserve(count * sizeof(T)));
-    PCC_HIP(hipMemcpyAsync(buf.p, user, count * sizeof(T), hipMemcpyHostToDevice, ix->stream));
-    *dev = buf.as<T>();
-    return PCC_OK;
-}
-
-// A radius fill's row offsets (nq + 1 of them) on the device, and their total offsets[nq] on the host.
-static int stage_offsets(pcc_index* ix, const int64_t* offsets, size_t nq, int mem, const int64_t** doff, int64_t* total) {
-    PCC_TRY(stage_in(ix, offsets, nq + 1, mem, ix->scratch_d, doff));
-    if (mem == PCC_MEM_HOST) {
-        *total = offsets[nq];
-    } else {
-        PCC_HIP(hipMemcpyAsync(total, offsets + nq, sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    if (*total < 0) { set_error("negative total"); return PCC_ERR_INVALID; }
-    return PCC_OK;
-}
-
-// A result array: the kernels write `dev`, which is the caller's own array in device memory and `buf` in host memory (nullptr
-// when the caller passed none).  finish() hands the results of a call over.
-template <class T>
-struct Out {
-    T* user = nullptr;
-    size_t count = 0;
-    T* dev = nullptr;
-    int stage(T* u, size_t n, int mem, DevBuf& buf) {
-        user = dev = u;
-        count = n;
-        if (mem != PCC_MEM_HOST) return PCC_OK;
-        PCC_TRY(buf.reserve(count * sizeof(T)));
-        if (user) dev = buf.as<T>();
-        return PCC_OK;
-    }
-};
-
-// one result into the caller's host array: large pageable arrays through the host pipe (host_pipe.hpp), else one copy
-template <class T>
-static int deliver(pcc_index* ix, const Out<T>& o) {
-    if (!o.user || o.count == 0) return PCC_OK;
-    const size_t bytes = o.count * sizeof(T);
-    if (ix->opt.host_pipe && bytes >= PIPE_MIN_BYTES && !host_pointer_is_pinned(o.user)) {
+// one result into the caller's host array (entry.hpp: finish): large pageable arrays through the host pipe (host_pipe.hpp), else one copy
+int deliver(pcc_index* ix, const void* dev, void* user, size_t bytes) {
+    if (!user || bytes == 0) return PCC_OK;
+    if (ix->opt.host_pipe && bytes >= PIPE_MIN_BYTES && !host_pointer_is_pinned(user)) {
         if (!ix->pipe) ix->pipe = new HostPipe();
         ix->small_raw_n = 0;  // (as in stage_points)
-        return ix->pipe->download(ix->stream, reinterpret_cast<const char*>(o.dev), reinterpret_cast<char*>(o.user), bytes);
+        return ix->pipe->download(ix->stream, static_cast<const char*>(dev), static_cast<char*>(user), bytes);
     }
-    PCC_HIP(hipMemcpyAsync(o.user, o.dev, bytes, hipMemcpyDeviceToHost, ix->stream));
-    return PCC_OK;
-}
-// host memory: every result in turn, then one wait.  Device memory: nothing to do.
-template <class... T>
-static int finish(pcc_index* ix, int mem, const Out<T>&... outs) {
-    if (mem != PCC_MEM_HOST) return PCC_OK;
-    int st = PCC_OK;
-    (void)(... && ((st = deliver(ix, outs)) == PCC_OK));  // (up to the first failure)
-    PCC_TRY(st);
-    PCC_HIP(hipStreamSynchronize(ix->stream));
+    PCC_HIP(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, ix->stream));
     return PCC_OK;
 }
 
@@ -532,12 +442,40 @@ struct PrepOverlap {
     ~PrepOverlap() { (void)end(); }
 };
 
+int ensure_grid(pcc_index* ix) {
+    if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
+    if (!ix->has_grid) PCC_TRY(grid_build(ix));
+    return PCC_OK;
+}
+
+// shared by pcc_index_create and pcc_index_clone_to_device: an empty handle on `device`
+int make_handle(int device, int engine, pcc_index** out) {
+    pcc_index* ix = new pcc_index();
+    ix->device = device;
+    ix->opt.from_env();
+    DeviceGuard g(device);
+    int st = PCC_OK;
+    auto fail = [&](int s) { pcc_index_destroy(ix); return s; };
+    if (!g.ok) { set_error("hipSetDevice(%d) failed", device); return fail(PCC_ERR_DEVICE); }
+    if (hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(PCC_ERR_DEVICE); }
+    ix->stream = ix->own_stream;
+    if (hipHostMalloc((void**)&ix->pinned, sizeof(PinnedWords), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
+    if ((st = ix->words_buf.reserve(sizeof(DevWords))) != PCC_OK) return fail(st);
+    if (hipMemset(ix->words_buf.p, 0, sizeof(DevWords)) != hipSuccess) { set_error("hipMemset failed"); return fail(PCC_ERR_DEVICE); }  // (the ticket words start at 0)
+    if ((st = ix->blk_stats.reserve(PACK_MAX_BLOCKS * 8 * sizeof(float))) != PCC_OK) return fail(st);
+    ix->engine_requested = engine;
+    ix->engine = engine;
+    memset(ix->pinned, 0, sizeof(PinnedWords));
+    if (hipHostMalloc((void**)&ix->h_grid, sizeof(GridDev), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
+    memset(ix->h_grid, 0, sizeof(GridDev));
+    *out = ix;
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
-
 extern "C" {
-
 int pcc_version(void) { return PCC_VERSION; }
 const char* pcc_last_error(void) { return g_err.c_str(); }
 
@@ -581,30 +519,6 @@ int pcc_index_destroy(pcc_index* ix) {
     return PCC_OK;
 }
 
-// shared by pcc_index_create and pcc_index_clone_to_device: an empty handle on `device`
-static int new_handle(int device, int engine, pcc_index** out) {
-    pcc_index* ix = new pcc_index();
-    ix->device = device;
-    ix->opt.from_env();
-    DeviceGuard g(device);
-    int st = PCC_OK;
-    auto fail = [&](int s) { pcc_index_destroy(ix); return s; };
-    if (!g.ok) { set_error("hipSetDevice(%d) failed", device); return fail(PCC_ERR_DEVICE); }
-    if (hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(PCC_ERR_DEVICE); }
-    ix->stream = ix->own_stream;
-    if (hipHostMalloc((void**)&ix->pinned, sizeof(PinnedWords), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
-    if ((st = ix->words_buf.reserve(sizeof(DevWords))) != PCC_OK) return fail(st);
-    if (hipMemset(ix->words_buf.p, 0, sizeof(DevWords)) != hipSuccess) { set_error("hipMemset failed"); return fail(PCC_ERR_DEVICE); }  // (the ticket words start at 0)
-    if ((st = ix->blk_stats.reserve(PACK_MAX_BLOCKS * 8 * sizeof(float))) != PCC_OK) return fail(st);
-    ix->engine_requested = engine;
-    ix->engine = engine;
-    memset(ix->pinned, 0, sizeof(PinnedWords));
-    if (hipHostMalloc((void**)&ix->h_grid, sizeof(GridDev), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
-    memset(ix->h_grid, 0, sizeof(GridDev));
-    *out = ix;
-    return PCC_OK;
-}
-
 int pcc_index_create(const void* pts, size_t n, size_t stride, int dim, int mem, int device, int engine,
                      pcc_index** out) {
     if (!out) { set_error("null out"); return PCC_ERR_INVALID; }
@@ -617,7 +531,7 @@ int pcc_index_create(const void* pts, size_t n, size_t stride, int dim, int mem,
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available (libpcc_nn has no CPU path)"); return PCC_ERR_DEVICE; }
     if (device < 0 || device >= ndev) { set_error("device %d out of range (%d present)", device, ndev); return PCC_ERR_INVALID; }
     pcc_index* ix = nullptr;
-    PCC_TRY(new_handle(device, engine, &ix));
+    PCC_TRY(make_handle(device, engine, &ix));
     DeviceGuard g(device);
     int st = PCC_OK;
     auto fail = [&](int s) { pcc_index_destroy(ix); return s; };
@@ -644,7 +558,7 @@ int pcc_index_clone_to_devices(pcc_index* src, const int* devices, int count, pc
     if (count == 0) return PCC_OK;
     // `src` stays locked until every peer copy has landed: a concurrent pcc_index_set_input on it may free or rewrite
     // the packed cloud the copies read
-    std::lock_guard<std::mutex> lock(src->mu);
+    HandleLock lock(src->mu);  // (no call ON src: it keeps its "the build was the last thing enqueued")
     {
         DeviceGuard g(src->device);
         if (!g.ok) { set_error("hipSetDevice(%d) failed", src->device); return PCC_ERR_DEVICE; }
@@ -661,7 +575,7 @@ int pcc_index_clone_to_devices(pcc_index* src, const int* devices, int count, pc
     auto one = [&](int k) {
         auto run = [&]() -> int {
             pcc_index* ix = nullptr;
-            PCC_TRY(new_handle(devices[k], src->engine_requested, &ix));
+            PCC_TRY(make_handle(devices[k], src->engine_requested, &ix));
             out[k] = ix;
             ix->opt = src->opt;
             ix->tie_mode = src->tie_mode;
@@ -817,12 +731,11 @@ int pcc_index_set_tie_order(pcc_index* ix, int ties) {
 int pcc_index_set_option(pcc_index* ix, int option, double value) {
     PCC_ENTER(ix);
     PCC_NOTHING_ENQUEUED(ix);
-    int* pi = nullptr;
-    double* pd = option_slot(ix->opt, option, &pi);
-    if (!pd && !pi) { set_error("unknown option %d", option); return PCC_ERR_INVALID; }
+    const OptionRow* r = option_row(option);
+    if (!r) { set_error("unknown option %d", option); return PCC_ERR_INVALID; }
     if (!std::isfinite(value)) { set_error("option %d: non-finite value", option); return PCC_ERR_INVALID; }
-    if (!option_in_range(option, value)) { set_error("option %d: value %g out of range", option, value); return PCC_ERR_INVALID; }
-    if (pd) *pd = value; else *pi = (int)value;
+    if (!r->takes(value)) { set_error("option %d: value %g out of range", option, value); return PCC_ERR_INVALID; }
+    if (r->d) ix->opt.*r->d = value; else ix->opt.*r->i = (int)value;
     if (option == PCC_OPT_FLANN_SPLIT) ix->flann_valid = false;  // the replayed tree has to be rebuilt with the other rule
     return PCC_OK;
 }
@@ -830,10 +743,9 @@ int pcc_index_get_option(pcc_index* ix, int option, double* value) {
     PCC_ENTER(ix);
     PCC_NOTHING_ENQUEUED(ix);
     if (!value) { set_error("null value"); return PCC_ERR_INVALID; }
-    int* pi = nullptr;
-    double* pd = option_slot(ix->opt, option, &pi);
-    if (!pd && !pi) { set_error("unknown option %d", option); return PCC_ERR_INVALID; }
-    *value = pd ? *pd : (double)*pi;
+    const OptionRow* r = option_row(option);
+    if (!r) { set_error("unknown option %d", option); return PCC_ERR_INVALID; }
+    *value = r->d ? ix->opt.*r->d : (double)(ix->opt.*r->i);
     return PCC_OK;
 }
 int pcc_debug_fail_alloc(int nth) {
@@ -932,13 +844,6 @@ int pcc_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
     return PCC_OK;
 }
 
-// the searches below need the cell grid whatever engine k=1 uses
-static int ensure_grid(pcc_index* ix) {
-    if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
-    if (!ix->has_grid) PCC_TRY(grid_build(ix));
-    return PCC_OK;
-}
-
 int pcc_knn(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int k, int32_t* idx, float* d2) {
     PCC_ENTER(ix);
     PCC_TRY(check_points(q, nq, stride, mem));
@@ -965,9 +870,6 @@ int pcc_knn(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
     ev_mark(ix, EV_CALL1);
     return finish(ix, mem, ri, rd);
 }
-
-// radiusSearch(pt, double radius): r2 = float(radius*radius) evaluated in double
-static inline float radius2(double radius) { return (float)(radius * radius); }
 
 int pcc_radius_count(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, double radius, int32_t* counts) {
     return pcc_radius_count_max(ix, q, nq, stride, mem, radius, 0u, counts);
@@ -1090,228 +992,6 @@ static int radius_fill_impl(pcc_index* ix, const void* q, size_t nq, size_t stri
     return finish(ix, mem, ri, rd);
 }
 
-int pcc_voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, float leaf, int has_rgb,
-                   void* out, size_t out_stride, size_t* out_n) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_points(pts, n, stride, mem));
-    if (!out || !out_n) { set_error("null output"); return PCC_ERR_INVALID; }
-    if (out_stride < 12 || out_stride % 4) { set_error("bad output stride"); return PCC_ERR_INVALID; }
-    if (has_rgb && (stride < 20 || out_stride < 20)) { set_error("rgb needs a stride of at least 20 bytes"); return PCC_ERR_INVALID; }
-    if (!(leaf > 0.f)) { set_error("leaf size must be positive"); return PCC_ERR_INVALID; }
-    *out_n = 0;
-    if (n == 0) return PCC_OK;
-    return voxel_grid(ix, pts, n, stride, mem, leaf, has_rgb, out, out_stride, out_n);
-}
-
-int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, int max_iterations,
-                  double threshold, double probability, int optimize, int32_t* inliers, size_t* n_inliers,
-                  float coeff[4], int* iterations) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_points(pts, n, stride, mem));
-    if (!n_inliers || !coeff || (n && !inliers)) { set_error("null output"); return PCC_ERR_INVALID; }
-    if (max_iterations < 0 || !(threshold >= 0) || !(probability > 0 && probability < 1)) {
-        set_error("bad RANSAC parameters");
-        return PCC_ERR_INVALID;
-    }
-    *n_inliers = 0;
-    coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.f;
-    if (iterations) *iterations = 0;
-    if (n == 0) return PCC_OK;
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    PCC_TRY(stage_queries(ix, pts, n, stride, mem));
-    const float4* dp = ix->q_packed.as<float4>();
-    // the sampling and the refit read single points on the host: from the caller's array when it is a host array; for a
-    // cloud in device memory the few points needed are gathered there (sac.hip) -- round 3 copied the whole cloud back
-    // (16 B x n per call; the -e plane-removal loop calls this a handful of times per cloud)
-    Out<int32_t> ri;
-    PCC_TRY(ri.stage(inliers, n, mem, ix->out_idx));
-    size_t m = 0;
-    int st = sac_plane(ix, dp, n, mem == PCC_MEM_HOST ? static_cast<const char*>(pts) : nullptr, stride, max_iterations, threshold,
-                       probability, optimize, ri.dev, &m, coeff, iterations);
-    if (st == PCC_ERR_RETRY_HOST) {
-        // a degenerate sample (PCL redraws it at once, which the gathered form cannot replay): with a host copy of the cloud
-        std::vector<float4> hp(n);
-        PCC_HIP(hipMemcpyAsync(hp.data(), dp, n * sizeof(float4), hipMemcpyDeviceToHost, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-        const float qnan = std::nanf("");
-        for (size_t i = 0; i < n; ++i)  // the staged copy zeroes non-finite points; PCL would see them as they are
-            if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
-        st = sac_plane(ix, dp, n, reinterpret_cast<const char*>(hp.data()), sizeof(float4), max_iterations, threshold, probability,
-                       optimize, ri.dev, &m, coeff, iterations);
-    }
-    PCC_TRY(st);
-    ev_mark(ix, EV_CALL1);
-    ri.count = m;  // (the first m of the n reserved)
-    if (m) PCC_TRY(finish(ix, mem, ri));
-    *n_inliers = m;
-    return PCC_OK;
-}
-
-// The self k-NN rows (keys) of the indexed cloud with k neighbours, for pcc_normals / pcc_region_growing.  With
-// PCC_OPT_KNN_CACHE_K the rows are searched with at least that many neighbours and kept until the next set_input; a request
-// the kept rows cover is their prefix (k-NN rows are ascending), copied row by row -- 0.15 ms at 1M x 50 against a 1.1 ms search.
-static int self_knn_keys(pcc_index* ix, int k, const unsigned long long** keys) {
-    const size_t n = ix->n_orig;
-    const int want_kept = ix->opt.knn_cache_k > 0 ? std::max(k, ix->opt.knn_cache_k) : 0;
-    if (ix->self_rows_k < k && want_kept > 0 && want_kept <= PCC_KNN_MAX_K) {
-        ix->self_rows_k = 0;
-        PCC_TRY(ix->self_rows.reserve(n * (size_t)want_kept * sizeof(unsigned long long)));
-        PCC_TRY(grid_knn(ix, ix->refs.as<float4>(), n, want_kept, ix->self_rows.as<unsigned long long>()));
-        ix->self_rows_k = want_kept;
-    }
-    if (ix->self_rows_k >= k) {
-        if (ix->self_rows_k == k) { *keys = ix->self_rows.as<unsigned long long>(); return PCC_OK; }
-        PCC_TRY(ix->out_packed.reserve(n * (size_t)k * sizeof(unsigned long long)));
-        PCC_TRY(launch_copy_row_prefix(ix->stream, ix->self_rows.as<unsigned long long>(), ix->self_rows_k,
-                                       ix->out_packed.as<unsigned long long>(), k, n));
-        *keys = ix->out_packed.as<unsigned long long>();
-        return PCC_OK;
-    }
-    PCC_TRY(ix->out_packed.reserve(n * (size_t)k * sizeof(unsigned long long)));
-    PCC_TRY(grid_knn(ix, ix->refs.as<float4>(), n, k, ix->out_packed.as<unsigned long long>()));
-    *keys = ix->out_packed.as<unsigned long long>();
-    return PCC_OK;
-}
-
-int pcc_normals(pcc_index* ix, int k, const float viewpoint[3], int mem, float* out) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_mem(mem));
-    if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
-    if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    const size_t n = ix->n_orig;
-    const float origin[3] = {0.f, 0.f, 0.f};
-    // self query on the packed references, as pcc_sor does
-    const unsigned long long* keys = nullptr;
-    PCC_TRY(self_knn_keys(ix, k, &keys));
-    Out<float4> rn;
-    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
-    PCC_TRY(launch_normals(ix->stream, keys, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, k,
-                           viewpoint ? viewpoint : origin, rn.dev));
-    ev_mark(ix, EV_CALL1);
-    return finish(ix, mem, rn);
-}
-
-int pcc_normals_radius(pcc_index* ix, double radius, const float viewpoint[3], int mem, float* out) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_mem(mem));
-    if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
-    if (!(radius >= 0)) { set_error("bad radius"); return PCC_ERR_INVALID; }
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    const size_t n = ix->n_orig;
-    const float origin[3] = {0.f, 0.f, 0.f};
-    Out<float4> rn;
-    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
-    PCC_TRY(normals_radius(ix, radius, viewpoint ? viewpoint : origin, rn.dev));
-    ev_mark(ix, EV_CALL1);
-    return finish(ix, mem, rn);
-}
-
-int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int mem, double normal_radius, double gradient_radius,
-                         double rift_radius, int nr_distance_bins, int nr_gradient_bins, float* out_hist, int32_t* out_index,
-                         size_t* n_out) {
-    // the arguments first: host arithmetic, refused before any device is looked at
-    PCC_TRY(check_mem(mem));
-    if (!rgb || !out_hist || !out_index || !n_out) { set_error("null argument"); return PCC_ERR_INVALID; }
-    if (rgb_stride < 4 || rgb_stride % 4 || reinterpret_cast<uintptr_t>(rgb) % 4) {
-        set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
-        return PCC_ERR_INVALID;
-    }
-    for (double r : {normal_radius, gradient_radius, rift_radius})
-        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
-    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
-        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
-        return PCC_ERR_UNSUPPORTED;
-    }
-    PCC_ENTER(ix);
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    const size_t n = ix->n_orig;
-    if (!ix->rift) ix->rift = new RiftScratch();
-    const unsigned char* drgb = nullptr;
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->rift->rgb, &drgb));
-    Out<float> rh;
-    Out<int32_t> ri;
-    PCC_TRY(rh.stage(out_hist, n * RIFT_BINS, mem, ix->rift->out_hist));
-    PCC_TRY(ri.stage(out_index, n, mem, ix->rift->out_index));
-    PCC_TRY(rift_descriptors(ix, drgb, rgb_stride, normal_radius, gradient_radius, rift_radius, rh.dev, ri.dev, n_out));
-    rh.count = *n_out * RIFT_BINS;  // (only the rows that were written travel)
-    ri.count = *n_out;
-    ev_mark(ix, EV_CALL1);
-    return finish(ix, mem, rh, ri);
-}
-
-int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, const void* rgb, size_t rgb_stride, int mem, float min_scale,
-                       int nr_octaves, int nr_scales_per_octave, float min_contrast, float* out_keypoints, size_t capacity, size_t* n_out) {
-    // the arguments first: host arithmetic, refused before any device is looked at
-    PCC_TRY(check_points(pts, n, stride, mem));
-    if (!n_out || (n && !rgb) || (capacity && !out_keypoints)) { set_error("null argument"); return PCC_ERR_INVALID; }
-    if (rgb_stride < 4 || rgb_stride % 4 || (n && (reinterpret_cast<uintptr_t>(rgb) % 4 || reinterpret_cast<uintptr_t>(pts) % 4)) ||
-        (capacity && reinterpret_cast<uintptr_t>(out_keypoints) % 4)) {
-        set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
-        return PCC_ERR_INVALID;
-    }
-    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
-    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
-    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
-    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
-        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
-                  SIFT_MAX_SCALES_PER_OCTAVE);
-        return PCC_ERR_UNSUPPORTED;
-    }
-    PCC_ENTER(ix);
-    *n_out = 0;
-    if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    if (!ix->sift) ix->sift = new SiftScratch();
-    const unsigned char *dpts = nullptr, *drgb = nullptr;
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(pts), (n - 1) * stride + 12, mem, ix->sift->pts, &dpts));
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->sift->rgb, &drgb));
-    size_t found = 0;
-    PCC_TRY(sift_keypoints(ix, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
-    ev_mark(ix, EV_CALL1);
-    *n_out = found;
-    if (found > capacity) {
-        set_error("%zu keypoints, room for %zu", found, capacity);
-        return PCC_ERR_OVERFLOW;
-    }
-    if (found == 0) return PCC_OK;
-    PCC_HIP(hipMemcpyAsync(out_keypoints, ix->sift->kp.p, found * 4 * sizeof(float), mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                           ix->stream));
-    if (mem == PCC_MEM_HOST) PCC_HIP(hipStreamSynchronize(ix->stream));
-    return PCC_OK;
-}
-
-int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, float smoothness,
-                       float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels,
-                       int32_t* n_clusters) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_mem(mem));
-    if (!normals || !labels || !n_clusters) { set_error("null argument"); return PCC_ERR_INVALID; }
-    if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    const size_t n = ix->n_orig;
-    // findPointNeighbours: one batched self k-NN over the packed references
-    const unsigned long long* keys = nullptr;
-    PCC_TRY(self_knn_keys(ix, k, &keys));
-    const float4* dn = nullptr;
-    PCC_TRY(stage_in(ix, reinterpret_cast<const float4*>(normals), n, mem, ix->out_d2, &dn));
-    Out<int32_t> rl;
-    PCC_TRY(rl.stage(labels, n, mem, ix->q_raw));
-    PCC_TRY(grid_region_growing(ix, keys, dn, k, smoothness, curvature_threshold, min_size, max_size, rl.dev, n_clusters));
-    ev_mark(ix, EV_CALL1);
-    return finish(ix, mem, rl);
-}
-
 int pcc_first_within(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, double radius, int32_t* idx) {
     PCC_ENTER(ix);
     PCC_TRY(check_points(q, nq, stride, mem));
@@ -1329,394 +1009,6 @@ int pcc_first_within(pcc_index* ix, const void* q, size_t nq, size_t stride, int
     return finish(ix, mem, ri);
 }
 
-int pcc_euclidean_clusters(pcc_index* ix, double tolerance, uint32_t min_size, uint32_t max_size, int mem,
-                           int32_t* labels, int32_t* n_clusters, int32_t* sizes, int max_sizes) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_mem(mem));
-    if (!labels) { set_error("null labels"); return PCC_ERR_INVALID; }
-    if (!(tolerance >= 0)) { set_error("bad tolerance"); return PCC_ERR_INVALID; }
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    // EuclideanClusterExtraction stores the tolerance as double, extractEuclideanClusters takes
-    // it as float, radiusSearch squares it in double: r2 = float(double(float(tol))^2)
-    const float tol_f = (float)tolerance;
-    const float r2 = radius2((double)tol_f);
-    Out<int32_t> rl;
-    PCC_TRY(rl.stage(labels, ix->n_orig, mem, ix->out_idx));
-    PCC_TRY(grid_clusters(ix, tol_f, r2, min_size, max_size, rl.dev, n_clusters, sizes, max_sizes));
-    ev_mark(ix, EV_CALL1);
-    return finish(ix, mem, rl);
-}
-
-int pcc_sor(pcc_index* ix, int mean_k, double stddev_mult, int mem, float* mean_dist, uint8_t* inlier,
-            double* threshold, size_t* kept) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_mem(mem));
-    if (mean_k < 1 || mean_k + 1 > PCC_KNN_MAX_K) { set_error("mean_k=%d outside [1, %d]", mean_k, PCC_KNN_MAX_K - 1); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(ensure_grid(ix));
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    const size_t n = ix->n_orig, no = ix->n_orig;
-    const int K = mean_k + 1;
-    // self query: the packed references ARE the queries (non-finite points are flagged, are
-    // skipped by the search and keep distance 0, as in PCL's applyFilterIndices)
-    // the mean needs the distances only: the search delivers rows of d2 (4 bytes an entry) where its wave kernels serve K
-    // and the staged mean kernel's tile fits LDS (K <= 126), rows of keys otherwise
-    const bool d2_only = grid_knn_delivers(K) && (size_t)2 * 64 * (K + 1) * sizeof(unsigned int) <= 64 * 1024;
-    PCC_TRY(ix->out_packed.reserve(n * (size_t)K * (d2_only ? sizeof(float) : sizeof(unsigned long long))));
-    auto* keys = d2_only ? nullptr : ix->out_packed.as<unsigned long long>();
-    float* d2_rows = d2_only ? ix->out_packed.as<float>() : nullptr;
-    PCC_TRY(grid_knn(ix, ix->refs.as<float4>(), n, K, keys, nullptr, d2_rows));
-    PCC_TRY(ix->out_d2.reserve(no * sizeof(float)));
-    float* dmean = ix->out_d2.as<float>();
-    PCC_HIP(hipMemsetAsync(dmean, 0, no * sizeof(float), ix->stream));
-    PCC_TRY(launch_sor_mean(ix->stream, keys, ix->refs.as<float4>(), n, K, dmean, d2_rows));
-    // statistics, threshold and mask on the device (pack.hip: exact whenever no addition of PCL's in-order sums rounds);
-    // the host sees one SorStats.  Round 3 copied the means back, added them up on one host thread and sent a mask: 0.94 ms
-    // beside a 1.2 ms search at 1M points
-    SorStats hs{};
-    PCC_TRY(ix->scratch_a.reserve((size_t)(3 * 1024 + 4) * sizeof(double) + 64));
-    PCC_TRY(ix->scratch_b.reserve(no + 64));
-    SorStats* st_dev = &ix->words()->sor;
-    uint8_t* dmask = mem == PCC_MEM_DEVICE && inlier ? inlier : ix->scratch_b.as<uint8_t>();
-    PCC_TRY(launch_sor_stats(ix->stream, dmean, no, ix->d_grid.as<GridDev>(), K, stddev_mult, ix->scratch_a.as<double>(), st_dev, dmask));
-    ev_mark(ix, EV_CALL1);
-    PCC_HIP(hipMemcpyAsync(&hs, st_dev, sizeof(hs), hipMemcpyDeviceToHost, ix->stream));
-    if (mem == PCC_MEM_HOST) {
-        PCC_TRY(ix->host_a.reserve(no * sizeof(float)));
-        PCC_TRY(ix->host_b.reserve(no));
-        if (mean_dist) PCC_HIP(hipMemcpyAsync(ix->host_a.p, dmean, no * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-        if (inlier) PCC_HIP(hipMemcpyAsync(ix->host_b.p, dmask, no, hipMemcpyDeviceToHost, ix->stream));
-    } else if (mean_dist) {
-        PCC_HIP(hipMemcpyAsync(mean_dist, dmean, no * sizeof(float), hipMemcpyDeviceToDevice, ix->stream));
-    }
-    PCC_HIP(hipStreamSynchronize(ix->stream));
-    double thr = hs.thr;
-    size_t k_in = (size_t)hs.kept;
-    if (!hs.exact) {
-        // some addition of the in-order sums rounds (terms spread over more than 28 bits below the total): PCL's order
-        // decides the last bits, so the sums are taken in that order -- on the host, as round 3 always did
-        PCC_TRY(ix->host_a.reserve(no * sizeof(float)));
-        PCC_TRY(ix->host_b.reserve(no));
-        float* hm = ix->host_a.as<float>();
-        uint8_t* hin = ix->host_b.as<uint8_t>();
-        PCC_HIP(hipMemcpyAsync(hm, dmean, no * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-        PCC_TRY(sync_info(ix));
-        const size_t valid = ix->n_valid >= (size_t)K ? ix->n_valid : 0;
-        double sum = 0, sq = 0;
-        for (size_t i = 0; i < no; ++i) { const float f = hm[i]; sum += f; sq += (double)(f * f); }  // PCL squares in float, then widens
-        const double mean = sum / (double)valid;
-        const double var = (sq - sum * sum / (double)valid) / ((double)valid - 1);
-        thr = mean + stddev_mult * std::sqrt(var);
-        k_in = 0;
-        for (size_t i = 0; i < no; ++i) { hin[i] = !(hm[i] > thr); k_in += hin[i]; }
-        if (mem == PCC_MEM_DEVICE && inlier) {
-            PCC_HIP(hipMemcpyAsync(inlier, hin, no, hipMemcpyHostToDevice, ix->stream));
-            PCC_HIP(hipStreamSynchronize(ix->stream));
-        }
-    }
-    if (threshold) *threshold = thr;
-    if (kept) *kept = k_in;
-    if (mem == PCC_MEM_HOST) {
-        if (mean_dist) memcpy(mean_dist, ix->host_a.p, no * sizeof(float));
-        if (inlier) memcpy(inlier, ix->host_b.p, no);
-    }
-    ix->sor_exact_last = hs.exact != 0;
-    return PCC_OK;
-}
-
-int pcc_index_sor_on_device(const pcc_index* ix, int* on_device) {
-    if (!ix || !on_device) { set_error("null argument"); return PCC_ERR_INVALID; }
-    *on_device = ix->sor_exact_last ? 1 : 0;
-    return PCC_OK;
-}
-
-// ---- ICP ------------------------------------------------------------------------------------
-// reduce the per-workgroup partial rows in a fixed order
-static int icp_reduce(pcc_index* ix, size_t n, double sums[17], const double* center = nullptr) {
-    PCC_TRY(ix->scratch_a.reserve((size_t)ICP_MAX_BLOCKS * 17 * sizeof(double)));
-    int nb = 0;
-    PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
-                            ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb,
-                            ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr, &ix->pinned->fb_mirror, center));
-    std::vector<double> h((size_t)nb * 17);
-    PCC_HIP(hipMemcpyAsync(h.data(), ix->scratch_a.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
-    PCC_HIP(hipStreamSynchronize(ix->stream));
-    for (int k = 0; k < 17; ++k) sums[k] = 0;
-    for (int b = 0; b < nb; ++b)
-        for (int k = 0; k < 17; ++k) sums[k] += h[(size_t)b * 17 + k];
-    return PCC_OK;
-}
-
-int pcc_rigid_from_sums(const double sums[17], float T[16]) { return pcc_rigid_from_sums_about(sums, nullptr, T); }
-
-int pcc_rigid_from_sums_about(const double sums[17], const double center[3], float T[16]) {
-    if (!sums || !T) { set_error("null argument"); return PCC_ERR_INVALID; }
-    if (rigid_from_sums(sums, T, center) != 0) { set_error("fewer than 3 correspondences"); return PCC_ERR_INVALID; }
-    return PCC_OK;
-}
-
-int pcc_icp_step(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, int32_t* idx, float* d2,
-                 double sums[17]) {
-    return pcc_icp_step_about(ix, src, n, stride, mem, nullptr, idx, d2, sums);
-}
-
-int pcc_icp_step_about(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, const double center[3],
-                       int32_t* idx, float* d2, double sums[17]) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_points(src, n, stride, mem));
-    if (center && !(std::isfinite(center[0]) && std::isfinite(center[1]) && std::isfinite(center[2]))) {
-        set_error("non-finite center");
-        return PCC_ERR_INVALID;
-    }
-    if (!sums) { set_error("null sums"); return PCC_ERR_INVALID; }
-    for (int k = 0; k < 17; ++k) sums[k] = 0;
-    if (n == 0) return PCC_OK;
-    if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
-    ev_next(ix);
-    ev_mark(ix, EV_CALL0);
-    Nn1Call call;
-    PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
-    PCC_TRY(nn1_packed(ix, n, call));
-    const double* center_dev = nullptr;
-    if (center) {  // the sums are taken about it (device copy behind the ICP loop state)
-        PCC_TRY(ix->icp_state.reserve(sizeof(IcpState) + (3 + 17) * sizeof(double)));
-        double* cd = reinterpret_cast<double*>(ix->icp_state.as<char>() + sizeof(IcpState));
-        PCC_HIP(hipMemcpyAsync(cd, center, 3 * sizeof(double), hipMemcpyHostToDevice, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));  // (center is the caller's memory)
-        center_dev = cd;
-    }
-    PCC_TRY(icp_reduce(ix, n, sums, center_dev));
-    ev_mark(ix, EV_CALL1);
-    if (idx || d2) {
-        Out<int32_t> ri;
-        Out<float> rd;
-        PCC_TRY(ri.stage(idx, n, mem, ix->out_idx));
-        PCC_TRY(rd.stage(d2, n, mem, ix->out_d2));
-        PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, n, ri.dev, rd.dev));
-        PCC_TRY(finish(ix, mem, ri, rd));
-    }
-    return PCC_OK;
-}
-
-int pcc_transform(pcc_index* ix, const float T[16], const void* src, size_t n, size_t sstride, void* dst,
-                  size_t dstride, int mem) {
-    PCC_ENTER(ix);
-    PCC_TRY(check_points(src, n, sstride, mem));
-    PCC_TRY(check_points(dst, n, dstride, mem));
-    if (!T) { set_error("null T"); return PCC_ERR_INVALID; }
-    if (n == 0) return PCC_OK;
-    if (mem == PCC_MEM_DEVICE) return launch_transform(ix->stream, nullptr, T, src, n, sstride, dst, dstride);
-    // host: stage src (and dst, so that its other fields survive) on the device
-    PCC_TRY(ix->q_raw.reserve(n * sstride));
-    PCC_HIP(hipMemcpyAsync(ix->q_raw.p, src, (n - 1) * sstride + 12, hipMemcpyHostToDevice, ix->stream));
-    void* ddst = ix->q_raw.p;
-    size_t dbytes = (n - 1) * dstride + 12;
-    if (dst != src || dstride != sstride) {
-        PCC_TRY(ix->scratch_d.reserve(n * dstride));
-        PCC_HIP(hipMemcpyAsync(ix->scratch_d.p, dst, dbytes, hipMemcpyHostToDevice, ix->stream));
-        ddst = ix->scratch_d.p;
-    }
-    PCC_TRY(launch_transform(ix->stream, nullptr, T, ix->q_raw.p, n, sstride, ddst, dstride));
-    PCC_HIP(hipMemcpyAsync(dst, ddst, dbytes, hipMemcpyDeviceToHost, ix->stream));
-    PCC_HIP(hipStreamSynchronize(ix->stream));
-    return PCC_OK;
-}
-
-int pcc_icp_align(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
-                  float T[16], double* fitness, int* iterations, int* converged) {
-    return pcc::icp_align_impl(ix, nullptr, src, n, stride, mem, max_iter, fixed, T, fitness, iterations, converged);
-}
-}  // extern "C"
-
-// pcc_icp_align, and -- with `hooks` -- its sharded form: this handle holds one SHARD of the source cloud, the 17 sums of
-// every pass are added up over the ranks (hooks->allreduce_sum_f64: RCCL on the handle's stream, comm.hip) before the
-// solver sees them, so every rank solves the same transform and moves its shard (reference
-// src/comparator.cpp:1089-1110).  With one rank the all-reduce is the identity and the result is pcc_icp_align's, bit for bit.
-int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter,
-                        int fixed, float T[16], double* fitness, int* iterations, int* converged) {
-    // (PCC_ENTER spelled out: a device that cannot be selected is a failure of this rank alone and has to reach the status
-    // exchange below like every other one -- an early return here would leave the peers waiting in it)
-    if (!ix) { set_error("null index"); return PCC_ERR_INVALID; }  // (the sharded entry point has checked this before its peers can wait)
-    std::lock_guard<std::mutex> _lock(ix->mu);
-    pcc::DeviceGuard _guard(ix->device);
-    pcc::entered(ix);
-    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    int it = 0;
-    bool conv = false;
-    double prev_mse = 1.79769313486231570e308;
-    double* center_dev = nullptr;
-    bool sorted = false;
-    Nn1Call call;  // every search below is an ICP pass: they share the first pass's lane order (Nn1Call::order_given)
-    call.icp_pass = true;
-    // Everything that can fail on ONE rank alone -- argument checks, staging, allocations -- comes before the first
-    // collective and ends in a status the ranks agree on (hooks->agree: all-reduce MIN of one word), so a rank that
-    // cannot go on takes the others out with it instead of leaving them in the broadcast below (comm.hip).
-    auto prepare = [&]() -> int {
-        if (!_guard.ok) { set_error("hipSetDevice(%d) failed", ix->device); return PCC_ERR_DEVICE; }
-        PCC_TRY(check_points(src, n, stride, mem));
-        if (!T) { set_error("null T"); return PCC_ERR_INVALID; }
-        if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
-        memcpy(T, I, sizeof(I));
-        if (iterations) *iterations = 0;
-        if (converged) *converged = 0;
-        if (n == 0 && hooks) { set_error("sharded ICP: every rank needs a non-empty shard"); return PCC_ERR_INVALID; }
-        if (n == 0) return PCC_OK;
-        // the source stays resident: q_packed is the moving cloud, icp_src keeps the input
-        PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
-        PCC_TRY(ix->icp_src.reserve(n * sizeof(float4)));
-        // Round 5: the loop's working set in the target grid's CELL order.  Nothing of the loop leaves per point -- T, fitness,
-        // counts -- so the permutation that a search pays per call (queries gathered through the sort order, keys scattered
-        // back: ~60 us of a 215-us pass at 2M points, tools/ubench/ubench_scatter.hip) is paid ONCE: the source is sorted by the
-        // cell it starts in, gathered into that order, and every pass reads it front to back with the identity as its order
-        // (a rigid motion keeps neighbouring points neighbours; any order is correct, as before).  The sums are added up in
-        // this order by every form of the loop -- device-resident, host-driven, sharded -- so they agree with each other to
-        // the bit as before; against the caller's order they differ in the last bits of a double sum.
-        sorted = ix->opt.icp_sorted != 0 && ix->engine == PCC_ENGINE_GRID && ix->has_grid && n >= 4096;
-        if (sorted) {
-            unsigned int *order = nullptr, *n_sorted = nullptr;
-            PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), n, &order, &n_sorted));
-            PCC_TRY(launch_gather_sorted(ix->stream, ix->q_packed.as<float4>(), order, n_sorted, n, ix->icp_src.as<float4>(),
-                                         &ix->words()->icp_nsorted));
-            PCC_HIP(hipMemcpyAsync(ix->q_packed.p, ix->icp_src.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
-        } else
-        PCC_HIP(hipMemcpyAsync(ix->icp_src.p, ix->q_packed.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
-        // the sums of every pass are taken about a point of the source cloud (k_icp_center: no cancellation in the
-        // covariance for clouds far from the origin); it sits behind the loop state in device memory
-        PCC_TRY(ix->icp_state.reserve(sizeof(IcpState) + (3 + 17) * sizeof(double)));
-        PCC_TRY(ix->scratch_a.reserve((size_t)ICP_MAX_BLOCKS * 17 * sizeof(double)));
-        center_dev = reinterpret_cast<double*>(ix->icp_state.as<char>() + sizeof(IcpState));
-        PCC_TRY(launch_icp_center(ix->stream, ix->q_packed.as<float4>(), n, center_dev));
-        return PCC_OK;
-    };
-    int st_prep = prepare();
-    if (hooks) st_prep = hooks->agree(hooks->ctx, st_prep);
-    if (st_prep != PCC_OK) return st_prep;
-    if (n == 0) return PCC_OK;
-    if (hooks) PCC_TRY(hooks->bcast_f64(hooks->ctx, center_dev, 3, 0, ix->stream));  // every rank about rank 0's point
-    const int warm_env = ix->opt.icp_warm;         // 0: every pass from scratch (measurements)
-    const int loop_env = hooks ? 1 : ix->opt.icp_device_loop;  // 0: the host-driven loop (kept for comparison: same bits)
-    double* sums_dev = center_dev + 3;  // (sharded: the 17 sums of a pass, all-reduced in place)
-    const bool fold = sorted && loop_env && grid_nn1_takes_transform(ix);  // the pass's transform applied by the next pass's search
-    if (sorted) {  // (the passes take the identity as their order; the count of valid points sits in a word of its own)
-        call.order_given = true; call.order_nq = n;
-        call.order = nullptr; call.n_sorted = &ix->words()->icp_nsorted;
-    }
-    if (loop_env) {
-        // The loop lives on the device: every pass is NN -> sums -> k_icp_solve (one workgroup: the transform, the running
-        // product and the convergence criteria) -> transform with the matrix the solver left in device memory.  Passes
-        // are enqueued in chunks without a host round trip (the host loop below pays a stream synchronisation, a
-        // read-back and a launch gap per pass, ~65 us of 0.44 ms); after each chunk the host looks whether the loop
-        // has stopped.  Passes enqueued past the stop are no-ops on the state (identity transform), so a chunk costs at
-        // most its own length in wasted searches -- none with a fixed count, where the whole loop is one chunk.
-        IcpState h0{};
-        memcpy(h0.Ti, I, sizeof(I));
-        memcpy(h0.T, I, sizeof(I));
-        h0.prev_mse = 1.79769313486231570e308;
-        PCC_HIP(hipMemcpyAsync(ix->icp_state.p, &h0, sizeof(h0), hipMemcpyHostToDevice, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));  // (h0 lives on this stack frame)
-        IcpState* st = ix->icp_state.as<IcpState>();
-        IcpState h1 = h0;
-        // passes per host look: 5 with criteria active; with a fixed count the loop would need none, but a source that
-        // leaves fewer than 3 correspondences stops it on the device and every pass enqueued beyond that is a wasted
-        // search -- so at most 32 at a time (one look costs ~20 us)
-        const int chunk = fixed ? (max_iter < 32 ? max_iter : 32) : 5;
-        for (int pass = 0; pass < max_iter && !h1.stopped;) {
-            for (int c = 0; c < chunk && pass < max_iter; ++c, ++pass) {
-                ev_next(ix);  // instrumentation: every pass is one "call" (NN kernel, far/fallback, whole pass)
-                ev_mark(ix, EV_CALL0);
-                // (cell-ordered loop: the search applies the previous pass's matrix -- the identity before the first -- to the
-                // queries it reads and writes them back; no transform kernel, grid.hip k_grid_nn1_flat2)
-                call.pre_transform = fold ? st->Ti : nullptr;
-                PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
-                call.pre_transform = nullptr;
-                call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
-                int nb = 0;
-                unsigned int* zw = ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr;
-                // (one GPU: the sums kernel's last workgroup solves the pass itself -- DevWords::icp_ticket is its ticket word;
-                // PCC_OPT_FUSE_PARAMS bit 1; the sharded loop keeps the solver's own launch: its sums pass through an all-reduce)
-                const bool fuse_solve = !hooks && (ix->opt.fuse_params & 2) != 0;
-                const IcpFuse fuse{&ix->words()->icp_ticket, st, max_iter, fixed, fold ? zw : nullptr};
-                PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
-                                        ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb, zw,
-                                        &ix->pinned->fb_mirror, center_dev, fuse_solve ? &fuse : nullptr));
-                if (fuse_solve) {
-                } else if (hooks) {  // rows -> 17 sums (workgroup order, as the solver adds them) -> sum over the ranks -> solve
-                    PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));
-                    PCC_TRY(hooks->allreduce_sum_f64(hooks->ctx, sums_dev, 17, ix->stream));
-                    PCC_TRY(launch_icp_solve(ix->stream, sums_dev, 1, st, max_iter, fixed, center_dev, fold ? zw : nullptr));
-                } else
-                PCC_TRY(launch_icp_solve(ix->stream, ix->scratch_a.as<double>(), nb, st, max_iter, fixed, center_dev, fold ? zw : nullptr));
-                // (the transform -- or, when the next search applies it itself, the solver -- also zeroes the counters of the next
-                // pass's search)
-                if (!fold) PCC_TRY(launch_transform(ix->stream, st->Ti, nullptr, ix->q_packed.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4), zw));
-                call.counters_cleared = zw != nullptr;
-                ev_mark(ix, EV_CALL1);
-            }
-            PCC_HIP(hipMemcpyAsync(&h1, ix->icp_state.p, sizeof(h1), hipMemcpyDeviceToHost, ix->stream));
-            PCC_HIP(hipStreamSynchronize(ix->stream));
-        }
-        memcpy(T, h1.T, sizeof(h1.T));
-        it = h1.it;
-        conv = h1.converged != 0;
-    } else {
-    double center[3] = {0, 0, 0};
-    bool have_center = false;
-    while (it < max_iter) {
-        ev_next(ix);  // instrumentation: every pass is one "call" (NN kernel, far/fallback, whole pass)
-        ev_mark(ix, EV_CALL0);
-        PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
-        call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
-        double sums[17];
-        PCC_TRY(icp_reduce(ix, n, sums, center_dev));
-        if (!have_center) {
-            PCC_HIP(hipMemcpyAsync(center, center_dev, sizeof(center), hipMemcpyDeviceToHost, ix->stream));
-            PCC_HIP(hipStreamSynchronize(ix->stream));
-            have_center = true;
-        }
-        float Ti[16];
-        if (rigid_from_sums(sums, Ti, center) != 0) { conv = false; break; }  // < 3 correspondences: not converged
-        PCC_TRY(launch_transform(ix->stream, nullptr, Ti, ix->q_packed.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4)));
-        ev_mark(ix, EV_CALL1);
-        mat4_mul_f(Ti, T, T);  // final = T_i * final
-        const double mse = sums[15] / sums[16];
-        ++it;
-        if (it >= max_iter) { conv = true; break; }  // DefaultConvergenceCriteria: iteration cap counts as converged
-        if (!fixed && std::fabs(mse - prev_mse) < 1e-12) { conv = true; break; }
-        prev_mse = mse;
-    }
-    }
-    if (iterations) *iterations = it;
-    if (converged) *converged = conv ? 1 : 0;
-    if (fitness) {
-        // getFitnessScore: re-transform the INPUT with the final matrix, one more NN pass, mean d2
-        PCC_TRY(launch_transform(ix->stream, nullptr, T, ix->icp_src.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4)));
-        // launch_transform writes x,y,z only: refresh the validity flags from the input
-        PCC_TRY(launch_copy_w(ix->stream, ix->icp_src.as<float4>(), ix->q_packed.as<float4>(), n));
-        ev_next(ix);
-        ev_mark(ix, EV_CALL0);
-        PCC_TRY(nn1_packed(ix, n, call));
-        double sums[17];
-        if (hooks) {  // sum of d2 and count over ALL shards
-            int nb = 0;
-            PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(), ix->refs.as<float4>(),
-                                    ix->scratch_a.as<double>(), &nb, nullptr, nullptr, nullptr));
-            PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));
-            PCC_TRY(hooks->allreduce_sum_f64(hooks->ctx, sums_dev, 17, ix->stream));
-            PCC_HIP(hipMemcpyAsync(sums, sums_dev, sizeof(sums), hipMemcpyDeviceToHost, ix->stream));
-            PCC_HIP(hipStreamSynchronize(ix->stream));
-        } else
-        PCC_TRY(icp_reduce(ix, n, sums));
-        ev_mark(ix, EV_CALL1);
-        *fitness = sums[16] > 0 ? sums[15] / sums[16] : 1.79769313486231570e308;
-    }
-    PCC_HIP(hipStreamSynchronize(ix->stream));
-    return PCC_OK;
-}
-
-extern "C" {
 int pcc_match_knn(pcc_index* ix, const void* des2, size_t n2, size_t stride, int mem, float threshold,
                   int32_t* out, int32_t* out_size) {
     PCC_ENTER(ix);
@@ -1745,10 +1037,4 @@ int pcc_match_knn(pcc_index* ix, const void* des2, size_t n2, size_t stride, int
     *out_size = c;
     return PCC_OK;
 }
-
 }  // extern "C"
-
-namespace pcc {
-int make_handle(int device, int engine, pcc_index** out) { return new_handle(device, engine, out); }
-int need_grid(pcc_index* ix) { return ensure_grid(ix); }
-}  // namespace pcc

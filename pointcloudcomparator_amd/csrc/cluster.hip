@@ -23,7 +23,7 @@
 // grid's cells (0.5 points per cell on average over the bounding box) hold tens of points each inside the
 // objects, where the per-point ball scan does 500-1000 distance tests to find ~90 neighbours; the cell
 // walk does a few tens.  Same components, hence the same clusters.
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "grid_device.hpp"
 #include "uf_device.hpp"
 #include "lane_ops.hpp"
@@ -770,3 +770,26 @@ int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t 
 PCC_PAIRS_TAKE(cluster)
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_euclidean_clusters(pcc_index* ix, double tolerance, uint32_t min_size, uint32_t max_size, int mem,
+                           int32_t* labels, int32_t* n_clusters, int32_t* sizes, int max_sizes) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_mem(mem));
+    if (!labels) { set_error("null labels"); return PCC_ERR_INVALID; }
+    if (!(tolerance >= 0)) { set_error("bad tolerance"); return PCC_ERR_INVALID; }
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    // EuclideanClusterExtraction stores the tolerance as double, extractEuclideanClusters takes
+    // it as float, radiusSearch squares it in double: r2 = float(double(float(tol))^2)
+    const float tol_f = (float)tolerance;
+    const float r2 = radius2((double)tol_f);
+    Out<int32_t> rl;
+    PCC_TRY(rl.stage(labels, ix->n_orig, mem, ix->out_idx));
+    PCC_TRY(grid_clusters(ix, tol_f, r2, min_size, max_size, rl.dev, n_clusters, sizes, max_sizes));
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rl);
+}
+}  // extern "C"

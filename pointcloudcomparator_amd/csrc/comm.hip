@@ -12,7 +12,7 @@
 // driving several GPUs from one thread per device (pcc_comm_create_local).  RCCL is loaded at the first communicator
 // (dlopen: librccl.so.1 -- the copy torch has already mapped when there is one): libpcc_nn.so has no link-time
 // dependency on it and single-GPU users never load it.
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include <rccl/rccl.h>
 #include <dlfcn.h>
 #include <cstring>
@@ -107,9 +107,7 @@ static int agree_hook(void* ctx, int local) { return agree_status(static_cast<pc
 }  // namespace pcc
 
 using namespace pcc;
-
 extern "C" {
-
 int pcc_comm_unique_id(void* id, size_t bytes) {
     if (!id || bytes < sizeof(ncclUniqueId)) { set_error("unique id needs %zu bytes", sizeof(ncclUniqueId)); return PCC_ERR_INVALID; }
     if (!rccl()) { set_error("librccl.so.1 not found (dlopen)"); return PCC_ERR_DEVICE; }
@@ -224,28 +222,28 @@ int pcc_index_create_broadcast(pcc_comm* c, int root, const void* pts, size_t n,
     st = PCC_OK;
     if (hipMemcpy(&n64, w, sizeof(n64), hipMemcpyDeviceToHost) != hipSuccess) { set_error("hipMemcpy failed: %s", hipGetErrorString(hipGetLastError())); st = PCC_ERR_DEVICE; }
     if (st == PCC_OK && c->rank != root) {
-        std::lock_guard<std::mutex> lock(ix->mu);
-        pcc::entered(ix);
-        st = n64 ? ix->icp_src.reserve((size_t)n64 * sizeof(float4)) : PCC_ERR_EMPTY;
+        Entry entry(ix);
+        if ((st = entry.status) == PCC_OK) st = n64 ? ix->icp_src.reserve((size_t)n64 * sizeof(float4)) : PCC_ERR_EMPTY;
     }
     if ((st = agree_status(c, st)) != PCC_OK) return fail(st);
     // step 4: the packed cloud, 16 B per point, in one broadcast on the handle's stream; every other rank builds over its copy
-    if (c->rank == root) {
-        std::lock_guard<std::mutex> lock(ix->mu);
-        pcc::entered(ix);
-        ncclResult_t r = rccl()->Broadcast(ix->refs.p, ix->refs.p, (size_t)n64 * 4, ncclFloat, root, c->nccl, ix->stream);
+    // (a handle whose device cannot be selected -- Entry::status -- still joins the broadcast: its peers are in it; the scope
+    // ends before fail() may destroy the handle)
+    {
+        Entry entry(ix);
+        st = entry.status;
+        void* cloud = c->rank == root ? ix->refs.p : ix->icp_src.p;
+        ncclResult_t r = rccl()->Broadcast(cloud, cloud, (size_t)n64 * 4, ncclFloat, root, c->nccl, ix->stream);
         if (r != ncclSuccess) { set_error("ncclBroadcast failed: %s", rccl()->GetErrorString(r)); st = PCC_ERR_DEVICE; }
-        else if (hipStreamSynchronize(ix->stream) != hipSuccess) { set_error("broadcast failed: %s", hipGetErrorString(hipGetLastError())); st = PCC_ERR_DEVICE; }
-    } else {
-        std::lock_guard<std::mutex> lock(ix->mu);
-        pcc::entered(ix);
-        ncclResult_t r = rccl()->Broadcast(ix->icp_src.p, ix->icp_src.p, (size_t)n64 * 4, ncclFloat, root, c->nccl, ix->stream);
-        if (r != ncclSuccess) { set_error("ncclBroadcast failed: %s", rccl()->GetErrorString(r)); st = PCC_ERR_DEVICE; }
-        // (non-finite points get their NaN back so that the build sees what the root's upload saw; then the usual build)
-        if (st == PCC_OK) st = launch_nanify(ix->stream, ix->icp_src.as<float4>(), (size_t)n64);
-        if (st == PCC_OK) st = set_input(ix, ix->icp_src.p, (size_t)n64, sizeof(float4), PCC_MEM_DEVICE);
-        if (st == PCC_OK) st = sync_info(ix);
-        if (st == PCC_OK && hipStreamSynchronize(ix->stream) != hipSuccess) { set_error("index build failed: %s", hipGetErrorString(hipGetLastError())); st = PCC_ERR_DEVICE; }
+        if (c->rank == root) {
+            if (st == PCC_OK && hipStreamSynchronize(ix->stream) != hipSuccess) { set_error("broadcast failed: %s", hipGetErrorString(hipGetLastError())); st = PCC_ERR_DEVICE; }
+        } else {
+            // (non-finite points get their NaN back so that the build sees what the root's upload saw; then the usual build)
+            if (st == PCC_OK) st = launch_nanify(ix->stream, ix->icp_src.as<float4>(), (size_t)n64);
+            if (st == PCC_OK) st = set_input(ix, ix->icp_src.p, (size_t)n64, sizeof(float4), PCC_MEM_DEVICE);
+            if (st == PCC_OK) st = sync_info(ix);
+            if (st == PCC_OK && hipStreamSynchronize(ix->stream) != hipSuccess) { set_error("index build failed: %s", hipGetErrorString(hipGetLastError())); st = PCC_ERR_DEVICE; }
+        }
     }
     // step 5: every rank holds an index, or none does
     if ((st = agree_status(c, st)) != PCC_OK) return fail(st);
@@ -266,60 +264,6 @@ int pcc_icp_align_sharded(pcc_index* ix, pcc_comm* c, const void* src_shard, siz
     return icp_align_impl(ix, &hooks, src_shard, n, stride, mem, max_iter, fixed, T, fitness, iterations, converged);
 }
 
-// ---- SOR over a shard of the indexed cloud --------------------------------------------------------------------------
-// mean distances of the points [start, start + count) of the indexed cloud (self query with mean_k + 1 neighbours, as
-// pcc_sor) and this shard's share of PCL's statistics: sums[0] = sum of the means, [1] = sum of their float squares,
-// [2], [3] = bit patterns (as doubles) of the smallest positive term of either sum (+inf's pattern when there is none).
-// Combine over shards with (+, +, min, min) and hand the result to pcc_sor_threshold.
-static int sor_shard_means(pcc_index* ix, size_t start, size_t count, int mean_k, float** dmean_out) {
-    if (mean_k < 1 || mean_k + 1 > PCC_KNN_MAX_K) { set_error("mean_k=%d outside [1, %d]", mean_k, PCC_KNN_MAX_K - 1); return PCC_ERR_UNSUPPORTED; }
-    if (start > ix->n_orig || count > ix->n_orig - start) { set_error("shard [%zu, %zu) outside the cloud (%zu points)", start, start + count, ix->n_orig); return PCC_ERR_INVALID; }
-    PCC_TRY(need_grid(ix));
-    const int K = mean_k + 1;
-    const bool d2_only = grid_knn_delivers(K) && (size_t)2 * 64 * (K + 1) * sizeof(unsigned int) <= 64 * 1024;
-    PCC_TRY(ix->out_packed.reserve((count + 1) * (size_t)K * (d2_only ? sizeof(float) : sizeof(unsigned long long))));
-    auto* keys = d2_only ? nullptr : ix->out_packed.as<unsigned long long>();
-    float* d2_rows = d2_only ? ix->out_packed.as<float>() : nullptr;
-    const float4* q = ix->refs.as<float4>() + start;
-    PCC_TRY(ix->out_d2.reserve((count + 1) * sizeof(float)));
-    float* dmean = ix->out_d2.as<float>();
-    if (count) {
-        PCC_TRY(grid_knn(ix, q, count, K, keys, nullptr, d2_rows));
-        PCC_HIP(hipMemsetAsync(dmean, 0, count * sizeof(float), ix->stream));
-        PCC_TRY(launch_sor_mean(ix->stream, keys, q, count, K, dmean, d2_rows));
-    }
-    *dmean_out = dmean;
-    return PCC_OK;
-}
-
-int pcc_sor_partial(pcc_index* ix, size_t start, size_t count, int mean_k, int mem, float* mean_dist, double sums[4]) {
-    if (!ix) { set_error("null index"); return PCC_ERR_INVALID; }
-    std::lock_guard<std::mutex> lock(ix->mu);
-    pcc::entered(ix);
-    DeviceGuard g(ix->device);
-    PCC_TRY(check_mem(mem));
-    if (!sums) { set_error("null sums"); return PCC_ERR_INVALID; }
-    float* dmean = nullptr;
-    PCC_TRY(sor_shard_means(ix, start, count, mean_k, &dmean));
-    PCC_TRY(ix->scratch_a.reserve((size_t)(3 * 1024 + 4) * sizeof(double) + 64));
-    double* out4 = ix->scratch_a.as<double>() + 3 * 1024;
-    PCC_TRY(launch_sor_partial(ix->stream, dmean, count, ix->scratch_a.as<double>(), out4));
-    PCC_HIP(hipMemcpyAsync(sums, out4, 4 * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
-    if (mean_dist && count)
-        PCC_HIP(hipMemcpyAsync(mean_dist, dmean, count * sizeof(float), mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ix->stream));
-    PCC_HIP(hipStreamSynchronize(ix->stream));
-    return PCC_OK;
-}
-
-// PCL's threshold from the combined sums of all shards (pure host arithmetic, no handle): *exact = 0 says that PCL's
-// in-order additions would round -- the combined sums then need not be PCL's bits and the caller should take the
-// sums of all mean distances in index order instead (pcc_sor does that on one GPU).
-int pcc_sor_threshold(const double sums[4], uint64_t n_valid, int mean_k, double stddev_mult, double* threshold, int* exact) {
-    if (!sums || !threshold || !exact) { set_error("null argument"); return PCC_ERR_INVALID; }
-    sor_threshold_host(sums, (double)n_valid, mean_k + 1, stddev_mult, threshold, exact);
-    return PCC_OK;
-}
-
 // pcc_sor over the ranks of `comm`: this rank filters the points [start, start + count) of the indexed cloud (the shards
 // of all ranks tile the cloud), the statistics are PCL's over the WHOLE cloud.  mean_dist / inlier: `count` entries in
 // memory space `mem`; *threshold and *kept_total (inliers over all shards) are the same on every rank.  Collective.
@@ -330,19 +274,18 @@ int pcc_sor_sharded(pcc_index* ix, pcc_comm* c, size_t start, size_t count, int 
     if (!ix) { set_error("null index"); return agree_status(c, PCC_ERR_INVALID); }
     if (ix->device != c->device) { set_error("index on device %d, communicator on device %d", ix->device, c->device); return agree_status(c, PCC_ERR_INVALID); }
     if (check_mem(mem) != PCC_OK) return agree_status(c, PCC_ERR_INVALID);
-    std::lock_guard<std::mutex> lock(ix->mu);
-    pcc::entered(ix);
-    DeviceGuard g(ix->device);
+    Entry entry(ix);
     hipStream_t s = ix->stream;
     const int K = mean_k + 1;
     float* dmean = nullptr;
     double* out4 = nullptr;
     uint8_t* dmask = nullptr;
     auto prepare = [&]() -> int {  // shard search + every allocation of the exact path
-        if (!g.ok) { set_error("hipSetDevice(%d) failed", ix->device); return PCC_ERR_DEVICE; }
-        PCC_TRY(sor_shard_means(ix, start, count, mean_k, &dmean));
-        PCC_TRY(ix->scratch_a.reserve((size_t)(3 * 1024 + 4) * sizeof(double) + 64));
-        out4 = ix->scratch_a.as<double>() + 3 * 1024;
+        PCC_TRY(entry.status);
+        PCC_TRY(sor_begin(ix, start, count, mean_k));
+        PCC_TRY(sor_means(ix, start, count, K, &dmean));
+        PCC_TRY(ix->scratch_a.reserve(SOR_STATS_SCRATCH_BYTES));
+        out4 = ix->scratch_a.as<double>() + SOR_STATS_OUT4;
         PCC_TRY(ix->scratch_b.reserve(count + 64));
         dmask = mem == PCC_MEM_DEVICE && inlier ? inlier : ix->scratch_b.as<uint8_t>();
         PCC_TRY(launch_sor_partial(s, dmean, count, ix->scratch_a.as<double>(), out4));
@@ -396,29 +339,20 @@ int pcc_sor_sharded(pcc_index* ix, pcc_comm* c, size_t start, size_t count, int 
         PCC_HIP(hipMemcpyAsync(hm, all, no * sizeof(float), hipMemcpyDeviceToHost, s));
         PCC_HIP(hipStreamSynchronize(s));
         PCC_TRY(sync_info(ix));
-        const size_t valid = ix->n_valid >= (size_t)K ? ix->n_valid : 0;
-        double sum = 0, sq = 0;
-        for (size_t i = 0; i < no; ++i) { const float f = hm[i]; sum += f; sq += (double)(f * f); }
-        const double mean = sum / (double)valid;
-        const double var = (sq - sum * sum / (double)valid) / ((double)valid - 1);
-        thr = mean + stddev_mult * std::sqrt(var);
-        kept = 0;
-        for (size_t i = 0; i < no; ++i) kept += !(hm[i] > thr);
         uint8_t* hin = ix->host_b.as<uint8_t>();
-        for (size_t i = 0; i < count; ++i) hin[i] = !(hm[start + i] > thr);
+        sor_in_order(hm, no, ix->n_valid, K, stddev_mult, start, count, &thr, &kept, hin);
         if (count) PCC_HIP(hipMemcpyAsync(dmask, hin, count, hipMemcpyHostToDevice, s));
         PCC_HIP(hipStreamSynchronize(s));
     }
     ix->sor_exact_last = hs.exact != 0;
     if (threshold) *threshold = thr;
     if (kept_total) *kept_total = kept;
+    // (no Out / finish: the shard's results leave the handle's own buffers by plain copies in either memory space, as pcc_sor_partial's)
     if (count) {
-        const hipMemcpyKind kind = mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-        if (mean_dist) PCC_HIP(hipMemcpyAsync(mean_dist, dmean, count * sizeof(float), kind, s));
-        if (inlier && dmask != inlier) PCC_HIP(hipMemcpyAsync(inlier, dmask, count, kind, s));
+        if (mean_dist) PCC_TRY(copy_out(ix, mean_dist, dmean, count * sizeof(float), mem));
+        if (inlier && dmask != inlier) PCC_TRY(copy_out(ix, inlier, dmask, count, mem));
         PCC_HIP(hipStreamSynchronize(s));
     }
     return PCC_OK;
 }
-
 }  // extern "C"

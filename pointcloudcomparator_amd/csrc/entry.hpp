@@ -1,0 +1,97 @@
+// entry.hpp -- the scaffold of a C-ABI entry point, included by every translation unit that defines one: the call prologue
+// (PCC_ENTER) and the staging of caller arrays that are not point clouds (stage_in, Out, finish).
+#pragma once
+#include "pcc_internal.hpp"
+
+namespace pcc {
+
+// a handle's mutex for a scope: bare for the one caller that is no call on the handle (pcc_index_clone_to_devices and its source)
+using HandleLock = std::lock_guard<std::mutex>;
+
+// The prologue of every call on a handle: its lock, its device, entered() -- in this order.  status is PCC_ERR_DEVICE (message set,
+// entered() not called) when the device cannot be selected.  PCC_ENTER returns it; a collective call cannot return before its
+// peers and folds it into its status exchange instead.
+struct Entry {
+    HandleLock lock;
+    DeviceGuard guard;
+    int status = PCC_OK;
+    explicit Entry(pcc_index* ix) : lock(ix->mu), guard(ix->device) {
+        if (!guard.ok) { set_error("hipSetDevice(%d) failed", ix->device); status = PCC_ERR_DEVICE; return; }
+        entered(ix);
+    }
+};
+#define PCC_ENTER(ix)                                                         \
+    if (!(ix)) { pcc::set_error("null index"); return PCC_ERR_INVALID; }      \
+    pcc::Entry _entry(ix);                                                    \
+    if (_entry.status != PCC_OK) return _entry.status;
+// entry points that put nothing on the stream leave "the build was the last thing enqueued" as they found it
+#define PCC_NOTHING_ENQUEUED(ix) (ix)->build_fresh = (ix)->after_build
+
+// the searches beyond k = 1 need the cell grid whatever engine k = 1 uses (api.hip)
+int ensure_grid(pcc_index* ix);
+// radiusSearch(pt, double radius): r2 = float(radius*radius) evaluated in double
+inline float radius2(double radius) { return (float)(radius * radius); }
+
+// ---- caller arrays that are not point clouds (PCC_MEM_HOST or PCC_MEM_DEVICE) -----------------------------------------------
+// An input on the device: the caller's own array, or for host memory a copy in `buf`.
+template <class T>
+int stage_in(pcc_index* ix, const T* user, size_t count, int mem, DevBuf& buf, const T** dev) {
+    *dev = user;
+    if (mem != PCC_MEM_HOST) return PCC_OK;
+    PCC_TRY(buf.reserve(count * sizeof(T)));
+    PCC_HIP(hipMemcpyAsync(buf.p, user, count * sizeof(T), hipMemcpyHostToDevice, ix->stream));
+    *dev = buf.as<T>();
+    return PCC_OK;
+}
+
+// A radius fill's row offsets (nq + 1 of them) on the device, and their total offsets[nq] on the host.
+inline int stage_offsets(pcc_index* ix, const int64_t* offsets, size_t nq, int mem, const int64_t** doff, int64_t* total) {
+    PCC_TRY(stage_in(ix, offsets, nq + 1, mem, ix->scratch_d, doff));
+    if (mem == PCC_MEM_HOST) {
+        *total = offsets[nq];
+    } else {
+        PCC_HIP(hipMemcpyAsync(total, offsets + nq, sizeof(int64_t), hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));
+    }
+    if (*total < 0) { set_error("negative total"); return PCC_ERR_INVALID; }
+    return PCC_OK;
+}
+
+// A result array: the kernels write `dev`, which is the caller's own array in device memory and `buf` in host memory (nullptr
+// when the caller passed none).  finish() hands the results of a call over.
+template <class T>
+struct Out {
+    T* user = nullptr;
+    size_t count = 0;
+    T* dev = nullptr;
+    int stage(T* u, size_t n, int mem, DevBuf& buf) {
+        user = dev = u;
+        count = n;
+        if (mem != PCC_MEM_HOST) return PCC_OK;
+        PCC_TRY(buf.reserve(count * sizeof(T)));
+        if (user) dev = buf.as<T>();
+        return PCC_OK;
+    }
+};
+
+// one result into the caller's host array: large pageable arrays through the host pipe (api.hip, host_pipe.hpp), else one copy
+int deliver(pcc_index* ix, const void* dev, void* user, size_t bytes);
+// host memory: every result in turn, then one wait.  Device memory: nothing to do.
+template <class... T>
+int finish(pcc_index* ix, int mem, const Out<T>&... outs) {
+    if (mem != PCC_MEM_HOST) return PCC_OK;
+    int st = PCC_OK;
+    (void)(... && ((st = deliver(ix, outs.dev, outs.user, outs.count * sizeof(T))) == PCC_OK));  // (up to the first failure)
+    PCC_TRY(st);
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+
+// A result the kernels left in a buffer of the library's, into the caller's array in either memory space: one plain copy, never
+// the host pipe, for the few calls whose results do not go through Out.  The caller waits.
+inline int copy_out(pcc_index* ix, void* user, const void* dev, size_t bytes, int mem) {
+    PCC_HIP(hipMemcpyAsync(user, dev, bytes, mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ix->stream));
+    return PCC_OK;
+}
+
+}  // namespace pcc

@@ -7,8 +7,9 @@
 // The sums are accumulated in double (PCL/Eigen use float; compared with a tolerance,
 // SURVEY hard part 6) as one partial row per workgroup, reduced on the host in a fixed
 // order -> bitwise reproducible run to run (no float atomics).
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "rigid_solve.hpp"
+#include <vector>
 
 namespace pcc {
 
@@ -215,3 +216,285 @@ int launch_icp_sums(hipStream_t s, const float4* src, size_t n, const unsigned l
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+// reduce the per-workgroup partial rows in a fixed order
+static int icp_reduce(pcc_index* ix, size_t n, double sums[17], const double* center = nullptr) {
+    PCC_TRY(ix->scratch_a.reserve((size_t)ICP_MAX_BLOCKS * 17 * sizeof(double)));
+    int nb = 0;
+    PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
+                            ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb,
+                            ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr, &ix->pinned->fb_mirror, center));
+    std::vector<double> h((size_t)nb * 17);
+    PCC_HIP(hipMemcpyAsync(h.data(), ix->scratch_a.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    for (int k = 0; k < 17; ++k) sums[k] = 0;
+    for (int b = 0; b < nb; ++b)
+        for (int k = 0; k < 17; ++k) sums[k] += h[(size_t)b * 17 + k];
+    return PCC_OK;
+}
+
+int pcc_rigid_from_sums(const double sums[17], float T[16]) { return pcc_rigid_from_sums_about(sums, nullptr, T); }
+
+int pcc_rigid_from_sums_about(const double sums[17], const double center[3], float T[16]) {
+    if (!sums || !T) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (rigid_from_sums(sums, T, center) != 0) { set_error("fewer than 3 correspondences"); return PCC_ERR_INVALID; }
+    return PCC_OK;
+}
+
+int pcc_icp_step(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, int32_t* idx, float* d2,
+                 double sums[17]) {
+    return pcc_icp_step_about(ix, src, n, stride, mem, nullptr, idx, d2, sums);
+}
+
+int pcc_icp_step_about(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, const double center[3],
+                       int32_t* idx, float* d2, double sums[17]) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_points(src, n, stride, mem));
+    if (center && !(std::isfinite(center[0]) && std::isfinite(center[1]) && std::isfinite(center[2]))) {
+        set_error("non-finite center");
+        return PCC_ERR_INVALID;
+    }
+    if (!sums) { set_error("null sums"); return PCC_ERR_INVALID; }
+    for (int k = 0; k < 17; ++k) sums[k] = 0;
+    if (n == 0) return PCC_OK;
+    if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    Nn1Call call;
+    PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
+    PCC_TRY(nn1_packed(ix, n, call));
+    const double* center_dev = nullptr;
+    if (center) {  // the sums are taken about it (device copy behind the ICP loop state)
+        PCC_TRY(ix->icp_state.reserve(sizeof(IcpState) + (3 + 17) * sizeof(double)));
+        double* cd = reinterpret_cast<double*>(ix->icp_state.as<char>() + sizeof(IcpState));
+        PCC_HIP(hipMemcpyAsync(cd, center, 3 * sizeof(double), hipMemcpyHostToDevice, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));  // (center is the caller's memory)
+        center_dev = cd;
+    }
+    PCC_TRY(icp_reduce(ix, n, sums, center_dev));
+    ev_mark(ix, EV_CALL1);
+    if (idx || d2) {
+        Out<int32_t> ri;
+        Out<float> rd;
+        PCC_TRY(ri.stage(idx, n, mem, ix->out_idx));
+        PCC_TRY(rd.stage(d2, n, mem, ix->out_d2));
+        PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, n, ri.dev, rd.dev));
+        PCC_TRY(finish(ix, mem, ri, rd));
+    }
+    return PCC_OK;
+}
+
+int pcc_transform(pcc_index* ix, const float T[16], const void* src, size_t n, size_t sstride, void* dst,
+                  size_t dstride, int mem) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_points(src, n, sstride, mem));
+    PCC_TRY(check_points(dst, n, dstride, mem));
+    if (!T) { set_error("null T"); return PCC_ERR_INVALID; }
+    if (n == 0) return PCC_OK;
+    if (mem == PCC_MEM_DEVICE) return launch_transform(ix->stream, nullptr, T, src, n, sstride, dst, dstride);
+    // host: stage src (and dst, so that its other fields survive) on the device
+    PCC_TRY(ix->q_raw.reserve(n * sstride));
+    PCC_HIP(hipMemcpyAsync(ix->q_raw.p, src, (n - 1) * sstride + 12, hipMemcpyHostToDevice, ix->stream));
+    void* ddst = ix->q_raw.p;
+    size_t dbytes = (n - 1) * dstride + 12;
+    if (dst != src || dstride != sstride) {
+        PCC_TRY(ix->scratch_d.reserve(n * dstride));
+        PCC_HIP(hipMemcpyAsync(ix->scratch_d.p, dst, dbytes, hipMemcpyHostToDevice, ix->stream));
+        ddst = ix->scratch_d.p;
+    }
+    PCC_TRY(launch_transform(ix->stream, nullptr, T, ix->q_raw.p, n, sstride, ddst, dstride));
+    PCC_HIP(hipMemcpyAsync(dst, ddst, dbytes, hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+
+int pcc_icp_align(pcc_index* ix, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
+                  float T[16], double* fitness, int* iterations, int* converged) {
+    return pcc::icp_align_impl(ix, nullptr, src, n, stride, mem, max_iter, fixed, T, fitness, iterations, converged);
+}
+}  // extern "C"
+
+// pcc_icp_align, and -- with `hooks` -- its sharded form: this handle holds one SHARD of the source cloud, the 17 sums of
+// every pass are added up over the ranks (hooks->allreduce_sum_f64: RCCL on the handle's stream, comm.hip) before the
+// solver sees them, so every rank solves the same transform and moves its shard (reference
+// src/comparator.cpp:1089-1110).  With one rank the all-reduce is the identity and the result is pcc_icp_align's, bit for bit.
+int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter,
+                        int fixed, float T[16], double* fitness, int* iterations, int* converged) {
+    // (PCC_ENTER without its early return: a device that cannot be selected is a failure of this rank alone and has to reach the
+    // status exchange below like every other one -- a return here would leave the peers waiting in it)
+    if (!ix) { set_error("null index"); return PCC_ERR_INVALID; }  // (the sharded entry point has checked this before its peers can wait)
+    pcc::Entry entry(ix);
+    const float I[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    int it = 0;
+    bool conv = false;
+    double prev_mse = 1.79769313486231570e308;
+    double* center_dev = nullptr;
+    bool sorted = false;
+    Nn1Call call;  // every search below is an ICP pass: they share the first pass's lane order (Nn1Call::order_given)
+    call.icp_pass = true;
+    // Everything that can fail on ONE rank alone -- argument checks, staging, allocations -- comes before the first
+    // collective and ends in a status the ranks agree on (hooks->agree: all-reduce MIN of one word), so a rank that
+    // cannot go on takes the others out with it instead of leaving them in the broadcast below (comm.hip).
+    auto prepare = [&]() -> int {
+        PCC_TRY(entry.status);
+        PCC_TRY(check_points(src, n, stride, mem));
+        if (!T) { set_error("null T"); return PCC_ERR_INVALID; }
+        if (ix->n_orig == 0) { set_error("index is empty"); return PCC_ERR_EMPTY; }
+        memcpy(T, I, sizeof(I));
+        if (iterations) *iterations = 0;
+        if (converged) *converged = 0;
+        if (n == 0 && hooks) { set_error("sharded ICP: every rank needs a non-empty shard"); return PCC_ERR_INVALID; }
+        if (n == 0) return PCC_OK;
+        // the source stays resident: q_packed is the moving cloud, icp_src keeps the input
+        PCC_TRY(stage_queries(ix, src, n, stride, mem, &call));
+        PCC_TRY(ix->icp_src.reserve(n * sizeof(float4)));
+        // Round 5: the loop's working set in the target grid's CELL order.  Nothing of the loop leaves per point -- T, fitness,
+        // counts -- so the permutation that a search pays per call (queries gathered through the sort order, keys scattered
+        // back: ~60 us of a 215-us pass at 2M points, tools/ubench/ubench_scatter.hip) is paid ONCE: the source is sorted by the
+        // cell it starts in, gathered into that order, and every pass reads it front to back with the identity as its order
+        // (a rigid motion keeps neighbouring points neighbours; any order is correct, as before).  The sums are added up in
+        // this order by every form of the loop -- device-resident, host-driven, sharded -- so they agree with each other to
+        // the bit as before; against the caller's order they differ in the last bits of a double sum.
+        sorted = ix->opt.icp_sorted != 0 && ix->engine == PCC_ENGINE_GRID && ix->has_grid && n >= 4096;
+        if (sorted) {
+            unsigned int *order = nullptr, *n_sorted = nullptr;
+            PCC_TRY(grid_sort_queries(ix, ix->q_packed.as<float4>(), n, &order, &n_sorted));
+            PCC_TRY(launch_gather_sorted(ix->stream, ix->q_packed.as<float4>(), order, n_sorted, n, ix->icp_src.as<float4>(),
+                                         &ix->words()->icp_nsorted));
+            PCC_HIP(hipMemcpyAsync(ix->q_packed.p, ix->icp_src.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
+        } else
+        PCC_HIP(hipMemcpyAsync(ix->icp_src.p, ix->q_packed.p, n * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
+        // the sums of every pass are taken about a point of the source cloud (k_icp_center: no cancellation in the
+        // covariance for clouds far from the origin); it sits behind the loop state in device memory
+        PCC_TRY(ix->icp_state.reserve(sizeof(IcpState) + (3 + 17) * sizeof(double)));
+        PCC_TRY(ix->scratch_a.reserve((size_t)ICP_MAX_BLOCKS * 17 * sizeof(double)));
+        center_dev = reinterpret_cast<double*>(ix->icp_state.as<char>() + sizeof(IcpState));
+        PCC_TRY(launch_icp_center(ix->stream, ix->q_packed.as<float4>(), n, center_dev));
+        return PCC_OK;
+    };
+    int st_prep = prepare();
+    if (hooks) st_prep = hooks->agree(hooks->ctx, st_prep);
+    if (st_prep != PCC_OK) return st_prep;
+    if (n == 0) return PCC_OK;
+    if (hooks) PCC_TRY(hooks->bcast_f64(hooks->ctx, center_dev, 3, 0, ix->stream));  // every rank about rank 0's point
+    const int warm_env = ix->opt.icp_warm;         // 0: every pass from scratch (measurements)
+    const int loop_env = hooks ? 1 : ix->opt.icp_device_loop;  // 0: the host-driven loop (kept for comparison: same bits)
+    double* sums_dev = center_dev + 3;  // (sharded: the 17 sums of a pass, all-reduced in place)
+    const bool fold = sorted && loop_env && grid_nn1_takes_transform(ix);  // the pass's transform applied by the next pass's search
+    if (sorted) {  // (the passes take the identity as their order; the count of valid points sits in a word of its own)
+        call.order_given = true; call.order_nq = n;
+        call.order = nullptr; call.n_sorted = &ix->words()->icp_nsorted;
+    }
+    if (loop_env) {
+        // The loop lives on the device: every pass is NN -> sums -> k_icp_solve (one workgroup: the transform, the running
+        // product and the convergence criteria) -> transform with the matrix the solver left in device memory.  Passes
+        // are enqueued in chunks without a host round trip (the host loop below pays a stream synchronisation, a
+        // read-back and a launch gap per pass, ~65 us of 0.44 ms); after each chunk the host looks whether the loop
+        // has stopped.  Passes enqueued past the stop are no-ops on the state (identity transform), so a chunk costs at
+        // most its own length in wasted searches -- none with a fixed count, where the whole loop is one chunk.
+        IcpState h0{};
+        memcpy(h0.Ti, I, sizeof(I));
+        memcpy(h0.T, I, sizeof(I));
+        h0.prev_mse = 1.79769313486231570e308;
+        PCC_HIP(hipMemcpyAsync(ix->icp_state.p, &h0, sizeof(h0), hipMemcpyHostToDevice, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));  // (h0 lives on this stack frame)
+        IcpState* st = ix->icp_state.as<IcpState>();
+        IcpState h1 = h0;
+        // passes per host look: 5 with criteria active; with a fixed count the loop would need none, but a source that
+        // leaves fewer than 3 correspondences stops it on the device and every pass enqueued beyond that is a wasted
+        // search -- so at most 32 at a time (one look costs ~20 us)
+        const int chunk = fixed ? (max_iter < 32 ? max_iter : 32) : 5;
+        for (int pass = 0; pass < max_iter && !h1.stopped;) {
+            for (int c = 0; c < chunk && pass < max_iter; ++c, ++pass) {
+                ev_next(ix);  // instrumentation: every pass is one "call" (NN kernel, far/fallback, whole pass)
+                ev_mark(ix, EV_CALL0);
+                // (cell-ordered loop: the search applies the previous pass's matrix -- the identity before the first -- to the
+                // queries it reads and writes them back; no transform kernel, grid.hip k_grid_nn1_flat2)
+                call.pre_transform = fold ? st->Ti : nullptr;
+                PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
+                call.pre_transform = nullptr;
+                call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
+                int nb = 0;
+                unsigned int* zw = ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr;
+                // (one GPU: the sums kernel's last workgroup solves the pass itself -- DevWords::icp_ticket is its ticket word;
+                // PCC_OPT_FUSE_PARAMS bit 1; the sharded loop keeps the solver's own launch: its sums pass through an all-reduce)
+                const bool fuse_solve = !hooks && (ix->opt.fuse_params & 2) != 0;
+                const IcpFuse fuse{&ix->words()->icp_ticket, st, max_iter, fixed, fold ? zw : nullptr};
+                PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
+                                        ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb, zw,
+                                        &ix->pinned->fb_mirror, center_dev, fuse_solve ? &fuse : nullptr));
+                if (fuse_solve) {
+                } else if (hooks) {  // rows -> 17 sums (workgroup order, as the solver adds them) -> sum over the ranks -> solve
+                    PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));
+                    PCC_TRY(hooks->allreduce_sum_f64(hooks->ctx, sums_dev, 17, ix->stream));
+                    PCC_TRY(launch_icp_solve(ix->stream, sums_dev, 1, st, max_iter, fixed, center_dev, fold ? zw : nullptr));
+                } else
+                PCC_TRY(launch_icp_solve(ix->stream, ix->scratch_a.as<double>(), nb, st, max_iter, fixed, center_dev, fold ? zw : nullptr));
+                // (the transform -- or, when the next search applies it itself, the solver -- also zeroes the counters of the next
+                // pass's search)
+                if (!fold) PCC_TRY(launch_transform(ix->stream, st->Ti, nullptr, ix->q_packed.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4), zw));
+                call.counters_cleared = zw != nullptr;
+                ev_mark(ix, EV_CALL1);
+            }
+            PCC_HIP(hipMemcpyAsync(&h1, ix->icp_state.p, sizeof(h1), hipMemcpyDeviceToHost, ix->stream));
+            PCC_HIP(hipStreamSynchronize(ix->stream));
+        }
+        memcpy(T, h1.T, sizeof(h1.T));
+        it = h1.it;
+        conv = h1.converged != 0;
+    } else {
+    double center[3] = {0, 0, 0};
+    bool have_center = false;
+    while (it < max_iter) {
+        ev_next(ix);  // instrumentation: every pass is one "call" (NN kernel, far/fallback, whole pass)
+        ev_mark(ix, EV_CALL0);
+        PCC_TRY(nn1_packed(ix, n, call));  // determineCorrespondences: one NN per source point
+        call.warm = warm_env != 0;  // from now on out_packed holds the last pass's keys of these same points
+        double sums[17];
+        PCC_TRY(icp_reduce(ix, n, sums, center_dev));
+        if (!have_center) {
+            PCC_HIP(hipMemcpyAsync(center, center_dev, sizeof(center), hipMemcpyDeviceToHost, ix->stream));
+            PCC_HIP(hipStreamSynchronize(ix->stream));
+            have_center = true;
+        }
+        float Ti[16];
+        if (rigid_from_sums(sums, Ti, center) != 0) { conv = false; break; }  // < 3 correspondences: not converged
+        PCC_TRY(launch_transform(ix->stream, nullptr, Ti, ix->q_packed.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4)));
+        ev_mark(ix, EV_CALL1);
+        mat4_mul_f(Ti, T, T);  // final = T_i * final
+        const double mse = sums[15] / sums[16];
+        ++it;
+        if (it >= max_iter) { conv = true; break; }  // DefaultConvergenceCriteria: iteration cap counts as converged
+        if (!fixed && std::fabs(mse - prev_mse) < 1e-12) { conv = true; break; }
+        prev_mse = mse;
+    }
+    }
+    if (iterations) *iterations = it;
+    if (converged) *converged = conv ? 1 : 0;
+    if (fitness) {
+        // getFitnessScore: re-transform the INPUT with the final matrix, one more NN pass, mean d2
+        PCC_TRY(launch_transform(ix->stream, nullptr, T, ix->icp_src.p, n, sizeof(float4), ix->q_packed.p, sizeof(float4)));
+        // launch_transform writes x,y,z only: refresh the validity flags from the input
+        PCC_TRY(launch_copy_w(ix->stream, ix->icp_src.as<float4>(), ix->q_packed.as<float4>(), n));
+        ev_next(ix);
+        ev_mark(ix, EV_CALL0);
+        PCC_TRY(nn1_packed(ix, n, call));
+        double sums[17];
+        if (hooks) {  // sum of d2 and count over ALL shards
+            int nb = 0;
+            PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(), ix->refs.as<float4>(),
+                                    ix->scratch_a.as<double>(), &nb, nullptr, nullptr, nullptr));
+            PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));
+            PCC_TRY(hooks->allreduce_sum_f64(hooks->ctx, sums_dev, 17, ix->stream));
+            PCC_HIP(hipMemcpyAsync(sums, sums_dev, sizeof(sums), hipMemcpyDeviceToHost, ix->stream));
+            PCC_HIP(hipStreamSynchronize(ix->stream));
+        } else
+        PCC_TRY(icp_reduce(ix, n, sums));
+        ev_mark(ix, EV_CALL1);
+        *fitness = sums[16] > 0 ? sums[15] / sums[16] : 1.79769313486231570e308;
+    }
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}

@@ -20,7 +20,7 @@
 // Same arithmetic as small.hip / nn1_brute.hip: d = dx * dx; d += dy * dy; d += dz * dz, every operation rounded
 // (-ffp-contract=off); non-finite references never take part; non-finite queries find nothing; a distance that overflowed
 // is no neighbour (key_none).
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include <algorithm>
 #include <thread>
 #include <unordered_map>
@@ -417,11 +417,7 @@ int pcc_match_knn_batch(pcc_index* ctx, size_t n_pairs, const void* const* des1,
     }
     if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
     if (n_pairs == 0) { out_offsets[0] = 0; return PCC_OK; }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) { set_error("hipSetDevice(%d) failed", ctx->device); return PCC_ERR_DEVICE; }
-    entered(ctx);
+    PCC_ENTER(ctx);
     return match_knn_batch(ctx, n_pairs, des1, n1, des2, n2, stride, threshold, out, out_offsets);
 }
-
 }  // extern "C"

@@ -12,7 +12,7 @@
 #include <cmath>
 #include <vector>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "lane_ops.hpp"
 #include "grid_device.hpp"
 #include "plane_fit.hpp"
@@ -219,3 +219,44 @@ int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* 
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_normals(pcc_index* ix, int k, const float viewpoint[3], int mem, float* out) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_mem(mem));
+    if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
+    if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const size_t n = ix->n_orig;
+    const float origin[3] = {0.f, 0.f, 0.f};
+    // self query on the packed references, as pcc_sor does
+    const unsigned long long* keys = nullptr;
+    PCC_TRY(self_knn_keys(ix, k, &keys));
+    Out<float4> rn;
+    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
+    PCC_TRY(launch_normals(ix->stream, keys, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, k,
+                           viewpoint ? viewpoint : origin, rn.dev));
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rn);
+}
+
+int pcc_normals_radius(pcc_index* ix, double radius, const float viewpoint[3], int mem, float* out) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_mem(mem));
+    if (!out) { set_error("null output"); return PCC_ERR_INVALID; }
+    if (!(radius >= 0)) { set_error("bad radius"); return PCC_ERR_INVALID; }
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const size_t n = ix->n_orig;
+    const float origin[3] = {0.f, 0.f, 0.f};
+    Out<float4> rn;
+    PCC_TRY(rn.stage(reinterpret_cast<float4*>(out), n, mem, ix->out_d2));
+    PCC_TRY(normals_radius(ix, radius, viewpoint ? viewpoint : origin, rn.dev));
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rn);
+}
+}  // extern "C"

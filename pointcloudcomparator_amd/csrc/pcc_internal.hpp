@@ -463,6 +463,16 @@ int launch_sor_partial(hipStream_t s, const float* m, size_t n, double* scratch,
 int launch_sor_threshold_mask(hipStream_t s, const float* m, size_t n, const GridDev* gd, int K, double stddev_mult,
                               const double* in4_dev, SorStats* stats_dev, uint8_t* inlier_dev);
 void sor_threshold_host(const double in4[4], double n_valid, int K, double stddev_mult, double* thr, int* exact);
+// ---- sor.hip: what pcc_sor, pcc_sor_partial and pcc_sor_sharded (comm.hip) share, over the points [start, start + count) ----
+constexpr size_t SOR_STATS_OUT4 = 3 * 1024;  // scratch of launch_sor_stats / _partial: 3 x 1024 partial doubles, then the four results
+constexpr size_t SOR_STATS_SCRATCH_BYTES = (SOR_STATS_OUT4 + 4) * sizeof(double) + 64;
+int sor_begin(pcc_index* ix, size_t start, size_t count, int mean_k);  // the arguments, and the grid the search needs
+// the mean stage: self K-NN of those points (K = mean_k + 1) and their mean distances, *dmean (ix->out_d2, `count` floats)
+int sor_means(pcc_index* ix, size_t start, size_t count, int K, float** dmean);
+// the in-order fallback: PCL's sums over ALL `no` mean distances (host memory) in index order -> threshold, kept count over the
+// whole cloud, and the inlier mask of those points in mask[0 .. count)
+void sor_in_order(const float* hm, size_t no, size_t n_valid, int K, double stddev_mult, size_t start, size_t count, double* thr,
+                  size_t* kept, uint8_t* mask);
 int launch_clamp_counts(hipStream_t s, int32_t* counts, size_t n, int32_t cap);
 int launch_knn_rows_to_csr(hipStream_t s, const unsigned long long* keys, const int32_t* ridx, const float* rd2, int K, float r2,
                            const int64_t* offsets, size_t nq, int32_t* idx_out, float* d2_out);
@@ -529,6 +539,8 @@ int voxel_grid(pcc_index* ctx, const void* pts, size_t n, size_t stride, int mem
 int grid_knn(pcc_index* ix, const float4* q, size_t nq, int K, unsigned long long* keys, int32_t* idx_out = nullptr,
              float* d2_out = nullptr);
 bool grid_knn_delivers(int K);
+// the self k-NN rows (keys) of the indexed cloud with k neighbours, kept between calls under PCC_OPT_KNN_CACHE_K
+int self_knn_keys(pcc_index* ix, int k, const unsigned long long** keys);
 // counts[i] = #refs with d2 < r2; with fill != 0 also writes keys at offsets[i]..
 // idx_out / d2_out / delivered (fill only): when given, a fill that takes the wave-per-query route writes the caller's
 // arrays itself (sorted in registers) and sets *delivered
@@ -536,13 +548,7 @@ int grid_radius(pcc_index* ix, const float4* q, size_t nq, float r, float r2, in
                 const int64_t* offsets, unsigned long long* keys, int sorted, size_t total = 0, int32_t* idx_out = nullptr,
                 float* d2_out = nullptr, bool* delivered = nullptr);
 constexpr int PCC_ERR_RETRY_HOST = -1000;  // sac_plane without a host array met a degenerate sample: repeat with one (internal)
-int sac_plane(pcc_index* ix, const float4* pts_dev, size_t n, const char* host_base, size_t host_stride,
-              int max_iterations, double threshold, double probability, int optimize, int32_t* inliers_dev,
-              size_t* n_inliers, float coeff[4], int* iterations_out);
-int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs,
-                   const GridDev* gd, size_t n, int K, const float vp[3], float4* out);
-int normals_radius(pcc_index* ix, double radius, const float vp[3], float4* out);
-// the two halves of normals_radius: the sorted self radius rows of the indexed cloud as a CSR (keys: d2 bits << 32 | point
+// the two halves of pcc_normals_radius (normals.hip): the sorted self radius rows of the indexed cloud as a CSR (keys: d2 bits << 32 | point
 // index; offsets[n + 1]; both stay valid until the next radius search on the handle), and the plane fit over such rows
 int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys, const unsigned int** offsets);
 int launch_normals_csr(pcc_index* ix, const unsigned long long* keys, const unsigned int* offsets, const float vp[3], float4* out);
@@ -569,17 +575,8 @@ int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pt
                            size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
                            int32_t* out_index, size_t* out_offsets);
 void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work handle
-// sift.hip: the SIFT keypoint detector on device arrays (ix->sift made by the caller); the keypoints stay in ix->sift->kp
-int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
-                   float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
 void sift_release(pcc_index* ix);  // frees ix->sift and its work handle
-int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const float4* normals, int K, float smoothness,
-                        float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels_dev,
-                        int32_t* n_clusters);
 int grid_first_within(pcc_index* ix, const float4* q, size_t nq, double radius, int32_t* idx_dev);
-// ---- cluster.hip ------------------------------------------------------------------------
-int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t max_size,
-                  int32_t* labels_dev /* n_orig, device */, int32_t* n_clusters, int32_t* sizes, int max_sizes);
 // ---- flann_order.hip: flags[i] = 1 when another reference shares query i's minimum distance; the tied queries walked
 // through FLANN's tree on the device
 int resolve_ties_flann(pcc_index* ix, const float4* q, unsigned long long* keys, size_t nq, bool may_wait = false);
@@ -616,10 +613,7 @@ struct IcpState {
 };
 int launch_icp_solve(hipStream_t s, const double* partials, int n_blocks, IcpState* state, int max_iter, int fixed,
                      const double* center_dev, unsigned int* zero_word = nullptr);
-int launch_icp_center(hipStream_t s, const float4* src, size_t n, double* center_dev);  // first valid point of src
-// the per-workgroup rows added up in workgroup order (what k_icp_solve does before it solves): sums17[k] on the device
-int launch_icp_rows_to_sums(hipStream_t s, const double* partials, int n_blocks, double* sums17);
-// collectives of the sharded ICP loop, supplied by comm.hip (RCCL on the handle's stream); api.hip knows no RCCL type
+// collectives of the sharded ICP loop, supplied by comm.hip (RCCL on the handle's stream); icp.hip knows no RCCL type
 struct IcpHooks {
     void* ctx;
     int (*allreduce_sum_f64)(void* ctx, double* dev, int count, hipStream_t s);
@@ -628,14 +622,13 @@ struct IcpHooks {
 };
 int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
                    float T[16], double* fitness, int* iterations, int* converged);
-// ---- api.hip internals comm.hip builds on -------------------------------------------------------------------------
+// ---- api.hip internals the other files build on ----------------------------------------------------------------------
 void match_batch_release(pcc_index* ix);  // match_batch.hip: frees ix->mb
 int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, Nn1Call* search = nullptr);
 int nn1_packed(pcc_index* ix, size_t nq, Nn1Call& call);
 int set_input(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem);
-int need_grid(pcc_index* ix);                              // (the GRID engine's index, built on demand)
 int make_handle(int device, int engine, pcc_index** out);  // an empty handle on `device`
 
 }  // namespace pcc

@@ -34,7 +34,7 @@
 #include <cmath>
 #include <vector>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "grid_device.hpp"
 #include "uf_device.hpp"
 
@@ -364,3 +364,29 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_region_growing(pcc_index* ix, const float* normals, int mem, int k, float smoothness,
+                       float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels,
+                       int32_t* n_clusters) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_mem(mem));
+    if (!normals || !labels || !n_clusters) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (k < 1 || k > PCC_KNN_MAX_K) { set_error("k=%d outside [1, %d]", k, PCC_KNN_MAX_K); return PCC_ERR_UNSUPPORTED; }
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const size_t n = ix->n_orig;
+    // findPointNeighbours: one batched self k-NN over the packed references
+    const unsigned long long* keys = nullptr;
+    PCC_TRY(self_knn_keys(ix, k, &keys));
+    const float4* dn = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const float4*>(normals), n, mem, ix->out_d2, &dn));
+    Out<int32_t> rl;
+    PCC_TRY(rl.stage(labels, n, mem, ix->q_raw));
+    PCC_TRY(grid_region_growing(ix, keys, dn, k, smoothness, curvature_threshold, min_size, max_size, rl.dev, n_clusters));
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rl);
+}
+}  // extern "C"

@@ -11,7 +11,7 @@
 // The arithmetic is rift_math.hpp's, shared with the host mirror of the tests: same operations, same order, same bits.
 #include <algorithm>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "lane_ops.hpp"
 #include "grid_device.hpp"
 #include "rift_math.hpp"
@@ -281,3 +281,41 @@ int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride,
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int mem, double normal_radius, double gradient_radius,
+                         double rift_radius, int nr_distance_bins, int nr_gradient_bins, float* out_hist, int32_t* out_index,
+                         size_t* n_out) {
+    // the arguments first: host arithmetic, refused before any device is looked at
+    PCC_TRY(check_mem(mem));
+    if (!rgb || !out_hist || !out_index || !n_out) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (rgb_stride < 4 || rgb_stride % 4 || reinterpret_cast<uintptr_t>(rgb) % 4) {
+        set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
+        return PCC_ERR_INVALID;
+    }
+    for (double r : {normal_radius, gradient_radius, rift_radius})
+        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
+    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
+        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    PCC_ENTER(ix);
+    PCC_TRY(ensure_grid(ix));
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const size_t n = ix->n_orig;
+    if (!ix->rift) ix->rift = new RiftScratch();
+    const unsigned char* drgb = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->rift->rgb, &drgb));
+    Out<float> rh;
+    Out<int32_t> ri;
+    PCC_TRY(rh.stage(out_hist, n * RIFT_BINS, mem, ix->rift->out_hist));
+    PCC_TRY(ri.stage(out_index, n, mem, ix->rift->out_index));
+    PCC_TRY(rift_descriptors(ix, drgb, rgb_stride, normal_radius, gradient_radius, rift_radius, rh.dev, ri.dev, n_out));
+    rh.count = *n_out * RIFT_BINS;  // (only the rows that were written travel)
+    ri.count = *n_out;
+    ev_mark(ix, EV_CALL1);
+    return finish(ix, mem, rh, ri);
+}
+}  // extern "C"

@@ -22,7 +22,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "lane_ops.hpp"
 #include "grid_device.hpp"
 #include "rift_math.hpp"
@@ -329,11 +329,7 @@ int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* cons
         if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
     }
     if (n_clouds == 0) { out_offsets[0] = 0; return PCC_OK; }  // (no device is touched: not even the handle's)
-    if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) { set_error("hipSetDevice(%d) failed", ctx->device); return PCC_ERR_DEVICE; }
-    entered(ctx);
+    PCC_ENTER(ctx);
     ev_next(ctx);
     ev_mark(ctx, EV_CALL0);
     if (!ctx->rift) ctx->rift = new RiftScratch();
@@ -342,5 +338,4 @@ int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* cons
     ev_mark(ctx, EV_CALL1);
     return st;
 }
-
 }  // extern "C"

@@ -22,7 +22,7 @@
 #include <cstring>
 #include <vector>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "plane_fit.hpp"
 
 namespace pcc {
@@ -365,3 +365,51 @@ int sac_plane(pcc_index* ix, const float4* pts_dev, size_t n_, const char* host_
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, int max_iterations,
+                  double threshold, double probability, int optimize, int32_t* inliers, size_t* n_inliers,
+                  float coeff[4], int* iterations) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (!n_inliers || !coeff || (n && !inliers)) { set_error("null output"); return PCC_ERR_INVALID; }
+    if (max_iterations < 0 || !(threshold >= 0) || !(probability > 0 && probability < 1)) {
+        set_error("bad RANSAC parameters");
+        return PCC_ERR_INVALID;
+    }
+    *n_inliers = 0;
+    coeff[0] = coeff[1] = coeff[2] = coeff[3] = 0.f;
+    if (iterations) *iterations = 0;
+    if (n == 0) return PCC_OK;
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    PCC_TRY(stage_queries(ix, pts, n, stride, mem));
+    const float4* dp = ix->q_packed.as<float4>();
+    // the sampling and the refit read single points on the host: from the caller's array when it is a host array; for a
+    // cloud in device memory the few points needed are gathered there (sac.hip) -- round 3 copied the whole cloud back
+    // (16 B x n per call; the -e plane-removal loop calls this a handful of times per cloud)
+    Out<int32_t> ri;
+    PCC_TRY(ri.stage(inliers, n, mem, ix->out_idx));
+    size_t m = 0;
+    int st = sac_plane(ix, dp, n, mem == PCC_MEM_HOST ? static_cast<const char*>(pts) : nullptr, stride, max_iterations, threshold,
+                       probability, optimize, ri.dev, &m, coeff, iterations);
+    if (st == PCC_ERR_RETRY_HOST) {
+        // a degenerate sample (PCL redraws it at once, which the gathered form cannot replay): with a host copy of the cloud
+        std::vector<float4> hp(n);
+        PCC_HIP(hipMemcpyAsync(hp.data(), dp, n * sizeof(float4), hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));
+        const float qnan = std::nanf("");
+        for (size_t i = 0; i < n; ++i)  // the staged copy zeroes non-finite points; PCL would see them as they are
+            if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
+        st = sac_plane(ix, dp, n, reinterpret_cast<const char*>(hp.data()), sizeof(float4), max_iterations, threshold, probability,
+                       optimize, ri.dev, &m, coeff, iterations);
+    }
+    PCC_TRY(st);
+    ev_mark(ix, EV_CALL1);
+    ri.count = m;  // (the first m of the n reserved)
+    if (m) PCC_TRY(finish(ix, mem, ri));
+    *n_inliers = m;
+    return PCC_OK;
+}
+}  // extern "C"

@@ -13,7 +13,7 @@
 #include <cmath>
 #include <vector>
 
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "lane_ops.hpp"
 #include "sift_math.hpp"
 
@@ -310,3 +310,48 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, const void* rgb, size_t rgb_stride, int mem, float min_scale,
+                       int nr_octaves, int nr_scales_per_octave, float min_contrast, float* out_keypoints, size_t capacity, size_t* n_out) {
+    // the arguments first: host arithmetic, refused before any device is looked at
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (!n_out || (n && !rgb) || (capacity && !out_keypoints)) { set_error("null argument"); return PCC_ERR_INVALID; }
+    if (rgb_stride < 4 || rgb_stride % 4 || (n && (reinterpret_cast<uintptr_t>(rgb) % 4 || reinterpret_cast<uintptr_t>(pts) % 4)) ||
+        (capacity && reinterpret_cast<uintptr_t>(out_keypoints) % 4)) {
+        set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
+        return PCC_ERR_INVALID;
+    }
+    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
+    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
+    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
+    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
+        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
+                  SIFT_MAX_SCALES_PER_OCTAVE);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    PCC_ENTER(ix);
+    *n_out = 0;
+    if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    if (!ix->sift) ix->sift = new SiftScratch();
+    const unsigned char *dpts = nullptr, *drgb = nullptr;
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(pts), (n - 1) * stride + 12, mem, ix->sift->pts, &dpts));
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->sift->rgb, &drgb));
+    size_t found = 0;
+    PCC_TRY(sift_keypoints(ix, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
+    ev_mark(ix, EV_CALL1);
+    *n_out = found;
+    if (found > capacity) {
+        set_error("%zu keypoints, room for %zu", found, capacity);
+        return PCC_ERR_OVERFLOW;
+    }
+    if (found == 0) return PCC_OK;
+    // (no Out / finish: the keypoints collect in the scratch's own buffer and leave it by one plain copy in either memory space)
+    PCC_TRY(copy_out(ix, out_keypoints, ix->sift->kp.p, found * 4 * sizeof(float), mem));
+    if (mem == PCC_MEM_HOST) PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+}  // extern "C"

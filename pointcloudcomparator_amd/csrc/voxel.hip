@@ -11,7 +11,7 @@
 // sort produced and rounds once, so each coordinate is within a float ulp or two of PCL's and
 // does not depend on the order; colour sums are integers (exact) divided in float exactly as PCL
 // does.  HBM-bound streaming passes apart from the sort's scatter.
-#include "pcc_internal.hpp"
+#include "entry.hpp"
 #include "grid_device.hpp"
 #include <cmath>
 #include <cstring>
@@ -156,3 +156,19 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
 }
 
 }  // namespace pcc
+
+using namespace pcc;
+extern "C" {
+int pcc_voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, float leaf, int has_rgb,
+                   void* out, size_t out_stride, size_t* out_n) {
+    PCC_ENTER(ix);
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (!out || !out_n) { set_error("null output"); return PCC_ERR_INVALID; }
+    if (out_stride < 12 || out_stride % 4) { set_error("bad output stride"); return PCC_ERR_INVALID; }
+    if (has_rgb && (stride < 20 || out_stride < 20)) { set_error("rgb needs a stride of at least 20 bytes"); return PCC_ERR_INVALID; }
+    if (!(leaf > 0.f)) { set_error("leaf size must be positive"); return PCC_ERR_INVALID; }
+    *out_n = 0;
+    if (n == 0) return PCC_OK;
+    return voxel_grid(ix, pts, n, stride, mem, leaf, has_rgb, out, out_stride, out_n);
+}
+}  // extern "C"

@@ -134,6 +134,24 @@ def test_python_sharding_helper_over_the_real_partial_sums(gpu):
     assert (_bits(smd) == _bits(md)).all() and (sinl == inl.astype(bool)).all()
 
 
+def test_sharded_sor_takes_the_in_order_fallback_as_pcc_sor_does(gpu):
+    """micrometre clumps next to decimetres (the cloud of test_sor_statistics_on_the_device_and_the_in_order_fallback, which ties
+    pcc_sor to the oracle there): additions of PCL's in-order sums round, so pcc_sor AND pcc_sor_sharded must walk the mean
+    distances in index order on the host -- one function behind both -- and agree bit for bit"""
+    rng = np.random.default_rng(5)
+    wide = synth.corridor_cloud(60000, synth.SEED_A)
+    seeds = wide[:300]
+    clumps = (seeds[:, None, :] + rng.normal(0, 2e-7, (300, 70, 3))).reshape(-1, 3).astype(np.float32)  # 70 points within a micrometre
+    wide = np.concatenate([wide[300:], clumps]).astype(np.float32)
+    with capi.Comm.from_id(capi.comm_unique_id(), 1, 0, 0) as comm, capi.Index(wide) as ix:
+        md, inl, thr, kept = ix.sor(50, 1.5)
+        assert not ix.sor_on_device(), "pcc_sor took its sums on the device: the fallback was not run"
+        smd, sinl, sthr, skept = ix.sor_sharded(comm, 0, len(wide), 50, 1.5)
+        assert not ix.sor_on_device(), "pcc_sor_sharded took its sums on the device: the fallback was not run"
+    assert (_bits(md) == _bits(smd)).all()
+    assert thr == sthr and (inl == sinl).all() and kept == skept
+
+
 def test_a_rank_that_cannot_allocate_returns_nomem_and_the_communicator_stays_usable(gpu):
     """Collectives that cannot hang: every failure of one rank alone (here an injected allocation failure, hook
     pcc_debug_fail_alloc) ends in the status word the ranks agree on before the data collective, so the call returns the
@@ -174,3 +192,19 @@ def test_a_rank_that_cannot_allocate_returns_nomem_and_the_communicator_stays_us
         capi.Comm.local([0])
     L.pcc_debug_fail_alloc(0)
     assert e.value.status == -4
+
+
+def test_sor_partial_into_device_memory_equals_the_host_call(gpu):
+    """pcc_sor_partial with PCC_MEM_DEVICE copies the shard's mean distances into the caller's device array and still waits for
+    `sums`; a 1000-point cloud, the middle shard, the host call's bits"""
+    import ctypes as C
+    import torch
+    pts = synth.corridor_cloud(1000, synth.SEED_A)
+    with capi.Index(pts) as ix:
+        md, sums = ix.sor_partial(300, 400, 20)
+        dev = torch.zeros(400, dtype=torch.float32, device="cuda:0")
+        dsums = (C.c_double * 4)()
+        torch.cuda.synchronize()
+        assert capi.LIB.pcc_sor_partial(ix._h, 300, 400, 20, capi.MEM_DEVICE, dev.data_ptr(), dsums) == 0
+        assert (_bits(dev.cpu().numpy()) == _bits(md)).all() and md.max() > 0
+        assert (np.array(list(dsums)).view(np.uint64) == sums.view(np.uint64)).all()

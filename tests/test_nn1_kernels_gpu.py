@@ -117,3 +117,83 @@ def test_options_are_per_handle_and_validated(gpu):
         for opt, bad in ((capi.OPT_GRID_PPC, 0.0), (capi.OPT_FAR_MODE, 2), (capi.OPT_NN1_KERNEL, 4), (99, 1), (capi.OPT_ICP_WARM, 0.5)):
             with pytest.raises(capi.PccError):
                 ix.set_option(opt, bad)
+
+
+_FLAG = "flag"  # exactly 0 or 1
+_INF = float("inf")
+# option, built-in default, lowest and highest accepted value, values just outside either end, (fractional value, what is stored) for
+# int options.  Read off the range switch and struct Options as they stood before the options became one table.
+_OPTION_RANGES = [
+    (capi.OPT_GRID_PPC, 0.75, 5e-324, 1024.0, [0.0, -5e-324, np.nextafter(1024.0, _INF)], None),
+    (capi.OPT_GRID_TRIM, 3, 0, 8, [-0.5, 8.5], (2.5, 2)),
+    (capi.OPT_FAR_MODE, -1, -1, 1, [-1.5, 1.5], (0.5, 0)),
+    (capi.OPT_ICP_WARM, 1, 0, 1, _FLAG, None),
+    (capi.OPT_ICP_DEVICE_LOOP, 1, 0, 1, _FLAG, None),
+    (capi.OPT_EC_CELLS, 3, 0, 4, [-0.5, 4.5], (1.5, 1)),
+    (capi.OPT_SORT_MP_MIN, 1.8e6, 0.0, 1.7e308, [-5e-324, -1.0], None),
+    (capi.OPT_SORT_MP_MIN_Q, 2.5e6, 0.0, 1.7e308, [-5e-324, -1.0], None),
+    (capi.OPT_NN1_KERNEL, 1, 0, 3, [-0.5, 3.5], (2.7, 2)),
+    (capi.OPT_FLANN_SPLIT, 0, 0, 2, [-0.5, 2.5], (1.5, 1)),
+    (capi.OPT_NN1_DENSE_MIN, 4, 1, 1000000, [0, 0.5, 1000000.5], (7.9, 7)),
+    (capi.OPT_KNN_KERNEL, 1, 0, 1, _FLAG, None),
+    (capi.OPT_KNN_CACHE_K, 0, 0, 512, [-0.5, 512.5], (50.5, 50)),
+    (capi.OPT_NN1_OPEN_FLAT, 1, 0, 1, _FLAG, None),
+    (capi.OPT_SORT_STAGE1, 1, 0, 2, [-0.5, 2.5], (1.5, 1)),
+    (capi.OPT_ICP_SORTED, 1, 0, 1, _FLAG, None),
+    (capi.OPT_OVERLAP_PREP, 1, 0, 2, [-0.5, 2.5], (1.9, 1)),
+    (capi.OPT_GRID_AXES, -1, -2, 5, [-2.5, 5.5], (3.5, 3)),
+    (capi.OPT_XCD_RUN, 256, 1, 4096, [0, 0.5, 4096.5], (32.5, 32)),
+    (capi.OPT_FUSE_PARAMS, 0, 0, 3, [-0.5, 3.5], (2.5, 2)),
+    (capi.OPT_HOST_PIPE, 1, 0, 1, _FLAG, None),
+    (capi.OPT_SCAN_CHAINED, 1, 0, 1, _FLAG, None),
+    (capi.OPT_KNN_RUN, 16, 1, 64, [0, 0.5, 64.5], (8.5, 8)),
+    (capi.OPT_RIFT_LAYOUT, 1, 0, 1, _FLAG, None),
+    (capi.OPT_SIFT_LAYOUT, 1, 0, 1, _FLAG, None),
+    (capi.OPT_RIFT_BATCH_BRUTE_MAX, 8192, 0, 1073741824, [-0.5, 1073741824.5], (4500.5, 4500)),
+]
+
+
+def test_every_option_keeps_its_range_and_default(gpu):
+    """all 26 options of pcc_index_set_option: the default a handle starts with, both ends of the accepted range (they
+    round-trip), a fractional value inside an int option's range (its truncation is stored), and what is refused -- values just
+    outside either end, anything but 0 and 1 for a flag, NaN, the infinities, an unknown option -- leaving the stored value alone"""
+    assert [row[0] for row in _OPTION_RANGES] == list(range(1, 27))
+    cloud = np.random.default_rng(3).random((100, 3), dtype=np.float32)
+    with capi.Index(cloud) as ix:
+        for opt, default, lo, hi, outside, frac in _OPTION_RANGES:
+            assert ix.get_option(opt) == default, opt
+            for v in (lo, hi):
+                ix.set_option(opt, v)
+                assert ix.get_option(opt) == v, (opt, v)
+            if frac is not None:
+                ix.set_option(opt, frac[0])
+                assert ix.get_option(opt) == frac[1], (opt, frac)
+            if outside is _FLAG:
+                outside = [-1, -0.5, 0.5, 1.5, 2]
+            before = ix.get_option(opt)
+            for bad in list(outside) + [float("nan"), _INF, -_INF]:
+                with pytest.raises(capi.PccError):
+                    ix.set_option(opt, bad)
+                assert ix.get_option(opt) == before, (opt, bad)
+        with pytest.raises(capi.PccError):
+            ix.set_option(99, 1)
+        with pytest.raises(capi.PccError):
+            ix.get_option(99)
+
+
+def test_environment_variables_give_a_new_handle_its_defaults(gpu):
+    """PCC_* variables in a fresh process: an int option keeps the truncation of a fractional value inside its range (2.7 -> 2),
+    values pcc_index_set_option would refuse are ignored (a grid of 0 points per cell, a flag of 2), others are taken (8)"""
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    child = ("import numpy as np\n"
+             "from pointcloudcomparator_amd import capi\n"
+             "with capi.Index(np.random.default_rng(3).random((100, 3), dtype=np.float32)) as ix:\n"
+             "    print('options', *[ix.get_option(o) for o in (capi.OPT_NN1_KERNEL, capi.OPT_GRID_PPC, capi.OPT_HOST_PIPE, capi.OPT_KNN_RUN)])\n")
+    env = dict(os.environ, PCC_NN1_KERNEL="2.7", PCC_GRID_PPC="0", PCC_HOST_PIPE="2", PCC_KNN_RUN="8")
+    out = subprocess.run([sys.executable, "-c", child], cwd=Path(__file__).resolve().parents[1], env=env, capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr
+    assert [ln for ln in out.stdout.splitlines() if ln.startswith("options")] == ["options 2.0 0.75 1.0 8.0"]

@@ -176,3 +176,17 @@ def test_normals_with_radius_search(radius):
     np.testing.assert_allclose(got[ok, 3], want[ok, 3], rtol=0, atol=1e-6)
     if radius == 0.03:
         assert both_nan.sum() > 1  # sparse corners: fewer than 3 points within 3 cm
+
+
+def test_normals_radius_into_device_memory_equals_the_host_call():
+    """pcc_normals_radius with PCC_MEM_DEVICE writes the caller's device array itself; 1000 points, the host call's bits"""
+    import ctypes as C
+    import torch
+    pts = _room(n_per=250)
+    with capi.Index(pts) as ix:
+        host = ix.normals_radius(0.3)
+        dev = torch.zeros((len(pts), 4), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        assert capi.LIB.pcc_normals_radius(ix._h, C.c_double(0.3), None, capi.MEM_DEVICE, dev.data_ptr()) == 0
+        ix.sync()
+        assert np.isfinite(host).all(1).sum() > 900 and _same_bits(dev.cpu().numpy(), host).all()

@@ -201,6 +201,26 @@ def test_sor_statistics_on_the_device_and_the_in_order_fallback(gpu):
     assert (_bits(md) == _bits(omd)).all() and thr == othr and (inl == oinl).all() and kept == okept
 
 
+def test_voxel_grid_and_clusters_with_device_arrays_equal_the_host_calls(gpu):
+    """pcc_voxel_grid and pcc_euclidean_clusters with PCC_MEM_DEVICE: the kernels write the caller's device arrays themselves,
+    nothing is staged; a 1000-point cloud, the host calls' results"""
+    import ctypes as C
+    import torch
+    pts = _scene(1000)
+    with capi.Index(pts) as ix:
+        vox = ix.voxel_grid(pts, 0.5)
+        dpts = torch.from_numpy(pts).cuda()
+        dvox = torch.zeros((len(pts), 3), dtype=torch.float32, device="cuda:0")
+        cnt = C.c_size_t(0)
+        torch.cuda.synchronize()
+        assert capi.LIB.pcc_voxel_grid(ix._h, dpts.data_ptr(), len(pts), 12, capi.MEM_DEVICE, C.c_float(0.5), 0, dvox.data_ptr(), 12, C.byref(cnt)) == 0
+        ix.sync()
+        assert cnt.value == len(vox) > 1 and (_bits(dvox.cpu().numpy()[:cnt.value]) == _bits(vox)).all()
+        labels, ncl, sizes = ix.euclidean_clusters(0.3, 5, 1000)
+        dl, dncl, dsizes = ix.euclidean_clusters(0.3, 5, 1000, device_out=dpts)
+        assert ncl == dncl > 0 and (sizes == dsizes).all() and (dl.cpu().numpy() == labels).all()
+
+
 @pytest.mark.parametrize("max_nn", [1, 7, 60, 600])
 def test_radius_search_with_max_nn_keeps_the_nearest(gpu, max_nn):
     """KdTreeFLANN::radiusSearch(..., max_nn): FLANN's KNNRadiusResultSet keeps the max_nn nearest within the radius,
