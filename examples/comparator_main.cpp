@@ -41,8 +41,9 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --rift (clusters of a scene without a descriptor file get their descriptors from pcc::processRIFT),
 // --sift (with --rift: clusters above 700 points take pcc::processRIFTwithSIFT, the reference's own choice),
 // --rift-loop (with --rift: one call per cluster as in the reference, :1224-1272, instead of one pcc::processRIFTBatch for all),
-// --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read)
-static int n_gpus = 1;
+// --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read),
+// --descriptor-dims N (the bins of a descriptor the cluster matching searches on)
+static int n_gpus = 1, descriptor_dims = 3;
 static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
@@ -67,6 +68,9 @@ static void printUsage() {
               << "--rift-loop        (this build, with --rift) one library call per cluster, as the reference's loop does; without it\n"
               << "                   every cluster of both scenes goes through ONE processRIFTBatch call (same descriptors)\n"
               << "--dump-descriptors P  (this build) write the descriptors in use as P_<scene>.txt (the format of --descriptors1/2)\n"
+              << "--descriptor-dims N  (this build) the cluster matching searches on the first N bins of every descriptor, 1 ... 32\n"
+              << "                   (default 3: what the reference's PCL does with a 32-bin histogram -- recalled, not re-checked;\n"
+              << "                   32 matches on the whole histogram; exact ties then go to the lowest index)\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
@@ -298,7 +302,7 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
             }
         }
     std::vector<int> matches;
-    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches);
+    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims);
 
     if (noise) {
         PointCloud<PointXYZRGB> nonoise[2];
@@ -357,10 +361,12 @@ int main(int argc, char** argv) {
         else if (a == "--sift") sift = true;
         else if (a == "--rift-loop") rift_loop = true;
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
+        else if (a == "--descriptor-dims" && i + 1 < argc) descriptor_dims = std::atoi(argv[++i]);
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }
     if (sift && !rift) { std::cerr << "--sift needs --rift\n"; printUsage(); return 1; }
+    if (descriptor_dims < 1 || descriptor_dims > 32) { std::cerr << "--descriptor-dims takes 1 ... 32\n"; printUsage(); return 1; }
     std::cout << (seeClusters ? "Visualization of clusters is on." : "Visualization of clusters is off.") << std::endl;
     std::cout << (noise ? "Noise analysis is on." : "Noise analysis is off.") << std::endl;
     std::cout << (icp ? "ICP matching pre-comparison is on." : "ICP matching pre-comparison is off.") << std::endl;

@@ -23,8 +23,15 @@ typedef Histogram<32> RIFT32;  // reference src/comparator.cpp:9
 // Tree on descriptors1, one k=1 query per element of descriptors2, match kept when
 // neighborCount == 1 && d2 < 0.05f.  The returned vector STARTS WITH ONE DUMMY 0 (:568), so
 // size() == matches + 1 -- callers divide size() by descriptor counts (:1336-1338).
+// dims: the bins of a descriptor the search reads, 1 ... 32.  3 is what the reference's PCL does (pcl::Histogram<32> has no
+// point representation of its own; recalled); any other value runs matchRIFTFeaturesKnnBatch on this one pair.
+inline std::vector<std::vector<int> > matchRIFTFeaturesKnnBatch(
+    const std::vector<std::pair<PointCloud<RIFT32>::Ptr, PointCloud<RIFT32>::Ptr> >& pairs, int dims);
 inline std::vector<int> matchRIFTFeaturesKnn(const PointCloud<RIFT32>::Ptr& descriptors1,
-                                             const PointCloud<RIFT32>::Ptr& descriptors2) {
+                                             const PointCloud<RIFT32>::Ptr& descriptors2, int dims = 3) {
+    if (dims != 3)
+        return matchRIFTFeaturesKnnBatch(std::vector<std::pair<PointCloud<RIFT32>::Ptr, PointCloud<RIFT32>::Ptr> >(
+                                             1, std::make_pair(descriptors1, descriptors2)), dims)[0];
     std::vector<int> correspondence(1);
     // `= new KdTreeFLANN<RIFT32>(false)` in the reference: sorted == true, and one (leaked) tree per
     // call.  Here one tree per thread is re-pointed at each descriptor cloud: the reference calls this
@@ -48,8 +55,10 @@ inline std::vector<int> matchRIFTFeaturesKnn(const PointCloud<RIFT32>::Ptr& desc
 // pairs[p] = (descriptors1, descriptors2) of one call; element p of the result is what matchRIFTFeaturesKnn(pairs[p]) returns
 // (PCC_TIES_FLANN as there; a null or empty cloud on either side gives the dummy alone).  One pcc_match_knn_batch: one
 // upload, one search launch and one wait for all pairs.  No pair at all makes no library call.
+// dims: the bins the search reads (pcc_match_knn_batch_dims when not 3: on the whole histogram with 32; exact ties then go to
+// the lowest index).
 inline std::vector<std::vector<int> > matchRIFTFeaturesKnnBatch(
-    const std::vector<std::pair<PointCloud<RIFT32>::Ptr, PointCloud<RIFT32>::Ptr> >& pairs) {
+    const std::vector<std::pair<PointCloud<RIFT32>::Ptr, PointCloud<RIFT32>::Ptr> >& pairs, int dims = 3) {
     std::vector<std::vector<int> > result(pairs.size(), std::vector<int>(1));
     if (pairs.empty()) return result;
     static thread_local KdTreeFLANN<RIFT32> context;  // lends device, stream and scratch; the cloud it indexes is never asked
@@ -72,8 +81,12 @@ inline std::vector<std::vector<int> > matchRIFTFeaturesKnnBatch(
         total += n2[p];
     }
     std::vector<int32_t> out(total);
-    check(pcc_match_knn_batch(context.handle(), pairs.size(), d1.data(), n1.data(), d2.data(), n2.data(), sizeof(RIFT32), PCC_MEM_HOST,
-                              0.05f, out.data(), offsets.data()));
+    if (dims == 3)
+        check(pcc_match_knn_batch(context.handle(), pairs.size(), d1.data(), n1.data(), d2.data(), n2.data(), sizeof(RIFT32), PCC_MEM_HOST,
+                                  0.05f, out.data(), offsets.data()));
+    else
+        check(pcc_match_knn_batch_dims(context.handle(), pairs.size(), d1.data(), n1.data(), d2.data(), n2.data(), sizeof(RIFT32), dims,
+                                       PCC_MEM_HOST, 0.05f, out.data(), nullptr, offsets.data()));
     for (size_t p = 0; p < pairs.size(); ++p) result[p].assign(out.begin() + offsets[p], out.begin() + offsets[p + 1]);
     return result;
 }

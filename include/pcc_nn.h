@@ -345,6 +345,32 @@ int pcc_match_knn_batch(pcc_index *ctx, size_t n_pairs,
                         const void *const *des2, const size_t *n2,
                         size_t stride_bytes, int mem, float threshold,
                         int32_t *out, size_t *out_offsets);
+/* The same on the first `dim` floats of every record, dim = 1 ... 32 -- matching on the descriptor itself.  The reference's
+ *   PCL searches three bins of a RIFT32 (pcl::Histogram<32> has no point representation of its own; recalled, SURVEY.md
+ *   3.2 / 9.1), which is what dim = 3 and pcc_match_knn_batch do; dim = 32 matches on the whole histogram (the calls of
+ *   src/comparator.cpp:560-588 made from :1296-1365, as above).  N-dimensional search exists for descriptor matching
+ *   only: pcc_index_create and pcc_index_set_input keep refusing dim != 3, and no index is built over N-D records.
+ *   Everything is as for pcc_match_knn_batch (rows, the dummy 0, d2 < threshold strict, out_offsets, ctx as context only,
+ *   host arrays only) except:
+ *   distance: FLANN's L2_Simple over dim terms in float32, every operation rounded on its own, in index order:
+ *     d = d0 * d0; d = d + d1 * d1; ... d = d + d(dim-1) * d(dim-1).  The order is part of the result.
+ *   validity: a record is valid when its first dim floats are all finite (PCL's isValid over nr_dimensions); floats at dim
+ *     and beyond are never read.  An invalid reference takes part in no search, an invalid query finds nothing, a distance
+ *     that overflowed to +inf is no neighbour.
+ *   stride_bytes: a multiple of 4 and >= 4 * dim; of the last record of an array only 4 * dim bytes are read.
+ *   out_d2 (nullable): parallel to out -- the squared distance of every kept match, 0.0f at each row's dummy.
+ *   dim == 3: the search of pcc_match_knn_batch itself, bit for bit, PCC_TIES_FLANN and pcc_index_stats [1]/[5]/[6]
+ *     included.
+ *   dim != 3, exact ties: among references at exactly the same distance the LOWEST INDEX wins, whatever tie order the
+ *     handle has -- FLANN's tree is built here in three dimensions only, so an N-dimensional FLANN visit order could not
+ *     be checked against anything.  pcc_index_stats [5] still reports the number of tied queries; [6] is 0.
+ *   Refused before the handle is looked at, in this order: dim outside 1 ... 32 (PCC_ERR_UNSUPPORTED), a bad stride
+ *     (PCC_ERR_INVALID), then everything pcc_match_knn_batch refuses, a null handle last.  A refused call writes nothing. */
+int pcc_match_knn_batch_dims(pcc_index *ctx, size_t n_pairs,
+                             const void *const *des1, const size_t *n1,
+                             const void *const *des2, const size_t *n2,
+                             size_t stride_bytes, int dim, int mem, float threshold,
+                             int32_t *out, float *out_d2 /* nullable */, size_t *out_offsets);
 
 /* ---- voxel-grid down-sampling -----------------------------------------------------------------------
  * replaces: pcl::VoxelGrid<PointXYZRGB> with setLeafSize(l, l, l) + filter, the first step of both

@@ -32,7 +32,7 @@ SYMBOLS = [
     "pcc_index_sync", "pcc_index_engine", "pcc_index_set_engine",
     "pcc_nn1", "pcc_knn", "pcc_radius_count", "pcc_radius_fill", "pcc_radius_count_max", "pcc_radius_fill_max",
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
-    "pcc_match_knn", "pcc_match_knn_batch", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
+    "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
@@ -119,6 +119,7 @@ def _load() -> C.CDLL:
                                   C.POINTER(C.c_double), C.POINTER(i32), C.POINTER(i32)]
     lib.pcc_match_knn.argtypes = [vp, vp, sz, sz, i32, C.c_float, vp, C.POINTER(C.c_int32)]
     lib.pcc_match_knn_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, C.c_float, vp, vp]
+    lib.pcc_match_knn_batch_dims.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, i32, C.c_float, vp, vp, vp]
     lib.pcc_comm_unique_id.argtypes = [vp, sz]
     lib.pcc_comm_create_rank.argtypes = [vp, sz, i32, i32, i32, C.POINTER(vp)]
     lib.pcc_comm_create_local.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
@@ -165,6 +166,14 @@ def _points(x):
         return x.data_ptr(), x.shape[0], x.stride(0) * 4 if x.shape[0] > 1 else x.shape[1] * 4, mem
     a = x
     assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 2 and a.shape[1] >= 3
+    assert a.shape[0] == 0 or a.strides[1] == 4
+    stride = a.strides[0] if a.shape[0] > 1 else a.shape[1] * 4
+    return a.ctypes.data, a.shape[0], stride, MEM_HOST
+
+
+def _records(a, dim):
+    """(pointer, n, stride_bytes, mem) of an (n, >= dim) float32 numpy array of descriptor records (host memory)."""
+    assert isinstance(a, np.ndarray) and a.dtype == np.float32 and a.ndim == 2 and a.shape[1] >= min(max(int(dim), 1), 32)
     assert a.shape[0] == 0 or a.strides[1] == 4
     stride = a.strides[0] if a.shape[0] > 1 else a.shape[1] * 4
     return a.ctypes.data, a.shape[0], stride, MEM_HOST
@@ -810,43 +819,56 @@ class Index:
                                  C.byref(sz)))
         return out[:sz.value]
 
-    def match_knn_batch(self, pairs, threshold: float = 0.05, ties=None):
+    def match_knn_batch(self, pairs, threshold: float = 0.05, ties=None, dim: int = 3, return_d2: bool = False):
         """pcc_match_knn_batch with this handle as the context: `pairs` is a sequence of (des1, des2) float32 numpy arrays of
         one row stride; returns one int32 array per pair, each what Index(des1).match_knn(des2) returns.  The cloud the
-        handle indexes is neither read nor changed.  ties: None = the handle's own tie order, else that order for this call."""
+        handle indexes is neither read nor changed.  ties: None = the handle's own tie order, else that order for this call.
+        dim: the number of leading floats of a record the search reads, 1 ... 32 (pcc_match_knn_batch_dims; 3 is what the
+        single call reads).  return_d2: also the squared distances -- the result is then (indices, d2), two lists of arrays
+        of equal shapes (0.0 beside each row's dummy)."""
         pairs = list(pairs)
         n = len(pairs)
-        args = [(_points(a), _points(b)) for a, b in pairs]
-        strides = {x[2] for ab in args for x in ab}
+        plain = dim == 3 and not return_d2
+        args = [(_points(a), _points(b)) if plain else (_records(a, dim), _records(b, dim)) for a, b in pairs]
+        strides = {x[2] for ab in args for x in ab} if plain else {x[2] for ab in args for x in ab if x[1] > 1}
         assert len(strides) <= 1, "every descriptor array of a batch must have the same row stride"
         assert all(x[3] == MEM_HOST for ab in args for x in ab), "pcc_match_knn_batch takes host arrays"
-        stride = strides.pop() if strides else 12
+        stride = strides.pop() if strides else (12 if plain else 4 * max(int(dim), 1))
         vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
         d1 = vps(*[a[0] if a[1] else None for a, _ in args])
         d2 = vps(*[b[0] if b[1] else None for _, b in args])
         n1 = szs(*[a[1] for a, _ in args])
         n2 = szs(*[b[1] for _, b in args])
         out = np.empty(sum(b[1] for _, b in args) + n, dtype=np.int32)
+        dist = np.empty(len(out), dtype=np.float32) if return_d2 else None
         off = np.zeros(n + 1, dtype=np.uintp)
         own = self._ties
         if ties is not None and ties != own:
             self.set_tie_order(ties)
         try:
-            _check(LIB.pcc_match_knn_batch(self._h, n, d1, n1, d2, n2, stride, MEM_HOST, np.float32(threshold),
-                                           out.ctypes.data, off.ctypes.data))
+            if plain:
+                _check(LIB.pcc_match_knn_batch(self._h, n, d1, n1, d2, n2, stride, MEM_HOST, np.float32(threshold),
+                                               out.ctypes.data, off.ctypes.data))
+            else:
+                _check(LIB.pcc_match_knn_batch_dims(self._h, n, d1, n1, d2, n2, stride, int(dim), MEM_HOST, np.float32(threshold),
+                                                    out.ctypes.data, dist.ctypes.data if return_d2 else None, off.ctypes.data))
         finally:
             if self._ties != own:
                 self.set_tie_order(own)
-        return [out[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
+        rows = [out[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
+        if not return_d2:
+            return rows
+        return rows, [dist[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
 
 
-def match_knn_batch(pairs, threshold: float = 0.05, ties: int = TIES_LOWEST_INDEX, ctx=None):
-    """Descriptor matching for every (des1, des2) pair at once (pcc_match_knn_batch).  ctx: an Index that lends its device,
-    stream and scratch (its own cloud and tie order are left as they are); None makes a one-point handle for the call."""
+def match_knn_batch(pairs, threshold: float = 0.05, ties: int = TIES_LOWEST_INDEX, ctx=None, dim: int = 3, return_d2: bool = False):
+    """Descriptor matching for every (des1, des2) pair at once (pcc_match_knn_batch; pcc_match_knn_batch_dims for another `dim`
+    than 3 or with return_d2).  ctx: an Index that lends its device, stream and scratch (its own cloud and tie order are left
+    as they are); None makes a one-point handle for the call."""
     if ctx is not None:
-        return ctx.match_knn_batch(pairs, threshold, ties)
+        return ctx.match_knn_batch(pairs, threshold, ties, dim, return_d2)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
-        return own.match_knn_batch(pairs, threshold, ties)
+        return own.match_knn_batch(pairs, threshold, ties, dim, return_d2)
 
 
 def rift_descriptors_batch(clouds, rgbs=None, normal_radius: float = 0.03, gradient_radius: float = 0.03, rift_radius: float = 0.05,

@@ -1,4 +1,5 @@
-// match_batch.hip -- descriptor matching for EVERY cluster pair of a comparison at once (gfx950): pcc_match_knn_batch.
+// match_batch.hip -- descriptor matching for EVERY cluster pair of a comparison at once (gfx950): pcc_match_knn_batch, and
+// pcc_match_knn_batch_dims, which is this search for dim == 3 and match_dims.hip's for every other dimension.
 //
 // The reference calls matchRIFTFeaturesKnn (src/comparator.cpp:560-588) from its cluster-matching loop (:1296-1365, call at
 // :1322): per cluster of cloud 1 the three nearest clusters of cloud 2, each behind two size gates.  No call depends on an
@@ -126,11 +127,6 @@ k_match_batch_walk(const MatchTree* __restrict__ trees, const FlannNode* __restr
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-struct MatchBatchScratch {
-    HostBuf up, down, tree_up, tree_down;  // pinned: table + records going up, best + second coming down; trees + walk items, found
-    DevBuf dev, res, tree_dev, tree_res;
-};
-
 void match_batch_release(pcc_index* ix) {
     if (!ix->mb) return;
     MatchBatchScratch* s = ix->mb;
@@ -167,7 +163,7 @@ struct PtrLenHash {
 };
 
 int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
-                    const size_t* n2, size_t stride, float threshold, int32_t* out, size_t* out_offsets) {
+                    const size_t* n2, size_t stride, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
     const bool flann = ix->tie_mode == PCC_TIES_FLANN;
     if (!ix->mb) ix->mb = new MatchBatchScratch();
     MatchBatchScratch* mb = ix->mb;
@@ -374,6 +370,7 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
     size_t o = 0;
     for (size_t p = 0; p < n_pairs; ++p) {
         out_offsets[p] = o;
+        if (out_d2) out_d2[o] = 0.0f;
         out[o++] = 0;
         if (!searched(p) || clouds[cloud_of[p]].finite == 0) continue;
         const float* q = rec + q_rec0[p] * 4;
@@ -386,10 +383,42 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
             float d;
             const uint32_t bits = (uint32_t)(key >> 32);
             memcpy(&d, &bits, 4);
-            if (d < threshold) out[o++] = (!flann_idx.empty() && flann_idx[s] >= 0) ? flann_idx[s] : (int32_t)(uint32_t)key;
+            if (!(d < threshold)) continue;
+            if (out_d2) out_d2[o] = d;  // (FLANN's walk names another reference only AT this distance)
+            out[o++] = (!flann_idx.empty() && flann_idx[s] >= 0) ? flann_idx[s] : (int32_t)(uint32_t)key;
         }
     }
     out_offsets[n_pairs] = o;
+    return PCC_OK;
+}
+
+static int check_batch_stride(size_t stride, int dim) {
+    if (stride < 4 * (size_t)dim || stride % 4) { set_error("stride %zu must be a multiple of 4 and >= %d", stride, 4 * dim); return PCC_ERR_INVALID; }
+    return PCC_OK;
+}
+
+// Everything pcc_match_knn_batch refuses before it looks at the handle, for records of which 4 * dim bytes are read: all of
+// it host arithmetic.  (check_points' own stride rule is the 3-D one, so the pairs are checked here.)
+static int check_batch_args(size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2, const size_t* n2,
+                            size_t stride, int dim, int mem, const int32_t* out, const size_t* out_offsets) {
+    PCC_TRY(check_mem(mem));
+    if (mem != PCC_MEM_HOST) { set_error("pcc_match_knn_batch takes host descriptor arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
+    PCC_TRY(check_batch_stride(stride, dim));
+    if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
+    if (n_pairs >= (1ull << 31)) { set_error("more than 2^31 pairs"); return PCC_ERR_UNSUPPORTED; }
+    if (n_pairs && (!des1 || !n1 || !des2 || !n2 || !out)) { set_error("null array argument"); return PCC_ERR_INVALID; }
+    size_t total1 = 0, total2 = n_pairs;
+    for (size_t p = 0; p < n_pairs; ++p) {
+        for (int side = 0; side < 2; ++side) {
+            const void* d = side ? des2[p] : des1[p];
+            const size_t n = side ? n2[p] : n1[p];
+            if (n && !d) { set_error("null point pointer"); return PCC_ERR_INVALID; }
+            if (n >= (1ull << 31)) { set_error("more than 2^31 points"); return PCC_ERR_UNSUPPORTED; }
+        }
+        total1 += n1[p];
+        total2 += n2[p];
+        if (total1 >= (1ull << 31) || total2 >= (1ull << 31)) { set_error("more than 2^31 - 1 descriptors in one batch"); return PCC_ERR_UNSUPPORTED; }
+    }
     return PCC_OK;
 }
 
@@ -400,24 +429,26 @@ extern "C" {
 int pcc_match_knn_batch(pcc_index* ctx, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                         const size_t* n2, size_t stride, int mem, float threshold, int32_t* out, size_t* out_offsets) {
     using namespace pcc;
-    // the arguments first: all of it host arithmetic, refused before any device is looked at
-    PCC_TRY(check_mem(mem));
-    if (mem != PCC_MEM_HOST) { set_error("pcc_match_knn_batch takes host descriptor arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(check_points(nullptr, 0, stride, mem));  // (the stride alone)
-    if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
-    if (n_pairs >= (1ull << 31)) { set_error("more than 2^31 pairs"); return PCC_ERR_UNSUPPORTED; }
-    if (n_pairs && (!des1 || !n1 || !des2 || !n2 || !out)) { set_error("null array argument"); return PCC_ERR_INVALID; }
-    size_t total1 = 0, total2 = n_pairs;
-    for (size_t p = 0; p < n_pairs; ++p) {
-        PCC_TRY(check_points(des1[p], n1[p], stride, mem));
-        PCC_TRY(check_points(des2[p], n2[p], stride, mem));
-        total1 += n1[p];
-        total2 += n2[p];
-        if (total1 >= (1ull << 31) || total2 >= (1ull << 31)) { set_error("more than 2^31 - 1 descriptors in one batch"); return PCC_ERR_UNSUPPORTED; }
-    }
+    // the arguments first, refused before any device is looked at
+    PCC_TRY(check_batch_args(n_pairs, des1, n1, des2, n2, stride, 3, mem, out, out_offsets));
     if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
     if (n_pairs == 0) { out_offsets[0] = 0; return PCC_OK; }
     PCC_ENTER(ctx);
-    return match_knn_batch(ctx, n_pairs, des1, n1, des2, n2, stride, threshold, out, out_offsets);
+    return match_knn_batch(ctx, n_pairs, des1, n1, des2, n2, stride, threshold, out, nullptr, out_offsets);
+}
+
+int pcc_match_knn_batch_dims(pcc_index* ctx, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
+                             const size_t* n2, size_t stride, int dim, int mem, float threshold, int32_t* out, float* out_d2,
+                             size_t* out_offsets) {
+    using namespace pcc;
+    if (dim < 1 || dim > 32) { set_error("descriptor matching searches 1 ... 32 dimensions, not %d", dim); return PCC_ERR_UNSUPPORTED; }
+    PCC_TRY(check_batch_stride(stride, dim));
+    PCC_TRY(check_batch_args(n_pairs, des1, n1, des2, n2, stride, dim, mem, out, out_offsets));
+    if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
+    if (n_pairs == 0) { out_offsets[0] = 0; return PCC_OK; }
+    PCC_ENTER(ctx);
+    // three dimensions: the search of pcc_match_knn_batch itself, tie order and FLANN walk included
+    if (dim == 3) return match_knn_batch(ctx, n_pairs, des1, n1, des2, n2, stride, threshold, out, out_d2, out_offsets);
+    return match_knn_batch_dims(ctx, n_pairs, des1, n1, des2, n2, stride, dim, threshold, out, out_d2, out_offsets);
 }
 }  // extern "C"

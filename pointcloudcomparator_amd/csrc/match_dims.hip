@@ -1,0 +1,163 @@
+// match_dims.hip -- pcc_match_knn_batch_dims for dim != 3 (gfx950): every cluster pair of a comparison at once, on the first
+// `dim` (1 ... 32) floats of every descriptor.  Reference: matchRIFTFeaturesKnn (src/comparator.cpp:560-588) called from the
+// cluster-matching loop (:1296-1365); SURVEY 3.2 / 9.1 for why the reference's PCL searches three bins and what this is the
+// hedge for.
+//
+// k_match_batch's shape (match_batch.hip) with a wider record: a host-built table of work items (64 queries of one pair, a
+// slice of that pair's references; match_dims_plan.hpp), one query per lane with its DP floats in VGPRs for the length of the
+// item, the references through wave-uniform (scalar) loads shared by the 64 lanes, the waves of a workgroup each taking a
+// share of the slice, partial minima meeting in LDS, the slices of a query block merging in device memory by
+//   best[q] = atomicMin of (bits(d2) << 32 | index),  second[q] = atomicMin of bits(d2) of every loser.
+// DP is the record padded to 4, 8, 16 or 32 floats with zeros; an invalid record is (+inf, 0, ...): no test on the record in
+// the loop.
+//
+// Arithmetic: FLANN's L2_Simple in index order, d = d0 * d0; d = d + d1 * d1; ..., every operation rounded on its own
+// (-ffp-contract=off).  The order is part of the result.  Among references at exactly the same distance the lowest index
+// wins whatever tie order the handle has: FLANN's tree and the oracle's are 3-D, an N-D visit order could not be checked.
+#include "entry.hpp"
+#include "match_dims_plan.hpp"
+
+namespace pcc {
+
+constexpr int MD_WAVES = 16;  // waves of a workgroup: each takes a sixteenth of the slice for the same 64 queries
+
+template <int DP>
+__global__ void __launch_bounds__(MD_WAVES * 64, 8)  // (8 waves a SIMD: two workgroups a CU need at most 64 VGPRs)
+k_match_dims(const MatchDimsItem* __restrict__ items, const float* __restrict__ rec, unsigned long long* __restrict__ best,
+             unsigned int* __restrict__ second) {
+    __shared__ unsigned long long sk[MD_WAVES][64];
+    __shared__ unsigned int ss[MD_WAVES][64];
+    const unsigned int lane = threadIdx.x & 63;
+    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const MatchDimsItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
+    const bool live = lane < it.nq;
+    // (a lane without a query computes with the item's first one and reports nothing)
+    const float4* __restrict__ qp = reinterpret_cast<const float4*>(rec + (size_t)(it.q0 + (live ? lane : 0u)) * DP);
+    float q[DP];
+#pragma unroll
+    for (int k = 0; k < DP / 4; ++k) {
+        const float4 v = qp[k];
+        q[4 * k] = v.x; q[4 * k + 1] = v.y; q[4 * k + 2] = v.z; q[4 * k + 3] = v.w;
+    }
+    const unsigned int per = (it.nr + MD_WAVES - 1) / MD_WAVES;
+    const unsigned int b0 = min(it.nr, wave * per), b1 = min(it.nr, b0 + per);
+    const float* __restrict__ refs = rec + (size_t)it.r0 * DP;
+    // this wave's minimum as (distance bits, position) and the second-smallest distance bits it met (with multiplicity)
+    unsigned int kd = 0xffffffffu, ki = 0xffffffffu, s2 = 0xffffffffu;
+#pragma unroll 2
+    for (unsigned int j = b0; j < b1; ++j) {  // (wave-uniform: the record arrives by scalar loads)
+        const float* __restrict__ r = refs + (size_t)j * DP;
+        const float t0 = q[0] - r[0];
+        float d = t0 * t0;
+#pragma unroll
+        for (int k = 1; k < DP; ++k) {
+            const float t = q[k] - r[k];
+            d = d + t * t;
+        }
+        // (squares and their sums are never negative: the bits order as the distances do; an invalid record's +inf and a
+        // NaN lie above every finite distance and are "no neighbour" to the host)
+        const unsigned int db = __float_as_uint(d);
+        // (positions ascend: an equal distance never replaces the minimum, it becomes the second)
+        const bool lt = db < kd;
+        s2 = lt ? kd : min(s2, db);
+        ki = lt ? j : ki;
+        kd = lt ? db : kd;
+    }
+    // (a wave without a reference keeps position ~0: its key is ~0, "nothing found")
+    sk[wave][lane] = ((unsigned long long)kd << 32) | (ki == 0xffffffffu ? 0xffffffffu : it.ridx0 + ki);
+    ss[wave][lane] = s2;
+    __syncthreads();
+    if (wave != 0) return;
+    unsigned long long key = sk[0][lane];
+#pragma unroll 4
+    for (int w = 1; w < MD_WAVES; ++w) {
+        const unsigned long long k = sk[w][lane];
+        const unsigned long long lose = k < key ? key : k;
+        s2 = min(min(s2, ss[w][lane]), (unsigned int)(lose >> 32));
+        key = k < key ? k : key;
+    }
+    if (!live || key == ~0ull) return;
+    const unsigned int slot = it.qslot0 + lane;
+    const unsigned long long old = atomicMin(best + slot, key);
+    const unsigned long long lose = old < key ? key : old;
+    s2 = min(s2, (unsigned int)(lose >> 32));
+    if (s2 != 0xffffffffu) atomicMin(second + slot, s2);
+}
+
+static size_t md_align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
+                         const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
+    if (!ix->mb) ix->mb = new MatchBatchScratch();
+    MatchBatchScratch* mb = ix->mb;
+    const int dp = match_dims_padded(dim);
+    MatchDimsPlan plan;
+    if (!match_dims_plan(n_pairs, des1, n1, n2, dp, &plan)) { set_error("more than 2^31 records or work items in one batch"); return PCC_ERR_UNSUPPORTED; }
+    const size_t n_items = plan.items.size(), n_slots = plan.n_slots;
+
+    const size_t items_bytes = md_align16(n_items * sizeof(MatchDimsItem));
+    const size_t up_bytes = items_bytes + plan.n_rec * (size_t)dp * sizeof(float);
+    const size_t best_bytes = md_align16(n_slots * sizeof(unsigned long long)), res_bytes = best_bytes + n_slots * sizeof(unsigned int);
+    PCC_TRY(mb->up.reserve(up_bytes + 16));
+    PCC_TRY(mb->dev.reserve(up_bytes + 16));
+    PCC_TRY(mb->down.reserve(res_bytes + 16));
+    PCC_TRY(mb->res.reserve(res_bytes + 16));
+    if (n_items) memcpy(mb->up.p, plan.items.data(), n_items * sizeof(MatchDimsItem));
+    float* rec = reinterpret_cast<float*>(mb->up.as<char>() + items_bytes);
+    for (const MatchDimsPlan::Cloud& c : plan.clouds) match_dims_pack(c.p, c.n, stride, dim, dp, rec + c.rec0 * dp);
+    for (size_t p = 0; p < n_pairs; ++p) match_dims_pack(des2[p], n2[p], stride, dim, dp, rec + plan.q_rec0[p] * dp);
+
+    // ---- one upload, one launch, one read-back, one wait --------------------------------------------------------------------
+    ix->stats[0] = 0;
+    ix->stats[1] = n_slots;
+    ix->stats_pending = false;
+    ix->ties_pending = false;
+    ix->ties_flagged = ix->ties_changed = 0;
+    const unsigned long long* h_best = mb->down.as<unsigned long long>();
+    const unsigned int* h_second = reinterpret_cast<const unsigned int*>(mb->down.as<char>() + best_bytes);
+    if (n_items) {
+        const MatchDimsItem* d_items = mb->dev.as<MatchDimsItem>();
+        const float* d_rec = reinterpret_cast<const float*>(mb->dev.as<char>() + items_bytes);
+        unsigned long long* d_best = mb->res.as<unsigned long long>();
+        unsigned int* d_second = reinterpret_cast<unsigned int*>(mb->res.as<char>() + best_bytes);
+        const dim3 grid((unsigned int)n_items), wg(MD_WAVES * 64);
+        PCC_HIP(hipMemcpyAsync(mb->dev.p, mb->up.p, up_bytes, hipMemcpyHostToDevice, ix->stream));
+        PCC_HIP(hipMemsetAsync(mb->res.p, 0xff, res_bytes, ix->stream));
+        switch (dp) {
+            case 4: hipLaunchKernelGGL(k_match_dims<4>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
+            case 8: hipLaunchKernelGGL(k_match_dims<8>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
+            case 16: hipLaunchKernelGGL(k_match_dims<16>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
+            default: hipLaunchKernelGGL(k_match_dims<32>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
+        }
+        PCC_HIP(hipGetLastError());
+        PCC_HIP(hipMemcpyAsync(mb->down.p, mb->res.p, res_bytes, hipMemcpyDeviceToHost, ix->stream));
+        PCC_HIP(hipStreamSynchronize(ix->stream));
+    }
+
+    // ---- rows: the dummy 0 (src/comparator.cpp:568), then one index per query with d2 < threshold (:579) ----------------------
+    // (an invalid query, an invalid reference and an overflowed distance all arrive as key_none; a pair without a work item
+    // never had its slots written)
+    size_t o = 0;
+    for (size_t p = 0; p < n_pairs; ++p) {
+        out_offsets[p] = o;
+        if (out_d2) out_d2[o] = 0.0f;
+        out[o++] = 0;
+        if (!n_items || !n1[p] || !n2[p]) continue;
+        for (size_t i = 0; i < n2[p]; ++i) {
+            const size_t s = plan.q_slot0[p] + i;
+            const unsigned long long key = h_best[s];
+            if (key_none(key)) continue;
+            const uint32_t bits = (uint32_t)(key >> 32);
+            if (h_second[s] == bits) ++ix->ties_flagged;  // (reported in pcc_index_stats[5]; the lowest index stands)
+            float d;
+            memcpy(&d, &bits, 4);
+            if (!(d < threshold)) continue;
+            if (out_d2) out_d2[o] = d;
+            out[o++] = (int32_t)(uint32_t)key;
+        }
+    }
+    out_offsets[n_pairs] = o;
+    return PCC_OK;
+}
+
+}  // namespace pcc

@@ -277,7 +277,11 @@ struct SiftScratch {
     DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
 };
 struct RiftBatchScratch;   // rift_batch.hip: the staging buffers, CSR and work handle of pcc_rift_descriptors_batch
-struct MatchBatchScratch;  // match_batch.hip: the staging and result buffers of pcc_match_knn_batch
+// the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
+struct MatchBatchScratch {
+    HostBuf up, down, tree_up, tree_down;  // pinned: table + records going up, best + second coming down; trees + walk items, found
+    DevBuf dev, res, tree_dev, tree_res;
+};
 struct HostPipe;           // host_pipe.hpp (api.hip): pipelined transfers between pageable host memory and the device
 }  // namespace pcc
 #define PCC_EV_SLOTS 64
@@ -624,6 +628,9 @@ int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t
                    float T[16], double* fitness, int* iterations, int* converged);
 // ---- api.hip internals the other files build on ----------------------------------------------------------------------
 void match_batch_release(pcc_index* ix);  // match_batch.hip: frees ix->mb
+// match_dims.hip: the search of pcc_match_knn_batch_dims for dim != 3 (arguments checked by the entry point in match_batch.hip)
+int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
+                         const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets);
 int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, Nn1Call* search = nullptr);

@@ -128,7 +128,8 @@ private:
 // Sections "Information of clusters of PCL2 / PCL 1", the cluster matching between them and "Information of
 // matches ...".  Returns the scores; matches[i] = cluster of PCL 2 matched to cluster i of PCL 1, or -1.
 inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1, const std::vector<CloudPtr>& clusters2,
-                              const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches) {
+                              const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches,
+                              int descriptor_dims = 3) {
     std::ofstream& f = w.file();
     std::vector<std::vector<float> > centroids2;
     w.sectionTitle("Information of clusters of PCL2:");
@@ -168,7 +169,7 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
         }
     }
     // (without descriptors nothing passes the gates and the library is not called: the report then needs no device)
-    const std::vector<std::vector<int> > correspondences = matchRIFTFeaturesKnnBatch(gated);
+    const std::vector<std::vector<int> > correspondences = matchRIFTFeaturesKnnBatch(gated, descriptor_dims);
     w.sectionTitle("Information of clusters of PCL 1:");
     matches.assign(clusters1.size(), -1);
     for (size_t i = 0; i < clusters1.size(); ++i) {
