@@ -19,10 +19,15 @@
 //   4. clusters outside [min, max] size are dropped.
 // PCL orders a region's neighbour list with std::sort, which leaves the order of equal distances unspecified; this mirror
 // (and the oracle) use a stable sort -- one of the orders PCL may produce.
+//
+// setDeviceSegmentation(true) hands ALL of it to the library instead: extract() is then one pcc_region_growing_rgb call (rows,
+// growing, segment statistics and segment pairs on the GPU, the merging on the host inside the library, labels back) -- the
+// same clusters, bit for bit; nothing but the labels crosses to this side.  Off by default: extract() above is untouched.
 #pragma once
 #include <algorithm>
 #include <limits>
 #include <queue>
+#include <stdexcept>
 #include <utility>
 #include <vector>
 #include "pcc/search.hpp"
@@ -36,13 +41,16 @@ public:
     typedef typename search::KdTree<PointT>::Ptr KdTreePtr;
     void setInputCloud(const CloudConstPtr& c) { input_ = c; }
     void setSearchMethod(const KdTreePtr& t) { search_ = t; }
-    void setDistanceThreshold(float t) { distance_threshold_ = t * t; }
-    void setPointColorThreshold(float t) { color_p2p_threshold_ = t * t; }
-    void setRegionColorThreshold(float t) { color_r2r_threshold_ = t * t; }
+    void setDistanceThreshold(float t) { distance_threshold_ = t * t; distance_given_ = t; }
+    void setPointColorThreshold(float t) { color_p2p_threshold_ = t * t; color_p2p_given_ = t; }
+    void setRegionColorThreshold(float t) { color_r2r_threshold_ = t * t; color_r2r_given_ = t; color_r2r_set_ = true; }
     void setMinClusterSize(int n) { min_pts_per_cluster_ = n; }
     void setMaxClusterSize(int n) { max_pts_per_cluster_ = n; }
     void setNumberOfNeighbours(unsigned int k) { neighbour_number_ = k; }
     void setNumberOfRegionNeighbours(unsigned int k) { region_neighbour_number_ = k; }
+    // (not in PCL) true: extract() is one pcc_region_growing_rgb call on the search method's handle
+    void setDeviceSegmentation(bool on) { device_segmentation_ = on; }
+    bool getDeviceSegmentation() const { return device_segmentation_; }
 
     void extract(std::vector<PointIndices>& clusters) {
         clusters.clear();
@@ -53,6 +61,7 @@ public:
         if (!search_) search_.reset(new search::KdTree<PointT>);
         search_->setInputCloud(input_);
         n_ = input_->size();
+        if (device_segmentation_) { extractOnDevice(clusters); return; }
         findPointNeighbours();
         growSegments();
         findSegmentNeighbours();
@@ -62,6 +71,21 @@ public:
     }
 
 private:
+    // the whole of extract() in the library: labels[i] = cluster of point i in PCL's output order, or -1
+    void extractOnDevice(std::vector<PointIndices>& clusters) {
+        if (!search_->handle()) return;  // no finite point: PCL's "empty input cloud"
+        // PCL's default region colour threshold is 10 SQUARED, which has no float root to hand to the library: the two paths
+        // would merge differently, so the device path asks for the threshold to be set (color_growing_segmentation does)
+        if (!color_r2r_set_) throw std::invalid_argument("pcc::RegionGrowingRGB: setRegionColorThreshold before extract() with setDeviceSegmentation(true)");
+        std::vector<int32_t> labels(n_, -1);
+        int32_t ncl = 0;
+        check(pcc_region_growing_rgb(search_->handle(), &input_->points[0].rgba, sizeof(PointT), PCC_MEM_HOST, distance_given_, color_p2p_given_,
+                                     color_r2r_given_, (uint32_t)std::max(min_pts_per_cluster_, 0), (uint32_t)std::max(max_pts_per_cluster_, 0),
+                                     neighbour_number_, region_neighbour_number_, labels.data(), &ncl));
+        clusters.resize((size_t)ncl);
+        for (size_t i = 0; i < n_; ++i)
+            if (labels[i] >= 0) clusters[(size_t)labels[i]].indices.push_back((int)i);
+    }
     // rows of the self k-NN: row_len_ entries per point, ascending by (d2, index) -- the one GPU call of this class
     void findPointNeighbours() {
         row_len_ = (int)std::min<size_t>(region_neighbour_number_, n_);
@@ -235,6 +259,10 @@ private:
     size_t n_ = 0;
     int row_len_ = 0;
     float distance_threshold_ = 0.05f * 0.05f, color_p2p_threshold_ = 1225.0f, color_r2r_threshold_ = 10.0f;
+    // the thresholds as given, for the device path, which squares them itself (0.05f and 35.0f square to the defaults above)
+    float distance_given_ = 0.05f, color_p2p_given_ = 35.0f, color_r2r_given_ = 0.0f;
+    bool color_r2r_set_ = false;
+    bool device_segmentation_ = false;
     unsigned int neighbour_number_ = 30, region_neighbour_number_ = 100;
     int min_pts_per_cluster_ = 10, max_pts_per_cluster_ = std::numeric_limits<int>::max();
     std::vector<int> nbr_, label_, seg_size_;
@@ -247,7 +275,8 @@ private:
 // color_growing_segmentation (reference src/segmentation.cpp:161-216) -- the number of colour segments is what the report
 // uses; the segments themselves are returned as the reference returns them
 template <class PointT>
-inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation(const typename PointCloud<PointT>::Ptr& cloud_in) {
+inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation(const typename PointCloud<PointT>::Ptr& cloud_in,
+                                                                                bool device_segmentation = false) {
     std::vector<typename PointCloud<PointT>::Ptr> out;
     typename PointCloud<PointT>::Ptr cloud(new PointCloud<PointT>);
     for (const PointT& p : cloud_in->points)  // pcl::removeNaNFromPointCloud
@@ -259,6 +288,7 @@ inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation(
     reg.setPointColorThreshold(6);
     reg.setRegionColorThreshold(5);
     reg.setMinClusterSize(200);
+    reg.setDeviceSegmentation(device_segmentation);
     std::vector<PointIndices> clusters;
     reg.extract(clusters);
     for (const PointIndices& c : clusters) {
@@ -267,6 +297,13 @@ inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation(
         out.push_back(seg);
     }
     return out;
+}
+
+// the same with the segmentation on the device (pcc_region_growing_rgb): the same gate of more than 10 points, the same NaN
+// strip, the same segments
+template <class PointT>
+inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation_device(const typename PointCloud<PointT>::Ptr& cloud_in) {
+    return color_growing_segmentation<PointT>(cloud_in, true);
 }
 
 }  // namespace pcc

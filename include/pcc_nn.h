@@ -525,6 +525,40 @@ int pcc_sift_keypoints(pcc_index *ctx, const void *pts, size_t n, size_t stride_
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);
+/* ---- colour region growing -----------------------------------------------------------------------------
+ * replaces: pcl::RegionGrowingRGB<PointXYZRGB>::extract as color_growing_segmentation configures it (src/segmentation.cpp:161-216:
+ *   setDistanceThreshold(10), setPointColorThreshold(6), setRegionColorThreshold(5), setMinClusterSize(200), PCL's defaults of 30
+ *   growing and 100 region neighbours; called twice per accepted match, src/comparator.cpp:1456-1495).  Nothing about normals or
+ *   curvature is built: the reference never sets them.  The PCL stages are restated ([recalled]; the test
+ *   oracle and pcc::RegionGrowingRGB are the same restatement): parity with PCL 1.7 itself is unpinned.
+ * rows     the self k-NN rows of the indexed cloud, K = min(nr_region_neighbours, finite points), ascending (d2, index), the point
+ *          itself first (PCL: findPointNeighbours); they stay on the device;
+ * growing  edge u -> v is valid when v is among the first min(nr_neighbours, K) entries of u's row and the squared colour
+ *          distance of the two (integer, cast to float) is <= point_color_threshold * point_color_threshold (a float product);
+ *          the segment of v is the lowest index that reaches v along valid edges -- what PCL's queue computes with seeds in index
+ *          order (region_rgb.hip) --, segments numbered by ascending seed index;
+ * segment neighbours  for each ordered pair (s, t != s) the smallest row distance from a point of s to a point of t over all K
+ *          entries; per s the nr_region_neighbours smallest by (d, t), handed on in descending (d, t);
+ * merging  PCL's applyRegionMergingAlgorithm: mean colours float(sum) / float(count) truncated, the channel sums in unsigned int;
+ *          segments within distance_threshold^2 whose means differ by less than region_color_threshold^2 join a region; regions
+ *          below min_size fold into the region of their nearest neighbouring segment (stable sort of equal distances); clusters
+ *          outside [min_size, max_size] are dropped.
+ * rgb: PCL's packed colour word of point i (bytes b, g, r, a from the low byte) at rgb + i * rgb_stride_bytes, memory space `mem`,
+ *   4-byte aligned, one per point of the indexed cloud -- as pcc_rift_descriptors takes it.
+ * labels[n_original] (memory space `mem`): index of the point's cluster in PCL's output order, or -1; *n_clusters (host).
+ *   Non-finite points of the indexed cloud take part in nothing and get -1; the finite points get what the NaN-stripped cloud
+ *   would (the reference strips first, :164).
+ * Only the per-segment records (16 bytes each) and the segment pair list (12 bytes each) cross to the host, where the merging
+ *   runs; pcc_index_stats afterwards reports the grown segments in [0], the distinct ordered segment pairs in [1] and the label
+ *   sweeps of the growing stage in [7].
+ * Refused before any device is touched: a bad memory space, null rgb / labels / n_clusters, a bad stride or alignment, a threshold
+ *   that is negative or not finite (PCC_ERR_INVALID); nr_neighbours == 0, nr_region_neighbours == 0 or > PCC_KNN_MAX_K
+ *   (PCC_ERR_UNSUPPORTED); a null handle last.  An index without a finite point: PCC_ERR_EMPTY. */
+int pcc_region_growing_rgb(pcc_index *index, const void *rgb, size_t rgb_stride_bytes, int mem,
+                           float distance_threshold, float point_color_threshold, float region_color_threshold,
+                           uint32_t min_size, uint32_t max_size,
+                           unsigned int nr_neighbours, unsigned int nr_region_neighbours,
+                           int32_t *labels, int32_t *n_clusters);
 
 /* ---- first point within a radius ----------------------------------------------------------------
  * replaces: the O(S*N) linear scan in processRIFTwithSIFT (src/comparator.cpp:696-713) that snaps
@@ -595,7 +629,9 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  the FLANN walk (PCC_TIES_FLANN, last search), [7] queries the 3x3x3 cube of the pruned k = 1 kernel left open
  *  (last search that listed them: from 2M queries on, or PCC_OPT_NN1_KERNEL = 2).
  *  After pcc_rift_descriptors_batch on the handle: [0] points whose radius rows the batch kernels built, [1] points of the
- *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX). */
+ *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX).
+ *  After pcc_region_growing_rgb on the handle: [0] grown colour segments, [1] distinct ordered segment pairs (s, t) with a row
+ *  entry leading from s to t, [7] label sweeps of the growing stage. */
 int pcc_index_stats(const pcc_index *index, uint64_t stats[8]);
 /* 1 when this library was built with the pair counter (-DPCC_COUNT_PAIRS: the profiling build), else 0 */
 int pcc_counts_pairs(void);

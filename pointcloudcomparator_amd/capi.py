@@ -34,7 +34,7 @@ SYMBOLS = [
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
     "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
-    "pcc_normals", "pcc_region_growing", "pcc_sac_plane", "pcc_rigid_from_sums",
+    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
@@ -106,6 +106,8 @@ def _load() -> C.CDLL:
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
+    lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
+                                           C.POINTER(C.c_int32)]
     lib.pcc_voxel_grid.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, vp, sz, C.POINTER(sz)]
     lib.pcc_radius_fill.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, vp, vp, vp]
     lib.pcc_radius_count_max.argtypes = [vp, vp, sz, sz, i32, C.c_double, C.c_uint, vp]
@@ -760,6 +762,33 @@ class Index:
                                       np.float32(curvature_threshold), min_size, max_size, labels.ctypes.data,
                                       C.byref(ncl)))
         return labels, ncl.value
+
+    def region_growing_rgb(self, rgb, distance: float = 10.0, point_colour: float = 6.0, region_colour: float = 5.0,
+                           min_size: int = 200, max_size: int = 2**31 - 1, nn: int = 30, region_nn: int = 100, device=None):
+        """pcc_region_growing_rgb: pcl::RegionGrowingRGB::extract as the reference's color_growing_segmentation sets it up
+        (src/segmentation.cpp:161-216) over the index's own points, rows and growing on the device: (labels, n_clusters).
+        rgb: one colour per point in any of rift_descriptors' three forms (a CUDA tensor gives CUDA labels).
+        device: a torch cuda device to get the labels as a device tensor whatever memory `rgb` lives in."""
+        n = self.n_original
+        assert len(rgb) == n, "one colour per point of the indexed cloud"
+        if device is not None and not (_is_torch(rgb) and rgb.is_cuda):
+            import torch
+            if not _is_torch(rgb):
+                rgb = np.ascontiguousarray(rgb)
+                rgb = torch.from_numpy(rgb.view(np.int32) if rgb.dtype == np.uint32 else rgb)
+            rgb = rgb.to(device)
+        words, ptr, stride, mem = _colour_words(rgb)
+        labels, pl = _out(words, (max(n, 1),), np.int32)
+        ncl = C.c_int32(0)
+        st = self._before(words, labels)
+        if mem == MEM_DEVICE and st is None:
+            import torch
+            torch.cuda.current_stream(words.device).synchronize()
+        _check(LIB.pcc_region_growing_rgb(self._h, ptr, stride, mem, np.float32(distance), np.float32(point_colour),
+                                          np.float32(region_colour), int(min_size), int(max_size), int(nn), int(region_nn), pl,
+                                          C.byref(ncl)))
+        self._after(st)
+        return labels[:n], ncl.value
 
     def icp_step(self, src, want_corr: bool = True, center=None):
         """correspondences of `src` against the index + the 17 Umeyama sums; center: take the sums about this point

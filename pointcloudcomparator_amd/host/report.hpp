@@ -129,7 +129,7 @@ private:
 // matches ...".  Returns the scores; matches[i] = cluster of PCL 2 matched to cluster i of PCL 1, or -1.
 inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1, const std::vector<CloudPtr>& clusters2,
                               const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches,
-                              int descriptor_dims = 3) {
+                              int descriptor_dims = 3, bool rgb_device = false) {
     std::ofstream& f = w.file();
     std::vector<std::vector<float> > centroids2;
     w.sectionTitle("Information of clusters of PCL2:");
@@ -210,8 +210,9 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
             w.compare("descriptors", d1, d2);
             s.des1 += d1; s.des2 += d2;
             // colour based segmentation of both clusters: which one has more elements of different colours
-            const size_t c1 = color_growing_segmentation<PointXYZRGB>(clusters1[i]).size();
-            const size_t c2 = color_growing_segmentation<PointXYZRGB>(clusters2[j]).size();
+            // (rgb_device: the whole segmentation in the library, pcc_region_growing_rgb -- the same segments)
+            const size_t c1 = color_growing_segmentation<PointXYZRGB>(clusters1[i], rgb_device).size();
+            const size_t c2 = color_growing_segmentation<PointXYZRGB>(clusters2[j], rgb_device).size();
             w.compareColour(c1, c2);
             s.colour1 += c1; s.colour2 += c2;
         } else {
