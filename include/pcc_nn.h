@@ -181,7 +181,10 @@ enum pcc_option {
                                     i.e. the stretch of the grid one L2 works on at a time (default 256) */
     PCC_OPT_FUSE_PARAMS = 20,    /* bits: 1 = index build: the grid (cell edge, dimensions, axes) is derived by the last workgroup of the
                                     pack kernel to finish instead of a kernel of its own behind it; 2 = a pass of pcc_icp_align is solved
-                                    by the last workgroup of its sums kernel.  Default 0: see DESIGN.md 4.3 (both were measured) */
+                                    by the last workgroup of its sums kernel.  Default 0: see DESIGN.md 4.3 (both were measured).
+                                    Clouds of up to 8192 points take the form of bit 1 whatever this option says while
+                                    PCC_OPT_HOST_PIPE is 1, host and device clouds alike: the kernel of its own runs for them only
+                                    with PCC_OPT_HOST_PIPE = 0 */
     PCC_OPT_HOST_PIPE = 21,      /* PCC_MEM_HOST clouds and results of 8 MB and more in PAGEABLE memory: 1 = staged by the library
                                     through two pinned chunk buffers by a few host threads (PCC_HOST_THREADS, default half the
                                     cores, at most 8), the DMA of a chunk running while the next is gathered; only x, y, z cross
@@ -189,7 +192,9 @@ enum pcc_option {
                                     array.  Memory the caller has pinned (hipHostMalloc / hipHostRegister) is always copied directly.
                                     Also the SMALL host calls (clouds and results up to 1 MB): 1 = kernels read the cloud from, and write
                                     the results into, the handle's pinned buffers, and a k = 1 query call against up to 4096
-                                    exhaustively searched points is one launch; 0 = copies and the separate launches */
+                                    exhaustively searched points is one launch; 0 = copies and the separate launches.
+                                    While it is 1 the index build of every cloud of up to 8192 points, in host or device memory,
+                                    derives its grid inside the pack kernel (PCC_OPT_FUSE_PARAMS bit 1) */
     PCC_OPT_SCAN_CHAINED = 22,   /* exclusive scans inside the sorts: 1 = one launch, workgroups hand their totals forward through tagged
                                     64-bit atomics (default); 0 = two launches (totals, then apply) that wait for nothing -- for
                                     environments where workgroups are not dispatched in order (preemption, shared devices) */

@@ -271,12 +271,12 @@ static int small_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, boo
     ev_mark(ix, EV_CALL1);
     // (the wait below is also what lets the next call overwrite the pinned query buffer: no event is recorded for it)
     PCC_HIP(hipStreamSynchronize(ix->stream));
+    ix->ties_pending = false;  // (whatever the tie order: pcc_index_stats reports THIS search, not a FLANN-order one before it)
+    ix->ties_flagged = ix->ties_changed = 0;
     if (!flann) return PCC_OK;
     unsigned int tied = 0;
     for (size_t b = 0; b < nblk; ++b) tied += tie_blocks[b];
-    ix->ties_pending = false;
     ix->ties_flagged = tied;
-    ix->ties_changed = 0;
     if (tied == 0) return PCC_OK;
     if (ix->small_raw_n == ix->n_orig) {
         unsigned int* changed_blocks = tie_blocks + nblk;
