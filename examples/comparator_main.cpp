@@ -251,14 +251,26 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
     bool have_descriptors = true;
     std::vector<PointCloud<PointXYZRGB>::Ptr> batch_clouds;  // --rift without --rift-loop: every cluster of both scenes that needs descriptors
     bool batch_scene[2] = {false, false};
+    // --sift without --rift-loop: the clusters above 700 points of both scenes (reference :1228-1231, :1264-1265) through ONE
+    // siftSnappedCloudBatch call; the loop below takes the snapped clouds in the order it meets their clusters
+    std::vector<PointCloud<PointXYZRGB>::Ptr> sift_snapped;
+    std::vector<size_t> sift_found;
+    size_t sift_at = 0;
+    if (rift && sift && !rift_loop) {
+        std::vector<PointCloud<PointXYZRGB>::Ptr> large;
+        for (int k = 0; k < 2; ++k)
+            if (descriptors_path[k].empty())
+                for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k])
+                    if (c->points.size() > 700) large.push_back(c);
+        if (!large.empty()) sift_snapped = siftSnappedCloudBatch(large, &sift_found);
+    }
     for (int k = 0; k < 2; ++k) {
         if (descriptors_path[k].empty() && rift && !rift_loop) {
             // the clouds the RIFT pipeline runs over, in cluster order; one processRIFTBatch call for both scenes below
             for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
-                if (sift && c->points.size() > 700) {  // reference :1228-1231, :1264-1265
-                    size_t n_keypoints = 0;
-                    batch_clouds.push_back(siftSnappedCloud(c, &n_keypoints));
-                    std::cout << "Computed " << n_keypoints << " SIFT Keypoints\n";  // reference :467
+                if (sift && c->points.size() > 700) {
+                    batch_clouds.push_back(sift_snapped[sift_at]);
+                    std::cout << "Computed " << sift_found[sift_at++] << " SIFT Keypoints\n";  // reference :467
                 } else {
                     batch_clouds.push_back(c);
                 }

@@ -9,6 +9,9 @@
 //                        skipped, duplicates are kept) -> a tree over the snapped cloud -> processRIFT on it
 //   siftSnappedCloud     the part of processRIFTwithSIFT in front of processRIFT: the snapped keypoint cloud, for callers
 //                        that hand it to pcc::processRIFTBatch with other clouds
+//   processSiftBatch / siftSnappedCloudBatch   processSift / siftSnappedCloud for every cluster of a comparison in ONE
+//                        library call (pcc_sift_keypoints_batch): the reference's loop over the clusters above 700 points
+//                        (:1228-1231, :1264-1265), no turn of which depends on an earlier one
 #pragma once
 #include <vector>
 #include "pcc/comparator_nn.hpp"
@@ -61,6 +64,98 @@ inline PointCloud<PointXYZRGB>::Ptr siftSnappedCloud(const PointCloud<PointXYZRG
     const PointCloud<PointWithScale>::Ptr keypoints = processSift(cloud, &tree);
     if (n_keypoints) *n_keypoints = keypoints->size();
     return snapKeypointsToCloud(cloud, *keypoints, 0.05, &tree);
+}
+
+namespace detail {
+// one pcc_sift_keypoints_batch call over `clouds` (null or empty ones are empty clouds of the batch); snap (nullable): the snapped
+// index of every keypoint at radius 0.05.  ctx (nullable): any tree whose handle may serve as the call's context
+inline void siftBatchCall(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds, std::vector<float>& keypoints, std::vector<int32_t>* snap,
+                          std::vector<size_t>& offsets, search::KdTree<PointXYZRGB>* ctx) {
+    const size_t nc = clouds.size();
+    offsets.assign(nc + 1, 0);
+    keypoints.clear();
+    if (snap) snap->clear();
+    std::vector<const void*> pts(nc, nullptr), rgb(nc, nullptr);
+    std::vector<size_t> n(nc, 0);
+    size_t total = 0;
+    for (size_t c = 0; c < nc; ++c) {
+        if (!clouds[c] || clouds[c]->empty()) continue;
+        pts[c] = &clouds[c]->points[0].x;
+        rgb[c] = &clouds[c]->points[0].rgba;
+        n[c] = clouds[c]->size();
+        total += n[c];
+    }
+    if (total == 0) return;  // (no library call)
+    static thread_local search::KdTree<PointXYZRGB> context;  // lends device, stream and scratch; the cloud it indexes is never asked
+    if (!ctx || !ctx->handle()) {
+        if (!context.handle()) {
+            PointCloud<PointXYZRGB>::Ptr one(new PointCloud<PointXYZRGB>);
+            PointXYZRGB p;
+            p.x = p.y = p.z = 0.f;
+            p.rgba = 0;
+            one->push_back(p);
+            context.setInputCloud(one);
+        }
+        ctx = &context;
+    }
+    size_t capacity = total / 8 + 256;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        keypoints.resize(capacity * 4);
+        if (snap) snap->resize(capacity);
+        const int st = pcc_sift_keypoints_batch(ctx->handle(), nc, pts.data(), n.data(), sizeof(PointXYZRGB), rgb.data(), sizeof(PointXYZRGB),
+                                                PCC_MEM_HOST, SIFT_MIN_SCALE, SIFT_NR_OCTAVES, SIFT_NR_SCALES_PER_OCTAVE, SIFT_MIN_CONTRAST, 0.05,
+                                                keypoints.data(), snap ? snap->data() : nullptr, capacity, offsets.data());
+        if (st == PCC_ERR_OVERFLOW && attempt == 0) { capacity = offsets[nc]; continue; }
+        check(st);
+        break;
+    }
+    keypoints.resize(offsets[nc] * 4);
+    if (snap) snap->resize(offsets[nc]);
+}
+}  // namespace detail
+
+// processSift for every cloud of `clouds` in ONE library call: element c of the result is what processSift(clouds[c]) returns, bit
+// for bit (a null or empty cloud, or one without a finite point, gives no keypoints).
+inline std::vector<PointCloud<PointWithScale>::Ptr> processSiftBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds,
+                                                                     search::KdTree<PointXYZRGB>* ctx = nullptr) {
+    std::vector<PointCloud<PointWithScale>::Ptr> result(clouds.size());
+    std::vector<float> kp;
+    std::vector<size_t> offsets;
+    detail::siftBatchCall(clouds, kp, nullptr, offsets, ctx);
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        result[c].reset(new PointCloud<PointWithScale>);
+        const size_t m = offsets[c + 1] - offsets[c];
+        result[c]->points.resize(m);
+        for (size_t i = 0; i < m; ++i) {
+            PointWithScale& k = result[c]->points[i];
+            const float* v = &kp[(offsets[c] + i) * 4];
+            k.x = v[0]; k.y = v[1]; k.z = v[2]; k.scale = v[3];
+        }
+        result[c]->width = (std::uint32_t)m;
+        result[c]->height = 1;
+    }
+    return result;
+}
+
+// siftSnappedCloud for every cloud of `clouds` in ONE library call: element c is the snapped keypoint cloud of clouds[c] (keypoints
+// without a point within 0.05 are skipped, duplicates are kept, as in snapKeypointsToCloud).
+// n_keypoints (nullable): per cloud, what processSift found (the reference prints it)
+inline std::vector<PointCloud<PointXYZRGB>::Ptr> siftSnappedCloudBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds,
+                                                                       std::vector<size_t>* n_keypoints = nullptr,
+                                                                       search::KdTree<PointXYZRGB>* ctx = nullptr) {
+    std::vector<PointCloud<PointXYZRGB>::Ptr> result(clouds.size());
+    std::vector<float> kp;
+    std::vector<int32_t> snap;
+    std::vector<size_t> offsets;
+    detail::siftBatchCall(clouds, kp, &snap, offsets, ctx);
+    if (n_keypoints) n_keypoints->assign(clouds.size(), 0);
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        result[c].reset(new PointCloud<PointXYZRGB>);
+        if (n_keypoints) (*n_keypoints)[c] = offsets[c + 1] - offsets[c];
+        for (size_t i = offsets[c]; i < offsets[c + 1]; ++i)
+            if (snap[i] >= 0) result[c]->push_back(clouds[c]->points[snap[i]]);
+    }
+    return result;
 }
 
 // point_indices (nullable): the index in the SNAPPED cloud of the point every returned descriptor belongs to;

@@ -208,11 +208,20 @@ enum pcc_option {
     PCC_OPT_SIFT_LAYOUT = 25,    /* pcc_sift_keypoints, the scale-space kernel: 1 = a wave per point -- every lane computes one row entry's
                                     Gaussian weights for all scales, then one lane per scale adds its shares in row order (default);
                                     0 = one lane per (point, scale) walking its row prefix.  Same bits either way. */
-    PCC_OPT_RIFT_BATCH_BRUTE_MAX = 26  /* pcc_rift_descriptors_batch: clouds of up to this many points get their radius rows from the
+    PCC_OPT_RIFT_BATCH_BRUTE_MAX = 26, /* pcc_rift_descriptors_batch: clouds of up to this many points get their radius rows from the
                                     exhaustive builder that serves the whole batch at once (n^2 distance tests per cloud); larger
                                     clouds take the single path inside the same call, one by one, on a work handle kept in ctx
                                     (default 8192; PCC_RIFT_BATCH_BRUTE_MAX in the environment of a new handle).  No result bit
                                     depends on it. */
+    PCC_OPT_SIFT_BATCH_BRUTE_MAX = 27  /* pcc_sift_keypoints_batch: clouds of up to this many points go through the batch kernels (one
+                                    segmented voxel grid, one exhaustive row build and one 25-NN pass per octave for the whole
+                                    batch); larger clouds take the single path inside the same call, one by one, on a work handle
+                                    kept in ctx (PCC_SIFT_BATCH_BRUTE_MAX in the environment of a new handle).  Default 8192, chosen from
+                                    profiles/sift_batch_exp.txt: a cloud ALONE is cheaper on the work handle from about 3000 points
+                                    (2.4 against 2.0 ms at 4096), but beside others the batch kernels win up to the 8000 points
+                                    measured -- 60 clusters of 701 ... 8000 points take 17.6 ms at 8192 and 54.8 ms at 4096, where
+                                    21 of them pay the single path's waits one after the other; above 8192 only the lone cloud
+                                    was measured (10.2 against 3.4 ms at 16 384).  No result bit depends on it. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -527,6 +536,42 @@ int pcc_sift_keypoints(pcc_index *ctx, const void *pts, size_t n, size_t stride_
                        size_t rgb_stride_bytes, int mem, float min_scale, int nr_octaves, int nr_scales_per_octave,
                        float min_contrast, float *out_keypoints /* [capacity][4]: x, y, z, scale */, size_t capacity,
                        size_t *n_out);
+/* The same for EVERY cluster of a comparison at once, with the keypoint snap behind it -- replaces the front of
+ *   processRIFTwithSIFT (src/comparator.cpp:686-822: processSift, :435-469, then every keypoint snapped to the first cluster
+ *   point within 0.05, :696-713), which the reference runs once per cluster above 700 points of both scenes (:1228-1231,
+ *   :1264-1265); no call depends on an earlier one.  The clouds of a call are concatenated on the device and every stage runs
+ *   once per octave over all clouds still in the batch: launches and host waits depend on nr_octaves (three waits per octave
+ *   round and one at the end), on the clouds above the brute limit and on buffer growth, never on n_clouds.
+ *   ctx: any index handle, as for pcc_rift_descriptors_batch: it supplies device, stream and scratch; the cloud it indexes is
+ *     neither read nor changed.
+ *   Cloud c is described as in pcc_rift_descriptors_batch.  Its slice, rows out_offsets[c] .. out_offsets[c + 1] of
+ *     out_keypoints, is bit for bit and in order (octave, point of the octave cloud, scale) what pcc_sift_keypoints returns for
+ *     that cloud alone with the same four parameters.  No point of another cloud enters a voxel, a radius row or a 25-NN row,
+ *     however the clouds overlap in space.  A cloud with n[c] == 0, without a finite point, or that stops at the 25-point gate
+ *     in its first octave yields an empty slice; a cloud that falls below 25 points at a later octave is finished (PCL's
+ *     break), the others go on.
+ *   out_snap_index (nullable; snap_radius must then be positive and finite, else it is ignored): row by row the lowest LOCAL
+ *     index j of the keypoint's own cloud with sqrt(dx^2 + dy^2 + dz^2) < snap_radius in pcc_first_within's arithmetic
+ *     (differences in float, squares, sum and sqrt in double, strict compare), -1 when there is none: what
+ *     pcc_index_create(cloud c) + pcc_first_within gives for those keypoints.
+ *   out_keypoints[capacity][4], out_snap_index[capacity], out_offsets[n_clouds + 1]: HOST arrays; mem must be PCC_MEM_HOST
+ *     (PCC_MEM_DEVICE: PCC_ERR_UNSUPPORTED).  More than capacity keypoints in total: PCC_ERR_OVERFLOW, out_offsets holds the
+ *     offsets that would have been returned (out_offsets[n_clouds] = the number needed), nothing else is written.
+ *     n_clouds == 0: PCC_OK, out_offsets[0] = 0, no device is touched.
+ *   Clouds above PCC_OPT_SIFT_BATCH_BRUTE_MAX points take the single path inside the call (same bits).  pcc_index_stats
+ *     afterwards reports in [0] the points that went through the batch kernels, in [1] the points of the clouds sent through
+ *     the work handle and in [2] the octave rounds the batch route ran.
+ *   Refused before the handle is looked at, with pcc_sift_keypoints' messages where it has one: null arrays, a null pts[c] or
+ *     rgb[c] with n[c] > 0, a bad stride or alignment, bad values of the four SIFT parameters, sum(n) >= 2^31
+ *     (PCC_ERR_UNSUPPORTED), and a first-octave lattice above 2^26 voxels for some cloud (PCC_ERR_UNSUPPORTED for the whole
+ *     call; the message names the cloud). */
+int pcc_sift_keypoints_batch(pcc_index *ctx, size_t n_clouds,
+                             const void *const *pts, const size_t *n, size_t stride_bytes,
+                             const void *const *rgb, size_t rgb_stride_bytes, int mem,
+                             float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
+                             double snap_radius,
+                             float *out_keypoints /* [capacity][4] */, int32_t *out_snap_index /* [capacity], nullable */,
+                             size_t capacity, size_t *out_offsets /* [n_clouds + 1] */);
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);
@@ -635,6 +680,8 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  (last search that listed them: from 2M queries on, or PCC_OPT_NN1_KERNEL = 2).
  *  After pcc_rift_descriptors_batch on the handle: [0] points whose radius rows the batch kernels built, [1] points of the
  *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX).
+ *  After pcc_sift_keypoints_batch on the handle: [0] points that went through the batch kernels, [1] points of the clouds sent
+ *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
  *  After pcc_region_growing_rgb on the handle: [0] grown colour segments, [1] distinct ordered segment pairs (s, t) with a row
  *  entry leading from s to t, [7] label sweeps of the growing stage. */
 int pcc_index_stats(const pcc_index *index, uint64_t stats[8]);

@@ -20,7 +20,7 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX) = range(1, 27)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX) = range(1, 28)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -36,7 +36,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -105,6 +105,7 @@ def _load() -> C.CDLL:
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
+    lib.pcc_sift_keypoints_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, C.c_double, vp, vp, sz, vp]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
                                            C.POINTER(C.c_int32)]
@@ -738,6 +739,49 @@ class Index:
             _check(status)
             break
         return out[:found.value]
+
+    def sift_keypoints_batch(self, clouds, rgbs=None, min_scale: float = 0.005, nr_octaves: int = 5, nr_scales_per_octave: int = 5,
+                             min_contrast: float = 0.001, snap_radius=None):
+        """pcc_sift_keypoints_batch with this handle as the context: the SIFT keypoints of every cloud in one call, and with
+        snap_radius the first point of its own cloud within that radius of every keypoint (the front of the reference's
+        processRIFTwithSIFT, src/comparator.cpp:686-822, for all clusters at once).  clouds[c] / rgbs[c]: host arrays in any
+        of sift_keypoints' forms ((n, >= 5) pcl::PointXYZRGB records with rgbs omitted: the colour word is read in place).
+        Returns (keypoints (m, 4) float32, offsets (n_clouds + 1,) -- cloud c owns rows offsets[c] .. offsets[c + 1], each slice
+        what sift_keypoints returns for that cloud alone --[, snap index (m,) int32, local to the cloud, -1 for none])."""
+        clouds = list(clouds)
+        rgbs = list(clouds if rgbs is None else rgbs)
+        n = len(clouds)
+        assert len(rgbs) == n, "one colour array per cloud"
+        args = [_points(a) for a in clouds]
+        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
+        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
+        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_sift_keypoints_batch takes host arrays"
+        strides = {a[2] for a in args if a[1] > 1}
+        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
+        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
+        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
+        stride = strides.pop() if strides else (single[0][0] if single else 12)
+        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
+        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+        pp = vps(*[a[0] if a[1] else None for a in args])
+        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
+        nn = szs(*[a[1] for a in args])
+        off = np.zeros(n + 1, dtype=np.uintp)
+        capacity = max(256, sum(a[1] for a in args) // 8)
+        for attempt in range(2):
+            kp = np.empty((capacity, 4), dtype=np.float32)
+            snap = np.empty(capacity, dtype=np.int32) if snap_radius is not None else None
+            status = LIB.pcc_sift_keypoints_batch(self._h, n, pp, nn, stride, cp, cstride, MEM_HOST, float(min_scale), int(nr_octaves),
+                                                  int(nr_scales_per_octave), float(min_contrast), 0.0 if snap_radius is None else float(snap_radius),
+                                                  kp.ctypes.data, None if snap is None else snap.ctypes.data, capacity, off.ctypes.data)
+            if status == -6 and attempt == 0:  # PCC_ERR_OVERFLOW: once more with the room it asks for
+                capacity = int(off[n])
+                continue
+            _check(status)
+            break
+        m = int(off[n])
+        offsets = off.astype(np.int64)
+        return (kp[:m], offsets) if snap is None else (kp[:m], offsets, snap[:m])
 
     def region_growing(self, normals, k: int = 100, smoothness: float = 3.0 / 180.0 * np.pi,
                        curvature_threshold: float = 1.0, min_size: int = 50, max_size: int = 1000000):

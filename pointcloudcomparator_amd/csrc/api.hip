@@ -74,6 +74,7 @@ static const OptionRow g_options[] = {
     {PCC_OPT_RIFT_LAYOUT, "PCC_RIFT_LAYOUT", &Options::rift_layout, nullptr, 0, 1, OptionRow::FLAG},
     {PCC_OPT_SIFT_LAYOUT, "PCC_SIFT_LAYOUT", &Options::sift_layout, nullptr, 0, 1, OptionRow::FLAG},
     {PCC_OPT_RIFT_BATCH_BRUTE_MAX, "PCC_RIFT_BATCH_BRUTE_MAX", &Options::rift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
+    {PCC_OPT_SIFT_BATCH_BRUTE_MAX, "PCC_SIFT_BATCH_BRUTE_MAX", &Options::sift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
 };
 static const OptionRow* option_row(int option) {
     for (const OptionRow& r : g_options)
@@ -506,6 +507,7 @@ int pcc_index_destroy(pcc_index* ix) {
     if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
     match_batch_release(ix);
     rift_batch_release(ix);
+    sift_batch_release(ix);
     rift_release(ix);
     sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);

@@ -183,6 +183,10 @@ struct Options {
     int rift_batch_brute_max = 8192;   // PCC_OPT_RIFT_BATCH_BRUTE_MAX: clouds of a pcc_rift_descriptors_batch call up to this many points get their radius
                                     // rows from the exhaustive builder over the whole batch (rift_batch.hip); larger ones take the single path, one by
                                     // one, on a work handle.  Measured (EXPERIMENTS.md, "Batched RIFT descriptors"): a cloud alone is cheaper there from ~4500 points, beside others from ~11 000
+    int sift_batch_brute_max = 8192;   // PCC_OPT_SIFT_BATCH_BRUTE_MAX: clouds of a pcc_sift_keypoints_batch call up to this many points go through the
+                                    // batch kernels (sift_batch.hip: segmented voxel grid, exhaustive rows and 25-NN over the whole batch); larger
+                                    // ones take the single path, one by one, on a work handle.  Measured (EXPERIMENTS.md, "Batched SIFT keypoints"): a
+                                    // cloud alone is cheaper there from ~3000 points, beside others not before the 8000 measured
     int overlap_prep = 1;           // PCC_OPT_OVERLAP_PREP: a k = 1 search that follows setInputCloud directly packs and sorts its queries on a
                                     // second stream while the build's cell sort is still running (they share nothing but the grid parameters);
                                     // from 2M queries on, 2 = at every size
@@ -277,6 +281,8 @@ struct SiftScratch {
     DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
 };
 struct RiftBatchScratch;   // rift_batch.hip: the staging buffers, CSR and work handle of pcc_rift_descriptors_batch
+struct SiftBatchScratch;   // sift_batch.hip: the staging buffers, voxel keys, CSR and work handle of pcc_sift_keypoints_batch
+struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
     HostBuf up, down, tree_up, tree_down;  // pinned: table + records going up, best + second coming down; trees + walk items, found
@@ -364,6 +370,7 @@ struct pcc_index {
     pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
     pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
+    pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -579,7 +586,17 @@ int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pt
                            size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
                            int32_t* out_index, size_t* out_offsets);
 void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work handle
+// rift_batch.hip: the sorted radius rows (d2 < r2, ascending (d2, index)) of a concatenation of clouds as one CSR, from the exhaustive
+// builder: d_items (device) are query blocks of one cloud each, d_pts the concatenation with w = bits(concatenated index).  offs / keys:
+// the caller's buffers for uint32 offsets[total + 1] (+ the same as int64) and the entries.  One wait: the CSR's total
+int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
+                      DevBuf& offs, DevBuf& keys, const unsigned long long** keys_out, const unsigned int** offsets_out);
 void sift_release(pcc_index* ix);  // frees ix->sift and its work handle
+// sift.hip: the detector on device arrays (ix->sift made by the caller): the keypoints are left in ix->sift->kp, *n_out of them
+int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
+                   float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
+// sift_batch.hip: pcc_sift_keypoints_batch behind its argument checks
+void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work handle
 int grid_first_within(pcc_index* ix, const float4* q, size_t nq, double radius, int32_t* idx_dev);
 // ---- flann_order.hip: flags[i] = 1 when another reference shares query i's minimum distance; the tied queries walked
 // through FLANN's tree on the device

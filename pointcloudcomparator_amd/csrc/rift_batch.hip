@@ -114,6 +114,35 @@ struct RiftBatchScratch {
     DevBuf slice;               // uint32[n_clouds + 1]
 };
 
+// The sorted radius rows of a concatenation of clouds as ONE CSR (pcc_internal.hpp): rows of d2 < r2 from the exhaustive builder
+// above, driven by a table of work items that never cross a cloud.  offs: uint32 offsets[total + 1] + the same as int64; keys:
+// the u64 entries.  One wait (the CSR's total).  Shared with sift_batch.hip, whose octave rounds are such concatenations.
+int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
+                      DevBuf& offs, DevBuf& keys_buf, const unsigned long long** keys_out, const unsigned int** offsets_out) {
+    hipStream_t s = ix->stream;
+    const size_t off32_bytes = align_up((total + 1) * sizeof(unsigned int), 16);
+    PCC_TRY(offs.reserve(off32_bytes + (total + 1) * sizeof(int64_t)));
+    unsigned int* off32 = offs.as<unsigned int>();
+    int64_t* off64 = reinterpret_cast<int64_t*>(offs.as<char>() + off32_bytes);
+    PCC_HIP(hipMemsetAsync(off32, 0, (total + 1) * sizeof(unsigned int), s));
+    hipLaunchKernelGGL((k_rift_batch_rows<false>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, off32, (const unsigned int*)nullptr,
+                       (unsigned long long*)nullptr);
+    PCC_HIP(hipGetLastError());
+    unsigned long long entries = 0;
+    PCC_TRY(csr_offsets(ix, off32, off64, total, &entries));
+    PCC_TRY(keys_buf.reserve((size_t)(entries ? entries : 1) * sizeof(unsigned long long)));
+    unsigned long long* keys = keys_buf.as<unsigned long long>();
+    if (entries) {
+        hipLaunchKernelGGL((k_rift_batch_rows<true>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, (unsigned int*)nullptr,
+                           (const unsigned int*)off32, keys);
+        PCC_HIP(hipGetLastError());
+        PCC_TRY(sort_csr_rows(s, off64, total, keys));
+    }
+    *keys_out = keys;
+    *offsets_out = off32;
+    return PCC_OK;
+}
+
 void rift_batch_release(pcc_index* ix) {
     if (!ix->rift_batch) return;
     RiftBatchScratch* b = ix->rift_batch;
@@ -172,31 +201,10 @@ static int rift_batch_brute(pcc_index* ix, size_t n_clouds, const void* const* p
     const float4* d_pts = reinterpret_cast<const float4*>(d + pts_at);
     const unsigned char* d_rgb = reinterpret_cast<const unsigned char*>(d + rgb_at);
 
-    // ---- the CSR at a radius: count, total (the wait), scan, fill, sort ---------------------------------------------------
-    const size_t off32_bytes = align_up((total + 1) * sizeof(unsigned int), 16);
-    PCC_TRY(b->offs.reserve(off32_bytes + (total + 1) * sizeof(int64_t)));
-    unsigned int* off32 = b->offs.as<unsigned int>();
-    int64_t* off64 = reinterpret_cast<int64_t*>(b->offs.as<char>() + off32_bytes);
+    // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
     const unsigned int n_items = (unsigned int)items.size();
     const RiftRows rows = [&](double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) -> int {
-        const float r2 = (float)(radius * radius);
-        PCC_HIP(hipMemsetAsync(off32, 0, (total + 1) * sizeof(unsigned int), s));
-        hipLaunchKernelGGL((k_rift_batch_rows<false>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, off32, (const unsigned int*)nullptr,
-                           (unsigned long long*)nullptr);
-        PCC_HIP(hipGetLastError());
-        unsigned long long entries = 0;
-        PCC_TRY(csr_offsets(ix, off32, off64, total, &entries));
-        PCC_TRY(b->keys.reserve((size_t)(entries ? entries : 1) * sizeof(unsigned long long)));
-        unsigned long long* keys = b->keys.as<unsigned long long>();
-        if (entries) {
-            hipLaunchKernelGGL((k_rift_batch_rows<true>), dim3(n_items), dim3(256), 0, s, d_items, d_pts, r2, (unsigned int*)nullptr,
-                               (const unsigned int*)off32, keys);
-            PCC_HIP(hipGetLastError());
-            PCC_TRY(sort_csr_rows(s, off64, total, keys));
-        }
-        *keys_out = keys;
-        *offsets_out = off32;
-        return PCC_OK;
+        return batch_radius_rows(ix, d_items, n_items, d_pts, total, (float)(radius * radius), b->offs, b->keys, keys_out, offsets_out);
     };
 
     // ---- the stages of the single call, once over the concatenation -------------------------------------------------------

@@ -15,19 +15,11 @@
 
 #include "entry.hpp"
 #include "lane_ops.hpp"
-#include "sift_math.hpp"
+#include "sift_stages.hpp"
 
 namespace pcc {
 
 namespace {
-
-// a record of an octave cloud: pcl::PointXYZRGB's layout, what voxel_grid reads and writes with colour
-struct SiftRec {
-    float x, y, z, w;
-    uint32_t rgb;
-    uint32_t pad[3];
-};
-static_assert(sizeof(SiftRec) == 32, "SiftRec layout");
 
 // the caller's points and colour words (two arrays, two strides) as records
 __global__ void __launch_bounds__(256)
@@ -213,6 +205,57 @@ static int sift_room(pcc_index* ix, DevBuf& kp, size_t have, size_t more) {
     return PCC_OK;
 }
 
+// ---- the stages behind the voxel grid, the rows and the neighbours (sift_stages.hpp: shared with sift_batch.hip) --------------
+int sift_intensity_stage(pcc_index* ix, const SiftRec* cloud, size_t n) {
+    SiftScratch* r = ix->sift;
+    PCC_TRY(r->inten.reserve(n * sizeof(float)));
+    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_sift_intensity, dim3(blocks), dim3(256), 0, ix->stream, cloud, (unsigned int)n, r->inten.as<float>());
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+int sift_space_stage(pcc_index* ix, size_t n, const unsigned long long* keys, const unsigned int* offsets, const SiftOctave* oc, int n_scales) {
+    SiftScratch* r = ix->sift;
+    const size_t S = (size_t)n_scales;
+    PCC_TRY(r->resp.reserve(n * S * sizeof(float)));
+    if (ix->opt.sift_layout == 1) {
+        const unsigned int wb = (unsigned int)std::min<size_t>((n + 3) / 4, 8192);
+        hipLaunchKernelGGL(k_sift_space_wave, dim3(wb), dim3(256), 0, ix->stream, keys, offsets, r->inten.as<float>(), oc, (unsigned int)n,
+                           r->resp.as<float>());
+    } else {
+        const unsigned int lb = (unsigned int)std::min<size_t>((n * S + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_sift_space_lane, dim3(lb), dim3(256), 0, ix->stream, keys, offsets, r->inten.as<float>(), oc, (unsigned int)n,
+                           r->resp.as<float>());
+    }
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+int sift_extrema_stage(pcc_index* ix, size_t n, const int32_t* nbr, int K, const SiftOctave* oc) {
+    hipStream_t s = ix->stream;
+    SiftScratch* r = ix->sift;
+    PCC_TRY(r->mask.reserve(n * sizeof(unsigned int)));
+    PCC_TRY(r->count.reserve((n + 1) * sizeof(unsigned int)));
+    PCC_HIP(hipMemsetAsync(r->count.p, 0, (n + 1) * sizeof(unsigned int), s));
+    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_sift_extrema, dim3(blocks), dim3(256), 0, s, r->resp.as<float>(), nbr, K, oc, (unsigned int)n, r->mask.as<unsigned int>(),
+                       r->count.as<unsigned int>());
+    PCC_HIP(hipGetLastError());
+    return launch_exclusive_scan(ix, s, r->count.as<unsigned int>(), n + 1, r->scan_tmp);
+}
+
+int sift_write_stage(pcc_index* ix, const SiftRec* cloud, size_t n, const SiftOctave* oc, size_t have, size_t found) {
+    SiftScratch* r = ix->sift;
+    if (!found) return PCC_OK;
+    PCC_TRY(sift_room(ix, r->kp, have, found));
+    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_sift_write, dim3(blocks), dim3(256), 0, ix->stream, cloud, r->mask.as<unsigned int>(), r->count.as<unsigned int>(), oc,
+                       (unsigned int)n, r->kp.as<float4>() + have);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
 // pts / rgb on the device; the keypoints are left in ix->sift->kp (device), *n_out of them
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out) {
@@ -255,8 +298,6 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
         // 2. PCL's min_nr_points
         if (n_oct < (size_t)SIFT_MIN_POINTS) break;
         const SiftRec* cloud = r->cloud[cur].as<SiftRec>();
-        const unsigned int un = (unsigned int)n_oct;
-        const unsigned int blocks = (unsigned int)std::min<size_t>((n_oct + 255) / 256, 2048);
         // 3. the octave's scales (uploaded in front of the loop)
         const SiftOctave& h_oc = h_octaves[(size_t)o];
         const int S = h_oc.n_scales;
@@ -265,45 +306,24 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
         PCC_TRY(set_input(w, cloud, n_oct, sizeof(SiftRec), PCC_MEM_DEVICE));
         entered(w);
         // 4. intensity
-        PCC_TRY(r->inten.reserve(n_oct * sizeof(float)));
-        hipLaunchKernelGGL(k_sift_intensity, dim3(blocks), dim3(256), 0, s, cloud, un, r->inten.as<float>());
-        PCC_HIP(hipGetLastError());
+        PCC_TRY(sift_intensity_stage(ix, cloud, n_oct));
         // 5. scale space over the sorted rows at 3 x the largest scale
         const float radius = 3.0f * h_oc.scales[S - 1];
         const unsigned long long* keys = nullptr;
         const unsigned int* off32 = nullptr;
         PCC_TRY(radius_csr(w, (double)radius, &keys, &off32));
-        PCC_TRY(r->resp.reserve(n_oct * (size_t)S * sizeof(float)));
-        if (ix->opt.sift_layout == 1) {
-            const unsigned int wb = (unsigned int)std::min<size_t>((n_oct + 3) / 4, 8192);
-            hipLaunchKernelGGL(k_sift_space_wave, dim3(wb), dim3(256), 0, s, keys, off32, r->inten.as<float>(), oc, un, r->resp.as<float>());
-        } else {
-            const unsigned int lb = (unsigned int)std::min<size_t>((n_oct * (size_t)S + 255) / 256, 8192);
-            hipLaunchKernelGGL(k_sift_space_lane, dim3(lb), dim3(256), 0, s, keys, off32, r->inten.as<float>(), oc, un, r->resp.as<float>());
-        }
-        PCC_HIP(hipGetLastError());
+        PCC_TRY(sift_space_stage(ix, n_oct, keys, off32, oc, S));
         // 6. extrema over the 25 nearest neighbours (the gate above: the cloud holds at least that many)
         const int K = (int)std::min<size_t>(SIFT_NEIGHBOURS, n_oct);
         PCC_TRY(r->nbr.reserve(n_oct * (size_t)K * sizeof(int32_t)));
         PCC_TRY(r->nbr_d2.reserve(n_oct * (size_t)K * sizeof(float)));
         PCC_TRY(grid_knn(w, w->refs.as<float4>(), n_oct, K, nullptr, r->nbr.as<int32_t>(), r->nbr_d2.as<float>()));
-        PCC_TRY(r->mask.reserve(n_oct * sizeof(unsigned int)));
-        PCC_TRY(r->count.reserve((n_oct + 1) * sizeof(unsigned int)));
-        PCC_HIP(hipMemsetAsync(r->count.p, 0, (n_oct + 1) * sizeof(unsigned int), s));
-        hipLaunchKernelGGL(k_sift_extrema, dim3(blocks), dim3(256), 0, s, r->resp.as<float>(), r->nbr.as<int32_t>(), K, oc, un,
-                           r->mask.as<unsigned int>(), r->count.as<unsigned int>());
-        PCC_HIP(hipGetLastError());
-        PCC_TRY(launch_exclusive_scan(w, s, r->count.as<unsigned int>(), n_oct + 1, r->scan_tmp));
+        PCC_TRY(sift_extrema_stage(ix, n_oct, r->nbr.as<int32_t>(), K, oc));
         unsigned int found = 0;
         PCC_TRY(read_back(ix, r->count.as<unsigned int>() + n_oct, &found));  // the octave's wait
         // 7. behind the keypoints of the octaves before
-        if (found) {
-            PCC_TRY(sift_room(ix, r->kp, total, found));
-            hipLaunchKernelGGL(k_sift_write, dim3(blocks), dim3(256), 0, s, cloud, r->mask.as<unsigned int>(), r->count.as<unsigned int>(), oc, un,
-                               r->kp.as<float4>() + total);
-            PCC_HIP(hipGetLastError());
-            total += found;
-        }
+        PCC_TRY(sift_write_stage(ix, cloud, n_oct, oc, total, found));
+        total += found;
     }
     *n_out = total;
     return PCC_OK;

@@ -1,0 +1,126 @@
+"""pcc_sift_keypoints_batch without a GPU (the front of the reference's processRIFTwithSIFT, src/comparator.cpp:686-822, for
+every cluster above 700 points at once, :1228-1231 and :1264-1265): the entry point and its option are declared, exported and
+bound; every argument is refused before the handle or any device is looked at; no cloud at all is PCC_OK; the host-built
+tables of every octave round cover every (cloud, point) exactly once; the new source is part of the library."""
+import ctypes as C
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+
+
+def test_entry_point_and_option_are_declared_exported_and_bound():
+    from pointcloudcomparator_amd import capi
+    text = (ROOT / "include" / "pcc_nn.h").read_text()
+    assert re.search(r"\bint\s+pcc_sift_keypoints_batch\s*\(\s*pcc_index \*ctx, size_t n_clouds,", text)
+    comment = text[:text.index("int pcc_sift_keypoints_batch(")].rsplit("/*", 1)[1]
+    assert "src/comparator.cpp:686-822" in comment and ":696-713" in comment and "PCC_ERR_OVERFLOW" in comment
+    assert re.search(r"\bPCC_OPT_RIFT_BATCH_BRUTE_MAX = 26,", text)  # the one before it keeps its number
+    assert re.search(r"\bPCC_OPT_SIFT_BATCH_BRUTE_MAX = 27\b", text)
+    assert capi.OPT_SIFT_BATCH_BRUTE_MAX == 27 and capi.OPT_RIFT_BATCH_BRUTE_MAX == 26
+    assert "PCC_SIFT_BATCH_BRUTE_MAX" in (ROOT / "pointcloudcomparator_amd" / "csrc" / "api.hip").read_text()
+    assert "pcc_sift_keypoints_batch" in capi.SYMBOLS
+    fn = capi.LIB.pcc_sift_keypoints_batch  # (raises when the library does not export it)
+    assert fn.restype is C.c_int and len(fn.argtypes) == 17
+    assert callable(capi.Index.sift_keypoints_batch)
+    stats = text[:text.index("int pcc_index_stats(")].rsplit("/*", 1)[1]
+    assert "pcc_sift_keypoints_batch" in stats and "octave rounds" in stats
+    mirror = (ROOT / "include" / "pcc" / "sift.hpp").read_text()
+    assert "processSiftBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds" in mirror
+    assert "siftSnappedCloudBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds" in mirror
+
+
+def test_arguments_are_refused_without_a_device():
+    """every refusal below happens with a NULL handle: nothing of it can have looked at a device"""
+    from pointcloudcomparator_amd import capi
+    L = capi.LIB
+    rec = np.zeros((8, 8), np.float32)  # pcl::PointXYZRGB records: the colour word 16 bytes into each
+    rec[:, :3] = np.arange(24, dtype=np.float32).reshape(8, 3) * 0.01
+    one_p, one_c, one_n = (C.c_void_p * 1)(rec.ctypes.data), (C.c_void_p * 1)(rec.ctypes.data + 16), (C.c_size_t * 1)(8)
+    nulls = (C.c_void_p * 1)(None)
+    kp, snap, off = np.zeros((8, 4), np.float32), np.zeros(8, np.int32), np.full(2, 99, np.uintp)
+
+    def call(k=1, p=one_p, n=one_n, stride=32, c=one_c, cstride=32, mem=0, ms=0.005, no=5, ns=5, mc=0.001, r=0.05, o_kp=kp.ctypes.data,
+             o_snap=snap.ctypes.data, cap=8, o=off.ctypes.data, ctx=None):
+        return L.pcc_sift_keypoints_batch(ctx, k, p, n, stride, c, cstride, mem, ms, no, ns, mc, r, o_kp, o_snap, cap, o)
+
+    def err():
+        return L.pcc_last_error()
+
+    assert call(mem=7) == -1 and b"mem space" in err()
+    assert call(mem=capi.MEM_DEVICE) == -5 and b"PCC_MEM_HOST" in err()
+    for kw in (dict(p=None), dict(n=None), dict(c=None), dict(o_kp=None), dict(o=None)):
+        assert call(**kw) == -1 and b"null" in err() and b"null index" not in err(), kw
+    assert call(p=nulls) == -1 and b"null point pointer" in err()
+    assert call(c=nulls) == -1 and b"null colour pointer" in err()
+    for stride in (0, 8, 10, 30):
+        assert call(stride=stride) == -1 and b"stride" in err(), stride
+    for kw in (dict(cstride=0), dict(cstride=6), dict(c=(C.c_void_p * 1)(rec.ctypes.data + 18)), dict(p=(C.c_void_p * 1)(rec.ctypes.data + 2)),
+               dict(o_kp=kp.ctypes.data + 2), dict(o_snap=snap.ctypes.data + 2)):
+        assert call(**kw) == -1 and b"4-byte aligned" in err(), kw
+    # the four SIFT parameters, with the single call's messages
+    for ms in (0.0, -0.005, float("nan"), float("inf")):
+        assert call(ms=ms) == -1 and b"min_scale must be positive and finite" in err(), ms
+    for mc in (-0.001, float("nan")):
+        assert call(mc=mc) == -1 and b"min_contrast must not be negative" in err(), mc
+    for no in (0, -3):
+        assert call(no=no) == -1 and b"at least one octave" in err(), no
+    for ns in (0, 14, -1):
+        assert call(ns=ns) == -5 and b"1 to 13 scales per octave are built" in err(), ns
+    # the snap radius counts only when the snap is asked for
+    for r in (0.0, -0.05, float("nan"), float("inf")):
+        assert call(r=r) == -1 and b"bad radius" in err(), r
+        assert call(r=r, o_snap=None) == -1 and b"null index" in err(), r  # ignored: everything else is good
+    # totals from 2^31 on (nothing is read: the sizes alone decide)
+    two_p = (C.c_void_p * 2)(rec.ctypes.data, rec.ctypes.data)
+    two_c = (C.c_void_p * 2)(rec.ctypes.data + 16, rec.ctypes.data + 16)
+    assert call(k=2, p=two_p, c=two_c, n=(C.c_size_t * 2)(2 ** 30, 2 ** 30)) == -5 and b"2^31" in err()
+    assert call(n=(C.c_size_t * 1)(2 ** 31)) == -5 and b"2^31" in err()
+    # a first-octave lattice above 2^26 voxels: the whole call, and the message names the cloud (the second of two here)
+    wide = rec.copy()
+    wide[:, :3] *= 100.0  # 0 .. 23 m at a leaf of 0.005: 4601 voxels along z alone
+    wp = (C.c_void_p * 2)(rec.ctypes.data, wide.ctypes.data)
+    wc = (C.c_void_p * 2)(rec.ctypes.data + 16, wide.ctypes.data + 16)
+    assert call(k=2, p=wp, c=wc, n=(C.c_size_t * 2)(8, 8)) == -5 and b"cloud 1: leaf size" in err() and b"too small for this cloud" in err()
+    assert call() == -1 and b"null index" in err()  # all arguments good: the handle is looked at last
+    assert off.tolist() == [99, 99] and not kp.any() and not snap.any()  # nothing was written by any refused call
+    # no cloud at all: PCC_OK, one offset, no device -- no array but the offsets is needed
+    assert call(k=0) == 0 and off.tolist() == [0, 99]
+    off[:] = 99
+    assert call(k=0, p=None, n=None, c=None, o_kp=None, o_snap=None, cap=0) == 0 and off.tolist() == [0, 99]
+    assert call(k=0, o=None) == -1 and b"null out_offsets" in err()
+
+
+def test_round_tables_cover_every_point_once():
+    """tests/cpp/test_sift_batch_plan.cpp compiles csrc/sift_batch_plan.hpp, the header sift_batch.hip builds its tables with:
+    sizes around the 25-point gate and the 2048-point LDS tile, empty clouds in front and in the middle, rounds in which clouds
+    shrink below the gate and to zero; then the splice of the rounds' keypoints"""
+    subprocess.check_call(["make", "build/test_sift_batch_plan"], cwd=ROOT)
+    exe = str(ROOT / "build" / "test_sift_batch_plan")
+    for sizes in ([0, 24, 25, 26, 2048, 2049, 0, 700], [300] * 60, [0, 65536, 1, 0], [3] * 7, [0]):
+        r = subprocess.run([exe] + [str(v) for v in sizes], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert f"sift batch plan ok: {len(sizes)} clouds, {sum(sizes)} points, " in r.stdout and "tile 2048" in r.stdout
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)  # its own default
+    assert r.returncode == 0 and "9 clouds, 11024 points" in r.stdout
+    assert int(re.search(r"(\d+) clouds dropped below the gate with points left", r.stdout).group(1)) > 0
+    assert int(re.search(r"(\d+) keypoints spliced", r.stdout).group(1)) > 0
+    src = (ROOT / "tests" / "cpp" / "test_sift_batch_plan.cpp").read_text()
+    for what in ("not the query of exactly one item", "cross the end of its cloud", "not the prefix sum", "a dropped cloud kept points",
+                 "names an empty or dropped cloud", "not copied exactly once"):
+        assert what in src
+    assert '#include "sift_batch_plan.hpp"' in (ROOT / "pointcloudcomparator_amd" / "csrc" / "sift_batch.hip").read_text()
+
+
+def test_new_source_and_binaries_are_in_the_makefile():
+    mk = (ROOT / "Makefile").read_text()
+    hip_srcs = re.search(r"^HIP_SRCS\s*:=(.*)$", mk, flags=re.M).group(1)
+    assert "sift_batch.hip" in hip_srcs
+    assert re.search(r"^hosttest:.*build/test_sift_batch_plan.*build/sift_batch_driver", mk, flags=re.M)
+    assert re.search(r"^asan:.*build/asan/test_sift_batch_plan", mk, flags=re.M)
+    # the row builder is shared with the RIFT batch, not copied
+    batch = (ROOT / "pointcloudcomparator_amd" / "csrc" / "sift_batch.hip").read_text()
+    assert "batch_radius_rows(" in batch and "k_rift_batch_rows" not in batch
