@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -56,6 +56,11 @@ build/ubench_valu: tools/ubench/ubench_valu.hip
 build/test_lane_ops: tests/cpp/test_lane_ops.hip $(CSRC)/lane_ops.hpp
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 -I$(CSRC) $< -o $@
+
+# the shared host/device arithmetic headers, device compile against host compile (the library's own flags: its code generation)
+build/test_device_math: tests/cpp/test_device_math.hip $(CSRC)/libm_f32.hpp $(CSRC)/plane_fit.hpp $(CSRC)/rift_math.hpp $(CSRC)/sift_math.hpp $(CSRC)/rigid_solve.hpp
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) $< -o $@ -pthread
 
 build/test_host_mirror: tests/cpp/test_host_mirror.cpp include/pcc/point_types.hpp include/pcc/search.hpp include/pcc/comparator_nn.hpp include/pcc/multi_device.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build

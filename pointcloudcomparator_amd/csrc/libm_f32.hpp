@@ -100,6 +100,47 @@ __host__ __device__ inline double lm_reduce_fast(double x, const LmSincos& p, in
     *np = n;
     return LM_MADD(-(double)n, p.hpi, x);
 }
+// 2 / pi in 32-bit windows one byte apart (__inv_pio4); a switch, not an array: no table in memory on the device
+__host__ __device__ inline uint32_t lm_inv_pio4(unsigned int i) {
+    switch (i) {
+#define LM_P(I, V) case I: return V
+        LM_P(0, 0xa2u); LM_P(1, 0xa2f9u); LM_P(2, 0xa2f983u); LM_P(3, 0xa2f9836eu);
+        LM_P(4, 0xf9836e4eu); LM_P(5, 0x836e4e44u); LM_P(6, 0x6e4e4415u); LM_P(7, 0x4e441529u);
+        LM_P(8, 0x441529fcu); LM_P(9, 0x1529fc27u); LM_P(10, 0x29fc2757u); LM_P(11, 0xfc2757d1u);
+        LM_P(12, 0x2757d1f5u); LM_P(13, 0x57d1f534u); LM_P(14, 0xd1f534ddu); LM_P(15, 0xf534ddc0u);
+        LM_P(16, 0x34ddc0dbu); LM_P(17, 0xddc0db62u); LM_P(18, 0xc0db6295u); LM_P(19, 0xdb629599u);
+        LM_P(20, 0x6295993cu); LM_P(21, 0x95993c43u); LM_P(22, 0x993c4390u);
+#undef LM_P
+        default: return 0x3c439041u;
+    }
+}
+// reduce_large: |y| >= 120, finite.  The argument's 24 significant bits times 96 bits of 2 / pi in integers; the quadrant is
+// the top two bits of the product, the rest (a signed 62-bit fraction of a quadrant) goes to double and is scaled by pi / 2.
+__host__ __device__ inline double lm_reduce_large(uint32_t xi, int* np) {
+    const unsigned int w = (xi >> 26) & 15u;
+    const int shift = (int)((xi >> 23) & 7u);
+    xi = (xi & 0xffffffu) | 0x800000u;
+    xi <<= shift;
+    uint64_t res0 = (uint64_t)(uint32_t)(xi * lm_inv_pio4(w));
+    const uint64_t res1 = (uint64_t)xi * lm_inv_pio4(w + 4), res2 = (uint64_t)xi * lm_inv_pio4(w + 8);
+    res0 = (res2 >> 32) | (res0 << 32);
+    res0 += res1;
+    const uint64_t n = (res0 + (1ull << 61)) >> 62;
+    res0 -= n << 62;
+    *np = (int)n;
+    return (double)(int64_t)res0 * 0x1.921FB54442D18p-62;
+}
+// |y| >= 120: sinf (odd = 0) or cosf (odd = 1) through reduce_large; Inf and NaN give NaN
+__host__ __device__ inline float lm_sincosf_large(float y, int odd) {
+    if (lm_abstop12(y) >= 0x7f8u) return (y - y) / (y - y);
+    const uint32_t xi = lm_bits(y);
+    const int sign = (int)(xi >> 31);
+    int n;
+    const double x = lm_reduce_large(xi, &n);
+    const LmSincos p0 = lm_sincos_table(0);
+    const double s = p0.sign[(n + sign) & 3];
+    return lm_sinf_poly(x * s, x * x, lm_sincos_table(((n + sign) & 2) ? 1 : 0), n ^ odd);
+}
 __host__ __device__ inline float lm_sinf(float y) {
     double x = (double)y;
     if (lm_abstop12(y) < lm_abstop12(0x1.921FB6p-1f)) {  // |y| < pi / 4
@@ -113,7 +154,8 @@ __host__ __device__ inline float lm_sinf(float y) {
         const double s = p0.sign[n & 3];
         return lm_sinf_poly(x * s, x * x, lm_sincos_table((n & 2) ? 1 : 0), n);
     }
-    return (float)sin((double)y);  // (large arguments: not glibc's reduction; no caller gets here)
+    // (no caller gets here: the branch is glibc's so that the whole-line sweep against the host's libm holds, see above)
+    return lm_sincosf_large(y, 0);
 }
 __host__ __device__ inline float lm_cosf(float y) {
     double x = (double)y;
@@ -128,7 +170,7 @@ __host__ __device__ inline float lm_cosf(float y) {
         const double s = p0.sign[n & 3];
         return lm_sinf_poly(x * s, x * x, lm_sincos_table((n & 2) ? 1 : 0), n ^ 1);
     }
-    return (float)cos((double)y);
+    return lm_sincosf_large(y, 1);
 }
 
 // ---- atanf / atan2f (fdlibm, float arithmetic) ---------------------------------------------------------------------------

@@ -190,3 +190,117 @@ def test_normals_radius_into_device_memory_equals_the_host_call():
         assert capi.LIB.pcc_normals_radius(ix._h, C.c_double(0.3), None, capi.MEM_DEVICE, dev.data_ptr()) == 0
         ix.sync()
         assert np.isfinite(host).all(1).sum() > 900 and _same_bits(dev.cpu().numpy(), host).all()
+
+
+# ---- degenerate neighbourhoods through k_normals' own accumulation ---------------------------------------------------------
+# tests/cpp/test_device_math.hip runs the plane fit function by function; these clouds run the kernels' sums as well, at the
+# neighbourhoods the painted rooms never produce.  2000 points each (the rooms: 4 x 500), one row non-finite.  The radius is
+# one per cloud, chosen so that most rows hold 3 to 100 neighbours.
+def _degenerate_cloud(name):
+    rng = np.random.default_rng(97)
+    n = 2000
+    if name == "plane_z0":          # an exact plane: the smallest root is 0 up to the cubic's rounding
+        pts = np.concatenate([rng.random((n, 2)), np.zeros((n, 1))], 1)
+    elif name == "plane_z3_grid":   # an exact plane away from the origin, every coordinate on a 2^-8 grid: exact sums
+        pts = np.concatenate([3.0 + rng.integers(0, 256, (n, 2)) / 256.0, np.full((n, 1), 3.0)], 1)
+    elif name == "lattice":         # pitch 2^-4: every neighbourhood is full of distance ties
+        g = np.stack(np.meshgrid(*[np.arange(13)] * 3, indexing="ij"), -1).reshape(-1, 3)
+        pts = g[rng.permutation(len(g))[:n]] / 16.0
+    elif name == "line_x":          # on the x axis: two rows of the covariance are exactly zero, every cross product too: NaN
+        pts = np.stack([rng.permutation(4096)[:n] / 1024.0, np.zeros(n), np.zeros(n)], 1)
+    elif name == "line_diagonal":   # (t, 2t, 3t), t of 22 bits so that 3t is exact: rank 1 only up to the rounding of the sums,
+        t = rng.integers(0, 1 << 22, n) / float(1 << 20)  # normals made of rounding noise; no regular spacing, so few distance ties
+        pts = np.stack([t, 2.0 * t, 3.0 * t], 1)
+    elif name == "duplicates":      # 40 points on a 2^-4 grid, 50 times each: every k <= 50 neighbourhood is one point, its
+        pts = np.repeat(rng.permutation(4096)[:40, None] // np.array([1, 16, 256]) % 16 / 16.0, 50, axis=0)[rng.permutation(n)]  # sums exact: the zero matrix
+    elif name == "room_1e-6":
+        pts = _room(500).astype(np.float64) * 1e-6
+    elif name == "room_1e4":
+        pts = _room(500).astype(np.float64) * 1e4
+    elif name == "room_offset_1000":  # the single-pass float covariance cancels: zero and negative variances
+        pts = _room(500).astype(np.float64) + 1000.0
+    else:
+        raise KeyError(name)
+    pts = np.ascontiguousarray(pts, dtype=np.float32)
+    assert pts.shape == (n, 3)
+    pts[1234] = (np.nan, np.inf, -np.inf) if name == "line_x" else np.nan
+    return pts
+
+
+# cloud -> (radius, share of rows whose neighbour list holds a distance tie as the oracle's exhaustive search gives it, what
+# is asked of those rows).  A tie row may be summed in another order on the two sides (FLANN's order against (d2, index)):
+#   "bits"  the sums do not depend on the order, so tie rows carry the oracle's bits like every other row.  lattice:
+#           coordinates m / 16 with m <= 12, at most 33 neighbours: every product and every partial sum is an integer below
+#           2^13 in units of 2^-8, exact in float.  duplicates: within 0.05 on a 1 / 16 grid there is one point, 50 times: 50
+#           equal terms.  line_x: y = z = 0 make two rows of the covariance exactly zero in any order, c0 = 0, the smallest
+#           root 0 and every cross product 0: NaN normal and curvature 0 whatever x sums to.
+#   "weak"  the rule of test_normals_with_radius_search: |dot| > 1 - 1e-5, curvature within 1e-6.  The plane at z = 3 has 10-bit
+#           coordinates and up to 38 neighbours: partial sums pass 2^24 and round by order, the normal stays (0, 0, +-1).
+#   "nan"   only the NaN rule that holds for every row (fewer than 3 neighbours: NaN on both sides): the normals of the
+#           diagonal line and of the room at offset 1000 are made of rounding noise, so a tie row there has no direction to
+#           compare.  The oracle finds 10 such rows on the line and none at offset 1000.
+_DEGENERATE = {
+    "plane_z0": (0.05, 0.0, "weak"),
+    "plane_z3_grid": (0.06, 0.911, "weak"),
+    "lattice": (0.13, 1.0, "bits"),
+    "line_x": (0.01, 0.9365, "bits"),
+    "line_diagonal": (0.04, 0.005, "nan"),
+    "duplicates": (0.05, 1.0, "bits"),
+    "room_1e-6": (0.12e-6, 0.0, "weak"),
+    "room_1e4": (0.12e4, 0.0, "weak"),
+    "room_offset_1000": (0.12, 0.0, "nan"),
+}
+
+
+def _tie_rows(pts, radius):
+    """rows whose radius neighbourhood, sorted by distance, holds two equal distances (the oracle's exhaustive search):
+    there FLANN's order and the (d2, index) order may sum the same points in a different order"""
+    cnt = oracle.radius_count_exhaustive(pts, pts, radius)
+    kmax = max(int(cnt.max()), 2)
+    _, d2 = oracle.knn_exhaustive(pts, pts, kmax)
+    col = np.arange(kmax - 1)[None, :]
+    return ((d2[:, 1:] == d2[:, :-1]) & (col + 1 < cnt[:, None])).any(axis=1), cnt
+
+
+@pytest.mark.parametrize("name", list(_DEGENERATE))
+def test_normals_of_degenerate_neighbourhoods(name):
+    pts = _degenerate_cloud(name)
+    ix = capi.Index(pts)
+    for k in (3, 10, 50):
+        got = ix.normals(k)
+        want = oracle.normals(pts, k, neighbours=ix.knn(pts, k)[0])
+        assert np.isnan(got[1234]).all()
+        _assert_normals_close(got, want)
+    # the class the cloud is there for (k = 50, still in got / want)
+    ok = np.arange(len(pts)) != 1234
+    if name.startswith("plane"):
+        assert (got[ok, 3] == 0).mean() > 0.5 and np.isfinite(got[ok]).all()
+    if name == "line_x":
+        assert np.isnan(got[ok, :3]).all()
+    if name == "duplicates":  # (sum / k can round an ulp off the coordinate for k = 50: such a group gets a normal of rounding noise)
+        assert np.isnan(got[ok, :3]).all(axis=1).mean() > 0.9 and (got[ok, 3] == 0).all()
+    if name == "line_diagonal":
+        assert (got[ok, 3] == 0).mean() > 0.5
+    if name == "room_offset_1000":
+        assert (got[ok, 3] == 0).mean() > 0.5  # zero and negative variances: the smallest root is clamped to 0
+    radius, tie_share, tie_rule = _DEGENERATE[name]
+    got = ix.normals_radius(radius)
+    want = oracle.normals_radius(pts, radius)
+    tie, cnt = _tie_rows(pts, radius)
+    assert ((cnt >= 3) & (cnt <= 100)).mean() > 0.5
+    assert abs(tie[ok].mean() - tie_share) <= 0.02, tie[ok].mean()
+    # every row: fewer than 3 neighbours (the non-finite row has none) is NaN on both sides, whatever the order
+    few = cnt < 3
+    assert few[1234] and np.isnan(got[few]).all() and np.isnan(want[few]).all()
+    # the oracle's bits on every row without a tie, and on the tie rows too where the sums are order-free
+    exact = np.ones(len(pts), bool) if tie_rule == "bits" else ~tie
+    assert (exact & ~few).sum() > 100  # rows with a neighbourhood to fit, compared bit for bit
+    same = _same_bits(got, want).all(axis=1)
+    assert same[exact].all(), (int((~same[exact]).sum()), int(exact.sum()), np.nonzero(~same & exact)[0][:5])
+    if tie_rule == "weak" and (~exact).any():
+        g, w = got[~exact], want[~exact]
+        assert (np.isnan(g) == np.isnan(w)).all()
+        fin = np.isfinite(g).all(axis=1)
+        dots = np.abs((g[fin, :3].astype(np.float64) * w[fin, :3]).sum(1))
+        assert (dots > 1 - 1e-5).all()
+        np.testing.assert_allclose(g[fin, 3], w[fin, 3], rtol=0, atol=1e-6)
