@@ -8,7 +8,7 @@ ARCH       ?= gfx950
 HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 -fPIC -Iinclude -Ipointcloudcomparator_amd/csrc
 CSRC       := pointcloudcomparator_amd/csrc
 LIBDIR     := pointcloudcomparator_amd/lib
-HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/sor.hip)
+HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/sor.hip)
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/pcc_nn.h
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 
@@ -26,8 +26,8 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math
-cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split
+cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -86,6 +86,10 @@ build/rgb_segments_device: tests/cpp/rgb_segments_device.cpp include/pcc/region_
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
+build/rgb_segments_batch: tests/cpp/rgb_segments_batch.cpp include/pcc/region_growing_rgb.hpp include/pcc/search.hpp include/pcc/point_types.hpp pointcloudcomparator_amd/host/ply_io.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
 # dev helper of tools/exp_rgb.py (not part of `all`)
 build/rgb_time: tools/rgb_time.cpp include/pcc/region_growing_rgb.hpp include/pcc/search.hpp include/pcc/point_types.hpp pointcloudcomparator_amd/host/ply_io.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
@@ -107,6 +111,19 @@ build/asan/test_rgb_merge: tests/cpp/test_rgb_merge.cpp $(CSRC)/rgb_merge.hpp bu
 test-rgb-merge: build/test_rgb_merge build/asan/test_rgb_merge
 	build/test_rgb_merge
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_rgb_merge
+
+# the host half of pcc_region_growing_rgb_batch (the per-cloud cut of a concatenation's segments and pairs) the same way
+build/test_rgb_batch_split: tests/cpp/test_rgb_batch_split.cpp $(CSRC)/rgb_batch_split.hpp $(CSRC)/rgb_merge.hpp build/pcc_oracle_host.o
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -pthread -I$(CSRC) -Ioracle $< build/pcc_oracle_host.o -o $@ -lm
+
+build/asan/test_rgb_batch_split: tests/cpp/test_rgb_batch_split.cpp $(CSRC)/rgb_batch_split.hpp $(CSRC)/rgb_merge.hpp build/asan/pcc_oracle.o
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -Wall -pthread -I$(CSRC) -Ioracle $< build/asan/pcc_oracle.o -o $@ -lm
+
+test-rgb-batch-split: build/test_rgb_batch_split build/asan/test_rgb_batch_split
+	build/test_rgb_batch_split
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_rgb_batch_split
 
 build/test_libm: tests/cpp/test_libm.cpp $(CSRC)/libm_f32.hpp
 	@mkdir -p build
@@ -173,12 +190,13 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_dims_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_sift_batch_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_rgb_batch_split
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -211,4 +229,4 @@ build/asan/test_sift_batch_plan: tests/cpp/test_sift_batch_plan.cpp $(CSRC)/sift
 clean:
 	rm -rf build $(LIBDIR)/*.so oracle/_build
 
-.PHONY: all lib prof oracle ubench hosttest cli clean asan test-rgb-merge
+.PHONY: all lib prof oracle ubench hosttest cli clean asan test-rgb-merge test-rgb-batch-split

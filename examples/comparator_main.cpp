@@ -43,9 +43,10 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --rift-loop (with --rift: one call per cluster as in the reference, :1224-1272, instead of one pcc::processRIFTBatch for all),
 // --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read),
 // --descriptor-dims N (the bins of a descriptor the cluster matching searches on),
-// --rgb-device (the colour segmentation of matched clusters, :1456-1495, as one pcc_region_growing_rgb call each: same report)
+// --rgb-device (the colour segmentation of matched clusters, :1456-1495, as one pcc_region_growing_rgb call each: same report),
+// --rgb-batch (the same for the clusters of ALL accepted matches in one pcc_region_growing_rgb_batch call: same report)
 static int n_gpus = 1, descriptor_dims = 3;
-static bool rgb_device = false;
+static bool rgb_device = false, rgb_batch = false;
 static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
@@ -75,6 +76,8 @@ static void printUsage() {
               << "                   32 matches on the whole histogram; exact ties then go to the lowest index)\n"
               << "--rgb-device       (this build) the colour segmentation of every matched cluster runs in the library, rows and growing on\n"
               << "                   the GPU (pcc_region_growing_rgb), instead of on the host over downloaded rows: the same report\n"
+              << "--rgb-batch        (this build) the colour segmentations of ALL accepted matches run in one library call\n"
+              << "                   (pcc_region_growing_rgb_batch) before the match sections are written: the same report\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
@@ -318,7 +321,7 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
             }
         }
     std::vector<int> matches;
-    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims, rgb_device);
+    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims, rgb_device, rgb_batch);
 
     if (noise) {
         PointCloud<PointXYZRGB> nonoise[2];
@@ -379,6 +382,7 @@ int main(int argc, char** argv) {
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a == "--descriptor-dims" && i + 1 < argc) descriptor_dims = std::atoi(argv[++i]);
         else if (a == "--rgb-device") rgb_device = true;
+        else if (a == "--rgb-batch") rgb_batch = true;
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }

@@ -23,6 +23,9 @@
 // setDeviceSegmentation(true) hands ALL of it to the library instead: extract() is then one pcc_region_growing_rgb call (rows,
 // growing, segment statistics and segment pairs on the GPU, the merging on the host inside the library, labels back) -- the
 // same clusters, bit for bit; nothing but the labels crosses to this side.  Off by default: extract() above is untouched.
+//
+// color_growing_segmentation_batch does the same for MANY clouds in one pcc_region_growing_rgb_batch call -- the two
+// segmentations of every accepted match of a comparison, none of which depends on another.
 #pragma once
 #include <algorithm>
 #include <limits>
@@ -304,6 +307,79 @@ inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation(
 template <class PointT>
 inline std::vector<typename PointCloud<PointT>::Ptr> color_growing_segmentation_device(const typename PointCloud<PointT>::Ptr& cloud_in) {
     return color_growing_segmentation<PointT>(cloud_in, true);
+}
+
+namespace detail {
+// One pcc_region_growing_rgb_batch call over `clouds` (null or empty ones are empty clouds of the batch): the labels of cloud c
+// are labels[offsets[c] .. offsets[c + 1]), its cluster count n_clusters[c].  ctx (nullable): any handle to lend device, stream
+// and scratch.  No cloud with a point: no library call.
+template <class PointT>
+inline void rgbBatchCall(const std::vector<typename PointCloud<PointT>::Ptr>& clouds, float distance_threshold, float point_color_threshold,
+                         float region_color_threshold, int min_cluster_size, pcc_index* ctx, std::vector<int32_t>& labels,
+                         std::vector<size_t>& offsets, std::vector<int32_t>& n_clusters) {
+    const size_t nc = clouds.size();
+    offsets.assign(nc + 1, 0);
+    n_clusters.assign(nc, 0);
+    std::vector<const void*> pts(nc, nullptr), rgb(nc, nullptr);
+    std::vector<size_t> n(nc, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        if (clouds[c] && !clouds[c]->empty()) {
+            pts[c] = &clouds[c]->points[0].x;
+            rgb[c] = &clouds[c]->points[0].rgba;
+            n[c] = clouds[c]->size();
+        }
+        offsets[c + 1] = offsets[c] + n[c];
+    }
+    labels.assign(offsets[nc], -1);
+    if (offsets[nc] == 0) return;
+    static thread_local search::KdTree<PointT> context;  // lends device, stream and scratch; the cloud it indexes is never asked
+    if (!ctx) {
+        if (!context.handle()) {
+            typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+            PointT p;
+            p.x = p.y = p.z = 0.f;
+            p.rgba = 0;
+            one->push_back(p);
+            context.setInputCloud(one);
+        }
+        ctx = context.handle();
+    }
+    // (PCL's defaults of 30 growing and 100 region neighbours, no upper size limit: what RegionGrowingRGB above starts with)
+    check(pcc_region_growing_rgb_batch(ctx, nc, pts.data(), n.data(), sizeof(PointT), rgb.data(), sizeof(PointT), PCC_MEM_HOST,
+                                       distance_threshold, point_color_threshold, region_color_threshold,
+                                       (uint32_t)std::max(min_cluster_size, 0), (uint32_t)std::numeric_limits<int>::max(), 30u, 100u,
+                                       labels.data(), n_clusters.data()));
+}
+}  // namespace detail
+
+// color_growing_segmentation for every cloud of `clouds` in ONE library call: element c of the result is what
+// color_growing_segmentation(clouds[c]) returns -- the same NaN strip, the same gate of more than 10 points (a cloud at or below
+// it is not sent and yields an empty list), the same segments in the same order.
+template <class PointT>
+inline std::vector<std::vector<typename PointCloud<PointT>::Ptr> > color_growing_segmentation_batch(
+    const std::vector<typename PointCloud<PointT>::Ptr>& clouds, pcc_index* ctx = nullptr) {
+    typedef typename PointCloud<PointT>::Ptr Ptr;
+    std::vector<std::vector<Ptr> > out(clouds.size());
+    std::vector<Ptr> sent(clouds.size());
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        if (!clouds[c]) continue;
+        Ptr cloud(new PointCloud<PointT>);
+        for (const PointT& p : clouds[c]->points)  // pcl::removeNaNFromPointCloud
+            if (isFinite(p)) cloud->push_back(p);
+        if (cloud->size() > 10) sent[c] = cloud;
+    }
+    std::vector<int32_t> labels, n_clusters;
+    std::vector<size_t> offsets;
+    detail::rgbBatchCall<PointT>(sent, 10.f, 6.f, 5.f, 200, ctx, labels, offsets, n_clusters);
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        if (!sent[c]) continue;
+        out[c].resize((size_t)n_clusters[c]);
+        for (Ptr& seg : out[c]) seg.reset(new PointCloud<PointT>);
+        const int32_t* l = labels.data() + offsets[c];
+        for (size_t i = 0; i < sent[c]->size(); ++i)
+            if (l[i] >= 0) out[c][(size_t)l[i]]->push_back(sent[c]->points[i]);
+    }
+    return out;
 }
 
 }  // namespace pcc

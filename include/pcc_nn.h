@@ -213,7 +213,7 @@ enum pcc_option {
                                     clouds take the single path inside the same call, one by one, on a work handle kept in ctx
                                     (default 8192; PCC_RIFT_BATCH_BRUTE_MAX in the environment of a new handle).  No result bit
                                     depends on it. */
-    PCC_OPT_SIFT_BATCH_BRUTE_MAX = 27  /* pcc_sift_keypoints_batch: clouds of up to this many points go through the batch kernels (one
+    PCC_OPT_SIFT_BATCH_BRUTE_MAX = 27, /* pcc_sift_keypoints_batch: clouds of up to this many points go through the batch kernels (one
                                     segmented voxel grid, one exhaustive row build and one 25-NN pass per octave for the whole
                                     batch); larger clouds take the single path inside the same call, one by one, on a work handle
                                     kept in ctx (PCC_SIFT_BATCH_BRUTE_MAX in the environment of a new handle).  Default 8192, chosen from
@@ -222,6 +222,16 @@ enum pcc_option {
                                     measured -- 60 clusters of 701 ... 8000 points take 17.6 ms at 8192 and 54.8 ms at 4096, where
                                     21 of them pay the single path's waits one after the other; above 8192 only the lone cloud
                                     was measured (10.2 against 3.4 ms at 16 384).  No result bit depends on it. */
+    PCC_OPT_RGB_BATCH_BRUTE_MAX = 28   /* pcc_region_growing_rgb_batch: clouds of up to this many points (and nr_region_neighbours <= 128) get
+                                    their k-NN rows from the segmented exhaustive kernel that serves the whole batch at once (n^2
+                                    distance tests per cloud) and grow in one pass over the concatenation; every other cloud takes
+                                    the single path inside the same call, one by one, on a work handle kept in ctx
+                                    (PCC_RGB_BATCH_BRUTE_MAX in the environment of a new handle).  Default 8192, chosen from
+                                    profiles/rgb_batch_exp.txt: 60 clusters of 11 ... 8000 points take 11.3 / 5.7 / 4.08 / 4.06 ms
+                                    at 2048 / 4096 / 8192 / 16 384 (13 / 3 / 0 / 0 of them on the work handle); a cloud ALONE takes
+                                    0.41 / 0.73 / 1.06 / 1.22 ms through the batch kernels against 0.52 / 0.89 / 1.06 / 1.21 ms on
+                                    the work handle at 2048 / 4096 / 8192 / 16 384 points: the batch kernels never lose up to 8192
+                                    and tie above it, where only the lone cloud was measured.  No result bit depends on it. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -609,6 +619,38 @@ int pcc_region_growing_rgb(pcc_index *index, const void *rgb, size_t rgb_stride_
                            uint32_t min_size, uint32_t max_size,
                            unsigned int nr_neighbours, unsigned int nr_region_neighbours,
                            int32_t *labels, int32_t *n_clusters);
+/* The same for EVERY cluster of a comparison at once -- replaces the two color_growing_segmentation calls per accepted match
+ *   (src/comparator.cpp:1456-1495; body src/segmentation.cpp:161-216): all matches are known before the first is reported and
+ *   no segmentation depends on another.  The clouds of a call are concatenated on the device and every stage runs once over
+ *   all of them: one upload, one segmented k-NN pass, one pass of each growing stage, one sorted pair list cut per cloud on the
+ *   host.  Launches and host waits do not depend on n_clouds: one wait per label sweep -- the sweeps end when no label moves in
+ *   ANY cloud -- and four more (the segment count with the clouds' first ids, the pair count, the pair list, the labels).
+ *   ctx: any index handle, as for pcc_rift_descriptors_batch: it supplies device, stream and scratch; the cloud it indexes,
+ *     its tie order and its kept k-NN rows are neither read nor changed.
+ *   Cloud c is described as in pcc_rift_descriptors_batch.  Its labels are rows sum(n[0..c)) .. sum(n[0..c]) of out_labels, its
+ *     cluster count is out_n_clusters[c]; both are bit for bit what pcc_index_create(pts[c], ...) + pcc_region_growing_rgb(...)
+ *     give on a fresh handle with the same seven parameters.  No point of another cloud enters a row, a segment or a segment
+ *     pair, however the clouds overlap in space.  Non-finite points get -1 and take part in nothing.  A cloud with n[c] == 0
+ *     writes nothing and reports 0 clusters; a cloud without a finite point gets all -1 and 0 clusters (the single path answers
+ *     PCC_ERR_EMPTY there).
+ *   out_labels[sum(n)], out_n_clusters[n_clouds]: HOST arrays.  mem must be PCC_MEM_HOST (PCC_MEM_DEVICE: PCC_ERR_UNSUPPORTED).
+ *     n_clouds == 0: PCC_OK, no device is touched.
+ *   Clouds above PCC_OPT_RGB_BATCH_BRUTE_MAX points, and every cloud when nr_region_neighbours > 128, take the single path
+ *     inside the call on a work handle kept in ctx (reused across calls, freed with ctx; same bits).  pcc_index_stats afterwards
+ *     reports, for the batch route, the grown segments in [0], the distinct ordered segment pairs in [1] and the label sweeps in
+ *     [7]; in [2] the points that went through the batch kernels and in [3] the points of the clouds sent through the work handle.
+ *   Refused before the handle is looked at, with pcc_region_growing_rgb's messages where it has one: null arrays, a null pts[c]
+ *     or rgb[c] with n[c] > 0, a bad stride or alignment, a threshold that is negative or not finite, nr_neighbours == 0,
+ *     nr_region_neighbours == 0 or > PCC_KNN_MAX_K (PCC_ERR_UNSUPPORTED), sum(n) >= 2^31 (PCC_ERR_UNSUPPORTED).  A batch route
+ *     whose rows would hold 2^32 entries or more (points on the route x nr_region_neighbours) is PCC_ERR_UNSUPPORTED: split
+ *     the call. */
+int pcc_region_growing_rgb_batch(pcc_index *ctx, size_t n_clouds,
+                                 const void *const *pts, const size_t *n, size_t stride_bytes,
+                                 const void *const *rgb, size_t rgb_stride_bytes, int mem,
+                                 float distance_threshold, float point_color_threshold, float region_color_threshold,
+                                 uint32_t min_size, uint32_t max_size,
+                                 unsigned int nr_neighbours, unsigned int nr_region_neighbours,
+                                 int32_t *out_labels /* [sum(n)] */, int32_t *out_n_clusters /* [n_clouds] */);
 
 /* ---- first point within a radius ----------------------------------------------------------------
  * replaces: the O(S*N) linear scan in processRIFTwithSIFT (src/comparator.cpp:696-713) that snaps
@@ -683,7 +725,10 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  After pcc_sift_keypoints_batch on the handle: [0] points that went through the batch kernels, [1] points of the clouds sent
  *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
  *  After pcc_region_growing_rgb on the handle: [0] grown colour segments, [1] distinct ordered segment pairs (s, t) with a row
- *  entry leading from s to t, [7] label sweeps of the growing stage. */
+ *  entry leading from s to t, [7] label sweeps of the growing stage.
+ *  After pcc_region_growing_rgb_batch on the handle: [0] grown colour segments, [1] distinct ordered segment pairs and [7] label
+ *  sweeps of the batch route (all its clouds together), [2] points that went through the batch kernels, [3] points of the
+ *  clouds sent through the work handle (above PCC_OPT_RGB_BATCH_BRUTE_MAX, or nr_region_neighbours > 128). */
 int pcc_index_stats(const pcc_index *index, uint64_t stats[8]);
 /* 1 when this library was built with the pair counter (-DPCC_COUNT_PAIRS: the profiling build), else 0 */
 int pcc_counts_pairs(void);

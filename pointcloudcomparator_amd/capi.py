@@ -20,7 +20,7 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX) = range(1, 28)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX) = range(1, 29)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -34,7 +34,7 @@ SYMBOLS = [
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
     "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
-    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_sac_plane", "pcc_rigid_from_sums",
+    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
@@ -109,6 +109,8 @@ def _load() -> C.CDLL:
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
                                            C.POINTER(C.c_int32)]
+    lib.pcc_region_growing_rgb_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint,
+                                                 C.c_uint, vp, vp]
     lib.pcc_voxel_grid.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, vp, sz, C.POINTER(sz)]
     lib.pcc_radius_fill.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, vp, vp, vp]
     lib.pcc_radius_count_max.argtypes = [vp, vp, sz, sz, i32, C.c_double, C.c_uint, vp]
@@ -834,6 +836,39 @@ class Index:
         self._after(st)
         return labels[:n], ncl.value
 
+    def region_growing_rgb_batch(self, clouds, rgbs=None, distance: float = 10.0, point_colour: float = 6.0, region_colour: float = 5.0,
+                                 min_size: int = 200, max_size: int = 2**31 - 1, nn: int = 30, region_nn: int = 100):
+        """pcc_region_growing_rgb_batch with this handle as the context: colour region growing of every cloud in one call (the
+        reference's two color_growing_segmentation calls per accepted match, src/comparator.cpp:1456-1495).  clouds[c] /
+        rgbs[c]: host arrays as rift_descriptors_batch takes them.  Returns one (labels (n,) int32, n_clusters) per cloud, each
+        what Index(clouds[c]).region_growing_rgb(rgbs[c], ...) returns; a cloud without a finite point gives all -1 and 0.  The
+        cloud the handle indexes is neither read nor changed."""
+        clouds = list(clouds)
+        rgbs = list(clouds if rgbs is None else rgbs)
+        n = len(clouds)
+        assert len(rgbs) == n, "one colour array per cloud"
+        args = [_points(a) for a in clouds]
+        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
+        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
+        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_region_growing_rgb_batch takes host arrays"
+        strides = {a[2] for a in args if a[1] > 1}
+        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
+        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
+        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
+        stride = strides.pop() if strides else (single[0][0] if single else 12)
+        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
+        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+        pp = vps(*[a[0] if a[1] else None for a in args])
+        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
+        sizes = [a[1] for a in args]
+        off = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+        labels = np.empty(max(int(off[n]), 1), dtype=np.int32)
+        ncl = np.zeros(max(n, 1), dtype=np.int32)
+        _check(LIB.pcc_region_growing_rgb_batch(self._h, n, pp, szs(*sizes), stride, cp, cstride, MEM_HOST, np.float32(distance),
+                                                np.float32(point_colour), np.float32(region_colour), int(min_size), int(max_size), int(nn),
+                                                int(region_nn), labels.ctypes.data, ncl.ctypes.data))
+        return [(labels[int(off[c]):int(off[c + 1])].copy(), int(ncl[c])) for c in range(n)]
+
     def icp_step(self, src, want_corr: bool = True, center=None):
         """correspondences of `src` against the index + the 17 Umeyama sums; center: take the sums about this point
         (every rank of a sharded loop the SAME one) -- needed for small clouds at large coordinates"""
@@ -953,3 +988,14 @@ def rift_descriptors_batch(clouds, rgbs=None, normal_radius: float = 0.03, gradi
         return ctx.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
         return own.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
+
+
+def region_growing_rgb_batch(clouds, rgbs=None, distance: float = 10.0, point_colour: float = 6.0, region_colour: float = 5.0,
+                             min_size: int = 200, max_size: int = 2**31 - 1, nn: int = 30, region_nn: int = 100, ctx=None):
+    """Colour region growing of every cloud at once (pcc_region_growing_rgb_batch): a list of (labels, n_clusters) per cloud.
+    ctx: an Index that lends its device, stream and scratch (its own cloud is left as it is); None makes a one-point handle
+    for the call."""
+    if ctx is not None:
+        return ctx.region_growing_rgb_batch(clouds, rgbs, distance, point_colour, region_colour, min_size, max_size, nn, region_nn)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.region_growing_rgb_batch(clouds, rgbs, distance, point_colour, region_colour, min_size, max_size, nn, region_nn)

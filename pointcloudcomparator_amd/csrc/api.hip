@@ -22,6 +22,7 @@ unsigned long long pairs_take_knn();
 unsigned long long pairs_take_cluster();
 unsigned long long pairs_take_flann();
 unsigned long long pairs_take_rift_batch();
+unsigned long long pairs_take_rgb_batch();
 #endif
 
 static thread_local std::string g_err;
@@ -75,6 +76,7 @@ static const OptionRow g_options[] = {
     {PCC_OPT_SIFT_LAYOUT, "PCC_SIFT_LAYOUT", &Options::sift_layout, nullptr, 0, 1, OptionRow::FLAG},
     {PCC_OPT_RIFT_BATCH_BRUTE_MAX, "PCC_RIFT_BATCH_BRUTE_MAX", &Options::rift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
     {PCC_OPT_SIFT_BATCH_BRUTE_MAX, "PCC_SIFT_BATCH_BRUTE_MAX", &Options::sift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
+    {PCC_OPT_RGB_BATCH_BRUTE_MAX, "PCC_RGB_BATCH_BRUTE_MAX", &Options::rgb_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
 };
 static const OptionRow* option_row(int option) {
     for (const OptionRow& r : g_options)
@@ -508,6 +510,7 @@ int pcc_index_destroy(pcc_index* ix) {
     match_batch_release(ix);
     rift_batch_release(ix);
     sift_batch_release(ix);
+    rgb_batch_release(ix);
     rift_release(ix);
     sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
@@ -769,7 +772,7 @@ int pcc_index_stats(const pcc_index* cix, uint64_t stats[8]) {
 #ifdef PCC_COUNT_PAIRS
     // profiling build: distances evaluated by the pruned kernels (process-wide, every handle) since the previous call
     PCC_HIP(hipStreamSynchronize(ix->stream));
-    ix->stats[4] = pairs_take_grid() + pairs_take_knn() + pairs_take_cluster() + pairs_take_flann() + pairs_take_rift_batch();
+    ix->stats[4] = pairs_take_grid() + pairs_take_knn() + pairs_take_cluster() + pairs_take_flann() + pairs_take_rift_batch() + pairs_take_rgb_batch();
 #endif
     if (ix->stats_pending) {
         PCC_HIP(hipStreamSynchronize(ix->stream));

@@ -187,6 +187,10 @@ struct Options {
                                     // batch kernels (sift_batch.hip: segmented voxel grid, exhaustive rows and 25-NN over the whole batch); larger
                                     // ones take the single path, one by one, on a work handle.  Measured (EXPERIMENTS.md, "Batched SIFT keypoints"): a
                                     // cloud alone is cheaper there from ~3000 points, beside others not before the 8000 measured
+    int rgb_batch_brute_max = 8192;    // PCC_OPT_RGB_BATCH_BRUTE_MAX: clouds of a pcc_region_growing_rgb_batch call up to this many points get their
+                                    // k-NN rows from the exhaustive segmented kernel over the whole batch (region_rgb_batch.hip); larger ones take
+                                    // the single path, one by one, on a work handle.  Measured (EXPERIMENTS.md, "Batched colour region growing"):
+                                    // beside others the batch kernels win at every size measured (up to 8000 points); a cloud alone ties from 8192 on
     int overlap_prep = 1;           // PCC_OPT_OVERLAP_PREP: a k = 1 search that follows setInputCloud directly packs and sorts its queries on a
                                     // second stream while the build's cell sort is still running (they share nothing but the grid parameters);
                                     // from 2M queries on, 2 = at every size
@@ -282,6 +286,7 @@ struct SiftScratch {
 };
 struct RiftBatchScratch;   // rift_batch.hip: the staging buffers, CSR and work handle of pcc_rift_descriptors_batch
 struct SiftBatchScratch;   // sift_batch.hip: the staging buffers, voxel keys, CSR and work handle of pcc_sift_keypoints_batch
+struct RgbBatchScratch;    // region_rgb_batch.hip: the staging buffers, rows and work handle of pcc_region_growing_rgb_batch
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
@@ -371,6 +376,7 @@ struct pcc_index {
     pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
+    pcc::RgbBatchScratch* rgb_batch = nullptr;    // made at the first pcc_region_growing_rgb_batch with this handle as its context (region_rgb_batch.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -597,6 +603,8 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
 // sift_batch.hip: pcc_sift_keypoints_batch behind its argument checks
 void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work handle
+// region_rgb_batch.hip: pcc_region_growing_rgb_batch behind its argument checks
+void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work handle
 int grid_first_within(pcc_index* ix, const float4* q, size_t nq, double radius, int32_t* idx_dev);
 // ---- flann_order.hip: flags[i] = 1 when another reference shares query i's minimum distance; the tied queries walked
 // through FLANN's tree on the device

@@ -40,6 +40,7 @@
 #include "entry.hpp"
 #include "grid_device.hpp"
 #include "rgb_merge.hpp"
+#include "rgb_stages.hpp"
 #include "uf_device.hpp"
 
 namespace pcc {
@@ -63,6 +64,22 @@ __device__ __forceinline__ unsigned int wave_sum(unsigned int x) {
     return x;
 }
 
+// Which points the wave-per-point kernels take, and in which order (a template parameter of theirs).  ByCell: the first
+// gd->n_valid entries of cell_refs name them -- one indexed cloud, in CELL order, so that a wave's gathers stay spatially compact.
+// ByIndex: every index 0 .. n itself -- a concatenation of clouds (region_rgb_batch.hip), which has no grid; the row of a
+// non-finite point is empty there, so its wave finds nothing to do.
+struct ByCell {
+    const float4* __restrict__ cell_refs;
+    const GridDev* __restrict__ gd;
+    __device__ __forceinline__ unsigned int count() const { return gd->n_valid; }
+    __device__ __forceinline__ unsigned int point(unsigned int w) const { return (unsigned int)__float_as_int(cell_refs[w].w); }
+};
+struct ByIndex {
+    unsigned int n;
+    __device__ __forceinline__ unsigned int count() const { return n; }
+    __device__ __forceinline__ unsigned int point(unsigned int w) const { return w; }
+};
+
 // P = min(nr_neighbours, K): the length of the growing prefix of a row
 __global__ void __launch_bounds__(256)
 k_rgb_prepare(const unsigned long long* __restrict__ keys, const unsigned char* __restrict__ rgb, size_t rgb_stride, unsigned int n,
@@ -76,16 +93,16 @@ k_rgb_prepare(const unsigned long long* __restrict__ keys, const unsigned char* 
     }
 }
 
-// wave w owns the w-th valid point in CELL order: its row is read coalesced, its neighbours' colours and prefix keys are
-// gathers into a spatially compact set
+// wave w owns the w-th point of the order (ByCell: the w-th valid point in CELL order): its row is read coalesced, its
+// neighbours' colours and prefix keys are gathers into a spatially compact set
+template <class Order>
 __global__ void __launch_bounds__(256)
 k_rgb_link(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ col,
-           const unsigned long long* __restrict__ kth, const float4* __restrict__ cell_refs, const GridDev* __restrict__ gd,
-           int K, int P, float p2p2, unsigned int* __restrict__ parent) {
+           const unsigned long long* __restrict__ kth, const Order order, int K, int P, float p2p2, unsigned int* __restrict__ parent) {
     const unsigned int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const unsigned int lane = threadIdx.x & 63;
-    if (w >= gd->n_valid) return;
-    const unsigned int u = (unsigned int)__float_as_int(cell_refs[w].w);
+    if (w >= order.count()) return;
+    const unsigned int u = order.point(w);
     const unsigned int cu = col[u];
     const unsigned long long* row = keys + (size_t)u * K;
     for (int base = 0; base < P; base += 64) {
@@ -110,21 +127,20 @@ k_rgb_flatten(unsigned int n, unsigned int* __restrict__ parent) {
 
 // parent[] is flat here.  FIRST: every point is visited, and the points with an edge into another component are LISTED;
 // the later sweeps are launched over that list alone.
-template <bool FIRST>
+template <bool FIRST, class Order>
 __global__ void __launch_bounds__(256)
-k_rgb_sweep(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ col,
-            const float4* __restrict__ cell_refs, const GridDev* __restrict__ gd, int K, int P, float p2p2,
+k_rgb_sweep(const unsigned long long* __restrict__ keys, const unsigned int* __restrict__ col, const Order order, int K, int P, float p2p2,
             const unsigned int* __restrict__ parent, unsigned int* __restrict__ label, unsigned int* __restrict__ changed,
             unsigned int* __restrict__ cross_list, unsigned int* __restrict__ cross_count, unsigned int list_n) {
     unsigned int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const unsigned int lane = threadIdx.x & 63;
     if (FIRST) {
-        if (w >= gd->n_valid) return;
+        if (w >= order.count()) return;
     } else {
         if (w >= list_n) return;
         w = cross_list[w];
     }
-    const unsigned int u = (unsigned int)__float_as_int(cell_refs[w].w);
+    const unsigned int u = order.point(w);
     const unsigned int cu = col[u];
     const unsigned int ru = parent[u];
     const unsigned int lu = __hip_atomic_load(&label[ru], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -164,12 +180,13 @@ k_rgb_segment_ids(const float4* __restrict__ refs, const unsigned int* __restric
         seg[i] = __float_as_int(refs[i].w) >= 0 ? (int)pos[label[parent[i]]] : -1;
 }
 
-// one lane per valid point in cell order (neighbouring lanes mostly share a segment): the lanes of a wave that share a
+// one lane per point of the order (neighbouring lanes mostly share a segment): the lanes of a wave that share a
 // segment add up first, one lane of them issues the four atomics
+template <class Order>
 __global__ void __launch_bounds__(256)
-k_rgb_stats(const float4* __restrict__ cell_refs, const GridDev* __restrict__ gd, const int* __restrict__ seg,
-            const unsigned int* __restrict__ col, unsigned int ns, RgbSegment* __restrict__ stats) {
-    const unsigned int n_valid = gd->n_valid;
+k_rgb_stats(const Order order, const int* __restrict__ seg, const unsigned int* __restrict__ col, unsigned int ns,
+            RgbSegment* __restrict__ stats) {
+    const unsigned int n_valid = order.count();
     const unsigned int lane = threadIdx.x & 63;
     // (the trip count is the wave's: every lane takes part in the exchanges)
     for (unsigned int t0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63u; t0 < n_valid; t0 += gridDim.x * blockDim.x) {
@@ -178,7 +195,7 @@ k_rgb_stats(const float4* __restrict__ cell_refs, const GridDev* __restrict__ gd
         int s = -1;
         unsigned int c = 0;
         if (pending) {
-            const unsigned int i = (unsigned int)__float_as_int(cell_refs[t].w);
+            const unsigned int i = order.point(t);
             s = seg[i];
             c = col[i];
         }
@@ -208,19 +225,19 @@ __device__ __forceinline__ size_t pair_slot(unsigned long long key, int log2_siz
     return (size_t)((key * 0x9E3779B97F4A7C15ull) >> (64 - log2_size));
 }
 
-// One wave per valid point in cell order, one lane per row entry, all K of them.  An entry is FOREIGN when its point lies in
+// One wave per point of the order, one lane per row entry, all K of them.  An entry is FOREIGN when its point lies in
 // another segment than the row's.  Of the foreign entries of a 64-entry chunk that name the same segment only the first
 // counts -- rows ascend, it holds their minimum.  INSERT = false: those are counted (an upper bound of the distinct pairs);
 // INSERT = true: they go into the table.
-template <bool INSERT>
+template <bool INSERT, class Order>
 __global__ void __launch_bounds__(256)
-k_rgb_pairs(const unsigned long long* __restrict__ keys, const int* __restrict__ seg, const float4* __restrict__ cell_refs,
-            const GridDev* __restrict__ gd, int K, unsigned int* __restrict__ count, unsigned long long* __restrict__ tkeys,
-            unsigned int* __restrict__ tdist, int log2_size, unsigned int* __restrict__ overflow) {
+k_rgb_pairs(const unsigned long long* __restrict__ keys, const int* __restrict__ seg, const Order order, int K,
+            unsigned int* __restrict__ count, unsigned long long* __restrict__ tkeys, unsigned int* __restrict__ tdist, int log2_size,
+            unsigned int* __restrict__ overflow) {
     const unsigned int w = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const unsigned int lane = threadIdx.x & 63;
-    if (w >= gd->n_valid) return;
-    const unsigned int u = (unsigned int)__float_as_int(cell_refs[w].w);
+    if (w >= order.count()) return;
+    const unsigned int u = order.point(w);
     const int su = seg[u];
     const unsigned long long* row = keys + (size_t)u * K;
     unsigned int firsts = 0;
@@ -285,25 +302,30 @@ k_rgb_label(const int* __restrict__ seg, const int32_t* __restrict__ cluster_of_
     }
 }
 
+// ids[c] = pos[bases[c]] for c <= n_clouds: the first segment id of every cloud of a concatenation (pos: the exclusive scan of
+// the seed flags; bases[n_clouds] = n, so ids[n_clouds] = the number of segments)
+__global__ void __launch_bounds__(256)
+k_rgb_cloud_ids(const unsigned int* __restrict__ pos, const unsigned int* __restrict__ bases, unsigned int n_clouds,
+                unsigned int* __restrict__ ids) {
+    for (unsigned int c = blockIdx.x * blockDim.x + threadIdx.x; c <= n_clouds; c += gridDim.x * blockDim.x) ids[c] = pos[bases[c]];
+}
+
 inline int g1(size_t n) {
     size_t b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
-}  // namespace
+// pairs that come down with their count, before the count is known (12 bytes each): a list beyond it costs one more wait
+constexpr unsigned int RGB_PAIRS_FIRST_COPY = 1u << 18;
 
-// keys: the self k-NN rows of the index (n x K); rgb: the colour words on the device (stride bytes apart); labels_dev[n]
-int grid_region_growing_rgb(pcc_index* ix, const unsigned long long* keys, int K, const unsigned char* rgb, size_t rgb_stride,
-                            float distance_threshold, float point_color_threshold, float region_color_threshold, uint32_t min_size,
-                            uint32_t max_size, unsigned int nr_neighbours, unsigned int nr_region_neighbours, int32_t* labels_dev,
-                            int32_t* n_clusters) {
+template <class Order>
+int rgb_stages_in(pcc_index* ix, const RgbRun& run, const Order& order, const RgbHostHalf& host_half) {
     hipStream_t s = ix->stream;
-    const unsigned int n = (unsigned int)ix->n_orig;
-    const int P = (int)std::min<unsigned int>(nr_neighbours, (unsigned int)K);
-    const float dist2 = distance_threshold * distance_threshold, p2p2 = point_color_threshold * point_color_threshold,
-                r2r2 = region_color_threshold * region_color_threshold;
-    const float4* cell_refs = ix->cell_refs.as<float4>();
-    const GridDev* gd = ix->d_grid.as<GridDev>();
+    const unsigned int n = run.n;
+    const unsigned long long* keys = run.keys;
+    const int K = run.K;
+    const int P = (int)std::min<unsigned int>(run.nr_neighbours, (unsigned int)K);
+    const float p2p2 = run.point_color_threshold * run.point_color_threshold;
     PCC_TRY(ix->scratch_a.reserve((size_t)n * 4));        // label
     PCC_TRY(ix->scratch_c.reserve((size_t)n * 4));        // parent
     PCC_TRY(ix->scratch_d.reserve((size_t)n * 4));        // colours
@@ -321,9 +343,9 @@ int grid_region_growing_rgb(pcc_index* ix, const unsigned long long* keys, int K
     unsigned int* d_words = ix->words()->op;  // growing: [0] changed, [1] -, [2] points with a cross edge; pairs: [0] foreign firsts, [1] pairs listed, [2] table overflow
     ev_mark(ix, EV_MAIN0);
     PCC_HIP(hipMemsetAsync(d_words, 0, sizeof(DevWords::op), s));
-    hipLaunchKernelGGL(k_rgb_prepare, dim3(g1(n)), dim3(256), 0, s, keys, rgb, rgb_stride, n, K, P, parent, label, kth, col);
+    hipLaunchKernelGGL(k_rgb_prepare, dim3(g1(n)), dim3(256), 0, s, keys, run.rgb, run.rgb_stride, n, K, P, parent, label, kth, col);
     const unsigned int wave_blocks = (n + 3) / 4;
-    hipLaunchKernelGGL(k_rgb_link, dim3(wave_blocks), dim3(256), 0, s, keys, col, kth, cell_refs, gd, K, P, p2p2, parent);
+    hipLaunchKernelGGL(k_rgb_link<Order>, dim3(wave_blocks), dim3(256), 0, s, keys, col, kth, order, K, P, p2p2, parent);
     hipLaunchKernelGGL(k_rgb_flatten, dim3(g1(n)), dim3(256), 0, s, n, parent);
     PCC_HIP(hipGetLastError());
     unsigned int n_cross = 0, sweeps = 0;
@@ -332,89 +354,149 @@ int grid_region_growing_rgb(pcc_index* ix, const unsigned long long* keys, int K
         if (sweep > n + 1) { set_error("colour region growing did not settle"); return PCC_ERR_DEVICE; }
         PCC_HIP(hipMemsetAsync(d_words, 0, 4, s));
         if (sweep == 0)
-            hipLaunchKernelGGL(k_rgb_sweep<true>, dim3(wave_blocks), dim3(256), 0, s, keys, col, cell_refs, gd, K, P, p2p2, parent, label,
+            hipLaunchKernelGGL((k_rgb_sweep<true, Order>), dim3(wave_blocks), dim3(256), 0, s, keys, col, order, K, P, p2p2, parent, label,
                                d_words, cross_list, d_words + 2, 0u);
         else
-            hipLaunchKernelGGL(k_rgb_sweep<false>, dim3((n_cross + 3) / 4), dim3(256), 0, s, keys, col, cell_refs, gd, K, P, p2p2, parent,
+            hipLaunchKernelGGL((k_rgb_sweep<false, Order>), dim3((n_cross + 3) / 4), dim3(256), 0, s, keys, col, order, K, P, p2p2, parent,
                                label, d_words, cross_list, d_words + 2, n_cross);
         PCC_HIP(hipGetLastError());
         unsigned int w[3];  // changed, -, cross count
         PCC_TRY(read_back<3>(ix, d_words, w));
         ++sweeps;
         if (sweep == 0) n_cross = w[2];
+        if (n_cross > n) { set_error("colour region growing: %u points with a cross edge among %u", n_cross, n); return PCC_ERR_DEVICE; }
         if (w[0] == 0 || n_cross == 0) break;
     }
     // dense segment ids in index order
     PCC_HIP(hipMemsetAsync(flags + n, 0, 4, s));
-    hipLaunchKernelGGL(k_rgb_seed_flags, dim3(g1(n)), dim3(256), 0, s, ix->refs.as<float4>(), parent, label, n, flags);
+    hipLaunchKernelGGL(k_rgb_seed_flags, dim3(g1(n)), dim3(256), 0, s, run.refs, parent, label, n, flags);
     PCC_HIP(hipGetLastError());
     PCC_TRY(launch_exclusive_scan(ix, s, flags, (size_t)n + 1, ix->vox_c));
-    hipLaunchKernelGGL(k_rgb_segment_ids, dim3(g1(n)), dim3(256), 0, s, ix->refs.as<float4>(), parent, label, flags, n, seg);
+    hipLaunchKernelGGL(k_rgb_segment_ids, dim3(g1(n)), dim3(256), 0, s, run.refs, parent, label, flags, n, seg);
     PCC_HIP(hipGetLastError());
     unsigned int ns = 0;
-    PCC_TRY(read_back(ix, flags + n, &ns));
-    if (ns == 0 || ns > n) { set_error("colour region growing: %u segments over %u points", ns, n); return PCC_ERR_DEVICE; }
-    // per-segment records, and the count of what the pair table has to hold
-    PCC_TRY(ix->scratch_b.reserve((size_t)ns * sizeof(RgbSegment)));
-    RgbSegment* d_stats = ix->scratch_b.as<RgbSegment>();
-    PCC_HIP(hipMemsetAsync(d_stats, 0, (size_t)ns * sizeof(RgbSegment), s));
-    PCC_HIP(hipMemsetAsync(d_words, 0, sizeof(DevWords::op), s));
-    hipLaunchKernelGGL(k_rgb_stats, dim3(g1(n)), dim3(256), 0, s, cell_refs, gd, seg, col, ns, d_stats);
-    hipLaunchKernelGGL(k_rgb_pairs<false>, dim3(wave_blocks), dim3(256), 0, s, keys, seg, cell_refs, gd, K, d_words,
-                       (unsigned long long*)nullptr, (unsigned int*)nullptr, 0, d_words + 2);
-    PCC_HIP(hipGetLastError());
-    unsigned int n_first = 0;
-    PCC_TRY(read_back(ix, d_words, &n_first));
-    PCC_TRY(ix->host_a.reserve((size_t)ns * sizeof(RgbSegment)));
-    RgbSegment* h_stats = ix->host_a.as<RgbSegment>();
-    PCC_HIP(hipMemcpyAsync(h_stats, d_stats, (size_t)ns * sizeof(RgbSegment), hipMemcpyDeviceToHost, s));
-    unsigned int np = 0;
-    RgbSegmentPair* h_pairs = nullptr;
-    if (n_first) {
-        int log2_size = 10;
-        while (((size_t)1 << log2_size) < (size_t)n_first * 2) ++log2_size;
-        const size_t tsize = (size_t)1 << log2_size;
-        PCC_TRY(ix->vox_a.reserve(tsize * sizeof(unsigned long long)));
-        PCC_TRY(ix->vox_b.reserve(tsize * sizeof(unsigned int)));
-        PCC_TRY(ix->rows_idx.reserve((size_t)n_first * sizeof(RgbSegmentPair)));
-        auto* tkeys = ix->vox_a.as<unsigned long long>();
-        auto* tdist = ix->vox_b.as<unsigned int>();
-        auto* d_pairs = ix->rows_idx.as<RgbSegmentPair>();
-        PCC_HIP(hipMemsetAsync(tkeys, 0xff, tsize * sizeof(unsigned long long), s));
-        PCC_HIP(hipMemsetAsync(tdist, 0xff, tsize * sizeof(unsigned int), s));
-        hipLaunchKernelGGL(k_rgb_pairs<true>, dim3(wave_blocks), dim3(256), 0, s, keys, seg, cell_refs, gd, K, d_words, tkeys, tdist,
-                           log2_size, d_words + 2);
-        hipLaunchKernelGGL(k_rgb_compact_pairs, dim3(g1(tsize)), dim3(256), 0, s, tkeys, tdist, tsize, d_pairs, d_words + 1, n_first);
+    if (run.d_bases) {
+        // a concatenation: ids are dense over all of it in index order, so cloud c owns the ids from pos[bases[c]] on
+        hipLaunchKernelGGL(k_rgb_cloud_ids, dim3(g1((size_t)run.n_clouds + 1)), dim3(256), 0, s, flags, run.d_bases, run.n_clouds, run.d_id_bases);
         PCC_HIP(hipGetLastError());
-        unsigned int w[3];  // -, pairs listed, table overflow
-        PCC_TRY(read_back<3>(ix, d_words, w));
-        np = w[1];
-        if (w[2] || np > n_first) { set_error("segment pair table overflow (%u pairs, room for %u)", np, n_first); return PCC_ERR_OVERFLOW; }
-        PCC_TRY(ix->host_b.reserve((size_t)np * sizeof(RgbSegmentPair)));
-        h_pairs = ix->host_b.as<RgbSegmentPair>();
-        PCC_HIP(hipMemcpyAsync(h_pairs, d_pairs, (size_t)np * sizeof(RgbSegmentPair), hipMemcpyDeviceToHost, s));
+        PCC_HIP(hipMemcpyAsync(run.h_id_bases, run.d_id_bases, ((size_t)run.n_clouds + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+        PCC_HIP(hipStreamSynchronize(s));
+        ns = run.h_id_bases[run.n_clouds];
+    } else {
+        PCC_TRY(read_back(ix, flags + n, &ns));
+        if (ns == 0) { set_error("colour region growing: no segment over %u points", n); return PCC_ERR_DEVICE; }
     }
-    PCC_HIP(hipStreamSynchronize(s));
+    if (ns > n) { set_error("colour region growing: %u segments over %u points", ns, n); return PCC_ERR_DEVICE; }
+    // per-segment records, and the count of what the pair table has to hold
+    unsigned int np = 0;
+    RgbSegment* h_stats = nullptr;
+    RgbSegmentPair* h_pairs = nullptr;
+    if (ns) {  // (a concatenation without a finite point has no segment: every label is -1)
+        PCC_TRY(ix->scratch_b.reserve((size_t)ns * sizeof(RgbSegment)));
+        RgbSegment* d_stats = ix->scratch_b.as<RgbSegment>();
+        PCC_HIP(hipMemsetAsync(d_stats, 0, (size_t)ns * sizeof(RgbSegment), s));
+        PCC_HIP(hipMemsetAsync(d_words, 0, sizeof(DevWords::op), s));
+        hipLaunchKernelGGL(k_rgb_stats<Order>, dim3(g1(n)), dim3(256), 0, s, order, seg, col, ns, d_stats);
+        hipLaunchKernelGGL((k_rgb_pairs<false, Order>), dim3(wave_blocks), dim3(256), 0, s, keys, seg, order, K, d_words,
+                           (unsigned long long*)nullptr, (unsigned int*)nullptr, 0, d_words + 2);
+        PCC_HIP(hipGetLastError());
+        unsigned int n_first = 0;
+        PCC_TRY(read_back(ix, d_words, &n_first));
+        PCC_TRY(ix->host_a.reserve((size_t)ns * sizeof(RgbSegment)));
+        h_stats = ix->host_a.as<RgbSegment>();
+        PCC_HIP(hipMemcpyAsync(h_stats, d_stats, (size_t)ns * sizeof(RgbSegment), hipMemcpyDeviceToHost, s));
+        if (n_first) {
+            int log2_size = 10;
+            while (((size_t)1 << log2_size) < (size_t)n_first * 2) ++log2_size;
+            const size_t tsize = (size_t)1 << log2_size;
+            PCC_TRY(ix->vox_a.reserve(tsize * sizeof(unsigned long long)));
+            PCC_TRY(ix->vox_b.reserve(tsize * sizeof(unsigned int)));
+            PCC_TRY(ix->rows_idx.reserve((size_t)n_first * sizeof(RgbSegmentPair)));
+            auto* tkeys = ix->vox_a.as<unsigned long long>();
+            auto* tdist = ix->vox_b.as<unsigned int>();
+            auto* d_pairs = ix->rows_idx.as<RgbSegmentPair>();
+            PCC_HIP(hipMemsetAsync(tkeys, 0xff, tsize * sizeof(unsigned long long), s));
+            PCC_HIP(hipMemsetAsync(tdist, 0xff, tsize * sizeof(unsigned int), s));
+            hipLaunchKernelGGL((k_rgb_pairs<true, Order>), dim3(wave_blocks), dim3(256), 0, s, keys, seg, order, K, d_words, tkeys, tdist,
+                               log2_size, d_words + 2);
+            hipLaunchKernelGGL(k_rgb_compact_pairs, dim3(g1(tsize)), dim3(256), 0, s, tkeys, tdist, tsize, d_pairs, d_words + 1, n_first);
+            PCC_HIP(hipGetLastError());
+            // the count and the list in one wait: the list's head comes down beside the count, the rest only when there is more
+            const unsigned int head = std::min(n_first, RGB_PAIRS_FIRST_COPY);
+            PCC_TRY(ix->host_b.reserve((size_t)head * sizeof(RgbSegmentPair)));
+            PCC_HIP(hipMemcpyAsync(ix->pinned->readback, d_words, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+            PCC_HIP(hipMemcpyAsync(ix->host_b.p, d_pairs, (size_t)head * sizeof(RgbSegmentPair), hipMemcpyDeviceToHost, s));
+            PCC_HIP(hipStreamSynchronize(s));
+            unsigned int w[3];  // -, pairs listed, table overflow
+            memcpy(w, ix->pinned->readback, sizeof(w));
+            np = w[1];
+            if (w[2] || np > n_first) { set_error("segment pair table overflow (%u pairs, room for %u)", np, n_first); return PCC_ERR_OVERFLOW; }
+            if (np > head) {
+                PCC_TRY(ix->host_b.reserve((size_t)np * sizeof(RgbSegmentPair)));  // (may move: everything comes down again)
+                PCC_HIP(hipMemcpyAsync(ix->host_b.p, d_pairs, (size_t)np * sizeof(RgbSegmentPair), hipMemcpyDeviceToHost, s));
+                PCC_HIP(hipStreamSynchronize(s));
+            }
+            h_pairs = ix->host_b.as<RgbSegmentPair>();
+        } else {
+            PCC_HIP(hipStreamSynchronize(s));
+        }
+    }
     // the host half: the nearest segments of every segment, PCL's merging, folding and size filter
-    const int min_pts = (int)std::min<uint32_t>(min_size, 0x7fffffffu), max_pts = (int)std::min<uint32_t>(max_size, 0x7fffffffu);
     std::vector<int32_t> cluster_of_segment;
-    const int ncl = rgb_merge_regions(h_stats, ns, h_pairs, np, dist2, r2r2, nr_region_neighbours, min_pts, max_pts, cluster_of_segment);
-    int32_t* h_ids = ix->host_a.as<int32_t>();  // (the records are used up; ns x 16 bytes hold ns ids)
-    std::copy(cluster_of_segment.begin(), cluster_of_segment.end(), h_ids);
-    PCC_TRY(ix->rows_d2.reserve((size_t)ns * sizeof(int32_t)));
-    int32_t* d_ids = ix->rows_d2.as<int32_t>();
-    PCC_HIP(hipMemcpyAsync(d_ids, h_ids, (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_rgb_label, dim3(g1(n)), dim3(256), 0, s, seg, d_ids, n, ns, labels_dev);
+    PCC_TRY(host_half(h_stats, ns, h_pairs, np, cluster_of_segment));
+    if (cluster_of_segment.size() != ns) { set_error("colour region growing: %zu cluster ids for %u segments", cluster_of_segment.size(), ns); return PCC_ERR_DEVICE; }
+    int32_t* d_ids = nullptr;
+    if (ns) {
+        int32_t* h_ids = ix->host_a.as<int32_t>();  // (the records are used up; ns x 16 bytes hold ns ids)
+        std::copy(cluster_of_segment.begin(), cluster_of_segment.end(), h_ids);
+        PCC_TRY(ix->rows_d2.reserve((size_t)ns * sizeof(int32_t)));
+        d_ids = ix->rows_d2.as<int32_t>();
+        PCC_HIP(hipMemcpyAsync(d_ids, h_ids, (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    }
+    hipLaunchKernelGGL(k_rgb_label, dim3(g1(n)), dim3(256), 0, s, seg, d_ids, n, ns, run.labels_dev);
     PCC_HIP(hipGetLastError());
+    if (run.labels_host) PCC_HIP(hipMemcpyAsync(run.labels_host, run.labels_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     ev_mark(ix, EV_MAIN1);
     PCC_HIP(hipStreamSynchronize(s));  // h_ids may be rewritten by the next call
-    *n_clusters = (int32_t)ncl;
     ix->stats[0] = ns;
     ix->stats[1] = np;
     ix->stats[7] = sweeps;
     ix->stats_pending = false;
     ix->open_pending = false;
     return PCC_OK;
+}
+
+}  // namespace
+
+// the stages behind the rows (rgb_stages.hpp), over one indexed cloud in cell order or over a concatenation in index order
+int rgb_stages(pcc_index* ix, const RgbRun& run, const RgbHostHalf& host_half) {
+    if (run.cell_refs) return rgb_stages_in(ix, run, ByCell{run.cell_refs, run.gd}, host_half);
+    return rgb_stages_in(ix, run, ByIndex{run.n}, host_half);
+}
+
+// keys: the self k-NN rows of the index (n x K); rgb: the colour words on the device (stride bytes apart); labels_dev[n]
+int grid_region_growing_rgb(pcc_index* ix, const unsigned long long* keys, int K, const unsigned char* rgb, size_t rgb_stride,
+                            float distance_threshold, float point_color_threshold, float region_color_threshold, uint32_t min_size,
+                            uint32_t max_size, unsigned int nr_neighbours, unsigned int nr_region_neighbours, int32_t* labels_dev,
+                            int32_t* n_clusters) {
+    RgbRun run;
+    run.refs = ix->refs.as<float4>();
+    run.n = (unsigned int)ix->n_orig;
+    run.keys = keys;
+    run.K = K;
+    run.rgb = rgb;
+    run.rgb_stride = rgb_stride;
+    run.cell_refs = ix->cell_refs.as<float4>();
+    run.gd = ix->d_grid.as<GridDev>();
+    run.point_color_threshold = point_color_threshold;
+    run.nr_neighbours = nr_neighbours;
+    run.labels_dev = labels_dev;
+    const float dist2 = distance_threshold * distance_threshold, r2r2 = region_color_threshold * region_color_threshold;
+    const int min_pts = (int)std::min<uint32_t>(min_size, 0x7fffffffu), max_pts = (int)std::min<uint32_t>(max_size, 0x7fffffffu);
+    return rgb_stages(ix, run, [&](const RgbSegment* segs, unsigned int ns, RgbSegmentPair* pairs, unsigned int np, std::vector<int32_t>& cluster_of_segment) {
+        *n_clusters = (int32_t)rgb_merge_regions(segs, ns, pairs, np, dist2, r2r2, nr_region_neighbours, min_pts, max_pts, cluster_of_segment);
+        return PCC_OK;
+    });
 }
 
 }  // namespace pcc

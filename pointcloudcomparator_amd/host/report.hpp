@@ -129,7 +129,7 @@ private:
 // matches ...".  Returns the scores; matches[i] = cluster of PCL 2 matched to cluster i of PCL 1, or -1.
 inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1, const std::vector<CloudPtr>& clusters2,
                               const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches,
-                              int descriptor_dims = 3, bool rgb_device = false) {
+                              int descriptor_dims = 3, bool rgb_device = false, bool rgb_batch = false) {
     std::ofstream& f = w.file();
     std::vector<std::vector<float> > centroids2;
     w.sectionTitle("Information of clusters of PCL2:");
@@ -197,6 +197,16 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
         }
     }
     w.sectionTitle("Information of matches of clusters of PCL 1 and PCL 2:");
+    // rgb_batch: every match is known here and no colour segmentation depends on another (reference :1456-1495), so the clusters
+    // of all accepted matches go through ONE pcc_region_growing_rgb_batch call before the first match section is written
+    std::vector<size_t> colour_counts;
+    if (rgb_batch) {
+        std::vector<CloudPtr> both;
+        for (size_t i = 0; i < matches.size(); ++i)
+            if (matches[i] != -1) { both.push_back(clusters1[i]); both.push_back(clusters2[(size_t)matches[i]]); }
+        for (const std::vector<CloudPtr>& segments : color_growing_segmentation_batch<PointXYZRGB>(both)) colour_counts.push_back(segments.size());
+    }
+    size_t next_count = 0;
     Scores s;
     for (size_t i = 0; i < matches.size(); ++i) {
         if (matches[i] != -1) {
@@ -211,8 +221,10 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
             s.des1 += d1; s.des2 += d2;
             // colour based segmentation of both clusters: which one has more elements of different colours
             // (rgb_device: the whole segmentation in the library, pcc_region_growing_rgb -- the same segments)
-            const size_t c1 = color_growing_segmentation<PointXYZRGB>(clusters1[i], rgb_device).size();
-            const size_t c2 = color_growing_segmentation<PointXYZRGB>(clusters2[j], rgb_device).size();
+            // (rgb_batch: the counts of the one batch call above, in match order)
+            const size_t c1 = rgb_batch ? colour_counts[next_count] : color_growing_segmentation<PointXYZRGB>(clusters1[i], rgb_device).size();
+            const size_t c2 = rgb_batch ? colour_counts[next_count + 1] : color_growing_segmentation<PointXYZRGB>(clusters2[j], rgb_device).size();
+            next_count += 2;
             w.compareColour(c1, c2);
             s.colour1 += c1; s.colour2 += c2;
         } else {
