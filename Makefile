@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -165,13 +165,18 @@ build/rift_batch_driver: tests/cpp/rift_batch_driver.cpp include/pcc/rift.hpp in
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 # the per-round tables and the keypoint splice of pcc_sift_keypoints_batch on the CPU (no library, no GPU)
-build/test_sift_batch_plan: tests/cpp/test_sift_batch_plan.cpp $(CSRC)/sift_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/test_sift_batch_plan: tests/cpp/test_sift_batch_plan.cpp $(CSRC)/sift_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/cloud_batch.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
 
 build/sift_batch_driver: tests/cpp/sift_batch_driver.cpp include/pcc/sift.hpp include/pcc/rift.hpp include/pcc/search.hpp include/pcc/comparator_nn.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
+# the host scaffold the batch calls share (route split, pack, upload layouts) on the CPU (no library, no GPU)
+build/test_cloud_batch: tests/cpp/test_cloud_batch.cpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/sift_batch_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
 
 # the record packing and work-item table of pcc_match_knn_batch_dims on the CPU (no library, no GPU)
 build/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/match_dims_plan.hpp
@@ -190,13 +195,14 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_dims_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_sift_batch_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_rgb_batch_split
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_cloud_batch
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -222,7 +228,11 @@ build/asan/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/matc
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
-build/asan/test_sift_batch_plan: tests/cpp/test_sift_batch_plan.cpp $(CSRC)/sift_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/asan/test_sift_batch_plan: tests/cpp/test_sift_batch_plan.cpp $(CSRC)/sift_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/cloud_batch.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
+
+build/asan/test_cloud_batch: tests/cpp/test_cloud_batch.cpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/sift_batch_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 

@@ -318,34 +318,13 @@ inline void rgbBatchCall(const std::vector<typename PointCloud<PointT>::Ptr>& cl
                          float region_color_threshold, int min_cluster_size, pcc_index* ctx, std::vector<int32_t>& labels,
                          std::vector<size_t>& offsets, std::vector<int32_t>& n_clusters) {
     const size_t nc = clouds.size();
-    offsets.assign(nc + 1, 0);
+    const BatchClouds b(clouds);
+    offsets = b.offsets;
     n_clusters.assign(nc, 0);
-    std::vector<const void*> pts(nc, nullptr), rgb(nc, nullptr);
-    std::vector<size_t> n(nc, 0);
-    for (size_t c = 0; c < nc; ++c) {
-        if (clouds[c] && !clouds[c]->empty()) {
-            pts[c] = &clouds[c]->points[0].x;
-            rgb[c] = &clouds[c]->points[0].rgba;
-            n[c] = clouds[c]->size();
-        }
-        offsets[c + 1] = offsets[c] + n[c];
-    }
     labels.assign(offsets[nc], -1);
     if (offsets[nc] == 0) return;
-    static thread_local search::KdTree<PointT> context;  // lends device, stream and scratch; the cloud it indexes is never asked
-    if (!ctx) {
-        if (!context.handle()) {
-            typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
-            PointT p;
-            p.x = p.y = p.z = 0.f;
-            p.rgba = 0;
-            one->push_back(p);
-            context.setInputCloud(one);
-        }
-        ctx = context.handle();
-    }
     // (PCL's defaults of 30 growing and 100 region neighbours, no upper size limit: what RegionGrowingRGB above starts with)
-    check(pcc_region_growing_rgb_batch(ctx, nc, pts.data(), n.data(), sizeof(PointT), rgb.data(), sizeof(PointT), PCC_MEM_HOST,
+    check(pcc_region_growing_rgb_batch(batchContext<PointT>(ctx), nc, b.pts.data(), b.n.data(), sizeof(PointT), b.rgb.data(), sizeof(PointT), PCC_MEM_HOST,
                                        distance_threshold, point_color_threshold, region_color_threshold,
                                        (uint32_t)std::max(min_cluster_size, 0), (uint32_t)std::numeric_limits<int>::max(), 30u, 100u,
                                        labels.data(), n_clusters.data()));

@@ -47,33 +47,15 @@ inline std::vector<PointCloud<RIFT32>::Ptr> processRIFTBatch(const std::vector<P
     std::vector<PointCloud<RIFT32>::Ptr> result(clouds.size());
     for (PointCloud<RIFT32>::Ptr& d : result) d.reset(new PointCloud<RIFT32>);
     if (point_indices) point_indices->assign(clouds.size(), std::vector<int>());
-    std::vector<const void*> pts(clouds.size(), nullptr), rgb(clouds.size(), nullptr);
-    std::vector<size_t> n(clouds.size(), 0), offsets(clouds.size() + 1, 0);
-    size_t total = 0;
-    for (size_t c = 0; c < clouds.size(); ++c) {
-        if (!clouds[c] || clouds[c]->empty()) continue;
-        pts[c] = &clouds[c]->points[0].x;
-        rgb[c] = &clouds[c]->points[0].rgba;
-        n[c] = clouds[c]->size();
-        total += n[c];
-    }
+    const detail::BatchClouds b(clouds);
+    const size_t total = b.total();
     if (total == 0) return result;  // (no library call)
-    static thread_local search::KdTree<PointXYZRGB> context;  // lends device, stream and scratch; the cloud it indexes is never asked
-    if (!ctx || !ctx->handle()) {
-        if (!context.handle()) {
-            PointCloud<PointXYZRGB>::Ptr one(new PointCloud<PointXYZRGB>);
-            PointXYZRGB p;
-            p.x = p.y = p.z = 0.f;
-            p.rgba = 0;
-            one->push_back(p);
-            context.setInputCloud(one);
-        }
-        ctx = &context;
-    }
+    std::vector<size_t> offsets(clouds.size() + 1, 0);
     std::vector<float> hist(total * 32);
     std::vector<int32_t> index(total);
-    check(pcc_rift_descriptors_batch(ctx->handle(), clouds.size(), pts.data(), n.data(), sizeof(PointXYZRGB), rgb.data(), sizeof(PointXYZRGB),
-                                     PCC_MEM_HOST, 0.03, 0.03, 0.05, 4, 8, hist.data(), index.data(), offsets.data()));
+    check(pcc_rift_descriptors_batch(detail::batchContext<PointXYZRGB>(ctx ? ctx->handle() : nullptr), clouds.size(), b.pts.data(), b.n.data(),
+                                     sizeof(PointXYZRGB), b.rgb.data(), sizeof(PointXYZRGB), PCC_MEM_HOST, 0.03, 0.03, 0.05, 4, 8, hist.data(),
+                                     index.data(), offsets.data()));
     for (size_t c = 0; c < clouds.size(); ++c) {
         const size_t m = offsets[c + 1] - offsets[c];
         PointCloud<RIFT32>& d = *result[c];

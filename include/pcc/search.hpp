@@ -182,4 +182,40 @@ private:
 template <class PointT>
 using KdTreeFLANN = search::KdTree<PointT>;
 
+namespace detail {
+// A vector of cloud pointers as the *_batch entry points take it (null or empty: an empty cloud of the batch): point and
+// colour pointers, sizes, and offsets[c] = the points in front of cloud c.
+struct BatchClouds {
+    std::vector<const void*> pts, rgb;
+    std::vector<size_t> n, offsets;
+    template <class CloudPtr>
+    explicit BatchClouds(const std::vector<CloudPtr>& clouds) : pts(clouds.size(), nullptr), rgb(clouds.size(), nullptr), n(clouds.size(), 0), offsets(clouds.size() + 1, 0) {
+        for (size_t c = 0; c < clouds.size(); ++c) {
+            if (clouds[c] && !clouds[c]->empty()) {
+                pts[c] = &clouds[c]->points[0].x;
+                rgb[c] = &clouds[c]->points[0].rgba;
+                n[c] = clouds[c]->size();
+            }
+            offsets[c + 1] = offsets[c] + n[c];
+        }
+    }
+    size_t total() const { return offsets.back(); }
+};
+// the context of a *_batch call: the caller's, or this thread's tree over one point (it lends device, stream and scratch)
+template <class PointT>
+inline pcc_index* batchContext(pcc_index* ctx) {
+    if (ctx) return ctx;
+    static thread_local search::KdTree<PointT> context;
+    if (!context.handle()) {
+        typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+        PointT p;
+        p.x = p.y = p.z = 0.f;
+        p.rgba = 0;
+        one->push_back(p);
+        context.setInputCloud(one);
+    }
+    return context.handle();
+}
+}  // namespace detail
+
 }  // namespace pcc

@@ -75,34 +75,14 @@ inline void siftBatchCall(const std::vector<PointCloud<PointXYZRGB>::Ptr>& cloud
     offsets.assign(nc + 1, 0);
     keypoints.clear();
     if (snap) snap->clear();
-    std::vector<const void*> pts(nc, nullptr), rgb(nc, nullptr);
-    std::vector<size_t> n(nc, 0);
-    size_t total = 0;
-    for (size_t c = 0; c < nc; ++c) {
-        if (!clouds[c] || clouds[c]->empty()) continue;
-        pts[c] = &clouds[c]->points[0].x;
-        rgb[c] = &clouds[c]->points[0].rgba;
-        n[c] = clouds[c]->size();
-        total += n[c];
-    }
-    if (total == 0) return;  // (no library call)
-    static thread_local search::KdTree<PointXYZRGB> context;  // lends device, stream and scratch; the cloud it indexes is never asked
-    if (!ctx || !ctx->handle()) {
-        if (!context.handle()) {
-            PointCloud<PointXYZRGB>::Ptr one(new PointCloud<PointXYZRGB>);
-            PointXYZRGB p;
-            p.x = p.y = p.z = 0.f;
-            p.rgba = 0;
-            one->push_back(p);
-            context.setInputCloud(one);
-        }
-        ctx = &context;
-    }
-    size_t capacity = total / 8 + 256;
+    const BatchClouds b(clouds);
+    if (b.total() == 0) return;  // (no library call)
+    pcc_index* context = batchContext<PointXYZRGB>(ctx ? ctx->handle() : nullptr);
+    size_t capacity = b.total() / 8 + 256;
     for (int attempt = 0; attempt < 2; ++attempt) {
         keypoints.resize(capacity * 4);
         if (snap) snap->resize(capacity);
-        const int st = pcc_sift_keypoints_batch(ctx->handle(), nc, pts.data(), n.data(), sizeof(PointXYZRGB), rgb.data(), sizeof(PointXYZRGB),
+        const int st = pcc_sift_keypoints_batch(context, nc, b.pts.data(), b.n.data(), sizeof(PointXYZRGB), b.rgb.data(), sizeof(PointXYZRGB),
                                                 PCC_MEM_HOST, SIFT_MIN_SCALE, SIFT_NR_OCTAVES, SIFT_NR_SCALES_PER_OCTAVE, SIFT_MIN_CONTRAST, 0.05,
                                                 keypoints.data(), snap ? snap->data() : nullptr, capacity, offsets.data());
         if (st == PCC_ERR_OVERFLOW && attempt == 0) { capacity = offsets[nc]; continue; }

@@ -6,6 +6,7 @@ is ever computed in Python -- a missing library is a hard error.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from pathlib import Path
@@ -219,6 +220,33 @@ def _colour_words(rgb):
         ptr = base + 16
     mem = MEM_DEVICE if torch_in and words.is_cuda else MEM_HOST
     return words, ptr, stride, mem
+
+
+# the host clouds of a *_batch call as the C-ABI takes them; `keep` holds the staged arrays the pointers point into
+_CloudBatch = collections.namedtuple("_CloudBatch", "n pts counts stride rgb rgb_stride keep")
+
+
+def _cloud_batch(clouds, rgbs, fn_name):
+    """_CloudBatch of clouds / rgbs (None: the clouds are pcl::PointXYZRGB records, their colour words read in place); counts is
+    the c_size_t array of the sizes.  The result must stay referenced for the length of the call."""
+    clouds = list(clouds)
+    rgbs = list(clouds if rgbs is None else rgbs)
+    n = len(clouds)
+    assert len(rgbs) == n, "one colour array per cloud"
+    args = [_points(a) for a in clouds]
+    cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
+    assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
+    assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), f"{fn_name} takes host arrays"
+    strides = {a[2] for a in args if a[1] > 1}
+    cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
+    assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
+    single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
+    stride = strides.pop() if strides else (single[0][0] if single else 12)
+    cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
+    vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+    pp = vps(*[a[0] if a[1] else None for a in args])
+    cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
+    return _CloudBatch(n, pp, szs(*[a[1] for a in args]), stride, cp, cstride, (clouds, cols))
 
 
 def rigid_from_sums(sums, center=None):
@@ -689,31 +717,14 @@ class Index:
         read in place).  Returns one (histograms (m, 32) float32, point index (m,) int32) per cloud, each what
         Index(clouds[c]).rift_descriptors(rgbs[c]) returns; an empty cloud or one without a finite point gives m = 0.  The
         cloud the handle indexes is neither read nor changed."""
-        clouds = list(clouds)
-        rgbs = list(clouds if rgbs is None else rgbs)
-        n = len(clouds)
-        assert len(rgbs) == n, "one colour array per cloud"
-        args = [_points(a) for a in clouds]
-        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
-        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
-        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_rift_descriptors_batch takes host arrays"
-        strides = {a[2] for a in args if a[1] > 1}
-        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
-        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
-        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
-        stride = strides.pop() if strides else (single[0][0] if single else 12)
-        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
-        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
-        pp = vps(*[a[0] if a[1] else None for a in args])
-        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
-        nn = szs(*[a[1] for a in args])
-        total = sum(a[1] for a in args)
+        b = _cloud_batch(clouds, rgbs, "pcc_rift_descriptors_batch")
+        n, total = b.n, sum(b.counts[:b.n])
         hist = np.empty((max(total, 1), 32), dtype=np.float32)
         index = np.empty(max(total, 1), dtype=np.int32)
         off = np.zeros(n + 1, dtype=np.uintp)
-        _check(LIB.pcc_rift_descriptors_batch(self._h, n, pp, nn, stride, cp, cstride, MEM_HOST, float(normal_radius), float(gradient_radius),
-                                              float(rift_radius), int(nr_distance_bins), int(nr_gradient_bins), hist.ctypes.data,
-                                              index.ctypes.data, off.ctypes.data))
+        _check(LIB.pcc_rift_descriptors_batch(self._h, n, b.pts, b.counts, b.stride, b.rgb, b.rgb_stride, MEM_HOST, float(normal_radius),
+                                              float(gradient_radius), float(rift_radius), int(nr_distance_bins), int(nr_gradient_bins),
+                                              hist.ctypes.data, index.ctypes.data, off.ctypes.data))
         return [(hist[int(off[c]):int(off[c + 1])].copy(), index[int(off[c]):int(off[c + 1])].copy()) for c in range(n)]
 
     def sift_keypoints(self, points, rgb, min_scale: float = 0.005, nr_octaves: int = 5, nr_scales_per_octave: int = 5,
@@ -750,30 +761,14 @@ class Index:
         of sift_keypoints' forms ((n, >= 5) pcl::PointXYZRGB records with rgbs omitted: the colour word is read in place).
         Returns (keypoints (m, 4) float32, offsets (n_clouds + 1,) -- cloud c owns rows offsets[c] .. offsets[c + 1], each slice
         what sift_keypoints returns for that cloud alone --[, snap index (m,) int32, local to the cloud, -1 for none])."""
-        clouds = list(clouds)
-        rgbs = list(clouds if rgbs is None else rgbs)
-        n = len(clouds)
-        assert len(rgbs) == n, "one colour array per cloud"
-        args = [_points(a) for a in clouds]
-        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
-        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
-        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_sift_keypoints_batch takes host arrays"
-        strides = {a[2] for a in args if a[1] > 1}
-        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
-        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
-        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
-        stride = strides.pop() if strides else (single[0][0] if single else 12)
-        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
-        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
-        pp = vps(*[a[0] if a[1] else None for a in args])
-        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
-        nn = szs(*[a[1] for a in args])
+        b = _cloud_batch(clouds, rgbs, "pcc_sift_keypoints_batch")
+        n = b.n
         off = np.zeros(n + 1, dtype=np.uintp)
-        capacity = max(256, sum(a[1] for a in args) // 8)
+        capacity = max(256, sum(b.counts[:n]) // 8)
         for attempt in range(2):
             kp = np.empty((capacity, 4), dtype=np.float32)
             snap = np.empty(capacity, dtype=np.int32) if snap_radius is not None else None
-            status = LIB.pcc_sift_keypoints_batch(self._h, n, pp, nn, stride, cp, cstride, MEM_HOST, float(min_scale), int(nr_octaves),
+            status = LIB.pcc_sift_keypoints_batch(self._h, n, b.pts, b.counts, b.stride, b.rgb, b.rgb_stride, MEM_HOST, float(min_scale), int(nr_octaves),
                                                   int(nr_scales_per_octave), float(min_contrast), 0.0 if snap_radius is None else float(snap_radius),
                                                   kp.ctypes.data, None if snap is None else snap.ctypes.data, capacity, off.ctypes.data)
             if status == -6 and attempt == 0:  # PCC_ERR_OVERFLOW: once more with the room it asks for
@@ -843,28 +838,12 @@ class Index:
         rgbs[c]: host arrays as rift_descriptors_batch takes them.  Returns one (labels (n,) int32, n_clusters) per cloud, each
         what Index(clouds[c]).region_growing_rgb(rgbs[c], ...) returns; a cloud without a finite point gives all -1 and 0.  The
         cloud the handle indexes is neither read nor changed."""
-        clouds = list(clouds)
-        rgbs = list(clouds if rgbs is None else rgbs)
-        n = len(clouds)
-        assert len(rgbs) == n, "one colour array per cloud"
-        args = [_points(a) for a in clouds]
-        cols = [_colour_words(r) if len(r) else (None, None, None, MEM_HOST) for r in rgbs]
-        assert all(len(r) == a[1] for r, a in zip(rgbs, args)), "one colour per point"
-        assert all(a[3] == MEM_HOST for a in args) and all(c[3] == MEM_HOST for c in cols), "pcc_region_growing_rgb_batch takes host arrays"
-        strides = {a[2] for a in args if a[1] > 1}
-        cstrides = {c[2] for c, a in zip(cols, args) if a[1] > 1}
-        assert len(strides) <= 1 and len(cstrides) <= 1, "every cloud of a batch must have the same row stride, and so every colour array"
-        single = [(a[2], c[2]) for c, a in zip(cols, args) if a[1] == 1]  # (one row: any stride the others use will do)
-        stride = strides.pop() if strides else (single[0][0] if single else 12)
-        cstride = cstrides.pop() if cstrides else (single[0][1] if single else 4)
-        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
-        pp = vps(*[a[0] if a[1] else None for a in args])
-        cp = vps(*[c[1] if a[1] else None for c, a in zip(cols, args)])
-        sizes = [a[1] for a in args]
-        off = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]).astype(np.int64)
+        b = _cloud_batch(clouds, rgbs, "pcc_region_growing_rgb_batch")
+        n = b.n
+        off = np.concatenate([[0], np.cumsum(b.counts[:n], dtype=np.int64)]).astype(np.int64)
         labels = np.empty(max(int(off[n]), 1), dtype=np.int32)
         ncl = np.zeros(max(n, 1), dtype=np.int32)
-        _check(LIB.pcc_region_growing_rgb_batch(self._h, n, pp, szs(*sizes), stride, cp, cstride, MEM_HOST, np.float32(distance),
+        _check(LIB.pcc_region_growing_rgb_batch(self._h, n, b.pts, b.counts, b.stride, b.rgb, b.rgb_stride, MEM_HOST, np.float32(distance),
                                                 np.float32(point_colour), np.float32(region_colour), int(min_size), int(max_size), int(nn),
                                                 int(region_nn), labels.ctypes.data, ncl.ctypes.data))
         return [(labels[int(off[c]):int(off[c + 1])].copy(), int(ncl[c])) for c in range(n)]

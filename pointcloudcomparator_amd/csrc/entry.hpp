@@ -1,5 +1,6 @@
 // entry.hpp -- the scaffold of a C-ABI entry point, included by every translation unit that defines one: the call prologue
-// (PCC_ENTER) and the staging of caller arrays that are not point clouds (stage_in, Out, finish).
+// (PCC_ENTER), the staging of caller arrays that are not point clouds (stage_in, Out, finish), and the batch calls' WorkLease and
+// check_cloud_batch.
 #pragma once
 #include "pcc_internal.hpp"
 
@@ -91,6 +92,44 @@ int finish(pcc_index* ix, int mem, const Out<T>&... outs) {
 // the host pipe, for the few calls whose results do not go through Out.  The caller waits.
 inline int copy_out(pcc_index* ix, void* user, const void* dev, size_t bytes, int mem) {
     PCC_HIP(hipMemcpyAsync(user, dev, bytes, mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ix->stream));
+    return PCC_OK;
+}
+
+// ---- the batch calls ------------------------------------------------------------------------------------------
+// A work handle for a scope: made in *slot at the first use, its launches join the caller's queue (under the caller's options
+// when with_options), and it has its own stream back at the end.
+struct WorkLease {
+    pcc_index* w = nullptr;
+    int take(pcc_index* ix, pcc_index** slot, bool with_options) {
+        if (!*slot) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, slot));
+        w = *slot;
+        w->stream = ix->stream;
+        if (with_options) w->opt = ix->opt;
+        return PCC_OK;
+    }
+    ~WorkLease() { if (w) w->stream = w->own_stream; }
+};
+
+// The argument checks the batch entry points share, all of it host arithmetic: check_cloud_batch (the memory space and the
+// stride) first; then the call's own checks of its outputs, arrays and parameters, whose order and statuses differ between the
+// calls; then check_batch_clouds (every cloud; pts, n and rgb are there by then).
+inline int check_cloud_batch(const char* fn_name, const CloudBatch& b, int mem) {
+    PCC_TRY(check_mem(mem));
+    if (mem != PCC_MEM_HOST) { set_error("%s takes host arrays only (PCC_MEM_HOST)", fn_name); return PCC_ERR_UNSUPPORTED; }
+    return check_points(nullptr, 0, b.stride, mem);  // (the stride alone)
+}
+inline int check_batch_clouds(const CloudBatch& b, int mem) {
+    size_t total = 0;
+    for (size_t c = 0; c < b.n_clouds; ++c) {
+        PCC_TRY(check_points(b.pts[c], b.n[c], b.stride, mem));
+        if (b.n[c] && !b.rgb[c]) { set_error("null colour pointer"); return PCC_ERR_INVALID; }
+        if (b.n[c] && (reinterpret_cast<uintptr_t>(b.rgb[c]) % 4 || reinterpret_cast<uintptr_t>(b.pts[c]) % 4)) {
+            set_error("points and colour words must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", b.rgb_stride);
+            return PCC_ERR_INVALID;
+        }
+        total += b.n[c];
+        if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
+    }
     return PCC_OK;
 }
 

@@ -143,7 +143,7 @@ static size_t pack_records(const void* raw, size_t n, size_t stride, float* out)
     for (size_t i = 0; i < n; ++i, out += 4) {
         float v[3];
         memcpy(v, p + i * stride, 12);
-        const bool fin = (v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f;
+        const bool fin = finite3(v[0], v[1], v[2]);
         const int32_t w = fin ? (int32_t)i : -1;
         out[0] = fin ? v[0] : 0.f;
         out[1] = fin ? v[1] : 0.f;

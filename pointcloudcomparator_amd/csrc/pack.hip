@@ -18,11 +18,6 @@ static inline int grid_for(size_t n, int block, int per_thread = 1) {
     return (int)b;
 }
 
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-    // all three finite <=> none is NaN/Inf; (v - v) == 0 only for finite v
-    return (x - x) == 0.0f && (y - y) == 0.0f && (z - z) == 0.0f;
-}
-
 // ---- pack -------------------------------------------------------------------
 // replaces pcl::KdTreeFLANN::convertCloudToArray's copy loop: the
 // first three floats of every element, invalid points flagged for the compaction.

@@ -9,6 +9,7 @@
 #include <string>
 #include "pcc_nn.h"
 #include "flann_tree.hpp"
+#include "cloud_batch.hpp"
 
 // every PCC_SEED_STRIDE-th reference is a "seed": the exhaustive scan of the seeds bounds a far query's ball
 #define PCC_SEED_SHIFT 6
@@ -284,9 +285,20 @@ struct SiftScratch {
     DevBuf octaves;              // SiftOctave per octave
     DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
 };
-struct RiftBatchScratch;   // rift_batch.hip: the staging buffers, CSR and work handle of pcc_rift_descriptors_batch
-struct SiftBatchScratch;   // sift_batch.hip: the staging buffers, voxel keys, CSR and work handle of pcc_sift_keypoints_batch
-struct RgbBatchScratch;    // region_rgb_batch.hip: the staging buffers, rows and work handle of pcc_region_growing_rgb_batch
+// What every batch call keeps of its OWN between calls: the work handle the clouds off the batch route are
+// indexed on (the caller's stream, scratch of its own), pinned staging going up and coming down, what `up` holds on the device.
+struct BatchStaging {
+    pcc_index* work = nullptr;
+    HostBuf up, down;
+    DevBuf dev;
+    ~BatchStaging() {
+        if (work) (void)pcc_index_destroy(work);
+        up.release(); down.release(); dev.release();
+    }
+};
+struct RiftBatchScratch;   // rift_batch.hip: BatchStaging and the CSR of pcc_rift_descriptors_batch
+struct SiftBatchScratch;   // sift_batch.hip: BatchStaging and the voxel keys, tables and CSR of pcc_sift_keypoints_batch
+struct RgbBatchScratch;    // region_rgb_batch.hip: BatchStaging and the rows of pcc_region_growing_rgb_batch
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
@@ -582,15 +594,16 @@ int sort_csr_rows(hipStream_t s, const int64_t* offsets, size_t n, unsigned long
 int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
                      double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out);
 void rift_release(pcc_index* ix);  // frees ix->rift
+// the radius and bin checks of pcc_rift_descriptors and its batch form (rift.hip)
+int check_rift_params(double normal_radius, double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins);
 // the same stages over any packed cloud (rift_batch.hip: the concatenation of a batch): see rift.hip
 typedef std::function<int(double radius, const unsigned long long** keys, const unsigned int** offsets)> RiftRows;
 int rift_stages(pcc_index* ix, const float4* refs, const float4* order, const GridDev* gd, size_t n, const RiftRows& rows,
                 const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius,
                 float* out_hist, int32_t* out_index);
 // rift_batch.hip: pcc_rift_descriptors_batch behind its argument checks (ix->rift made by the caller)
-int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                           size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
-                           int32_t* out_index, size_t* out_offsets);
+int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
+                           float* out_hist, int32_t* out_index, size_t* out_offsets);
 void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work handle
 // rift_batch.hip: the sorted radius rows (d2 < r2, ascending (d2, index)) of a concatenation of clouds as one CSR, from the exhaustive
 // builder: d_items (device) are query blocks of one cloud each, d_pts the concatenation with w = bits(concatenated index).  offs / keys:

@@ -499,6 +499,18 @@ int grid_region_growing_rgb(pcc_index* ix, const unsigned long long* keys, int K
     });
 }
 
+int check_rgb_params(float distance_threshold, float point_color_threshold, float region_color_threshold, unsigned int nr_neighbours,
+                     unsigned int nr_region_neighbours) {
+    for (float t : {distance_threshold, point_color_threshold, region_color_threshold})
+        if (!(t >= 0.f) || !std::isfinite(t)) { set_error("bad threshold"); return PCC_ERR_INVALID; }
+    if (nr_neighbours == 0 || nr_region_neighbours == 0 || nr_region_neighbours > PCC_KNN_MAX_K) {
+        set_error("colour region growing with %u / %u neighbours: both must be at least 1, the region neighbours at most %d", nr_neighbours,
+                  nr_region_neighbours, PCC_KNN_MAX_K);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -513,13 +525,7 @@ int pcc_region_growing_rgb(pcc_index* ix, const void* rgb, size_t rgb_stride, in
         set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
     }
-    for (float t : {distance_threshold, point_color_threshold, region_color_threshold})
-        if (!(t >= 0.f) || !std::isfinite(t)) { set_error("bad threshold"); return PCC_ERR_INVALID; }
-    if (nr_neighbours == 0 || nr_region_neighbours == 0 || nr_region_neighbours > PCC_KNN_MAX_K) {
-        set_error("colour region growing with %u / %u neighbours: both must be at least 1, the region neighbours at most %d", nr_neighbours,
-                  nr_region_neighbours, PCC_KNN_MAX_K);
-        return PCC_ERR_UNSUPPORTED;
-    }
+    PCC_TRY(check_rgb_params(distance_threshold, point_color_threshold, region_color_threshold, nr_neighbours, nr_region_neighbours));
     PCC_ENTER(ix);
     PCC_TRY(ensure_grid(ix));
     PCC_TRY(sync_info(ix));

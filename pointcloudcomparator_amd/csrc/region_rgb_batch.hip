@@ -22,7 +22,8 @@
 // Launches and waits do not depend on the number of clouds: the waits are one per label sweep and four more.
 //
 // Clouds above PCC_OPT_RGB_BATCH_BRUTE_MAX points -- the exhaustive rows are quadratic in the cloud --, and every cloud when
-// nr_region_neighbours > 128, take the single path inside the same call, one by one, on a work handle kept in ctx.
+// nr_region_neighbours > 128, take the single path inside the same call, one by one, on a work handle kept in ctx.  The host
+// scaffold (route split, pack, upload layout, lease, shared argument checks) is cloud_batch.hpp's and entry.hpp's: DESIGN.md 4.16.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -130,35 +131,16 @@ k_rgb_batch_knn(const RiftBatchItem* __restrict__ items, const float4* __restric
     }
 }
 
-size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
-
-bool any_finite(const void* pts, size_t n, size_t stride) {
-    const char* p = static_cast<const char*>(pts);
-    for (size_t i = 0; i < n; ++i) {
-        float v[3];
-        memcpy(v, p + i * stride, 12);
-        if ((v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f) return true;
-    }
-    return false;
-}
-
 }  // namespace
 
-struct RgbBatchScratch {
-    pcc_index* work = nullptr;  // the handle clouds off the batch route are indexed on (the caller's stream, scratch of its own)
-    HostBuf up, down;           // pinned: bases + table + points + colour words going up; the clouds' first ids + labels coming down
-    DevBuf dev;                 // what `up` holds, on the device
-    DevBuf keys;                // u64[total][K]: the rows
-    DevBuf id_bases, labels;    // uint32[n_clouds + 1]; int32[total]
+struct RgbBatchScratch : BatchStaging {  // (up: bases + table + points + colour words; down: the clouds' first ids + labels)
+    DevBuf keys;              // u64[total][K]: the rows
+    DevBuf id_bases, labels;  // uint32[n_clouds + 1]; int32[total]
+    ~RgbBatchScratch() { keys.release(); id_bases.release(); labels.release(); }
 };
 
 void rgb_batch_release(pcc_index* ix) {
-    if (!ix->rgb_batch) return;
-    RgbBatchScratch* b = ix->rgb_batch;
-    if (b->work) (void)pcc_index_destroy(b->work);
-    b->up.release(); b->down.release();
-    b->dev.release(); b->keys.release(); b->id_bases.release(); b->labels.release();
-    delete b;
+    delete ix->rgb_batch;
     ix->rgb_batch = nullptr;
 }
 
@@ -170,14 +152,14 @@ struct RgbParams {
     unsigned int nr_neighbours, nr_region_neighbours;
 };
 
-// the clouds of sizes n[] (0: not on this route) through the batch kernels: labels at out_labels + off[c], counts for EVERY cloud
-int rgb_batch_route(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                    size_t rgb_stride, const RgbParams& par, const size_t* off, int32_t* out_labels, int32_t* out_n_clusters) {
+// the clouds of sizes batch.n[] (0: not on this route) through the batch kernels: labels at out_labels + off[c], counts for EVERY cloud
+int rgb_batch_route(pcc_index* ix, const CloudBatch& batch, const RgbParams& par, const size_t* off, int32_t* out_labels, int32_t* out_n_clusters) {
     hipStream_t s = ix->stream;
     RgbBatchScratch* b = ix->rgb_batch;
+    const size_t n_clouds = batch.n_clouds;
     std::vector<uint32_t> bases;
     std::vector<RiftBatchItem> items;
-    rift_batch_plan(n, n_clouds, &bases, &items);
+    rift_batch_plan(batch.n, n_clouds, &bases, &items);
     const size_t total = bases[n_clouds];
     for (size_t c = 0; c < n_clouds; ++c) out_n_clusters[c] = 0;
     ix->stats[0] = ix->stats[1] = ix->stats[7] = 0;
@@ -189,36 +171,15 @@ int rgb_batch_route(pcc_index* ix, size_t n_clouds, const void* const* pts, cons
     }
 
     // ---- one pinned buffer, one copy: bases, table, 16 bytes + 4 bytes a point -----------------------------------------------
-    const size_t bases_bytes = align_up((n_clouds + 1) * sizeof(uint32_t), 16), items_bytes = items.size() * sizeof(RiftBatchItem);
-    const size_t pts_at = bases_bytes + items_bytes, rgb_at = pts_at + total * sizeof(float4);
-    const size_t up_bytes = rgb_at + total * sizeof(uint32_t);
-    PCC_TRY(b->up.reserve(up_bytes));
-    PCC_TRY(b->dev.reserve(up_bytes));
-    char* u = b->up.as<char>();
-    memset(u, 0, bases_bytes);
-    memcpy(u, bases.data(), (n_clouds + 1) * sizeof(uint32_t));
-    memcpy(u + bases_bytes, items.data(), items_bytes);
-    float* p4 = reinterpret_cast<float*>(u + pts_at);
-    uint32_t* words = reinterpret_cast<uint32_t*>(u + rgb_at);
-    for (size_t c = 0; c < n_clouds; ++c) {
-        const char* src = static_cast<const char*>(pts[c]);
-        const char* col = static_cast<const char*>(rgb[c]);
-        for (size_t i = 0; i < n[c]; ++i) {
-            const size_t at = bases[c] + i;
-            float v[3];
-            memcpy(v, src + i * stride, 12);
-            const bool finite = (v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f;
-            const uint32_t w = finite ? (uint32_t)at : 0xffffffffu;
-            memcpy(p4 + at * 4, v, 12);
-            memcpy(p4 + at * 4 + 3, &w, 4);
-            memcpy(words + at, col + i * rgb_stride, 4);
-        }
-    }
-    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
+    const ConcatLayout up(0, 1, n_clouds, items.size(), total);
+    PCC_TRY(b->up.reserve(up.bytes));
+    PCC_TRY(b->dev.reserve(up.bytes));
+    up.fill(b->up.as<char>(), batch, bases, items, true);
+    PCC_HIP(hipMemcpyAsync(b->dev.p, b->up.p, up.bytes, hipMemcpyHostToDevice, s));
     const char* d = b->dev.as<char>();
-    const unsigned int* d_bases = reinterpret_cast<const unsigned int*>(d);
-    const RiftBatchItem* d_items = reinterpret_cast<const RiftBatchItem*>(d + bases_bytes);
-    const float4* d_pts = reinterpret_cast<const float4*>(d + pts_at);
+    const unsigned int* d_bases = reinterpret_cast<const unsigned int*>(d + up.bases_at);
+    const RiftBatchItem* d_items = reinterpret_cast<const RiftBatchItem*>(d + up.items_at);
+    const float4* d_pts = reinterpret_cast<const float4*>(d + up.pts_at);
 
     // ---- the rows ------------------------------------------------------------------------------------------------------------
     PCC_TRY(b->keys.reserve(total * (size_t)K * sizeof(unsigned long long)));
@@ -240,7 +201,7 @@ int rgb_batch_route(pcc_index* ix, size_t n_clouds, const void* const* pts, cons
     run.n = (unsigned int)total;
     run.keys = keys;
     run.K = K;
-    run.rgb = reinterpret_cast<const unsigned char*>(d + rgb_at);
+    run.rgb = reinterpret_cast<const unsigned char*>(d + up.rgb_at);
     run.rgb_stride = sizeof(uint32_t);
     run.point_color_threshold = par.point_color_threshold;
     run.nr_neighbours = par.nr_neighbours;
@@ -261,57 +222,48 @@ int rgb_batch_route(pcc_index* ix, size_t n_clouds, const void* const* pts, cons
         return (int)PCC_OK;
     }));
     for (size_t c = 0; c < n_clouds; ++c)
-        if (n[c]) memcpy(out_labels + off[c], run.labels_host + bases[c], n[c] * sizeof(int32_t));
+        if (batch.n[c]) memcpy(out_labels + off[c], run.labels_host + bases[c], batch.n[c] * sizeof(int32_t));
     return PCC_OK;
 }
 
 }  // namespace
 
 // pcc_region_growing_rgb_batch behind its argument checks (both out arrays on the host)
-int region_growing_rgb_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                             size_t rgb_stride, float distance_threshold, float point_color_threshold, float region_color_threshold,
-                             uint32_t min_size, uint32_t max_size, unsigned int nr_neighbours, unsigned int nr_region_neighbours,
-                             int32_t* out_labels, int32_t* out_n_clusters) {
+int region_growing_rgb_batch(pcc_index* ix, const CloudBatch& batch, float distance_threshold, float point_color_threshold,
+                             float region_color_threshold, uint32_t min_size, uint32_t max_size, unsigned int nr_neighbours,
+                             unsigned int nr_region_neighbours, int32_t* out_labels, int32_t* out_n_clusters) {
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
     if (!ix->rgb_batch) ix->rgb_batch = new RgbBatchScratch();
     RgbBatchScratch* b = ix->rgb_batch;
     const RgbParams par{distance_threshold, point_color_threshold, region_color_threshold, min_size, max_size, nr_neighbours, nr_region_neighbours};
+    const size_t n_clouds = batch.n_clouds;
     const size_t brute_max = nr_region_neighbours <= RGB_BATCH_MAX_K ? (size_t)ix->opt.rgb_batch_brute_max : 0;
-    std::vector<size_t> small_n(n, n + n_clouds), off(n_clouds + 1, 0);
-    size_t n_brute = 0, n_large = 0;
-    for (size_t c = 0; c < n_clouds; ++c) {
-        off[c + 1] = off[c] + n[c];
-        (n[c] > brute_max ? n_large : n_brute) += n[c];
-        if (n[c] > brute_max) small_n[c] = 0;  // (an empty cloud of the batch: its slice comes from the work handle)
-    }
-    PCC_TRY(rgb_batch_route(ix, n_clouds, pts, small_n.data(), stride, rgb, rgb_stride, par, off.data(), out_labels, out_n_clusters));
-    ix->stats[2] = n_brute;
-    ix->stats[3] = n_large;
+    const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
+    std::vector<size_t> off(n_clouds + 1, 0);
+    for (size_t c = 0; c < n_clouds; ++c) off[c + 1] = off[c] + batch.n[c];
+    CloudBatch small = batch;
+    small.n = routes.small_n.data();
+    PCC_TRY(rgb_batch_route(ix, small, par, off.data(), out_labels, out_n_clusters));
+    ix->stats[2] = routes.n_brute;
+    ix->stats[3] = routes.n_large;
     ix->stats_pending = false;
     ix->open_pending = false;
-    if (n_large == 0) return PCC_OK;
+    if (routes.n_large == 0) return PCC_OK;
 
     // ---- the other clouds: one by one on the work handle ----------------------------------------------------------------------
-    if (!b->work) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &b->work));
-    pcc_index* w = b->work;
-    // the work handle's launches join the caller's queue for the length of this call, under the caller's options
-    struct Borrow {
-        pcc_index* w;
-        ~Borrow() { w->stream = w->own_stream; }
-    } borrow{w};
-    w->stream = ix->stream;
-    w->opt = ix->opt;
+    WorkLease lease;
+    PCC_TRY(lease.take(ix, &b->work, true));
     for (size_t c = 0; c < n_clouds; ++c) {
-        if (n[c] <= brute_max) continue;
+        if (batch.n[c] <= brute_max) continue;
         int32_t* labels = out_labels + off[c];
-        if (!any_finite(pts[c], n[c], stride)) {  // (the single path answers PCC_ERR_EMPTY there)
-            std::fill(labels, labels + n[c], (int32_t)-1);
+        if (!cloud_any_finite(batch.pts[c], batch.n[c], batch.stride)) {  // (the single path answers PCC_ERR_EMPTY there)
+            std::fill(labels, labels + batch.n[c], (int32_t)-1);
             out_n_clusters[c] = 0;
             continue;
         }
-        PCC_TRY(pcc_index_set_input(w, pts[c], n[c], stride, 3, PCC_MEM_HOST));
-        PCC_TRY(pcc_region_growing_rgb(w, rgb[c], rgb_stride, PCC_MEM_HOST, distance_threshold, point_color_threshold, region_color_threshold,
-                                       min_size, max_size, nr_neighbours, nr_region_neighbours, labels, out_n_clusters + c));
+        PCC_TRY(pcc_index_set_input(lease.w, batch.pts[c], batch.n[c], batch.stride, 3, PCC_MEM_HOST));
+        PCC_TRY(pcc_region_growing_rgb(lease.w, batch.rgb[c], batch.rgb_stride, PCC_MEM_HOST, distance_threshold, point_color_threshold,
+                                       region_color_threshold, min_size, max_size, nr_neighbours, nr_region_neighbours, labels, out_n_clusters + c));
     }
     return PCC_OK;
 }
@@ -328,40 +280,22 @@ int pcc_region_growing_rgb_batch(pcc_index* ctx, size_t n_clouds, const void* co
                                  unsigned int nr_region_neighbours, int32_t* out_labels, int32_t* out_n_clusters) {
     using namespace pcc;
     // the arguments first: all of it host arithmetic, refused before the handle or any device is looked at
-    PCC_TRY(check_mem(mem));
-    if (mem != PCC_MEM_HOST) { set_error("pcc_region_growing_rgb_batch takes host arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(check_points(nullptr, 0, stride, mem));  // (the stride alone)
+    const CloudBatch batch{n_clouds, pts, n, stride, rgb, rgb_stride};
+    PCC_TRY(check_cloud_batch("pcc_region_growing_rgb_batch", batch, mem));
     if (n_clouds >= (1ull << 31)) { set_error("more than 2^31 clouds"); return PCC_ERR_UNSUPPORTED; }
     if (n_clouds && (!pts || !n || !rgb || !out_labels || !out_n_clusters)) { set_error("null array argument"); return PCC_ERR_INVALID; }
     if (rgb_stride < 4 || rgb_stride % 4 || reinterpret_cast<uintptr_t>(out_labels) % 4 || reinterpret_cast<uintptr_t>(out_n_clusters) % 4) {
         set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
     }
-    for (float t : {distance_threshold, point_color_threshold, region_color_threshold})
-        if (!(t >= 0.f) || !std::isfinite(t)) { set_error("bad threshold"); return PCC_ERR_INVALID; }
-    if (nr_neighbours == 0 || nr_region_neighbours == 0 || nr_region_neighbours > PCC_KNN_MAX_K) {
-        set_error("colour region growing with %u / %u neighbours: both must be at least 1, the region neighbours at most %d", nr_neighbours,
-                  nr_region_neighbours, PCC_KNN_MAX_K);
-        return PCC_ERR_UNSUPPORTED;
-    }
-    size_t total = 0;
-    for (size_t c = 0; c < n_clouds; ++c) {
-        PCC_TRY(check_points(pts[c], n[c], stride, mem));
-        if (n[c] && !rgb[c]) { set_error("null colour pointer"); return PCC_ERR_INVALID; }
-        if (n[c] && (reinterpret_cast<uintptr_t>(rgb[c]) % 4 || reinterpret_cast<uintptr_t>(pts[c]) % 4)) {
-            set_error("points and colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
-            return PCC_ERR_INVALID;
-        }
-        total += n[c];
-        if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
-    }
+    PCC_TRY(check_rgb_params(distance_threshold, point_color_threshold, region_color_threshold, nr_neighbours, nr_region_neighbours));
+    PCC_TRY(check_batch_clouds(batch, mem));
     if (n_clouds == 0) return PCC_OK;  // (no device is touched: not even the handle's)
     PCC_ENTER(ctx);
     ev_next(ctx);
     ev_mark(ctx, EV_CALL0);
-    const int st = region_growing_rgb_batch(ctx, n_clouds, pts, n, stride, rgb, rgb_stride, distance_threshold, point_color_threshold,
-                                            region_color_threshold, min_size, max_size, nr_neighbours, nr_region_neighbours, out_labels,
-                                            out_n_clusters);
+    const int st = region_growing_rgb_batch(ctx, batch, distance_threshold, point_color_threshold, region_color_threshold, min_size, max_size,
+                                            nr_neighbours, nr_region_neighbours, out_labels, out_n_clusters);
     ev_mark(ctx, EV_CALL1);
     return st;
 }

@@ -42,6 +42,10 @@ typedef std::function<int(const RgbSegment* segs, unsigned int ns, RgbSegmentPai
                           std::vector<int32_t>& cluster_of_segment)>
     RgbHostHalf;
 
+// the thresholds and neighbour counts as pcc_region_growing_rgb and its batch form check them (region_rgb.hip)
+int check_rgb_params(float distance_threshold, float point_color_threshold, float region_color_threshold, unsigned int nr_neighbours,
+                     unsigned int nr_region_neighbours);
+
 // Waits: one per label sweep, one for the segment count (and the clouds' first ids), one for the pair count, one for the pair
 // list (a second one beyond 2^18 pairs), one at the end.  Leaves segments, pairs and sweeps in ix->stats[0], [1], [7].
 int rgb_stages(pcc_index* ix, const RgbRun& run, const RgbHostHalf& host_half);

@@ -280,6 +280,16 @@ int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride,
     return PCC_OK;
 }
 
+int check_rift_params(double normal_radius, double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins) {
+    for (double r : {normal_radius, gradient_radius, rift_radius})
+        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
+    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
+        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -294,12 +304,7 @@ int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int 
         set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
     }
-    for (double r : {normal_radius, gradient_radius, rift_radius})
-        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
-    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
-        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
-        return PCC_ERR_UNSUPPORTED;
-    }
+    PCC_TRY(check_rift_params(normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins));
     PCC_ENTER(ix);
     PCC_TRY(ensure_grid(ix));
     ev_next(ix);

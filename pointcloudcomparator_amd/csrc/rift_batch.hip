@@ -18,7 +18,8 @@
 // concatenated index within a cloud is ascending local index, so a row is the single path's row with base[c] added.
 //
 // Clouds above PCC_OPT_RIFT_BATCH_BRUTE_MAX points would make the quadratic builder the bottleneck: they take the single path
-// inside the same call, one by one, on a work handle kept in ctx (as sift.hip keeps one), and their slices are spliced in.
+// inside the same call, one by one, on a work handle kept in ctx, and their slices are spliced in.  The host scaffold (route
+// split, pack, upload layout, lease of the work handle, shared argument checks) is cloud_batch.hpp's and entry.hpp's: DESIGN.md 4.16.
 #include <algorithm>
 #include <vector>
 
@@ -102,16 +103,12 @@ k_rift_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __
     }
 }
 
-size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
-
 }  // namespace
 
-struct RiftBatchScratch {
-    pcc_index* work = nullptr;  // the handle clouds above the brute limit are indexed on (the caller's stream, scratch of its own)
-    HostBuf up, down;           // pinned: order words + bases + table + points + colour words going up; the slice bounds coming down
-    DevBuf dev;                 // what `up` holds, on the device
-    DevBuf offs, keys;          // the CSR of the radius in use: uint32 offsets[n + 1] + the same as int64; u64 keys
-    DevBuf slice;               // uint32[n_clouds + 1]
+struct RiftBatchScratch : BatchStaging {  // (up: order words + bases + table + points + colour words; down: the slice bounds)
+    DevBuf offs, keys;  // the CSR of the radius in use: uint32 offsets[n + 1] + the same as int64; u64 keys
+    DevBuf slice;       // uint32[n_clouds + 1]
+    ~RiftBatchScratch() { offs.release(); keys.release(); slice.release(); }
 };
 
 // The sorted radius rows of a concatenation of clouds as ONE CSR (pcc_internal.hpp): rows of d2 < r2 from the exhaustive builder
@@ -144,62 +141,40 @@ int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int 
 }
 
 void rift_batch_release(pcc_index* ix) {
-    if (!ix->rift_batch) return;
-    RiftBatchScratch* b = ix->rift_batch;
-    if (b->work) (void)pcc_index_destroy(b->work);
-    b->up.release(); b->down.release();
-    b->dev.release(); b->offs.release(); b->keys.release(); b->slice.release();
-    delete b;
+    delete ix->rift_batch;
     ix->rift_batch = nullptr;
 }
 
 // every cloud of the call through the exhaustive builder: out_hist / out_index / offsets (n_clouds + 1) are host arrays
-static int rift_batch_brute(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                            size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
-                            int32_t* out_index, size_t* out_offsets) {
+static int rift_batch_brute(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
+                            float* out_hist, int32_t* out_index, size_t* out_offsets) {
     hipStream_t s = ix->stream;
     RiftBatchScratch* b = ix->rift_batch;
+    const size_t n_clouds = batch.n_clouds;
     std::vector<uint32_t> bases;
     std::vector<RiftBatchItem> items;
-    rift_batch_plan(n, n_clouds, &bases, &items);
+    rift_batch_plan(batch.n, n_clouds, &bases, &items);
     const size_t total = bases[n_clouds];
     for (size_t c = 0; c <= n_clouds; ++c) out_offsets[c] = 0;
     if (total == 0) return PCC_OK;
 
     // ---- one pinned buffer, one copy: the order's n_valid word, bases, table, 16 bytes + 4 bytes a point ------------------
-    const size_t gd_bytes = align_up(sizeof(GridDev), 128), bases_bytes = align_up((n_clouds + 1) * sizeof(uint32_t), 16);
-    const size_t items_bytes = items.size() * sizeof(RiftBatchItem);
-    const size_t pts_at = gd_bytes + bases_bytes + items_bytes, rgb_at = pts_at + total * sizeof(float4);
-    const size_t up_bytes = rgb_at + total * sizeof(uint32_t);
-    PCC_TRY(b->up.reserve(up_bytes));
-    PCC_TRY(b->dev.reserve(up_bytes));
+    static_assert(sizeof(GridDev) == 112, "tests/cpp/test_cloud_batch.cpp records this upload's offsets for a header of 112 bytes");
+    const ConcatLayout up(sizeof(GridDev), 128, n_clouds, items.size(), total);
+    PCC_TRY(b->up.reserve(up.bytes));
+    PCC_TRY(b->dev.reserve(up.bytes));
     char* u = b->up.as<char>();
+    up.fill(u, batch, bases, items, false);
     // (the consumers read nothing of the grid but n_valid: every point of the concatenation is taken, in its order -- the
     // non-finite ones have empty rows and end as the points outside cloud2 do)
-    memset(u, 0, gd_bytes);
     reinterpret_cast<GridDev*>(u)->n_valid = (unsigned int)total;
-    memcpy(u + gd_bytes, bases.data(), (n_clouds + 1) * sizeof(uint32_t));
-    memcpy(u + gd_bytes + bases_bytes, items.data(), items_bytes);
-    float* p4 = reinterpret_cast<float*>(u + pts_at);
-    uint32_t* words = reinterpret_cast<uint32_t*>(u + rgb_at);
-    for (size_t c = 0; c < n_clouds; ++c) {
-        const char* src = static_cast<const char*>(pts[c]);
-        const char* col = static_cast<const char*>(rgb[c]);
-        for (size_t i = 0; i < n[c]; ++i) {
-            const size_t at = bases[c] + i;
-            const uint32_t w = (uint32_t)at;
-            memcpy(p4 + at * 4, src + i * stride, 12);
-            memcpy(p4 + at * 4 + 3, &w, 4);
-            memcpy(words + at, col + i * rgb_stride, 4);
-        }
-    }
-    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
+    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up.bytes, hipMemcpyHostToDevice, s));
     const char* d = b->dev.as<char>();
     const GridDev* gd = reinterpret_cast<const GridDev*>(d);
-    const unsigned int* d_bases = reinterpret_cast<const unsigned int*>(d + gd_bytes);
-    const RiftBatchItem* d_items = reinterpret_cast<const RiftBatchItem*>(d + gd_bytes + bases_bytes);
-    const float4* d_pts = reinterpret_cast<const float4*>(d + pts_at);
-    const unsigned char* d_rgb = reinterpret_cast<const unsigned char*>(d + rgb_at);
+    const unsigned int* d_bases = reinterpret_cast<const unsigned int*>(d + up.bases_at);
+    const RiftBatchItem* d_items = reinterpret_cast<const RiftBatchItem*>(d + up.items_at);
+    const float4* d_pts = reinterpret_cast<const float4*>(d + up.pts_at);
+    const unsigned char* d_rgb = reinterpret_cast<const unsigned char*>(d + up.rgb_at);
 
     // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
     const unsigned int n_items = (unsigned int)items.size();
@@ -233,52 +208,31 @@ static int rift_batch_brute(pcc_index* ix, size_t n_clouds, const void* const* p
     return PCC_OK;
 }
 
-static bool any_finite(const void* pts, size_t n, size_t stride) {
-    const char* p = static_cast<const char*>(pts);
-    for (size_t i = 0; i < n; ++i) {
-        float v[3];
-        memcpy(v, p + i * stride, 12);
-        if ((v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f) return true;
-    }
-    return false;
-}
-
-int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                           size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius, float* out_hist,
-                           int32_t* out_index, size_t* out_offsets) {
+int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
+                           float* out_hist, int32_t* out_index, size_t* out_offsets) {
     if (!ix->rift_batch) ix->rift_batch = new RiftBatchScratch();
     RiftBatchScratch* b = ix->rift_batch;
-    const size_t brute_max = (size_t)ix->opt.rift_batch_brute_max;
-    size_t n_brute = 0, n_large = 0;
-    for (size_t c = 0; c < n_clouds; ++c) (n[c] > brute_max ? n_large : n_brute) += n[c];
-    ix->stats[0] = n_brute;
-    ix->stats[1] = n_large;
+    const size_t n_clouds = batch.n_clouds, brute_max = (size_t)ix->opt.rift_batch_brute_max;
+    const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
+    ix->stats[0] = routes.n_brute;
+    ix->stats[1] = routes.n_large;
     ix->stats_pending = false;
-    if (n_large == 0)
-        return rift_batch_brute(ix, n_clouds, pts, n, stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius, out_hist, out_index,
-                                out_offsets);
+    if (routes.n_large == 0) return rift_batch_brute(ix, batch, normal_radius, gradient_radius, rift_radius, out_hist, out_index, out_offsets);
 
     // ---- some clouds are above the limit: the others as a batch into arrays of their own, these one by one, then the splice --
-    std::vector<size_t> small_n(n, n + n_clouds), small_off(n_clouds + 1, 0);
-    for (size_t c = 0; c < n_clouds; ++c)
-        if (n[c] > brute_max) small_n[c] = 0;  // (an empty cloud of the batch: its slice stays empty)
-    std::vector<float> small_hist(std::max<size_t>(n_brute, 1) * RIFT_BINS);
-    std::vector<int32_t> small_index(std::max<size_t>(n_brute, 1));
-    PCC_TRY(rift_batch_brute(ix, n_clouds, pts, small_n.data(), stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius,
-                             small_hist.data(), small_index.data(), small_off.data()));
-    if (!b->work) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &b->work));
-    pcc_index* w = b->work;
-    // the work handle's launches join the caller's queue for the length of this call, under the caller's options
-    struct Borrow {
-        pcc_index* w;
-        ~Borrow() { w->stream = w->own_stream; }
-    } borrow{w};
-    w->stream = ix->stream;
-    w->opt = ix->opt;
+    CloudBatch small = batch;
+    small.n = routes.small_n.data();
+    std::vector<size_t> small_off(n_clouds + 1, 0);
+    std::vector<float> small_hist(std::max<size_t>(routes.n_brute, 1) * RIFT_BINS);
+    std::vector<int32_t> small_index(std::max<size_t>(routes.n_brute, 1));
+    PCC_TRY(rift_batch_brute(ix, small, normal_radius, gradient_radius, rift_radius, small_hist.data(), small_index.data(), small_off.data()));
+    WorkLease lease;
+    PCC_TRY(lease.take(ix, &b->work, true));
+    pcc_index* w = lease.w;
     size_t at = 0;
     for (size_t c = 0; c < n_clouds; ++c) {
         out_offsets[c] = at;
-        if (n[c] <= brute_max) {
+        if (batch.n[c] <= brute_max) {
             const size_t m = small_off[c + 1] - small_off[c];
             if (m) {
                 memcpy(out_hist + at * RIFT_BINS, small_hist.data() + small_off[c] * RIFT_BINS, m * RIFT_BINS * sizeof(float));
@@ -287,11 +241,11 @@ int rift_descriptors_batch(pcc_index* ix, size_t n_clouds, const void* const* pt
             at += m;
             continue;
         }
-        if (!any_finite(pts[c], n[c], stride)) continue;  // (the single path answers PCC_ERR_EMPTY there)
+        if (!cloud_any_finite(batch.pts[c], batch.n[c], batch.stride)) continue;  // (the single path answers PCC_ERR_EMPTY there)
         size_t m = 0;
-        PCC_TRY(pcc_index_set_input(w, pts[c], n[c], stride, 3, PCC_MEM_HOST));
-        PCC_TRY(pcc_rift_descriptors(w, rgb[c], rgb_stride, PCC_MEM_HOST, normal_radius, gradient_radius, rift_radius, RIFT_D_BINS, RIFT_G_BINS,
-                                     out_hist + at * RIFT_BINS, out_index + at, &m));
+        PCC_TRY(pcc_index_set_input(w, batch.pts[c], batch.n[c], batch.stride, 3, PCC_MEM_HOST));
+        PCC_TRY(pcc_rift_descriptors(w, batch.rgb[c], batch.rgb_stride, PCC_MEM_HOST, normal_radius, gradient_radius, rift_radius, RIFT_D_BINS,
+                                     RIFT_G_BINS, out_hist + at * RIFT_BINS, out_index + at, &m));
         at += m;
     }
     out_offsets[n_clouds] = at;
@@ -309,9 +263,8 @@ int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* cons
                                int nr_distance_bins, int nr_gradient_bins, float* out_hist, int32_t* out_index, size_t* out_offsets) {
     using namespace pcc;
     // the arguments first: all of it host arithmetic, refused before the handle or any device is looked at
-    PCC_TRY(check_mem(mem));
-    if (mem != PCC_MEM_HOST) { set_error("pcc_rift_descriptors_batch takes host arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(check_points(nullptr, 0, stride, mem));  // (the stride alone)
+    const CloudBatch batch{n_clouds, pts, n, stride, rgb, rgb_stride};
+    PCC_TRY(check_cloud_batch("pcc_rift_descriptors_batch", batch, mem));
     if (rgb_stride < 4 || rgb_stride % 4) {
         set_error("colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
@@ -319,30 +272,14 @@ int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* cons
     if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
     if (n_clouds >= (1ull << 31)) { set_error("more than 2^31 clouds"); return PCC_ERR_UNSUPPORTED; }
     if (n_clouds && (!pts || !n || !rgb || !out_hist || !out_index)) { set_error("null array argument"); return PCC_ERR_INVALID; }
-    for (double r : {normal_radius, gradient_radius, rift_radius})
-        if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
-    if (nr_distance_bins != RIFT_D_BINS || nr_gradient_bins != RIFT_G_BINS) {
-        set_error("RIFT with %d x %d bins: only %d distance x %d gradient bins are built", nr_distance_bins, nr_gradient_bins, RIFT_D_BINS, RIFT_G_BINS);
-        return PCC_ERR_UNSUPPORTED;
-    }
-    size_t total = 0;
-    for (size_t c = 0; c < n_clouds; ++c) {
-        PCC_TRY(check_points(pts[c], n[c], stride, mem));
-        if (n[c] && !rgb[c]) { set_error("null colour pointer"); return PCC_ERR_INVALID; }
-        if (n[c] && (reinterpret_cast<uintptr_t>(rgb[c]) % 4 || reinterpret_cast<uintptr_t>(pts[c]) % 4)) {
-            set_error("points and colour words must be 4-byte aligned, stride %zu a multiple of 4 and >= 4", rgb_stride);
-            return PCC_ERR_INVALID;
-        }
-        total += n[c];
-        if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
-    }
+    PCC_TRY(check_rift_params(normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins));
+    PCC_TRY(check_batch_clouds(batch, mem));
     if (n_clouds == 0) { out_offsets[0] = 0; return PCC_OK; }  // (no device is touched: not even the handle's)
     PCC_ENTER(ctx);
     ev_next(ctx);
     ev_mark(ctx, EV_CALL0);
     if (!ctx->rift) ctx->rift = new RiftScratch();
-    const int st = rift_descriptors_batch(ctx, n_clouds, pts, n, stride, rgb, rgb_stride, normal_radius, gradient_radius, rift_radius, out_hist,
-                                          out_index, out_offsets);
+    const int st = rift_descriptors_batch(ctx, batch, normal_radius, gradient_radius, rift_radius, out_hist, out_index, out_offsets);
     ev_mark(ctx, EV_CALL1);
     return st;
 }

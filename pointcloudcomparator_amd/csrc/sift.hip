@@ -262,14 +262,10 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
     hipStream_t s = ix->stream;
     SiftScratch* r = ix->sift;
     *n_out = 0;
-    if (!r->work) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &r->work));
-    pcc_index* w = r->work;
-    // the work handle's launches join the caller's queue for the length of this call
-    struct Borrow {
-        pcc_index* w;
-        ~Borrow() { w->stream = w->own_stream; }
-    } borrow{w};
-    w->stream = s;
+    // the work handle's launches join the caller's queue for the length of this call (under options of its own)
+    WorkLease lease;
+    PCC_TRY(lease.take(ix, &r->work, false));
+    pcc_index* w = lease.w;
     PCC_TRY(r->cloud[0].reserve(n * sizeof(SiftRec)));
     PCC_TRY(r->cloud[1].reserve(n * sizeof(SiftRec)));
     // (a float doubles fewer than 300 times before it is +inf: the 25-point gate has ended the loop long before)
@@ -329,6 +325,18 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
     return PCC_OK;
 }
 
+int check_sift_params(float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast) {
+    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
+    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
+    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
+    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
+        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
+                  SIFT_MAX_SCALES_PER_OCTAVE);
+        return PCC_ERR_UNSUPPORTED;
+    }
+    return PCC_OK;
+}
+
 }  // namespace pcc
 
 using namespace pcc;
@@ -343,14 +351,7 @@ int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, 
         set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
     }
-    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
-    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
-    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
-    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
-        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
-                  SIFT_MAX_SCALES_PER_OCTAVE);
-        return PCC_ERR_UNSUPPORTED;
-    }
+    PCC_TRY(check_sift_params(min_scale, nr_octaves, nr_scales_per_octave, min_contrast));
     PCC_ENTER(ix);
     *n_out = 0;
     if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }

@@ -27,7 +27,8 @@
 // copy brings both down and the host splices them into (cloud, octave, point, scale) order.
 //
 // Clouds above PCC_OPT_SIFT_BATCH_BRUTE_MAX points would make the quadratic builders the bottleneck: they take the single path
-// inside the same call, one by one, on a work handle kept in ctx, and their slices are spliced in.
+// inside the same call, one by one, on a work handle kept in ctx, and their slices are spliced in.  The host scaffold (route
+// split, lease, shared argument checks) is cloud_batch.hpp's and entry.hpp's: DESIGN.md 4.16; the 32-byte record pack is this file's.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -43,8 +44,6 @@ namespace {
 
 constexpr unsigned int SB_MAX_CELLS = 1u << 26;   // voxel.hip's limit
 constexpr unsigned int SB_NO_VOXEL = 0xffffffffu;  // the voxel of a non-finite point: behind every voxel of its cloud
-
-__device__ __forceinline__ bool sb_finite(float x, float y, float z) { return (x - x) == 0.0f && (y - y) == 0.0f && (z - z) == 0.0f; }
 
 // ---- 1. segmented voxel grid ---------------------------------------------------------------------------------------------
 // A workgroup per cloud: bounding box of the finite points -> the lattice (voxel.hip:101-112: min_b = floor(lo * inv), dim =
@@ -63,7 +62,7 @@ k_sb_voxel_keys(const unsigned int* __restrict__ bases, const SiftRec* __restric
     float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
     for (unsigned int i = threadIdx.x; i < n; i += 256) {
         const SiftRec p = in[base + i];
-        if (!sb_finite(p.x, p.y, p.z)) continue;
+        if (!finite3(p.x, p.y, p.z)) continue;
         lo[0] = fminf(lo[0], p.x); lo[1] = fminf(lo[1], p.y); lo[2] = fminf(lo[2], p.z);
         hi[0] = fmaxf(hi[0], p.x); hi[1] = fmaxf(hi[1], p.y); hi[2] = fmaxf(hi[2], p.z);
     }
@@ -101,7 +100,7 @@ k_sb_voxel_keys(const unsigned int* __restrict__ bases, const SiftRec* __restric
     for (unsigned int i = threadIdx.x; i < n; i += 256) {
         const SiftRec p = in[base + i];
         unsigned int v = SB_NO_VOXEL;
-        if (d0 > 0 && sb_finite(p.x, p.y, p.z)) {
+        if (d0 > 0 && finite3(p.x, p.y, p.z)) {
             // (grid_device.hpp's voxel_id, the lattice in registers)
             const int i0 = min(max((int)(floorf(p.x * inv) - o0), 0), d0 - 1);
             const int i1 = min(max((int)(floorf(p.y * inv) - o1), 0), d1 - 1);
@@ -277,31 +276,12 @@ k_sb_snap(const float4* __restrict__ kp, const unsigned int* __restrict__ kp_clo
     }
 }
 
-size_t align_up(size_t b, size_t a) { return (b + a - 1) / a * a; }
 unsigned int blocks_for(size_t n) { return (unsigned int)std::min<size_t>((n + 255) / 256, 2048); }
-
-// bases + bases64 + items of a round, laid out for one copy
-struct TableLayout {
-    size_t bases_at, bases64_at, items_at, bytes;
-    TableLayout(size_t n_clouds, size_t n_items, size_t at0 = 0) {
-        bases64_at = align_up(at0, 16);
-        bases_at = bases64_at + (n_clouds + 1) * sizeof(int64_t);
-        items_at = align_up(bases_at + (n_clouds + 1) * sizeof(uint32_t), 16);
-        bytes = align_up(items_at + n_items * sizeof(RiftBatchItem), 16);
-    }
-    void fill(char* u, const SiftBatchRound& r) const {
-        memcpy(u + bases64_at, r.bases64.data(), r.bases64.size() * sizeof(int64_t));
-        memcpy(u + bases_at, r.bases.data(), r.bases.size() * sizeof(uint32_t));
-        if (!r.items.empty()) memcpy(u + items_at, r.items.data(), r.items.size() * sizeof(RiftBatchItem));
-    }
-};
 
 }  // namespace
 
-struct SiftBatchScratch {
-    pcc_index* work = nullptr;   // the handle clouds above the brute limit go through (the caller's stream, scratch of its own)
-    HostBuf up, down;            // pinned: octaves + table + records going up (then every round's table); sizes, counts, keypoints coming down
-    DevBuf init;                 // the first upload on the device: SiftOctave per octave, the first table, the original records (the snap reads them)
+// (up: octaves + table + records, then every round's table; down: sizes, counts, keypoints; dev: the first upload, whose records the snap reads)
+struct SiftBatchScratch : BatchStaging {
     DevBuf table[2];             // the tables of the later rounds, in turn
     DevBuf cloud[2], pts4;       // octave concatenations as records (the voxel stage reads one, writes the other); the current one as float4
     DevBuf vkeys, cloud_of;      // voxel keys u64[n]; the cloud of every position uint32[n]
@@ -310,17 +290,14 @@ struct SiftBatchScratch {
     DevBuf offs, keys;           // the CSR of the round's radius rows
     DevBuf nbr;                  // int32[n][25]
     DevBuf kp_cloud, snap;       // per keypoint: its cloud; the snapped index
+    ~SiftBatchScratch() {
+        for (DevBuf* d : {&table[0], &table[1], &cloud[0], &cloud[1], &pts4, &vkeys, &cloud_of, &flags, &scan_tmp, &words, &offs, &keys, &nbr, &kp_cloud, &snap})
+            d->release();
+    }
 };
 
 void sift_batch_release(pcc_index* ix) {
-    if (!ix->sift_batch) return;
-    SiftBatchScratch* b = ix->sift_batch;
-    if (b->work) (void)pcc_index_destroy(b->work);
-    b->up.release(); b->down.release();
-    DevBuf* bufs[] = {&b->init, &b->table[0], &b->table[1], &b->cloud[0], &b->cloud[1], &b->pts4, &b->vkeys, &b->cloud_of, &b->flags, &b->scan_tmp,
-                      &b->words, &b->offs, &b->keys, &b->nbr, &b->kp_cloud, &b->snap};
-    for (DevBuf* d : bufs) d->release();
-    delete b;
+    delete ix->sift_batch;
     ix->sift_batch = nullptr;
 }
 
@@ -337,14 +314,15 @@ struct BatchResult {
     unsigned int rounds = 0;
 };
 
-// the clouds of sizes n[] (0: not part of the batch) through the octave rounds
-int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                      size_t rgb_stride, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, BatchResult* res) {
+// the clouds of sizes batch.n[] (0: not part of the batch) through the octave rounds
+int sift_batch_rounds(pcc_index* ix, const CloudBatch& batch, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
+                      BatchResult* res) {
     hipStream_t s = ix->stream;
+    const size_t n_clouds = batch.n_clouds;
     SiftBatchScratch* b = ix->sift_batch;
     SiftScratch* r = ix->sift;
     SiftBatchRound cur, next;
-    sift_batch_round(n, n_clouds, 0, &cur);
+    sift_batch_round(batch.n, n_clouds, 0, &cur);
     res->bases0 = cur.bases;
     if (cur.total == 0) return PCC_OK;
     // (a float doubles fewer than 300 times before it is +inf: the 25-point gate has ended every cloud long before)
@@ -355,7 +333,7 @@ int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const void* const* pts, co
     const TableLayout t0(n_clouds, 0, oct_bytes);  // (the first round needs no items: the voxel stage works by cloud)
     const size_t rec_at = align_up(t0.bytes, 32), up_bytes = rec_at + cur.total * sizeof(SiftRec);
     PCC_TRY(b->up.reserve(up_bytes));
-    PCC_TRY(b->init.reserve(up_bytes));
+    PCC_TRY(b->dev.reserve(up_bytes));
     char* u = b->up.as<char>();
     std::vector<SiftOctave> h_octaves((size_t)nr_octaves);
     {
@@ -368,18 +346,18 @@ int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const void* const* pts, co
     SiftRec* rec = reinterpret_cast<SiftRec*>(u + rec_at);
     for (size_t c = 0; c < n_clouds; ++c) {
         if (!cur.n[c]) continue;
-        const char* src = static_cast<const char*>(pts[c]);
-        const char* col = static_cast<const char*>(rgb[c]);
+        const char* src = static_cast<const char*>(batch.pts[c]);
+        const char* col = static_cast<const char*>(batch.rgb[c]);
         for (size_t i = 0; i < cur.n[c]; ++i) {
             SiftRec& p = rec[cur.bases[c] + i];
-            memcpy(&p.x, src + i * stride, 12);
+            memcpy(&p.x, src + i * batch.stride, 12);
             p.w = 1.0f;
-            memcpy(&p.rgb, col + i * rgb_stride, 4);
+            memcpy(&p.rgb, col + i * batch.rgb_stride, 4);
             p.pad[0] = p.pad[1] = p.pad[2] = 0u;
         }
     }
-    PCC_HIP(hipMemcpyAsync(b->init.p, u, up_bytes, hipMemcpyHostToDevice, s));
-    const char* d0 = b->init.as<char>();
+    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
+    const char* d0 = b->dev.as<char>();
     const SiftOctave* d_octaves = reinterpret_cast<const SiftOctave*>(d0);
     res->d_bases0 = reinterpret_cast<const unsigned int*>(d0 + t0.bases_at);
     res->d_rec0 = reinterpret_cast<const SiftRec*>(d0 + rec_at);
@@ -474,14 +452,15 @@ int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const void* const* pts, co
     return PCC_OK;
 }
 
-// the single path for one cloud above the brute limit, on the work handle: its keypoints into kp (host)
-int sift_single(pcc_index* w, const void* pts, size_t n, size_t stride, const void* rgb, size_t rgb_stride, float min_scale, int nr_octaves,
-                int nr_scales_per_octave, float min_contrast, std::vector<float>* kp) {
+// the single path for cloud c, which is above the brute limit, on the work handle: its keypoints into kp (host)
+int sift_single(pcc_index* w, const CloudBatch& batch, size_t c, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
+                std::vector<float>* kp) {
+    const size_t n = batch.n[c], stride = batch.stride, rgb_stride = batch.rgb_stride;
     if (!w->sift) w->sift = new SiftScratch();
     entered(w);
     const unsigned char *dpts = nullptr, *drgb = nullptr;
-    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(pts), (n - 1) * stride + 12, PCC_MEM_HOST, w->sift->pts, &dpts));
-    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, PCC_MEM_HOST, w->sift->rgb, &drgb));
+    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.pts[c]), (n - 1) * stride + 12, PCC_MEM_HOST, w->sift->pts, &dpts));
+    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.rgb[c]), (n - 1) * rgb_stride + 4, PCC_MEM_HOST, w->sift->rgb, &drgb));
     size_t found = 0;
     PCC_TRY(sift_keypoints(w, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
     kp->resize(found * 4);
@@ -495,46 +474,33 @@ int sift_single(pcc_index* w, const void* pts, size_t n, size_t stride, const vo
 }  // namespace
 
 // pcc_sift_keypoints_batch behind its argument checks (every out array on the host; out_snap nullable)
-int sift_keypoints_batch(pcc_index* ix, size_t n_clouds, const void* const* pts, const size_t* n, size_t stride, const void* const* rgb,
-                         size_t rgb_stride, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, double snap_radius,
-                         float* out_kp, int32_t* out_snap, size_t capacity, size_t* out_offsets) {
+int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
+                         double snap_radius, float* out_kp, int32_t* out_snap, size_t capacity, size_t* out_offsets) {
     hipStream_t s = ix->stream;
+    const size_t n_clouds = batch.n_clouds;
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
     if (!ix->sift_batch) ix->sift_batch = new SiftBatchScratch();
     if (!ix->sift) ix->sift = new SiftScratch();
     SiftBatchScratch* b = ix->sift_batch;
     const size_t brute_max = (size_t)ix->opt.sift_batch_brute_max;
-    std::vector<size_t> small_n(n, n + n_clouds);
-    size_t n_brute = 0, n_large = 0;
-    for (size_t c = 0; c < n_clouds; ++c) {
-        (n[c] > brute_max ? n_large : n_brute) += n[c];
-        if (n[c] > brute_max) small_n[c] = 0;  // (an empty cloud of the batch: its slice comes from the work handle)
-    }
+    const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
+    CloudBatch small = batch;
+    small.n = routes.small_n.data();
     BatchResult res;
-    PCC_TRY(sift_batch_rounds(ix, n_clouds, pts, small_n.data(), stride, rgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast,
-                              &res));
-    ix->stats[0] = n_brute;
-    ix->stats[1] = n_large;
+    PCC_TRY(sift_batch_rounds(ix, small, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &res));
+    ix->stats[0] = routes.n_brute;
+    ix->stats[1] = routes.n_large;
     ix->stats[2] = res.rounds;
     ix->stats_pending = false;
 
     // ---- clouds above the limit: one by one on the work handle ----------------------------------------------------------------
     std::vector<std::vector<float>> large_kp(n_clouds);
-    pcc_index* w = nullptr;
-    struct Borrow {
-        pcc_index* w = nullptr;
-        ~Borrow() { if (w) w->stream = w->own_stream; }
-    } borrow;
-    if (n_large) {
-        if (!b->work) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &b->work));
-        w = b->work;
-        // the work handle's launches join the caller's queue for the length of this call, under the caller's options
-        borrow.w = w;
-        w->stream = s;
-        w->opt = ix->opt;
+    WorkLease lease;
+    if (routes.n_large) {
+        PCC_TRY(lease.take(ix, &b->work, true));
         for (size_t c = 0; c < n_clouds; ++c)
-            if (n[c] > brute_max)
-                PCC_TRY(sift_single(w, pts[c], n[c], stride, rgb[c], rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &large_kp[c]));
+            if (batch.n[c] > brute_max)
+                PCC_TRY(sift_single(lease.w, batch, c, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &large_kp[c]));
     }
 
     // ---- the slices: (cloud, octave, point, scale) ----------------------------------------------------------------------------
@@ -588,8 +554,8 @@ int sift_keypoints_batch(pcc_index* ix, size_t n_clouds, const void* const* pts,
         if (!m) continue;
         memcpy(out_kp + out_offsets[c] * 4, large_kp[c].data(), m * 4 * sizeof(float));
         if (out_snap) {
-            PCC_TRY(pcc_index_set_input(w, pts[c], n[c], stride, 3, PCC_MEM_HOST));
-            PCC_TRY(pcc_first_within(w, large_kp[c].data(), m, 4 * sizeof(float), PCC_MEM_HOST, snap_radius, out_snap + out_offsets[c]));
+            PCC_TRY(pcc_index_set_input(lease.w, batch.pts[c], batch.n[c], batch.stride, 3, PCC_MEM_HOST));
+            PCC_TRY(pcc_first_within(lease.w, large_kp[c].data(), m, 4 * sizeof(float), PCC_MEM_HOST, snap_radius, out_snap + out_offsets[c]));
         }
     }
     return PCC_OK;
@@ -604,9 +570,8 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
                              double snap_radius, float* out_keypoints, int32_t* out_snap_index, size_t capacity, size_t* out_offsets) {
     using namespace pcc;
     // the arguments first: all of it host arithmetic, refused before the handle or any device is looked at
-    PCC_TRY(check_mem(mem));
-    if (mem != PCC_MEM_HOST) { set_error("pcc_sift_keypoints_batch takes host arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
-    PCC_TRY(check_points(nullptr, 0, stride, mem));  // (the stride alone)
+    const CloudBatch batch{n_clouds, pts, n, stride, rgb, rgb_stride};
+    PCC_TRY(check_cloud_batch("pcc_sift_keypoints_batch", batch, mem));
     if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
     if (n_clouds >= (1ull << 31)) { set_error("more than 2^31 clouds"); return PCC_ERR_UNSUPPORTED; }
     if ((n_clouds && (!pts || !n || !rgb)) || (capacity && !out_keypoints)) { set_error("null argument"); return PCC_ERR_INVALID; }
@@ -614,26 +579,9 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
         set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
         return PCC_ERR_INVALID;
     }
-    if (!(min_scale > 0.f) || !std::isfinite(min_scale)) { set_error("min_scale must be positive and finite"); return PCC_ERR_INVALID; }
-    if (!(min_contrast >= 0.f)) { set_error("min_contrast must not be negative"); return PCC_ERR_INVALID; }
-    if (nr_octaves < 1) { set_error("nr_octaves %d: at least one octave", nr_octaves); return PCC_ERR_INVALID; }
-    if (nr_scales_per_octave < SIFT_MIN_SCALES_PER_OCTAVE || nr_scales_per_octave > SIFT_MAX_SCALES_PER_OCTAVE) {
-        set_error("SIFT with %d scales per octave: %d to %d scales per octave are built", nr_scales_per_octave, SIFT_MIN_SCALES_PER_OCTAVE,
-                  SIFT_MAX_SCALES_PER_OCTAVE);
-        return PCC_ERR_UNSUPPORTED;
-    }
+    PCC_TRY(check_sift_params(min_scale, nr_octaves, nr_scales_per_octave, min_contrast));
     if (out_snap_index && (!(snap_radius > 0) || !std::isfinite(snap_radius))) { set_error("bad radius"); return PCC_ERR_INVALID; }
-    size_t total = 0;
-    for (size_t c = 0; c < n_clouds; ++c) {
-        PCC_TRY(check_points(pts[c], n[c], stride, mem));
-        if (n[c] && !rgb[c]) { set_error("null colour pointer"); return PCC_ERR_INVALID; }
-        if (n[c] && (reinterpret_cast<uintptr_t>(rgb[c]) % 4 || reinterpret_cast<uintptr_t>(pts[c]) % 4)) {
-            set_error("points, colour words and keypoints must be 4-byte aligned, the colour stride %zu a multiple of 4 and >= 4", rgb_stride);
-            return PCC_ERR_INVALID;
-        }
-        total += n[c];
-        if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
-    }
+    PCC_TRY(check_batch_clouds(batch, mem));
     // the first octave's lattice of every cloud (voxel.hip:101-112 on the host; the later octaves' leaves are larger)
     const float inv = 1.0f / min_scale;
     for (size_t c = 0; c < n_clouds; ++c) {
@@ -643,7 +591,7 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
         for (size_t i = 0; i < n[c]; ++i) {
             float v[3];
             memcpy(v, p + i * stride, 12);
-            if (!((v[0] - v[0]) == 0.0f && (v[1] - v[1]) == 0.0f && (v[2] - v[2]) == 0.0f)) continue;
+            if (!finite3(v[0], v[1], v[2])) continue;
             any = true;
             for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
         }
@@ -659,8 +607,8 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
     PCC_ENTER(ctx);
     ev_next(ctx);
     ev_mark(ctx, EV_CALL0);
-    const int st = sift_keypoints_batch(ctx, n_clouds, pts, n, stride, rgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast,
-                                        snap_radius, out_keypoints, out_snap_index, capacity, out_offsets);
+    const int st = sift_keypoints_batch(ctx, batch, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, snap_radius, out_keypoints,
+                                        out_snap_index, capacity, out_offsets);
     ev_mark(ctx, EV_CALL1);
     return st;
 }

@@ -13,7 +13,7 @@
 #include <stdint.h>
 #include <vector>
 
-#include "rift_batch_plan.hpp"
+#include "cloud_batch.hpp"
 
 namespace pcc {
 
@@ -36,6 +36,22 @@ inline void sift_batch_round(const Size* sizes, size_t n_clouds, size_t min_poin
     r->bases64.assign(r->bases.begin(), r->bases.end());
     r->total = r->bases[n_clouds];
 }
+
+// bases + bases64 + items of a round, laid out for one copy behind at0 bytes of the caller's
+struct TableLayout {
+    size_t bases_at, bases64_at, items_at, bytes;
+    TableLayout(size_t n_clouds, size_t n_items, size_t at0 = 0) {
+        bases64_at = align_up(at0, 16);
+        bases_at = bases64_at + (n_clouds + 1) * sizeof(int64_t);
+        items_at = align_up(bases_at + (n_clouds + 1) * sizeof(uint32_t), 16);
+        bytes = align_up(items_at + n_items * sizeof(RiftBatchItem), 16);
+    }
+    void fill(char* u, const SiftBatchRound& r) const {
+        memcpy(u + bases64_at, r.bases64.data(), r.bases64.size() * sizeof(int64_t));
+        memcpy(u + bases_at, r.bases.data(), r.bases.size() * sizeof(uint32_t));
+        if (!r.items.empty()) memcpy(u + items_at, r.items.data(), r.items.size() * sizeof(RiftBatchItem));
+    }
+};
 
 // one copy of the splice: `count` keypoints from row `src` of the round-major buffer to row `dst` of the caller's array
 struct SiftBatchCopy {

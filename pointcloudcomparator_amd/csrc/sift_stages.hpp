@@ -16,6 +16,8 @@ struct SiftRec {
 };
 static_assert(sizeof(SiftRec) == 32, "SiftRec layout");
 
+// the four detector parameters as pcc_sift_keypoints and its batch form check them (sift.hip)
+int check_sift_params(float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast);
 // ix->sift->inten[i] = intensity of record i
 int sift_intensity_stage(pcc_index* ix, const SiftRec* cloud, size_t n);
 // ix->sift->resp[i][s]: the Gaussian responses over the sorted radius rows (keys / offsets), either PCC_OPT_SIFT_LAYOUT
