@@ -47,6 +47,8 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --rgb-batch (the same for the clusters of ALL accepted matches in one pcc_region_growing_rgb_batch call: same report)
 static int n_gpus = 1, descriptor_dims = 3;
 static bool rgb_device = false, rgb_batch = false;
+// --planes-device (with -e): the plane-removal loop runs in one library call (pcc_plane_removal through removePlanes): same lines
+static bool planes_device = false;
 static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
@@ -78,6 +80,9 @@ static void printUsage() {
               << "                   the GPU (pcc_region_growing_rgb), instead of on the host over downloaded rows: the same report\n"
               << "--rgb-batch        (this build) the colour segmentations of ALL accepted matches run in one library call\n"
               << "                   (pcc_region_growing_rgb_batch) before the match sections are written: the same report\n"
+              << "--planes-device    (this build, with -e) the plane-removal loop in front of the clustering runs in ONE library call\n"
+              << "                   (pcc_plane_removal: the cloud uploaded once, compacted on the GPU) instead of one call and one\n"
+              << "                   host compaction per plane: the same lines, the same clusters\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
@@ -100,6 +105,13 @@ static std::vector<PointCloud<PointXYZRGB>::Ptr> euclidean_cluster_segmentation(
     seg.setMaxIterations(100);
     seg.setDistanceThreshold(0.02);
     const int nr_points = (int)cloud_filtered->points.size();
+    if (planes_device) {
+        RemovedPlanes planes;
+        cloud_filtered = removePlanes<PointXYZRGB>(cloud_filtered, planes, 0.3, 100, 0.02, true);
+        for (std::uint32_t size : planes.sizes)
+            std::cout << "PointCloud representing the planar component: " << size << " data points." << std::endl;
+        if (planes.ended_without_model) std::cout << "Could not estimate a planar model for the given dataset." << std::endl;
+    } else
     while (cloud_filtered->points.size() > 0.3 * nr_points) {
         seg.setInputCloud(cloud_filtered);
         seg.segment(*inliers, coefficients);
@@ -383,6 +395,7 @@ int main(int argc, char** argv) {
         else if (a == "--descriptor-dims" && i + 1 < argc) descriptor_dims = std::atoi(argv[++i]);
         else if (a == "--rgb-device") rgb_device = true;
         else if (a == "--rgb-batch") rgb_batch = true;
+        else if (a == "--planes-device") planes_device = true;
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }

@@ -6,6 +6,7 @@
 //   IterativeClosestPoint           the PCL object performICP drives (:1091-1099)
 //   StatisticalOutlierRemoval       the -n noise pass (:1520-1549)
 //   EuclideanClusterExtraction      the -e path (src/segmentation.cpp:119-131)
+//   removePlanes                    the plane-removal loop in front of it (src/segmentation.cpp:79-117) as one call
 // Everything numerical happens behind the C-ABI; this header is plumbing a maintainer of the
 // reference can include instead of the PCL headers for these five call sites.
 #pragma once
@@ -424,5 +425,51 @@ private:
     std::shared_ptr<const PointIndices> indices_;
     bool negative_ = false;
 };
+
+// ---- the whole plane-removal loop (src/segmentation.cpp:79-117) in one library call ---------------------
+// What the SACSegmentation::segment + ExtractIndices loop leaves: the remaining cloud (whole records, order kept) and, per
+// plane removed, its inlier count and coefficients.  pcc_plane_removal uploads the cloud once and compacts it on the device.
+struct RemovedPlanes {
+    std::vector<std::uint32_t> sizes;                 // |cloud_plane| of every turn (:110-111)
+    std::vector<std::array<float, 4> > coefficients;  // a, b, c, d of every turn
+    bool ended_without_model = false;                 // the loop ended at :95-100
+};
+template <class PointT>
+inline typename PointCloud<PointT>::Ptr removePlanes(const typename PointCloud<PointT>::ConstPtr& cloud, RemovedPlanes& planes,
+                                                     double stop_fraction = 0.3, int max_iterations = 100,
+                                                     double distance_threshold = 0.02, bool optimize = true,
+                                                     double probability = 0.99) {
+    typename PointCloud<PointT>::Ptr rest(new PointCloud<PointT>);
+    planes = RemovedPlanes();
+    if (!cloud || cloud->empty()) return rest;
+    const float one[3] = {0.f, 0.f, 0.f};  // any index handle supplies device, stream and scratch (SACSegmentation above)
+    pcc_index* ctx = nullptr;
+    check(pcc_index_create(one, 1, 12, 3, PCC_MEM_HOST, 0, PCC_ENGINE_BRUTE, &ctx));
+    struct Closer { pcc_index* h; ~Closer() { pcc_index_destroy(h); } } closer{ctx};
+    const size_t n = cloud->size();
+    rest->points.resize(n);
+    size_t capacity = 64, found = 0, left = 0;
+    int ended = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        planes.sizes.resize(capacity);
+        planes.coefficients.resize(capacity);
+        const int st = pcc_plane_removal(ctx, cloud->points.data(), n, sizeof(PointT), PCC_MEM_HOST, stop_fraction, max_iterations,
+                                         distance_threshold, probability, optimize ? 1 : 0, capacity, planes.coefficients[0].data(),
+                                         planes.sizes.data(), nullptr, &found, &ended, nullptr, nullptr, &left, rest->points.data(),
+                                         sizeof(PointT), sizeof(PointT));
+        // every plane removes at least one point: n planes always suffice
+        if (st == PCC_ERR_OVERFLOW && attempt == 0) { capacity = n; continue; }
+        check(st);
+        break;
+    }
+    planes.sizes.resize(found);
+    planes.coefficients.resize(found);
+    planes.ended_without_model = ended != 0;
+    rest->points.resize(left);
+    rest->width = (std::uint32_t)left;
+    rest->height = 1;
+    rest->is_dense = true;
+    return rest;
+}
 
 }  // namespace pcc

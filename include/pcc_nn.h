@@ -426,6 +426,45 @@ int pcc_sac_plane(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes
                   int max_iterations, double distance_threshold, double probability, int optimize,
                   int32_t *inliers, size_t *n_inliers, float coefficients[4], int *iterations);
 
+/* ---- the plane-removal loop around it, the cloud staged once -------------------------------------------
+ * replaces: the whole loop of src/segmentation.cpp:79-117 -- "segment the largest plane, extract its inliers, keep the
+ *   rest" until at most stop_fraction (0.3 there) of the input cloud remains.  The result is that of
+ *
+ *     cur = the n input points; p = 0
+ *     while ((double)|cur| > stop_fraction * (double)n) {                      (:91, the comparison in double)
+ *         (inliers, coeff, its) = pcc_sac_plane(cur, max_iterations, distance_threshold, probability, optimize)
+ *         if (|inliers| == 0) { *ended_without_model = 1; break; }             (:95-100)
+ *         plane p = (coeff, |inliers|, its); cur = cur without the inliers, order kept (ExtractIndices, negative); ++p
+ *     }
+ *
+ *   bit for bit: every turn is a fresh segment() (generator seeded again, sampling over the current cloud).  The cloud is
+ *   uploaded and packed once; a turn compacts it on the device and brings only what pcc_sac_plane brings to the host.
+ *   Non-finite points are never inliers: they stay in the cloud to the end, count in its size and can be drawn as samples.
+ * out_coefficients[max_planes][4], out_plane_sizes[max_planes], out_iterations[max_planes] (may be NULL), *n_planes,
+ *   *ended_without_model (may be NULL) and *n_remaining are HOST values.
+ * out_plane_of_point[n] (space `mem`, may be NULL): the turn that removed input point i, -1 if it remains.
+ * out_remaining_index[n] (space `mem`, may be NULL): the first *n_remaining entries are the input indices of the remaining
+ *   points, ascending.
+ * out_points (space `mem`, may be NULL; capacity n records of out_stride_bytes, not overlapping pts): for the j-th remaining
+ *   point the first record_bytes of its input record, verbatim, at out_points + j * out_stride_bytes -- what
+ *   pcc_index_set_input(..., *n_remaining, out_stride_bytes, mem) takes next.  record_bytes is a multiple of 4 with
+ *   12 <= record_bytes <= min(stride_bytes, out_stride_bytes), out_stride_bytes a multiple of 4; record_bytes must be
+ *   readable in every input record (32 for pcl::PointXYZRGB carries the colour word).
+ * max_planes: when the loop condition still holds after max_planes planes the call returns PCC_ERR_OVERFLOW with
+ *   *n_planes = max_planes, those planes in the host tables and *n_remaining = the points then left; the arrays in space
+ *   `mem` are unspecified.  0 is accepted when no turn runs (stop_fraction >= 1, n == 0).
+ * Refused before any device is touched, nothing written: what pcc_sac_plane refuses (same messages); stop_fraction negative
+ *   or not finite; a NULL n_planes or n_remaining; NULL out_coefficients or out_plane_sizes with max_planes > 0; a bad
+ *   record_bytes or out_stride_bytes with out_points given; a null handle last.
+ * `ctx` is any index handle (device, stream, scratch), as for pcc_sac_plane.  Afterwards pcc_index_stats reports in [0] the
+ *   planes removed and in [1] the turns that took a host copy of the current cloud (a degenerate sample, see sac.hip). */
+int pcc_plane_removal(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                      double stop_fraction, int max_iterations, double distance_threshold, double probability, int optimize,
+                      size_t max_planes, float *out_coefficients, uint32_t *out_plane_sizes, int *out_iterations,
+                      size_t *n_planes, int *ended_without_model, int32_t *out_plane_of_point,
+                      int32_t *out_remaining_index, size_t *n_remaining, void *out_points, size_t out_stride_bytes,
+                      size_t record_bytes);
+
 /* ---- normals + region growing (default segmentation path) --------------------------------------
  * pcc_normals replaces: pcl::NormalEstimation<PointXYZRGB, pcl::Normal> with setSearchMethod(tree),
  *   setKSearch(k), compute (src/segmentation.cpp:232-241, k = 50; viewpoint left at (0,0,0)).

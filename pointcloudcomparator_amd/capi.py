@@ -35,7 +35,7 @@ SYMBOLS = [
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
     "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
-    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_rigid_from_sums",
+    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
@@ -101,6 +101,8 @@ def _load() -> C.CDLL:
     lib.pcc_rigid_from_sums_about.argtypes = [vp, vp, vp]
     lib.pcc_icp_step_about.argtypes = [vp, vp, sz, sz, i32, vp, vp, vp, C.POINTER(C.c_double)]
     lib.pcc_sac_plane.argtypes = [vp, vp, sz, sz, i32, i32, C.c_double, C.c_double, i32, vp, C.POINTER(sz), vp, vp]
+    lib.pcc_plane_removal.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, C.c_double, C.c_double, i32, sz, vp, vp, vp, C.POINTER(sz),
+                                      C.POINTER(i32), vp, vp, C.POINTER(sz), vp, sz, sz]
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
@@ -658,6 +660,43 @@ class Index:
                                  int(optimize), pi, C.byref(cnt), coeff.ctypes.data, C.byref(its)))
         self._after(st)
         return inl[:cnt.value], coeff, its.value
+
+    def plane_removal(self, points, stop_fraction: float = 0.3, max_iterations: int = 100, threshold: float = 0.02,
+                      probability: float = 0.99, optimize: bool = True, max_planes: int = 64, with_points: bool = False,
+                      record_bytes: int | None = None):
+        """pcc_plane_removal: the reference's plane-removal loop (src/segmentation.cpp:79-117) with the cloud staged once.
+        points: (n, >= 3) float32 numpy array or torch tensor (a CUDA tensor gives CUDA index arrays and points).
+        Returns (remaining_index, plane_of_point, coefficients (p, 4), sizes (p,), iterations (p,), ended_without_model
+        [, points]): with_points adds the remaining points' records, the first record_bytes of each input row (default: the
+        whole row) as an (n_remaining, record_bytes / 4) float32 array.  More than max_planes planes raises PccError
+        (PCC_ERR_OVERFLOW) whose `partial` holds (coefficients, sizes, iterations, n_remaining) of the planes found."""
+        ptr, n, stride, mem = _points(points)
+        max_planes = int(max_planes)
+        assert max_planes >= 0, "max_planes must not be negative"
+        row = int(points.shape[1]) * 4
+        record_bytes = row if record_bytes is None else int(record_bytes)
+        if with_points:
+            assert record_bytes % 4 == 0 and 12 <= record_bytes <= row, "record_bytes: a multiple of 4 from 12 to the row's length"
+        rem, p_rem = _out(points, (max(n, 1),), np.int32)
+        pop, p_pop = _out(points, (max(n, 1),), np.int32)
+        out, p_out = _out(points, (max(n, 1), record_bytes // 4), np.float32) if with_points else (None, None)
+        coeff = np.zeros((max(max_planes, 1), 4), dtype=np.float32)
+        sizes = np.zeros(max(max_planes, 1), dtype=np.uint32)
+        its = np.zeros(max(max_planes, 1), dtype=np.int32)
+        n_planes, n_rem, ended = C.c_size_t(0), C.c_size_t(0), C.c_int(0)
+        st = self._before(points)
+        status = LIB.pcc_plane_removal(self._h, ptr, n, stride, mem, float(stop_fraction), int(max_iterations), float(threshold),
+                                       float(probability), int(optimize), max_planes, coeff.ctypes.data, sizes.ctypes.data,
+                                       its.ctypes.data, C.byref(n_planes), C.byref(ended), p_pop, p_rem, C.byref(n_rem), p_out,
+                                       record_bytes, record_bytes)
+        self._after(st)
+        p = n_planes.value
+        if status != 0:
+            err = PccError(status, (LIB.pcc_last_error() or b"").decode())
+            err.partial = (coeff[:p], sizes[:p], its[:p], n_rem.value)
+            raise err
+        res = (rem[:n_rem.value], pop[:n], coeff[:p], sizes[:p], its[:p], bool(ended.value))
+        return res + (out[:n_rem.value],) if with_points else res
 
     def normals(self, k: int = 50, viewpoint=None, device=None):
         """pcl::NormalEstimation over the index's own points: (n, 4) = nx, ny, nz, curvature.

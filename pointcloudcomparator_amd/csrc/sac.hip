@@ -146,7 +146,52 @@ inline int g1(size_t n) {
     return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
-// ascending list of the points within the threshold of `model`; *m = their number
+// ---- pcc_plane_removal: the loop around sac_plane() on the device ------------------------------------------
+__global__ void __launch_bounds__(256)
+k_planes_begin(unsigned int n, int32_t* __restrict__ orig, int32_t* __restrict__ plane_of_point) {
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        orig[i] = (int32_t)i;
+        if (plane_of_point) plane_of_point[i] = -1;
+    }
+}
+
+// The stable two-way partition of a turn, from the exclusive scan select_inliers leaves behind (pos[n + 1]; point i is an inlier
+// when pos[i + 1] != pos[i], and pos[i] inliers lie before it): a point that stays goes to slot i - pos[i] of the other buffer,
+// its float4 verbatim and its original index beside it; an inlier records the turn under its original index.  Every slot and
+// every plane_of_point word has exactly one writer: no atomics, no arithmetic, nothing that depends on the order of execution.
+__global__ void __launch_bounds__(256)
+k_planes_partition(const float4* __restrict__ cur, const int32_t* __restrict__ orig, unsigned int n,
+                   const unsigned int* __restrict__ pos, int32_t plane, float4* __restrict__ rest,
+                   int32_t* __restrict__ rest_orig, int32_t* __restrict__ plane_of_point) {
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const unsigned int before = pos[i];
+        const int32_t o = orig[i];
+        if (pos[i + 1] != before) {
+            if (plane_of_point) plane_of_point[o] = plane;
+        } else {
+            rest[i - before] = cur[i];
+            rest_orig[i - before] = o;
+        }
+    }
+}
+
+// out record j = the first `words` 4-byte words of input record idx[j]; VEC: 16 bytes at a time (both bases, both strides and
+// the record length are multiples of 16; `words` then counts 16-byte pieces)
+template <class W>
+__global__ void __launch_bounds__(256)
+k_planes_records(const char* __restrict__ in, size_t stride, const int32_t* __restrict__ idx, size_t m, unsigned int words,
+                 char* __restrict__ out, size_t out_stride) {
+    const size_t total = m * words;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t j = t / words;
+        const size_t w = t - j * words;
+        *reinterpret_cast<W*>(out + j * out_stride + w * sizeof(W)) =
+            *reinterpret_cast<const W*>(in + (size_t)idx[j] * stride + w * sizeof(W));
+    }
+}
+
+// ascending list of the points within the threshold of `model`; *m = their number.  The exclusive scan of the inlier flags
+// stays in scratch_c (n + 1 words, the last one the total) until the next call: plane_removal() partitions the cloud from it
 int select_inliers(pcc_index* ix, const float4* pts, unsigned int n, const float c[4], double threshold,
                    int32_t* out_dev, size_t* m) {
     hipStream_t s = ix->stream;
@@ -410,6 +455,148 @@ int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int m
     ri.count = m;  // (the first m of the n reserved)
     if (m) PCC_TRY(finish(ix, mem, ri));
     *n_inliers = m;
+    return PCC_OK;
+}
+
+// The plane-removal loop of the -e path (reference src/segmentation.cpp:79-117) with the cloud staged ONCE: every turn is a
+// fresh sac_plane() on the current device cloud, then k_planes_partition moves what stays into the other ping-pong buffer.
+// The staged float4 holds bits(original index) in w for a finite point and -1 for a non-finite one; sac_plane's kernels read
+// only its sign, and the partition copies it verbatim, so a compacted cloud differs from a restaged one in no bit that is read.
+// A turn waits for nothing beyond sac_plane()'s own waits: the inlier count it returns decides the loop.
+int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, double stop_fraction, int max_iterations,
+                      double threshold, double probability, int optimize, size_t max_planes, float* out_coefficients,
+                      uint32_t* out_plane_sizes, int* out_iterations, size_t* n_planes, int* ended_without_model,
+                      int32_t* out_plane_of_point, int32_t* out_remaining_index, size_t* n_remaining, void* out_points,
+                      size_t out_stride, size_t record_bytes) {
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (max_iterations < 0 || !(threshold >= 0) || !(probability > 0 && probability < 1)) {
+        set_error("bad RANSAC parameters");
+        return PCC_ERR_INVALID;
+    }
+    if (!(stop_fraction >= 0) || !std::isfinite(stop_fraction)) {
+        set_error("stop_fraction must be finite and >= 0");
+        return PCC_ERR_INVALID;
+    }
+    if (!n_planes || !n_remaining || (max_planes && (!out_coefficients || !out_plane_sizes))) {
+        set_error("null output");
+        return PCC_ERR_INVALID;
+    }
+    if (out_points && (record_bytes < 12 || record_bytes % 4 || record_bytes > stride || record_bytes > out_stride || out_stride % 4)) {
+        set_error("record_bytes %zu must be a multiple of 4, >= 12 and at most both strides (%zu, %zu, the output's a multiple of 4)",
+                  record_bytes, stride, out_stride);
+        return PCC_ERR_INVALID;
+    }
+    PCC_ENTER(ix);
+    *n_planes = 0;
+    *n_remaining = n;
+    if (ended_without_model) *ended_without_model = 0;
+    ix->stats[0] = ix->stats[1] = 0;
+    ix->stats_pending = false;
+    if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
+    hipStream_t s = ix->stream;
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    const double stop_size = stop_fraction * (double)n;  // (:91: size() > 0.3 * nr_points, in double)
+    const bool any_turn = (double)n > stop_size;
+    // every buffer before any pointer into one is taken (a DevBuf that grows moves)
+    if (any_turn) PCC_TRY(stage_queries(ix, pts, n, stride, mem));
+    PCC_TRY(ix->vox_a.reserve(n * sizeof(float4)));
+    PCC_TRY(ix->vox_b.reserve(n * sizeof(int32_t)));
+    PCC_TRY(ix->vox_c.reserve(n * sizeof(int32_t)));
+    PCC_TRY(ix->out_idx.reserve(n * sizeof(int32_t)));
+    Out<int32_t> plane_of;
+    PCC_TRY(plane_of.stage(out_plane_of_point, n, mem, ix->scratch_g));
+    const float4* cur = ix->q_packed.as<float4>();
+    float4* other = ix->vox_a.as<float4>();
+    int32_t* orig = ix->vox_b.as<int32_t>();
+    int32_t* other_orig = ix->vox_c.as<int32_t>();
+    hipLaunchKernelGGL(k_planes_begin, dim3(g1(n)), dim3(256), 0, s, (unsigned int)n, orig, plane_of.dev);
+    PCC_HIP(hipGetLastError());
+
+    size_t cur_n = n, planes = 0;
+    uint64_t host_copies = 0;
+    int status = PCC_OK;
+    while ((double)cur_n > stop_size) {
+        if (planes == max_planes) { set_error("more than max_planes = %zu planes", max_planes); status = PCC_ERR_OVERFLOW; break; }
+        size_t m = 0;
+        float coeff[4];
+        int its = 0;
+        // turn 0 of a host cloud reads single points from the caller's own array, as pcc_sac_plane does; every other turn
+        // gathers the few points the host needs on the device
+        const char* own = (planes == 0 && mem == PCC_MEM_HOST) ? static_cast<const char*>(pts) : nullptr;
+        int st = sac_plane(ix, cur, cur_n, own, stride, max_iterations, threshold, probability, optimize, ix->out_idx.as<int32_t>(), &m,
+                           coeff, &its);
+        if (st == PCC_ERR_RETRY_HOST) {
+            // a degenerate sample (pcc_sac_plane above): this turn alone with a host copy of the CURRENT cloud
+            PCC_TRY(ix->host_b.reserve(cur_n * sizeof(float4)));
+            float4* hp = ix->host_b.as<float4>();
+            PCC_HIP(hipMemcpyAsync(hp, cur, cur_n * sizeof(float4), hipMemcpyDeviceToHost, s));
+            PCC_HIP(hipStreamSynchronize(s));
+            const float qnan = std::nanf("");
+            for (size_t i = 0; i < cur_n; ++i)
+                if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
+            ++host_copies;
+            st = sac_plane(ix, cur, cur_n, reinterpret_cast<const char*>(hp), sizeof(float4), max_iterations, threshold, probability,
+                           optimize, ix->out_idx.as<int32_t>(), &m, coeff, &its);
+        }
+        PCC_TRY(st);
+        if (m == 0) {  // :95-100 "Could not estimate a planar model for the given dataset."
+            if (ended_without_model) *ended_without_model = 1;
+            break;
+        }
+        std::memcpy(out_coefficients + 4 * planes, coeff, sizeof(coeff));
+        out_plane_sizes[planes] = (uint32_t)m;
+        if (out_iterations) out_iterations[planes] = its;
+        hipLaunchKernelGGL(k_planes_partition, dim3(g1(cur_n)), dim3(256), 0, s, cur, orig, (unsigned int)cur_n,
+                           ix->scratch_c.as<unsigned int>(), (int32_t)planes, other, other_orig, plane_of.dev);
+        PCC_HIP(hipGetLastError());
+        float4* freed = const_cast<float4*>(cur);  // (turn 0 frees q_packed: the staged cloud is not needed again)
+        cur = other;
+        other = freed;
+        std::swap(orig, other_orig);
+        cur_n -= m;
+        ++planes;
+    }
+    *n_planes = planes;
+    *n_remaining = cur_n;
+    ix->stats[0] = planes;
+    ix->stats[1] = host_copies;
+    if (status != PCC_OK) {
+        PCC_HIP(hipStreamSynchronize(s));  // (the arrays in space `mem` are unspecified, but nothing is in flight at the return)
+        return status;
+    }
+    ev_mark(ix, EV_CALL1);
+
+    // the remaining points' original indices, and their records
+    Out<int32_t> remaining;
+    remaining.user = out_remaining_index;
+    remaining.dev = orig;
+    remaining.count = cur_n;
+    if (mem == PCC_MEM_DEVICE) {
+        if (out_remaining_index && cur_n)
+            PCC_HIP(hipMemcpyAsync(out_remaining_index, orig, cur_n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if (out_points && cur_n) {
+            const bool vec = record_bytes % 16 == 0 && stride % 16 == 0 && out_stride % 16 == 0 &&
+                             reinterpret_cast<uintptr_t>(pts) % 16 == 0 && reinterpret_cast<uintptr_t>(out_points) % 16 == 0;
+            const unsigned int words = (unsigned int)(record_bytes / (vec ? 16 : 4));
+            auto kernel = vec ? k_planes_records<uint4> : k_planes_records<unsigned int>;
+            hipLaunchKernelGGL(kernel, dim3(g1(cur_n * words)), dim3(256), 0, s, static_cast<const char*>(pts), stride, orig, cur_n,
+                               words, static_cast<char*>(out_points), out_stride);
+            PCC_HIP(hipGetLastError());
+        }
+        return PCC_OK;
+    }
+    // host memory: the records are the caller's own, copied on the host in the order of the index list
+    std::vector<int32_t> own_index;
+    if (out_points && !out_remaining_index) {
+        own_index.resize(cur_n);
+        remaining.user = own_index.data();
+    }
+    PCC_TRY(finish(ix, mem, plane_of, remaining));
+    if (out_points)
+        for (size_t j = 0; j < cur_n; ++j)
+            std::memcpy(static_cast<char*>(out_points) + j * out_stride, static_cast<const char*>(pts) + (size_t)remaining.user[j] * stride,
+                        record_bytes);
     return PCC_OK;
 }
 }  // extern "C"
