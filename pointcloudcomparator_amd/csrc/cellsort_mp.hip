@@ -11,13 +11,15 @@
 //   level 2   inside every level-1 bucket, B2 = 128 buckets of F2 cells.  The input is already grouped, so a slice
 //             touches a short window of (b1, b2) pairs: LDS counts over the window, ONE returning global atomic per
 //             non-empty pair reserves the slice's run in that bucket, LDS cursors place the points.
-//   level 3   one workgroup per (b1, b2) bucket, as cellsort.hip's last pass: LDS histogram over its F2 cells, scan
-//             (= cell_start), cursor scatter -- but the points are read front to back from level 2's output.
+//   level 3   per (b1, b2) bucket, as cellsort.hip's last pass: LDS histogram over its F2 cells, scan (= cell_start),
+//             placement -- but the points are read front to back from level 2's output, ONCE where the bucket fits
+//             registers: by one wave (up to LIGHT elements, four buckets to a workgroup) or by a workgroup (up to 4 LIGHT).
 // Same results as cell_sort() (order inside a cell is arbitrary in both); plays the role of
 // KDTreeSingleIndex::buildIndex (reference src/comparator.cpp:565) and of the per-call query ordering.
 #include "pcc_internal.hpp"
 #include "grid_device.hpp"
 #include "lane_ops.hpp"
+#include <algorithm>
 
 namespace pcc {
 
@@ -286,22 +288,15 @@ __device__ __forceinline__ void mp_store_point(float4* out, unsigned int pos, co
 __device__ __forceinline__ void mp_store_point(float4*, unsigned int, const uint2&) {}
 
 // ---- level 3 ---------------------------------------------------------------------------------------------------
+// One bucket by the whole workgroup: two reads of its points (count, then place), five barriers.  The form every bucket
+// took before the wave form below; it still takes the buckets that form cannot hold.
 template <bool REFS, class E>
-__global__ void __launch_bounds__(MP_T)
-k_mp_fine(const E* __restrict__ in, const unsigned int* __restrict__ ends /* cursors after level 2: bucket ends */, const GridDev* __restrict__ gd,
-          unsigned int F2, float4* __restrict__ out_pts, unsigned int* __restrict__ out_order,
-          unsigned int* __restrict__ cell_start) {
-    extern __shared__ __attribute__((aligned(16))) unsigned int lds[];  // F2 counters + 4 scan words
-    unsigned int* cnt = lds;
+__device__ __forceinline__ void mp_fine_block(unsigned int* lds, const E* __restrict__ in, unsigned int beg, unsigned int end, unsigned int cell0,
+                                              const GridParams& g, bool voxel, unsigned int F2, float4* __restrict__ out_pts,
+                                              unsigned int* __restrict__ out_order, unsigned int* __restrict__ cell_start) {
+    unsigned int* cnt = lds;  // F2 counters + 4 scan words
     unsigned int* wsum = lds + F2;
-    const GridParams g = gd->g;
-    const bool voxel = gd->voxel != 0;
     const unsigned int ncells = (unsigned int)g.ncells;
-    const unsigned int b = blockIdx.x;
-    const unsigned int cell0 = b * F2;
-    if (cell0 > ncells) return;  // (entry [ncells] of cell_start belongs to the bucket that holds it)
-    const unsigned int beg = b ? ends[b - 1] : 0u, end = ends[b];
-    if (!REFS && beg == end) return;
     for (unsigned int f = threadIdx.x; f < F2; f += MP_T) cnt[f] = 0;
     __syncthreads();
     for (unsigned int j0 = beg + threadIdx.x; j0 < end; j0 += 4 * MP_T) {
@@ -332,8 +327,8 @@ k_mp_fine(const E* __restrict__ in, const unsigned int* __restrict__ ends /* cur
         run += c;
     }
     __syncthreads();
-    // A bucket of up to stage_cap elements (the usual case) is placed in LDS and leaves in whole lines; bigger ones
-    // scatter their 16-byte (or 4-byte) pieces straight to memory.
+    // A bucket of up to stage_cap elements is placed in LDS and leaves in whole lines; bigger ones scatter their 16-byte
+    // (or 4-byte) pieces straight to memory.
     const unsigned int stage_cap = out_pts ? MP_FINE_STAGE_PTS : MP_FINE_STAGE_ORD;
     const bool staged = end - beg <= stage_cap;
     float4* st_pts = reinterpret_cast<float4*>(lds + ((F2 + 4 + 3) & ~3u));
@@ -362,6 +357,180 @@ k_mp_fine(const E* __restrict__ in, const unsigned int* __restrict__ ends /* cur
             if (out_pts) out_pts[beg + i] = st_pts[i];
             if (out_order) out_order[beg + i] = st_ord[i];
         }
+    }
+}
+
+// The wave form: a bucket of at most LIGHT elements is sorted by ONE wave -- one read of its elements, which stay in
+// registers, no workgroup barrier -- and a workgroup takes four such buckets at once.  Per wave, LDS holds
+// F2 16-bit counters, two to a word (a cell's count and rank stay below LIGHT, so a half never carries into its
+// neighbour), and the stage the bucket leaves from in whole lines: 4 KB + LIGHT elements, 80 KB a workgroup for points.
+// Measured at 10M points, same box (EXPERIMENTS.md): points 768 / 1024 / 1536 -> 132 / 111 / 164 us for the reference
+// cloud's pass (1536 leaves one workgroup per CU); order words 1024 / 2048 -> 42.5 / 44.1 us for the query cloud's.
+#ifndef PCC_MP_LIGHT_PTS
+#define PCC_MP_LIGHT_PTS 1024
+#endif
+#ifndef PCC_MP_LIGHT_ORD
+#define PCC_MP_LIGHT_ORD 1024
+#endif
+template <class E> struct MpWave;
+template <> struct MpWave<float4> {  // the point travels: 16 bytes staged
+    typedef float4 Staged;
+    static constexpr unsigned int LIGHT = PCC_MP_LIGHT_PTS;
+    static __device__ __forceinline__ float4 staged(const float4& v) { return v; }  // (.w: the original index)
+    static __device__ __forceinline__ void store(float4* out_pts, unsigned int*, unsigned int pos, const float4& v) { out_pts[pos] = v; }
+};
+template <> struct MpWave<uint2> {  // only the order is wanted: 4 bytes staged
+    typedef unsigned int Staged;
+    static constexpr unsigned int LIGHT = PCC_MP_LIGHT_ORD;
+    static __device__ __forceinline__ unsigned int staged(const uint2& v) { return v.y; }
+    static __device__ __forceinline__ void store(float4*, unsigned int* out_order, unsigned int pos, unsigned int v) { out_order[pos] = v; }
+};
+template <class E> constexpr unsigned int mp_wave_words() {  // LDS words of one wave
+    return MP_F2 / 2 + MpWave<E>::LIGHT * (unsigned int)(sizeof(typename MpWave<E>::Staged) / sizeof(unsigned int));
+}
+static_assert(PCC_MP_LIGHT_PTS % 64 == 0 && PCC_MP_LIGHT_ORD % 64 == 0 && PCC_MP_LIGHT_PTS < 65536 && PCC_MP_LIGHT_ORD < 65536,
+              "a light bucket is whole rounds of a wave and fits a 16-bit counter");
+
+template <bool REFS, class E>
+__device__ __forceinline__ void mp_fine_wave(unsigned int* cnt /* this wave's LDS */, const E* __restrict__ in, unsigned int beg, unsigned int n,
+                                             unsigned int cell0, const GridParams& g, bool voxel, float4* __restrict__ out_pts,
+                                             unsigned int* __restrict__ out_order, unsigned int* __restrict__ cell_start) {
+    typedef MpWave<E> W;
+    constexpr unsigned int PER = W::LIGHT / 64;  // elements a lane keeps
+    const unsigned int ncells = (unsigned int)g.ncells;
+    const unsigned int lane = threadIdx.x & 63;
+    if (n == 0) {  // (reference clouds only) an empty bucket still owns its cell_start entries
+        for (unsigned int f = lane; f < MP_F2; f += 64)
+            if (cell0 + f <= ncells) cell_start[cell0 + f] = beg;
+        return;
+    }
+    unsigned short* cnt16 = reinterpret_cast<unsigned short*>(cnt);
+    typename W::Staged* stage = reinterpret_cast<typename W::Staged*>(cnt + MP_F2 / 2);
+    // every load of the bucket is issued at once and unconditionally (rounds past the end read the last element again): a
+    // branch per round made the compiler wait for the round before it
+    E v[PER];
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u) v[u] = in[beg + min(lane + 64 * u, n - 1)];
+    for (unsigned int k = lane; k < MP_F2 / 8; k += 64) reinterpret_cast<uint4*>(cnt)[k] = make_uint4(0u, 0u, 0u, 0u);
+    wave_lds_sync();
+    unsigned int key[PER];  // cell inside the bucket | rank inside the cell << 16
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)
+        if (lane + 64 * u < n) {
+            const unsigned int c = (mp_cell(v[u], g, voxel) - cell0) & (MP_F2 - 1), sh = 16 * (c & 1);
+            const unsigned int old = atomicAdd(&cnt[c >> 1], 1u << sh);
+            key[u] = c | ((old >> sh) & 0xffffu) << 16;
+        }
+    wave_lds_sync();
+    // counts -> first positions: 64 consecutive cells per step, the running base in a scalar; a step's cell_start words
+    // are 256 contiguous bytes
+    unsigned int base = 0;
+#pragma unroll 8
+    for (unsigned int step = 0; step < MP_F2 / 64; ++step) {
+        const unsigned int f = 64 * step + lane;
+        const unsigned int c = cnt16[f];
+        const unsigned int inc = wave_incl_scan_add(c);
+        const unsigned int first = base + inc - c;
+        cnt16[f] = (unsigned short)first;
+        if (REFS && cell0 + f <= ncells) cell_start[cell0 + f] = beg + first;
+        base += __builtin_amdgcn_readlane(inc, 63);
+    }
+    wave_lds_sync();
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)  // (all the reads first: behind a stage store the compiler must assume they alias)
+        if (lane + 64 * u < n) key[u] = cnt16[key[u] & 0xffffu] + (key[u] >> 16);
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)
+        if (lane + 64 * u < n) stage[key[u]] = W::staged(v[u]);
+    wave_lds_sync();
+    for (unsigned int i = lane; i < n; i += 64) W::store(out_pts, out_order, beg + i, stage[i]);
+}
+
+// The whole workgroup on a bucket of up to MP_T * PER elements, each read ONCE and kept in registers: the rank comes from
+// the counting atomic, so the second read of the block form above (and its second pass of cell arithmetic) is gone and the
+// bucket leaves through the stage in whole lines.  32-bit counters, the block form's scan.
+template <class E> constexpr unsigned int mp_once_cap() { return MP_T * MpWave<E>::LIGHT / 64; }
+template <class E> constexpr unsigned int mp_once_words() {
+    return MP_F2 + 4 + mp_once_cap<E>() * (unsigned int)(sizeof(typename MpWave<E>::Staged) / sizeof(unsigned int));
+}
+template <bool REFS, class E>
+__device__ __forceinline__ void mp_fine_once(unsigned int* lds, const E* __restrict__ in, unsigned int beg, unsigned int n, unsigned int cell0,
+                                             const GridParams& g, bool voxel, float4* __restrict__ out_pts,
+                                             unsigned int* __restrict__ out_order, unsigned int* __restrict__ cell_start) {
+    typedef MpWave<E> W;
+    constexpr unsigned int PER = W::LIGHT / 64;
+    unsigned int* cnt = lds;
+    unsigned int* wsum = lds + MP_F2;
+    typename W::Staged* stage = reinterpret_cast<typename W::Staged*>(lds + MP_F2 + 4);
+    const unsigned int ncells = (unsigned int)g.ncells;
+    E v[PER];
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u) v[u] = in[beg + min(threadIdx.x + MP_T * u, n - 1)];  // (n > 0: the light ones went elsewhere)
+    for (unsigned int f = threadIdx.x; f < MP_F2; f += MP_T) cnt[f] = 0;
+    __syncthreads();
+    unsigned int key[PER];  // cell inside the bucket | rank inside the cell << 16
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)
+        if (threadIdx.x + MP_T * u < n) {
+            const unsigned int c = (mp_cell(v[u], g, voxel) - cell0) & (MP_F2 - 1);
+            key[u] = c | atomicAdd(&cnt[c], 1u) << 16;
+        }
+    __syncthreads();
+    constexpr unsigned int per = MP_F2 / MP_T;
+    const unsigned int f0 = threadIdx.x * per;
+    unsigned int s = 0;
+#pragma unroll
+    for (unsigned int f = f0; f < f0 + per; ++f) s += cnt[f];
+    const unsigned int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned int inc = wave_incl_scan_add(s);
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    unsigned int run = inc - s;
+    for (unsigned int w = 0; w < wave; ++w) run += wsum[w];
+#pragma unroll
+    for (unsigned int f = f0; f < f0 + per; ++f) {
+        const unsigned int c = cnt[f];
+        cnt[f] = run;  // first position of cell f inside the bucket
+        if (REFS && cell0 + f <= ncells) cell_start[cell0 + f] = beg + run;
+        run += c;
+    }
+    __syncthreads();
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)
+        if (threadIdx.x + MP_T * u < n) key[u] = cnt[key[u] & 0xffffu] + (key[u] >> 16);
+#pragma unroll
+    for (unsigned int u = 0; u < PER; ++u)
+        if (threadIdx.x + MP_T * u < n) stage[key[u]] = W::staged(v[u]);
+    __syncthreads();
+    for (unsigned int i = threadIdx.x; i < n; i += MP_T) W::store(out_pts, out_order, beg + i, stage[i]);
+}
+static_assert(MP_T * PCC_MP_LIGHT_PTS / 64 < 65536 && MP_T * PCC_MP_LIGHT_ORD / 64 < 65536, "a rank of the one-read block form fits 16 bits");
+
+// The first n_block workgroups take one bucket each -- read once while it fits their registers, twice beyond -- and leave the
+// light ones (at most `light` elements) alone: those go to the workgroups behind them, four buckets each, one per wave.
+// light = 0: every bucket takes the two-read block form.
+// The heavy buckets come first in launch order: the longest pieces of work start earliest.
+template <bool REFS, class E>
+__global__ void __launch_bounds__(MP_T)
+k_mp_fine(const E* __restrict__ in, const unsigned int* __restrict__ ends /* cursors after level 2: bucket ends */, const GridDev* __restrict__ gd,
+          unsigned int F2, unsigned int n_block, unsigned int light, float4* __restrict__ out_pts, unsigned int* __restrict__ out_order,
+          unsigned int* __restrict__ cell_start) {
+    extern __shared__ __attribute__((aligned(16))) unsigned int lds[];
+    const GridParams g = gd->g;
+    const bool voxel = gd->voxel != 0;
+    const unsigned int ncells = (unsigned int)g.ncells;
+    const bool block = blockIdx.x < n_block;
+    const unsigned int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned int b = block ? blockIdx.x : 4 * (blockIdx.x - n_block) + wave;
+    const unsigned int cell0 = b * F2;
+    if (cell0 > ncells) return;  // (entry [ncells] of cell_start belongs to the bucket that holds it)
+    const unsigned int beg = b ? ends[b - 1] : 0u, end = ends[b];
+    if (!REFS && beg == end) return;
+    if (block) {
+        if (light == 0 || end - beg > mp_once_cap<E>()) mp_fine_block<REFS, E>(lds, in, beg, end, cell0, g, voxel, F2, out_pts, out_order, cell_start);
+        else if (end - beg > light) mp_fine_once<REFS, E>(lds, in, beg, end - beg, cell0, g, voxel, out_pts, out_order, cell_start);
+    } else if (end - beg <= light) {
+        mp_fine_wave<REFS, E>(lds + wave * mp_wave_words<E>(), in, beg, end - beg, cell0, g, voxel, out_pts, out_order, cell_start);
     }
 }
 
@@ -399,10 +568,17 @@ int cell_sort_mp(pcc_index* ix, const float4* pts, size_t n_pts, bool refs, floa
     PCC_TRY(launch_exclusive_scan(ix, s, H, h_elems, ix->scratch_a));
     unsigned int* n_valid = H + h_elems - 1;  // grand total == number of valid points
     if (n_sorted_dev) *n_sorted_dev = n_valid;
-    // counters + scan words, then the staged output (points and / or order words)
-    const size_t lds3 = (((size_t)p.F2 + 4 + 3) & ~(size_t)3) * sizeof(unsigned int) +
-                        (out_pts ? (size_t)MP_FINE_STAGE_PTS * (sizeof(float4) + (out_order ? sizeof(unsigned int) : 0))
-                                 : (size_t)MP_FINE_STAGE_ORD * sizeof(unsigned int));
+    // level 3 in LDS: the whole-workgroup form's counters + scan words, then its staged output (points and / or order
+    // words); or the four waves' slices of the wave form, whichever is larger
+    const size_t lds3_block = (((size_t)p.F2 + 4 + 3) & ~(size_t)3) * sizeof(unsigned int) +
+                              (out_pts ? (size_t)MP_FINE_STAGE_PTS * (sizeof(float4) + (out_order ? sizeof(unsigned int) : 0))
+                                       : (size_t)MP_FINE_STAGE_ORD * sizeof(unsigned int));
+    // (the wave form holds F2 = MP_F2 cells and stages one output)
+    const unsigned int light = p.F2 != MP_F2 || (out_pts != nullptr) == (out_order != nullptr) ? 0u : out_pts ? MpWave<float4>::LIGHT : MpWave<uint2>::LIGHT;
+    const size_t lds3_wave = !light ? 0 : 4 * sizeof(unsigned int) * (out_pts ? mp_wave_words<float4>() : mp_wave_words<uint2>());
+    const size_t lds3_once = !light ? 0 : sizeof(unsigned int) * (out_pts ? mp_once_words<float4>() : mp_once_words<uint2>());
+    const size_t lds3 = std::max(lds3_block, std::max(lds3_wave, lds3_once));
+    const unsigned int g3 = np + (light ? np / 4 : 0u);  // one workgroup per bucket, then one per four light buckets
     const unsigned int g2c = (n + MP_SLICE2 - 1) / MP_SLICE2;
     if (out_pts) {  // the points travel (reference clouds)
         float4* t1 = ix->mp_a.as<float4>();
@@ -416,9 +592,9 @@ int cell_sort_mp(pcc_index* ix, const float4* pts, size_t n_pts, bool refs, floa
         PCC_TRY(launch_exclusive_scan(ix, s, C, np, ix->scratch_a));
         hipLaunchKernelGGL((k_mp_level2<true, float4>), dim3(g2p), dim3(MP_T), 0, s, t1, n_valid, gd, p.F1, p.F2, C, t2);
         if (refs)
-            hipLaunchKernelGGL((k_mp_fine<true, float4>), dim3(np), dim3(MP_T), lds3, s, t2, C, gd, p.F2, out_pts, out_order, cell_start);
+            hipLaunchKernelGGL((k_mp_fine<true, float4>), dim3(g3), dim3(MP_T), lds3, s, t2, C, gd, p.F2, np, light, out_pts, out_order, cell_start);
         else
-            hipLaunchKernelGGL((k_mp_fine<false, float4>), dim3(np), dim3(MP_T), lds3, s, t2, C, gd, p.F2, out_pts, out_order, cell_start);
+            hipLaunchKernelGGL((k_mp_fine<false, float4>), dim3(g3), dim3(MP_T), lds3, s, t2, C, gd, p.F2, np, light, out_pts, out_order, cell_start);
     } else {        // only the order is wanted (query clouds): (cell, position) pairs travel, half the bytes
         uint2* t1 = ix->mp_a.as<uint2>();
         uint2* t2 = ix->mp_b.as<uint2>();
@@ -435,9 +611,9 @@ int cell_sort_mp(pcc_index* ix, const float4* pts, size_t n_pts, bool refs, floa
         PCC_TRY(launch_exclusive_scan(ix, s, C, np, ix->scratch_a));
         hipLaunchKernelGGL((k_mp_level2<true, uint2>), dim3(g2p), dim3(MP_T), 0, s, t1, n_valid, gd, p.F1, p.F2, C, t2);
         if (refs)
-            hipLaunchKernelGGL((k_mp_fine<true, uint2>), dim3(np), dim3(MP_T), lds3, s, t2, C, gd, p.F2, out_pts, out_order, cell_start);
+            hipLaunchKernelGGL((k_mp_fine<true, uint2>), dim3(g3), dim3(MP_T), lds3, s, t2, C, gd, p.F2, np, light, out_pts, out_order, cell_start);
         else
-            hipLaunchKernelGGL((k_mp_fine<false, uint2>), dim3(np), dim3(MP_T), lds3, s, t2, C, gd, p.F2, out_pts, out_order, cell_start);
+            hipLaunchKernelGGL((k_mp_fine<false, uint2>), dim3(g3), dim3(MP_T), lds3, s, t2, C, gd, p.F2, np, light, out_pts, out_order, cell_start);
     }
     PCC_HIP(hipGetLastError());
     return PCC_OK;
