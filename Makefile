@@ -8,7 +8,7 @@ ARCH       ?= gfx950
 HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 -fPIC -Iinclude -Ipointcloudcomparator_amd/csrc
 CSRC       := pointcloudcomparator_amd/csrc
 LIBDIR     := pointcloudcomparator_amd/lib
-HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/sor.hip)
+HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/sor.hip $(CSRC)/segment.hip)
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/pcc_nn.h
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 
@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -189,6 +189,11 @@ build/match_dims_driver: tests/cpp/match_dims_driver.cpp include/pcc/comparator_
 
 # pcc::removePlanes against the SACSegmentation + ExtractIndices loop it replaces
 build/plane_removal_driver: tests/cpp/plane_removal_driver.cpp include/pcc/comparator_nn.hpp include/pcc/search.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
+# pcc::regionGrowingSegmentation against the VoxelGrid + NormalEstimation + RegionGrowing objects it replaces
+build/segment_driver: tests/cpp/segment_driver.cpp include/pcc/comparator_nn.hpp include/pcc/search.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 

@@ -49,6 +49,9 @@ static int n_gpus = 1, descriptor_dims = 3;
 static bool rgb_device = false, rgb_batch = false;
 // --planes-device (with -e): the plane-removal loop runs in one library call (pcc_plane_removal through removePlanes): same lines
 static bool planes_device = false;
+// --segment-device (without -e): the whole default segmentation runs in one library call (pcc_region_growing_segmentation through
+// regionGrowingSegmentation): same lines, same clusters
+static bool segment_device = false;
 static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
@@ -83,6 +86,9 @@ static void printUsage() {
               << "--planes-device    (this build, with -e) the plane-removal loop in front of the clustering runs in ONE library call\n"
               << "                   (pcc_plane_removal: the cloud uploaded once, compacted on the GPU) instead of one call and one\n"
               << "                   host compaction per plane: the same lines, the same clusters\n"
+              << "--segment-device   (this build, without -e) the default segmentation -- voxel grid, normals, region growing, one cloud\n"
+              << "                   per cluster -- runs in ONE library call (pcc_region_growing_segmentation: the filtered cloud, its\n"
+              << "                   index, normals and labels stay on the GPU): the same lines, the same clusters; ignored with -e\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
@@ -156,6 +162,14 @@ static std::vector<PointCloud<PointXYZRGB>::Ptr> euclidean_cluster_segmentation(
 // src/segmentation.cpp:218-327 region_growing_segmentation: VoxelGrid 0.025 -> NormalEstimation K = 50 ->
 // RegionGrowing (50..1000000 points, 100 neighbours, 3 degrees, curvature 1)
 static std::vector<PointCloud<PointXYZRGB>::Ptr> region_growing_segmentation(const PointCloud<PointXYZRGB>::Ptr& point_cloud_ptr) {
+    if (segment_device) {
+        PointCloud<PointXYZRGB>::Ptr filtered;
+        std::vector<PointCloud<PointXYZRGB>::Ptr> found = regionGrowingSegmentation<PointXYZRGB>(
+            point_cloud_ptr, 0.025f, 50, 100, (float)(3.0 / 180.0 * M_PI), 1.0f, 50, 1000000, &filtered);
+        std::cout << "PointCloud after filtering has: " << filtered->points.size() << " data points." << std::endl;
+        std::cout << "Number of clusters is equal to " << found.size() << std::endl;
+        return found;
+    }
     VoxelGrid<PointXYZRGB> vg;
     PointCloud<PointXYZRGB>::Ptr cloud_filtered(new PointCloud<PointXYZRGB>);
     vg.setInputCloud(point_cloud_ptr);
@@ -396,6 +410,7 @@ int main(int argc, char** argv) {
         else if (a == "--rgb-device") rgb_device = true;
         else if (a == "--rgb-batch") rgb_batch = true;
         else if (a == "--planes-device") planes_device = true;
+        else if (a == "--segment-device") segment_device = true;
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }

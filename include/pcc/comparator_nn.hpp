@@ -7,6 +7,7 @@
 //   StatisticalOutlierRemoval       the -n noise pass (:1520-1549)
 //   EuclideanClusterExtraction      the -e path (src/segmentation.cpp:119-131)
 //   removePlanes                    the plane-removal loop in front of it (src/segmentation.cpp:79-117) as one call
+//   regionGrowingSegmentation       the default path (src/segmentation.cpp:218-327) as one call
 // Everything numerical happens behind the C-ABI; this header is plumbing a maintainer of the
 // reference can include instead of the PCL headers for these five call sites.
 #pragma once
@@ -470,6 +471,105 @@ inline typename PointCloud<PointT>::Ptr removePlanes(const typename PointCloud<P
     rest->height = 1;
     rest->is_dense = true;
     return rest;
+}
+
+// ---- region_growing_segmentation (src/segmentation.cpp:218-327) in one library call ----------------------
+// VoxelGrid leaf -> NormalEstimation normal_k -> RegionGrowing k -> one cloud per cluster: what the VoxelGrid, KdTree,
+// NormalEstimation and RegionGrowing objects above give together (same filtered points, same clusters, same order), but the
+// filtered cloud, its index, its normals and its labels never leave the device (pcc_region_growing_segmentation).  *filtered
+// (may be null) receives the filtered cloud.  A leaf too small for the cloud (PCC_ERR_UNSUPPORTED, PCL: "leaf size is too
+// small", output = input) takes the class path, as VoxelGrid::filter does.
+template <class PointT>
+inline std::vector<typename PointCloud<PointT>::Ptr> regionGrowingSegmentation(
+    const typename PointCloud<PointT>::ConstPtr& cloud, float leaf = 0.025f, int normal_k = 50, int k = 100,
+    float smoothness = (float)(3.0 / 180.0 * 3.14159265358979323846), float curvature = 1.0f, int min_size = 50, int max_size = 1000000,
+    typename PointCloud<PointT>::Ptr* filtered = nullptr) {
+    std::vector<typename PointCloud<PointT>::Ptr> clusters;
+    typename PointCloud<PointT>::Ptr kept(new PointCloud<PointT>);
+    kept->height = 1;
+    kept->is_dense = true;
+    if (filtered) *filtered = kept;
+    if (!cloud || cloud->empty()) return clusters;
+    // any index handle supplies device, stream and scratch; this one stays with the thread, and the work handle the filtered
+    // cloud is indexed on stays with it
+    struct Context {
+        pcc_index* h = nullptr;
+        ~Context() { pcc_index_destroy(h); }
+    };
+    static thread_local Context context;
+    if (!context.h) {
+        const float one[3] = {0.f, 0.f, 0.f};
+        check(pcc_index_create(one, 1, 12, 3, PCC_MEM_HOST, 0, PCC_ENGINE_BRUTE, &context.h));
+    }
+    const size_t n = cloud->size();
+    // what the call answers with PCC_ERR_UNSUPPORTED besides a leaf too small for the cloud: refused here, so that the status
+    // below can only mean the leaf
+    if (normal_k < 1 || normal_k > PCC_KNN_MAX_K || k < 1 || k > PCC_KNN_MAX_K)
+        throw Error(PCC_ERR_UNSUPPORTED, "regionGrowingSegmentation: normal_k and k must lie in [1, PCC_KNN_MAX_K]");
+    if (n >= (1ull << 31)) throw Error(PCC_ERR_UNSUPPORTED, "regionGrowingSegmentation: more than 2^31 points");
+    const int has_rgb = sizeof(PointT) >= 20 ? 1 : 0;
+    kept->points.resize(n);
+    std::vector<PointT> members(n);
+    std::vector<size_t> offsets;
+    size_t capacity = 256, nv = 0;
+    int32_t ncl = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        offsets.assign(capacity + 1, 0);
+        const int st = pcc_region_growing_segmentation(context.h, cloud->points.data(), n, sizeof(PointT), PCC_MEM_HOST, leaf, has_rgb,
+                                                       normal_k, k, smoothness, curvature, (uint32_t)min_size, (uint32_t)max_size,
+                                                       kept->points.data(), sizeof(PointT), &nv, nullptr, nullptr, capacity, &ncl,
+                                                       offsets.data(), members.data(), nullptr);
+        if (st == PCC_ERR_OVERFLOW && attempt == 0) { capacity = (size_t)ncl; continue; }  // once more with the room it asks for
+        if (st == PCC_ERR_UNSUPPORTED) {
+            // (k, normal_k and n were checked above: what is left is the voxel grid's "leaf size too small")
+            // the objects the call replaces, as examples/comparator_main.cpp drives them
+            VoxelGrid<PointT> vg;
+            vg.setInputCloud(cloud);
+            vg.setLeafSize(leaf, leaf, leaf);
+            vg.filter(*kept);
+            typename search::KdTree<PointT>::Ptr tree(new search::KdTree<PointT>);
+            tree->setOption(PCC_OPT_KNN_CACHE_K, std::max(normal_k, k));
+            typename PointCloud<Normal>::Ptr normals(new PointCloud<Normal>);
+            NormalEstimation<PointT, Normal> ne;
+            ne.setSearchMethod(tree);
+            ne.setInputCloud(kept);
+            ne.setKSearch(normal_k);
+            ne.compute(*normals);
+            RegionGrowing<PointT, Normal> reg;
+            reg.setMinClusterSize(min_size);
+            reg.setMaxClusterSize(max_size);
+            reg.setSearchMethod(tree);
+            reg.setNumberOfNeighbours((unsigned int)k);
+            reg.setInputCloud(kept);
+            reg.setInputNormals(normals);
+            reg.setSmoothnessThreshold(smoothness);
+            reg.setCurvatureThreshold(curvature);
+            std::vector<PointIndices> found;
+            reg.extract(found);
+            for (const PointIndices& c : found) {
+                typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+                for (int j : c.indices) one->points.push_back(kept->points[j]);
+                one->width = (std::uint32_t)one->points.size();
+                one->height = 1;
+                one->is_dense = true;
+                clusters.push_back(one);
+            }
+            return clusters;
+        }
+        check(st);
+        break;
+    }
+    kept->points.resize(nv);
+    kept->width = (std::uint32_t)nv;
+    for (int32_t c = 0; c < ncl; ++c) {
+        typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+        one->points.assign(members.begin() + offsets[c], members.begin() + offsets[c + 1]);
+        one->width = (std::uint32_t)one->points.size();
+        one->height = 1;
+        one->is_dense = true;
+        clusters.push_back(one);
+    }
+    return clusters;
 }
 
 }  // namespace pcc

@@ -492,6 +492,67 @@ int pcc_normals(pcc_index *index, int k, const float viewpoint[3], int mem, floa
  * src/comparator.cpp:628-635, radius 0.03): the neighbourhood is the sorted radiusSearch result
  * (d2 < float(radius^2), ascending (d2, index)); NaN where it holds fewer than 3 points. */
 int pcc_normals_radius(pcc_index *index, double radius, const float viewpoint[3], int mem, float *out);
+
+/* ---- labels -> one cloud per cluster -----------------------------------------------------------------------
+ * replaces: the loop both segmentation paths of the reference end with (src/segmentation.cpp:133-152 and :290-318): for every
+ *   cluster, in order, a new cloud of cloud[j] for every index j of the cluster.  With the clusters given as labels[n]
+ *   (pcc_region_growing, pcc_euclidean_clusters): for c = 0 .. n_clusters - 1, in that order, the points i with
+ *   labels[i] == c in ASCENDING i -- what `for i: clusters[labels[i]].push_back(i)` gives, the order of
+ *   np.argsort(labels, kind="stable") without the -1 entries, the same on every run (a stable radix partition on the
+ *   device, segment.hip).
+ * out_offsets[n_clusters + 1] (HOST): cluster c is the slice out_offsets[c] .. out_offsets[c + 1] of
+ *   out_index[n] (space `mem`, may be NULL): the indices i (entries from out_offsets[n_clusters] on are unspecified), and of
+ *   out_records (space `mem`, may be NULL; capacity n records of out_stride_bytes, not overlapping records): the first
+ *   record_bytes of record i, verbatim, at slot j * out_stride_bytes; the rest of a slot is not touched.
+ * A label of -1 is left out; a cluster no point carries is an empty slice; a label outside [-1, n_clusters) gives
+ *   PCC_ERR_INVALID -- found on the device (no table is indexed by such a label) and reported after the call's one wait;
+ *   nothing is promised about the outputs then.  n == 0 or n_clusters == 0: PCC_OK, every offset 0.
+ * records (read only with out_records), labels, out_records and out_index are in space `mem`.  record_bytes is a multiple of 4
+ *   with 12 <= record_bytes <= min(stride_bytes, out_stride_bytes), both strides multiples of 4 (pcc_plane_removal's rules).
+ * Refused before any device is touched, nothing written: a bad memory space, 2^31 points or more (PCC_ERR_UNSUPPORTED), a
+ *   negative n_clusters, NULL labels with n > 0, a NULL out_offsets, with out_records a NULL records or a bad stride or
+ *   record_bytes; a null handle last.  `ctx` is any index handle (device, stream, scratch), as for pcc_plane_removal. */
+int pcc_extract_clusters(pcc_index *ctx, const void *records, size_t n, size_t stride_bytes, size_t record_bytes,
+                         const int32_t *labels, int32_t n_clusters, int mem,
+                         void *out_records, size_t out_stride_bytes, int32_t *out_index, size_t *out_offsets);
+
+/* ---- the default segmentation path in one call -----------------------------------------------------------
+ * replaces: region_growing_segmentation (src/segmentation.cpp:218-327): VoxelGrid leaf (0.025, :224-229) -> NormalEstimation
+ *   K = normal_k (50, :232-241) -> RegionGrowing K = k (100, :259-271) -> one cloud per cluster (:290-318).  Every output is
+ *   bit for bit what this sequence of calls gives, and where a step of it fails the call returns that step's status:
+ *
+ *     pcc_voxel_grid(ctx, pts, n, stride_bytes, mem, leaf, has_rgb, F, out_stride_bytes, &nv)   -> out_points, *n_filtered
+ *     H = pcc_index_create(F, nv, out_stride_bytes, ...)            (a fresh handle, default tie order)
+ *     pcc_normals(H, normal_k, NULL, ...)                                                         -> out_normals[0 .. nv)
+ *     pcc_region_growing(H, normals, k, smoothness, curvature_threshold, min_size, max_size, ...) -> out_labels[0 .. nv), *n_clusters
+ *     pcc_extract_clusters(ctx, F, nv, out_stride_bytes, out_stride_bytes, labels, *n_clusters, ...) -> out_offsets, out_cluster_*
+ *
+ *   but the filtered cloud, its index, its k-NN rows (searched once with max(normal_k, k) neighbours), its normals and its
+ *   labels stay on the device from the raw cloud to the cluster clouds.  Only scalars cross to the host inside the call: the
+ *   voxel grid's block statistics and count, region growing's words per sweep and its seed list, the offsets.
+ * out_points (space `mem`, capacity n records of out_stride_bytes): the filtered cloud, *n_filtered (HOST) records; the bytes
+ *   of a record pcc_voxel_grid does not write are zero in both memory spaces.  out_normals[n][4], out_labels[n] (space `mem`,
+ *   may be NULL): their first *n_filtered rows.  *n_clusters (HOST).  out_offsets[max_clusters + 1] (HOST): its first
+ *   *n_clusters + 1 entries, as pcc_extract_clusters writes them over the filtered cloud.  out_cluster_points (space `mem`,
+ *   may be NULL, capacity n records of out_stride_bytes): whole filtered records, cluster by cluster.  out_cluster_index[n]
+ *   (space `mem`, may be NULL): their indices in the filtered cloud.
+ * No finite point (or n == 0): PCC_OK, *n_filtered = *n_clusters = 0, out_offsets[0] = 0.
+ * *n_clusters > max_clusters: PCC_ERR_OVERFLOW with *n_clusters set and *n_filtered, out_points, out_normals, out_labels
+ *   valid; the cluster outputs are unspecified (as max_planes of pcc_plane_removal).
+ * Refused before any device is touched, nothing written: what pcc_voxel_grid refuses (same messages); a NULL n_filtered,
+ *   n_clusters or out_offsets; out_cluster_points or out_cluster_index with max_clusters == 0; a smoothness or curvature
+ *   threshold that is not finite; normal_k or k outside [1, PCC_KNN_MAX_K] (PCC_ERR_UNSUPPORTED); a null handle last.
+ * `ctx` is any index handle: the cloud it indexes, its tie order and its kept rows are neither read nor changed.  The filtered
+ *   cloud is indexed on a work handle kept in `ctx` (under ctx's options, PCC_OPT_KNN_CACHE_K = max(normal_k, k)) and freed
+ *   with it.  Afterwards pcc_index_stats reports in [0] the filtered points, [1] the clusters, [2] the clustered points and
+ *   [7] region growing's sweeps. */
+int pcc_region_growing_segmentation(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                                    float leaf, int has_rgb, int normal_k, int k, float smoothness, float curvature_threshold,
+                                    uint32_t min_size, uint32_t max_size,
+                                    void *out_points, size_t out_stride_bytes, size_t *n_filtered,
+                                    float *out_normals, int32_t *out_labels,
+                                    size_t max_clusters, int32_t *n_clusters, size_t *out_offsets,
+                                    void *out_cluster_points, int32_t *out_cluster_index);
 /* ---- RIFT descriptors of the indexed cloud ---------------------------------------------------------
  * replaces: processRIFT (src/comparator.cpp:590-684) for one cloud: pcl::PointCloudXYZRGBtoXYZI, pcl::NormalEstimation
  *   (setRadiusSearch 0.03, :628-635), removeNaNNormalsFromPointCloud (:637-646), pcl::IntensityGradientEstimation

@@ -35,7 +35,7 @@ SYMBOLS = [
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
     "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
-    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_rigid_from_sums",
+    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
@@ -103,6 +103,9 @@ def _load() -> C.CDLL:
     lib.pcc_sac_plane.argtypes = [vp, vp, sz, sz, i32, i32, C.c_double, C.c_double, i32, vp, C.POINTER(sz), vp, vp]
     lib.pcc_plane_removal.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, C.c_double, C.c_double, i32, sz, vp, vp, vp, C.POINTER(sz),
                                       C.POINTER(i32), vp, vp, C.POINTER(sz), vp, sz, sz]
+    lib.pcc_extract_clusters.argtypes = [vp, vp, sz, sz, sz, vp, i32, i32, vp, sz, vp, vp]
+    lib.pcc_region_growing_segmentation.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, i32, i32, C.c_float, C.c_float, C.c_uint32,
+                                                    C.c_uint32, vp, sz, C.POINTER(sz), vp, vp, sz, C.POINTER(i32), vp, vp, vp]
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
@@ -697,6 +700,80 @@ class Index:
             raise err
         res = (rem[:n_rem.value], pop[:n], coeff[:p], sizes[:p], its[:p], bool(ended.value))
         return res + (out[:n_rem.value],) if with_points else res
+
+    def extract_clusters(self, records, labels, n_clusters: int, record_bytes: int | None = None, with_records: bool = True):
+        """pcc_extract_clusters: labels -> one cloud per cluster (the loop both segmentation paths of the reference end with,
+        src/segmentation.cpp:133-152 and :290-318), a stable partition of the point indices by label on the device.
+        records: (n, >= 3) float32 numpy array or torch tensor; labels: (n,) int32 in the same memory space, -1 = left out.
+        Returns (index, offsets[, records]): cluster c is index[offsets[c]:offsets[c + 1]] -- its points in ascending order --
+        and, with_records, the first record_bytes (default: the whole row) of each of them as an (m, record_bytes / 4) float32
+        array.  A label outside [-1, n_clusters) raises PccError (PCC_ERR_INVALID)."""
+        ptr, n, stride, mem = _points(records)
+        n_clusters = int(n_clusters)
+        assert n_clusters >= 0, "n_clusters must not be negative"
+        if _is_torch(labels):
+            import torch
+            assert labels.dtype == torch.int32 and labels.dim() == 1 and labels.is_contiguous() and labels.shape[0] == n
+            assert labels.is_cuda == (mem == MEM_DEVICE), "records and labels must be in the same memory space"
+            p_lab = labels.data_ptr()
+        else:
+            assert mem == MEM_HOST, "records and labels must be in the same memory space"
+            labels = np.ascontiguousarray(labels, dtype=np.int32)
+            assert labels.shape == (n,)
+            p_lab = labels.ctypes.data
+        row = int(records.shape[1]) * 4
+        record_bytes = row if record_bytes is None else int(record_bytes)
+        assert record_bytes % 4 == 0 and 12 <= record_bytes <= row, "record_bytes: a multiple of 4 from 12 to the row's length"
+        index, p_index = _out(records, (max(n, 1),), np.int32)
+        out, p_out = _out(records, (max(n, 1), record_bytes // 4), np.float32) if with_records else (None, None)
+        offsets = np.zeros(n_clusters + 1, dtype=np.uintp)
+        st = self._before(records, labels)
+        status = LIB.pcc_extract_clusters(self._h, ptr, n, stride, record_bytes, p_lab, n_clusters, mem, p_out, record_bytes, p_index,
+                                          offsets.ctypes.data)
+        self._after(st)
+        _check(status)
+        m = int(offsets[n_clusters])
+        offsets = offsets.astype(np.int64)
+        return (index[:m], offsets, out[:m]) if with_records else (index[:m], offsets)
+
+    def region_growing_segmentation(self, points, leaf: float = 0.025, has_rgb: bool = False, normal_k: int = 50, k: int = 100,
+                                    smoothness: float = 3.0 / 180.0 * np.pi, curvature_threshold: float = 1.0, min_size: int = 50,
+                                    max_size: int = 1000000, max_clusters: int = 4096):
+        """pcc_region_growing_segmentation: the reference's default segmentation path (src/segmentation.cpp:218-327) in one call:
+        VoxelGrid -> NormalEstimation (normal_k) -> RegionGrowing (k) -> one cloud per cluster, nothing cloud-sized crossing to
+        the host in between.  points: (n, >= 3) float32 numpy array or torch tensor (a CUDA tensor gives CUDA results); has_rgb:
+        the colour word in column 4 is averaged.  Returns a dict: filtered (nv, columns) records, normals (nv, 4), labels (nv,),
+        n_clusters, offsets (n_clusters + 1,), cluster_points (m, columns), cluster_index (m,): cluster c is the slice
+        offsets[c]:offsets[c + 1] of the last two.  More than max_clusters clusters raises PccError (PCC_ERR_OVERFLOW) whose
+        `partial` holds the dict without the cluster arrays."""
+        ptr, n, stride, mem = _points(points)
+        max_clusters = int(max_clusters)
+        assert max_clusters >= 0, "max_clusters must not be negative"
+        cols = int(points.shape[1])
+        cap = max(n, 1)
+        filtered, p_f = _out(points, (cap, cols), np.float32)
+        normals, p_n = _out(points, (cap, 4), np.float32)
+        labels, p_l = _out(points, (cap,), np.int32)
+        cpts, p_cp = _out(points, (cap, cols), np.float32) if max_clusters else (None, None)
+        cidx, p_ci = _out(points, (cap,), np.int32) if max_clusters else (None, None)
+        offsets = np.zeros(max_clusters + 1, dtype=np.uintp)
+        nv, ncl = C.c_size_t(0), C.c_int32(0)
+        st = self._before(points)
+        status = LIB.pcc_region_growing_segmentation(self._h, ptr, n, stride, mem, float(leaf), int(has_rgb), int(normal_k), int(k),
+                                                     float(smoothness), float(curvature_threshold), int(min_size), int(max_size), p_f,
+                                                     cols * 4, C.byref(nv), p_n, p_l, max_clusters, C.byref(ncl), offsets.ctypes.data, p_cp,
+                                                     p_ci)
+        self._after(st)
+        res = dict(filtered=filtered[:nv.value], normals=normals[:nv.value], labels=labels[:nv.value], n_clusters=ncl.value)
+        if status != 0:
+            err = PccError(status, (LIB.pcc_last_error() or b"").decode())
+            err.partial = res
+            raise err
+        offs = offsets[:ncl.value + 1].astype(np.int64)
+        m = int(offs[-1])
+        res.update(offsets=offs, cluster_points=cpts[:m] if cpts is not None else None,
+                   cluster_index=cidx[:m] if cidx is not None else None)
+        return res
 
     def normals(self, k: int = 50, viewpoint=None, device=None):
         """pcl::NormalEstimation over the index's own points: (n, 4) = nx, ny, nz, curvature.

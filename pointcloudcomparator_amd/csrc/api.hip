@@ -511,6 +511,7 @@ int pcc_index_destroy(pcc_index* ix) {
     rift_batch_release(ix);
     sift_batch_release(ix);
     rgb_batch_release(ix);
+    segment_release(ix);
     rift_release(ix);
     sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);

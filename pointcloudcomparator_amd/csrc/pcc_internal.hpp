@@ -299,6 +299,8 @@ struct BatchStaging {
 struct RiftBatchScratch;   // rift_batch.hip: BatchStaging and the CSR of pcc_rift_descriptors_batch
 struct SiftBatchScratch;   // sift_batch.hip: BatchStaging and the voxel keys, tables and CSR of pcc_sift_keypoints_batch
 struct RgbBatchScratch;    // region_rgb_batch.hip: BatchStaging and the rows of pcc_region_growing_rgb_batch
+struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
+                           // and the orders and tables of pcc_extract_clusters
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
@@ -389,6 +391,7 @@ struct pcc_index {
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
     pcc::RgbBatchScratch* rgb_batch = nullptr;    // made at the first pcc_region_growing_rgb_batch with this handle as its context (region_rgb_batch.hip)
+    pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -618,6 +621,15 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
 void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work handle
 // region_rgb_batch.hip: pcc_region_growing_rgb_batch behind its argument checks
 void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work handle
+// segment.hip: pcc_extract_clusters and pcc_region_growing_segmentation
+void segment_release(pcc_index* ix);  // frees ix->segment and its work handle
+// normals.hip: the plane fit over the self k-NN rows `keys` (n x K) of a packed cloud
+int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n,
+                   int K, const float vp[3], float4* out);
+// region.hip: pcl::RegionGrowing over the self k-NN rows of the index; *sweeps (nullable) = the sweeps it took to settle
+int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const float4* normals, int K, float smoothness,
+                        float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels_dev, int32_t* n_clusters,
+                        unsigned int* sweeps = nullptr);
 int grid_first_within(pcc_index* ix, const float4* q, size_t nq, double radius, int32_t* idx_dev);
 // ---- flann_order.hip: flags[i] = 1 when another reference shares query i's minimum distance; the tied queries walked
 // through FLANN's tree on the device

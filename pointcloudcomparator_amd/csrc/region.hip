@@ -260,7 +260,7 @@ inline int g1(size_t n) {
 // keys: the self k-NN rows of the index (n x K); normals: float4 (nx, ny, nz, curvature) on the device
 int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const float4* normals, int K, float smoothness,
                         float curvature_threshold, uint32_t min_size, uint32_t max_size, int32_t* labels_dev,
-                        int32_t* n_clusters) {
+                        int32_t* n_clusters, unsigned int* sweeps_out) {
     hipStream_t s = ix->stream;
     const unsigned int n = (unsigned int)ix->n_orig;
     const float cos_thr = cosf(smoothness);
@@ -288,6 +288,7 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
     unsigned int no_spread;
     PCC_TRY(read_back(ix, d_words, &no_spread));
     const bool general = no_spread != 0;  // some point would join a region without spreading
+    unsigned int sweeps = 0;
     const unsigned int wave_blocks = (n + 3) / 4;
     hipLaunchKernelGGL(k_rg_link, dim3(wave_blocks), dim3(256), 0, s, keys, normals, kth, ix->cell_refs.as<float4>(),
                        ix->d_grid.as<GridDev>(), K, cos_thr, curvature_threshold, parent);
@@ -316,6 +317,7 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
             unsigned int changed;
             PCC_TRY(read_back(ix, d_words + 1, &changed));
             cur ^= 1;
+            ++sweeps;
             if (changed == 0) break;
         }
         PCC_HIP(hipMemcpyAsync(comp_label, lab[cur], (size_t)n * 8, hipMemcpyDeviceToDevice, s));
@@ -337,6 +339,7 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
             unsigned int w[3];  // changed, (list count of collect), cross count
             PCC_TRY(read_back<3>(ix, d_words + 1, w));
             if (sweep == 0) n_cross = w[2];
+            ++sweeps;
             if (w[0] == 0 || n_cross == 0) break;
         }
     }
@@ -360,6 +363,7 @@ int grid_region_growing(pcc_index* ix, const unsigned long long* keys, const flo
     ev_mark(ix, EV_MAIN1);
     PCC_HIP(hipStreamSynchronize(s));  // host_list must outlive the H2D copy
     *n_clusters = (int32_t)ncl;
+    if (sweeps_out) *sweeps_out = sweeps;
     return PCC_OK;
 }
 
