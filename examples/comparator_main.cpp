@@ -52,6 +52,9 @@ static bool planes_device = false;
 // --segment-device (without -e): the whole default segmentation runs in one library call (pcc_region_growing_segmentation through
 // regionGrowingSegmentation): same lines, same clusters
 static bool segment_device = false;
+// --euclidean-device (with -e): the whole -e segmentation runs in one library call (pcc_euclidean_cluster_segmentation through
+// euclideanClusterSegmentation): same lines, same clusters
+static bool euclidean_device = false;
 static bool rift = false, sift = false, rift_loop = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
@@ -89,12 +92,29 @@ static void printUsage() {
               << "--segment-device   (this build, without -e) the default segmentation -- voxel grid, normals, region growing, one cloud\n"
               << "                   per cluster -- runs in ONE library call (pcc_region_growing_segmentation: the filtered cloud, its\n"
               << "                   index, normals and labels stay on the GPU): the same lines, the same clusters; ignored with -e\n"
+              << "--euclidean-device (this build, with -e) the -e segmentation -- voxel grid, plane removal, Euclidean clustering, one\n"
+              << "                   cloud per cluster -- runs in ONE library call (pcc_euclidean_cluster_segmentation: the filtered\n"
+              << "                   cloud, what remains after the planes, its index and labels stay on the GPU): the same lines, the\n"
+              << "                   same clusters; ignored without -e\n"
               << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
 }
 
 // src/segmentation.cpp:64-156 euclidean_cluster_segmentation: VoxelGrid 0.025 (:69-76) -> RANSAC plane
 // removal until <= 30 % of the points remain (:79-117) -> KdTree + EuclideanClusterExtraction (:119-156)
 static std::vector<PointCloud<PointXYZRGB>::Ptr> euclidean_cluster_segmentation(const PointCloud<PointXYZRGB>::Ptr& point_cloud_ptr) {
+    if (euclidean_device) {
+        RemovedPlanes planes;
+        size_t n_filtered = 0;
+        std::vector<PointCloud<PointXYZRGB>::Ptr> found = euclideanClusterSegmentation<PointXYZRGB>(
+            point_cloud_ptr, 0.025f, 0.3, 100, 0.02, true, 0.05, 100, 250000, planes, nullptr, &n_filtered);
+        std::cout << "PointCloud after filtering has: " << n_filtered << " data points." << std::endl;
+        for (std::uint32_t size : planes.sizes)
+            std::cout << "PointCloud representing the planar component: " << size << " data points." << std::endl;
+        if (planes.ended_without_model) std::cout << "Could not estimate a planar model for the given dataset." << std::endl;
+        for (const PointCloud<PointXYZRGB>::Ptr& c : found)
+            std::cout << "PointCloud representing the Cluster: " << c->points.size() << " data points." << std::endl;
+        return found;
+    }
     VoxelGrid<PointXYZRGB> vg;
     PointCloud<PointXYZRGB>::Ptr cloud_filtered(new PointCloud<PointXYZRGB>);
     vg.setInputCloud(point_cloud_ptr);
@@ -411,6 +431,7 @@ int main(int argc, char** argv) {
         else if (a == "--rgb-batch") rgb_batch = true;
         else if (a == "--planes-device") planes_device = true;
         else if (a == "--segment-device") segment_device = true;
+        else if (a == "--euclidean-device") euclidean_device = true;
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }

@@ -8,6 +8,7 @@
 //   EuclideanClusterExtraction      the -e path (src/segmentation.cpp:119-131)
 //   removePlanes                    the plane-removal loop in front of it (src/segmentation.cpp:79-117) as one call
 //   regionGrowingSegmentation       the default path (src/segmentation.cpp:218-327) as one call
+//   euclideanClusterSegmentation    the -e path (src/segmentation.cpp:64-156) as one call
 // Everything numerical happens behind the C-ABI; this header is plumbing a maintainer of the
 // reference can include instead of the PCL headers for these five call sites.
 #pragma once
@@ -561,6 +562,114 @@ inline std::vector<typename PointCloud<PointT>::Ptr> regionGrowingSegmentation(
     }
     kept->points.resize(nv);
     kept->width = (std::uint32_t)nv;
+    for (int32_t c = 0; c < ncl; ++c) {
+        typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+        one->points.assign(members.begin() + offsets[c], members.begin() + offsets[c + 1]);
+        one->width = (std::uint32_t)one->points.size();
+        one->height = 1;
+        one->is_dense = true;
+        clusters.push_back(one);
+    }
+    return clusters;
+}
+
+// ---- euclidean_cluster_segmentation (src/segmentation.cpp:64-156) in one library call ----------------------
+// VoxelGrid leaf -> the plane-removal loop -> EuclideanClusterExtraction -> one cloud per cluster: what the VoxelGrid,
+// SACSegmentation, ExtractIndices, KdTree and EuclideanClusterExtraction objects above give together (same planes, same
+// remaining points, same clusters, same order), but the filtered cloud, what remains of it, its index and its labels never leave
+// the device (pcc_euclidean_cluster_segmentation).  planes: what removePlanes reports.  *remaining (may be null) receives the cloud
+// the clusters are taken from, *n_filtered (may be null) the size of the voxel grid's output.  The call starts with room for
+// first_planes planes and first_clusters clusters and is repeated once with the room it asks for (tests start it with less).  A
+// leaf too small for the cloud (PCC_ERR_UNSUPPORTED) takes the class path, as in regionGrowingSegmentation.
+template <class PointT>
+inline std::vector<typename PointCloud<PointT>::Ptr> euclideanClusterSegmentation(
+    const typename PointCloud<PointT>::ConstPtr& cloud, float leaf, double stop_fraction, int max_iterations, double distance_threshold,
+    bool optimize, double tolerance, int min_size, int max_size, RemovedPlanes& planes,
+    typename PointCloud<PointT>::Ptr* remaining = nullptr, size_t* n_filtered = nullptr, size_t first_planes = 64,
+    size_t first_clusters = 256) {
+    std::vector<typename PointCloud<PointT>::Ptr> clusters;
+    typename PointCloud<PointT>::Ptr rest(new PointCloud<PointT>);
+    rest->height = 1;
+    rest->is_dense = true;
+    planes = RemovedPlanes();
+    if (remaining) *remaining = rest;
+    if (n_filtered) *n_filtered = 0;
+    if (!cloud || cloud->empty()) return clusters;
+    struct Context {
+        pcc_index* h = nullptr;
+        ~Context() { pcc_index_destroy(h); }
+    };
+    static thread_local Context context;
+    if (!context.h) {
+        const float one[3] = {0.f, 0.f, 0.f};
+        check(pcc_index_create(one, 1, 12, 3, PCC_MEM_HOST, 0, PCC_ENGINE_BRUTE, &context.h));
+    }
+    const size_t n = cloud->size();
+    // (the one other PCC_ERR_UNSUPPORTED of the call: refused here, so that the status below can only mean the leaf)
+    if (n >= (1ull << 31)) throw Error(PCC_ERR_UNSUPPORTED, "euclideanClusterSegmentation: more than 2^31 points");
+    const int has_rgb = sizeof(PointT) >= 20 ? 1 : 0;
+    const double probability = 0.99;  // (SACSegmentation's default, as removePlanes)
+    rest->points.resize(n);
+    std::vector<PointT> members(n);
+    std::vector<size_t> offsets;
+    size_t plane_room = first_planes, cluster_room = first_clusters, found = 0, nv = 0, left = 0;
+    int ended = 0;
+    int32_t ncl = 0;
+    for (int attempt = 0; attempt < 3; ++attempt) {
+        planes.sizes.resize(std::max<size_t>(plane_room, 1));
+        planes.coefficients.resize(std::max<size_t>(plane_room, 1));
+        offsets.assign(cluster_room + 1, 0);
+        const int st = pcc_euclidean_cluster_segmentation(
+            context.h, cloud->points.data(), n, sizeof(PointT), PCC_MEM_HOST, leaf, has_rgb, stop_fraction, max_iterations, distance_threshold,
+            probability, optimize ? 1 : 0, plane_room, planes.coefficients[0].data(), planes.sizes.data(), nullptr, &found, &ended, tolerance,
+            (uint32_t)min_size, (uint32_t)max_size, rest->points.data(), sizeof(PointT), &nv, &left, nullptr, cluster_room, &ncl,
+            offsets.data(), cluster_room ? members.data() : nullptr, nullptr);
+        if (st == PCC_ERR_OVERFLOW && attempt < 2) {
+            // once more with the room it asks for: every plane removes at least one point, so nv planes always suffice; the
+            // cluster count is reported.  (Too many planes are met before any cluster: at most two repeats, one of each kind)
+            if (found == plane_room && (size_t)ncl <= cluster_room) plane_room = std::max<size_t>(nv, 1);
+            else cluster_room = (size_t)ncl;
+            continue;
+        }
+        if (st == PCC_ERR_UNSUPPORTED) {
+            // the objects the call replaces, as examples/comparator_main.cpp drives them
+            typename PointCloud<PointT>::Ptr kept(new PointCloud<PointT>);
+            VoxelGrid<PointT> vg;
+            vg.setInputCloud(cloud);
+            vg.setLeafSize(leaf, leaf, leaf);
+            vg.filter(*kept);
+            if (n_filtered) *n_filtered = kept->size();
+            rest = removePlanes<PointT>(kept, planes, stop_fraction, max_iterations, distance_threshold, optimize, probability);
+            if (remaining) *remaining = rest;
+            typename search::KdTree<PointT>::Ptr tree(new search::KdTree<PointT>);
+            tree->setInputCloud(rest);
+            std::vector<PointIndices> found_clusters;
+            EuclideanClusterExtraction<PointT> ec;
+            ec.setClusterTolerance(tolerance);
+            ec.setMinClusterSize(min_size);
+            ec.setMaxClusterSize(max_size);
+            ec.setSearchMethod(tree);
+            ec.setInputCloud(rest);
+            ec.extract(found_clusters);
+            for (const PointIndices& c : found_clusters) {
+                typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
+                for (int j : c.indices) one->points.push_back(rest->points[j]);
+                one->width = (std::uint32_t)one->points.size();
+                one->height = 1;
+                one->is_dense = true;
+                clusters.push_back(one);
+            }
+            return clusters;
+        }
+        check(st);
+        break;
+    }
+    planes.sizes.resize(found);
+    planes.coefficients.resize(found);
+    planes.ended_without_model = ended != 0;
+    if (n_filtered) *n_filtered = nv;
+    rest->points.resize(left);
+    rest->width = (std::uint32_t)left;
     for (int32_t c = 0; c < ncl; ++c) {
         typename PointCloud<PointT>::Ptr one(new PointCloud<PointT>);
         one->points.assign(members.begin() + offsets[c], members.begin() + offsets[c + 1]);

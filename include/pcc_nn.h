@@ -553,6 +553,51 @@ int pcc_region_growing_segmentation(pcc_index *ctx, const void *pts, size_t n, s
                                     float *out_normals, int32_t *out_labels,
                                     size_t max_clusters, int32_t *n_clusters, size_t *out_offsets,
                                     void *out_cluster_points, int32_t *out_cluster_index);
+/* ---- the -e segmentation path in one call ------------------------------------------------------------------
+ * replaces: euclidean_cluster_segmentation (src/segmentation.cpp:64-156): VoxelGrid leaf (0.025, :69-74) -> the plane-removal
+ *   loop (:79-117) -> EuclideanClusterExtraction (0.05, 100, 250000, :122-131) -> one cloud per cluster (:133-152).  Every output
+ *   is bit for bit what this sequence of calls gives, and where a step of it fails the call returns that step's status:
+ *
+ *     pcc_voxel_grid(ctx, pts, n, stride_bytes, mem, leaf, has_rgb, F, out_stride_bytes, &nv)      -> *n_filtered = nv
+ *     pcc_plane_removal(ctx, F, nv, out_stride_bytes, mem, stop_fraction, max_iterations, distance_threshold, probability,
+ *                       optimize, max_planes, ..., R, out_stride_bytes, record_bytes = out_stride_bytes)
+ *                                        -> the plane tables, *n_planes, *ended_without_model, *n_remaining = nr, out_points = R
+ *     H = pcc_index_create(R, nr, out_stride_bytes, ...)            (a fresh handle, default tie order)
+ *     pcc_euclidean_clusters(H, tolerance, min_size, max_size, ...)                                 -> out_labels[0 .. nr), *n_clusters
+ *     pcc_extract_clusters(ctx, R, nr, out_stride_bytes, out_stride_bytes, labels, *n_clusters, ...) -> out_offsets, out_cluster_*
+ *
+ *   but the filtered cloud, the cloud that remains, its index and its labels stay on the device from the raw cloud to the cluster
+ *   clouds.  Only scalars cross to the host inside the call: the voxel grid's block statistics and count, what the plane fit
+ *   brings per turn (pcc_plane_removal), the cluster count, the offsets.  Up to 2048 clusters are numbered on the device; with
+ *   more, the cluster list takes pcc_euclidean_clusters' host sort.
+ * out_points (space `mem`, capacity n records of out_stride_bytes): the cloud that remains after the planes (the reference's
+ *   cloud_filtered at :119), *n_remaining (HOST) whole voxel-grid records; the bytes of a record pcc_voxel_grid does not write are
+ *   zero in both memory spaces.  *n_filtered (HOST): the points after the voxel grid.  out_labels[n] (space `mem`, may be NULL):
+ *   its first *n_remaining entries.  out_offsets[max_clusters + 1] (HOST), out_cluster_points (space `mem`, may be NULL, capacity n
+ *   records of out_stride_bytes), out_cluster_index[n] (space `mem`, may be NULL): as in pcc_region_growing_segmentation, over
+ *   the remaining cloud.  out_coefficients, out_plane_sizes, out_iterations, *n_planes, *ended_without_model, max_planes: as in
+ *   pcc_plane_removal; its PCC_ERR_OVERFLOW leaves *n_filtered valid and the arrays in space `mem` unspecified.
+ * *n_clusters > max_clusters: PCC_ERR_OVERFLOW with *n_clusters, *n_filtered, *n_remaining, the plane outputs, out_points and
+ *   out_labels valid; the cluster outputs are unspecified.
+ * No finite point (or n == 0): PCC_OK, every count 0, out_offsets[0] = 0.  Nothing remaining after the planes: PCC_OK, 0 clusters.
+ * Refused before any device is touched, nothing written, in this order: what pcc_voxel_grid refuses (same messages); what
+ *   pcc_plane_removal refuses about its own parameters and tables (same messages); a tolerance that is negative or NaN; a NULL
+ *   n_filtered, n_remaining, n_clusters or out_offsets; out_cluster_points or out_cluster_index with max_clusters == 0; a null
+ *   handle last.
+ * `ctx` is any index handle: the cloud it indexes, its tie order and its kept rows are neither read nor changed.  The remaining
+ *   cloud is indexed on the work handle pcc_region_growing_segmentation keeps in `ctx` (under ctx's options), freed with it.
+ *   Afterwards pcc_index_stats reports in [0] the filtered points, [1] the clusters, [2] the clustered points, [3] the planes
+ *   removed and [4] the turns that took a host copy of the current cloud. */
+int pcc_euclidean_cluster_segmentation(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                                       float leaf, int has_rgb,
+                                       double stop_fraction, int max_iterations, double distance_threshold, double probability,
+                                       int optimize, size_t max_planes, float *out_coefficients, uint32_t *out_plane_sizes,
+                                       int *out_iterations, size_t *n_planes, int *ended_without_model,
+                                       double tolerance, uint32_t min_size, uint32_t max_size,
+                                       void *out_points, size_t out_stride_bytes, size_t *n_filtered, size_t *n_remaining,
+                                       int32_t *out_labels,
+                                       size_t max_clusters, int32_t *n_clusters, size_t *out_offsets,
+                                       void *out_cluster_points, int32_t *out_cluster_index);
 /* ---- RIFT descriptors of the indexed cloud ---------------------------------------------------------
  * replaces: processRIFT (src/comparator.cpp:590-684) for one cloud: pcl::PointCloudXYZRGBtoXYZI, pcl::NormalEstimation
  *   (setRadiusSearch 0.03, :628-635), removeNaNNormalsFromPointCloud (:637-646), pcl::IntensityGradientEstimation

@@ -35,7 +35,7 @@ SYMBOLS = [
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
     "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
-    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_rigid_from_sums",
+    "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_euclidean_cluster_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
@@ -106,6 +106,9 @@ def _load() -> C.CDLL:
     lib.pcc_extract_clusters.argtypes = [vp, vp, sz, sz, sz, vp, i32, i32, vp, sz, vp, vp]
     lib.pcc_region_growing_segmentation.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, i32, i32, C.c_float, C.c_float, C.c_uint32,
                                                     C.c_uint32, vp, sz, C.POINTER(sz), vp, vp, sz, C.POINTER(i32), vp, vp, vp]
+    lib.pcc_euclidean_cluster_segmentation.argtypes = [vp, vp, sz, sz, i32, C.c_float, i32, C.c_double, i32, C.c_double, C.c_double, i32, sz,
+                                                       vp, vp, vp, C.POINTER(sz), C.POINTER(i32), C.c_double, C.c_uint32, C.c_uint32, vp,
+                                                       sz, C.POINTER(sz), C.POINTER(sz), vp, sz, C.POINTER(i32), vp, vp, vp]
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
@@ -765,6 +768,54 @@ class Index:
                                                      p_ci)
         self._after(st)
         res = dict(filtered=filtered[:nv.value], normals=normals[:nv.value], labels=labels[:nv.value], n_clusters=ncl.value)
+        if status != 0:
+            err = PccError(status, (LIB.pcc_last_error() or b"").decode())
+            err.partial = res
+            raise err
+        offs = offsets[:ncl.value + 1].astype(np.int64)
+        m = int(offs[-1])
+        res.update(offsets=offs, cluster_points=cpts[:m] if cpts is not None else None,
+                   cluster_index=cidx[:m] if cidx is not None else None)
+        return res
+
+    def euclidean_cluster_segmentation(self, points, leaf: float = 0.025, has_rgb: bool = False, stop_fraction: float = 0.3,
+                                       max_iterations: int = 100, threshold: float = 0.02, probability: float = 0.99,
+                                       optimize: bool = True, max_planes: int = 64, tolerance: float = 0.05, min_size: int = 100,
+                                       max_size: int = 250000, max_clusters: int = 4096):
+        """pcc_euclidean_cluster_segmentation: the reference's -e segmentation path (src/segmentation.cpp:64-156) in one call:
+        VoxelGrid -> the plane-removal loop -> EuclideanClusterExtraction -> one cloud per cluster, nothing cloud-sized crossing to
+        the host in between.  points: (n, >= 3) float32 numpy array or torch tensor (a CUDA tensor gives CUDA results); has_rgb:
+        the colour word in column 4 is averaged.  Returns a dict: n_filtered (the points after the voxel grid), points
+        (n_remaining, columns) the records that remain after the planes, labels (n_remaining,), n_clusters, offsets
+        (n_clusters + 1,), cluster_points (m, columns), cluster_index (m,): cluster c is the slice offsets[c]:offsets[c + 1] of
+        the last two; coefficients (p, 4), plane_sizes (p,), iterations (p,), ended_without_model as Index.plane_removal gives
+        them.  More than max_planes planes or max_clusters clusters raises PccError (PCC_ERR_OVERFLOW) whose `partial` holds the
+        dict without the cluster arrays (after too many planes only its counts and plane tables are valid)."""
+        ptr, n, stride, mem = _points(points)
+        max_planes, max_clusters = int(max_planes), int(max_clusters)
+        assert max_planes >= 0, "max_planes must not be negative"
+        assert max_clusters >= 0, "max_clusters must not be negative"
+        cols = int(points.shape[1])
+        cap = max(n, 1)
+        remaining, p_r = _out(points, (cap, cols), np.float32)
+        labels, p_l = _out(points, (cap,), np.int32)
+        cpts, p_cp = _out(points, (cap, cols), np.float32) if max_clusters else (None, None)
+        cidx, p_ci = _out(points, (cap,), np.int32) if max_clusters else (None, None)
+        offsets = np.zeros(max_clusters + 1, dtype=np.uintp)
+        coeff = np.zeros((max(max_planes, 1), 4), dtype=np.float32)
+        sizes = np.zeros(max(max_planes, 1), dtype=np.uint32)
+        its = np.zeros(max(max_planes, 1), dtype=np.int32)
+        nv, nr, n_planes, ended, ncl = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_int32(0), C.c_int32(0)
+        st = self._before(points)
+        status = LIB.pcc_euclidean_cluster_segmentation(
+            self._h, ptr, n, stride, mem, float(leaf), int(has_rgb), float(stop_fraction), int(max_iterations), float(threshold),
+            float(probability), int(optimize), max_planes, coeff.ctypes.data, sizes.ctypes.data, its.ctypes.data, C.byref(n_planes),
+            C.byref(ended), float(tolerance), int(min_size), int(max_size), p_r, cols * 4, C.byref(nv), C.byref(nr), p_l, max_clusters,
+            C.byref(ncl), offsets.ctypes.data, p_cp, p_ci)
+        self._after(st)
+        p = n_planes.value
+        res = dict(n_filtered=nv.value, points=remaining[:nr.value], labels=labels[:nr.value], n_clusters=ncl.value,
+                   coefficients=coeff[:p], plane_sizes=sizes[:p], iterations=its[:p], ended_without_model=bool(ended.value))
         if status != 0:
             err = PccError(status, (LIB.pcc_last_error() or b"").decode())
             err.partial = res

@@ -584,6 +584,55 @@ k_uf_label(const float4* __restrict__ refs, const unsigned int* __restrict__ par
         if (__float_as_int(refs[i].w) >= 0) labels[i] = id_of_root[parent[i]];  // position == original index
 }
 
+// The cluster numbering on the device: PCL's order is size descending, and among equal sizes the lowest member index first.  The
+// collect kernels fill their list in atomicAdd order, but the keys (size, lowest member) are unique: a cluster's id is the number
+// of list entries that precede it.  One workgroup: the list (root, size, lowest member, -) goes into LDS, every thread ranks
+// its entries by a counting pass over the LDS copy -- the loop is uniform over the wave and every lane reads the same entry, one
+// LDS broadcast per step --, and writes id_of_root[root] = rank and sizes[rank].  No atomics, one writer per word, nothing that
+// depends on the order of execution.  WIDE: the cells form's uint4 entries; else (root, size) with the root the lowest member.
+template <bool WIDE>
+__global__ void __launch_bounds__(256)
+k_ec_rank(const void* __restrict__ list, unsigned int ncl, int* __restrict__ id_of_root, unsigned int* __restrict__ sizes) {
+    __shared__ uint4 e[EC_RANK_MAX];
+    if (ncl > EC_RANK_MAX) return;  // (the caller takes the host sort then: never launched so)
+    for (unsigned int k = threadIdx.x; k < ncl; k += 256) {
+        if (WIDE) {
+            e[k] = static_cast<const uint4*>(list)[k];
+        } else {
+            const uint2 v = static_cast<const uint2*>(list)[k];
+            e[k] = make_uint4(v.x, v.y, v.x, 0u);
+        }
+    }
+    __syncthreads();
+    for (unsigned int k = threadIdx.x; k < ncl; k += 256) {
+        const uint4 me = e[k];
+        unsigned int rank = 0;
+        for (unsigned int j = 0; j < ncl; ++j) {
+            const uint4 o = e[j];
+            rank += (o.y > me.y || (o.y == me.y && o.z < me.z)) ? 1u : 0u;
+        }
+        id_of_root[me.x] = (int)rank;  // (rank < ncl: the keys are distinct)
+        sizes[rank] = me.y;
+    }
+}
+
+// the list numbered on the device (ncl <= EC_RANK_MAX; sizes_dev lies behind the list in scratch_b); the caller's sizes, if any,
+// come down with a wait of their own
+template <bool WIDE>
+static int rank_on_device(pcc_index* ix, const void* list, unsigned int ncl, int* id_of_root, unsigned int* sizes_dev) {
+    hipLaunchKernelGGL(k_ec_rank<WIDE>, dim3(1), dim3(256), 0, ix->stream, list, ncl, id_of_root, sizes_dev);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+static int rank_sizes_to_host(pcc_index* ix, const unsigned int* sizes_dev, unsigned int ncl, int32_t* sizes, int max_sizes) {
+    const size_t k = std::min<size_t>(ncl, (size_t)std::max(max_sizes, 0));
+    if (!sizes || k == 0) return PCC_OK;
+    PCC_HIP(hipMemcpyAsync(sizes, sizes_dev, k * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+static inline size_t rank_sizes_offset(size_t list_bytes) { return (list_bytes + 16 + 15) / 16 * 16; }
+
 static inline int g1(size_t n) {
     size_t b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -592,7 +641,7 @@ static inline int g1(size_t n) {
 // the union-find over cells (kernels k_ecc_*): the clustering grid is built (vox_a: points in its cell order, vox_c: CSR
 // starts, vox_b: its GridDev)
 static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint32_t max_size, int32_t* labels_dev,
-                               int32_t* n_clusters, int32_t* sizes, int max_sizes) {
+                               int32_t* n_clusters, int32_t* sizes, int max_sizes, bool device_rank) {
     hipStream_t s = ix->stream;
     const unsigned int n = (unsigned int)ix->n_orig;
     const unsigned int cap = min_size > 0 ? n / min_size + 1 : n;
@@ -600,7 +649,8 @@ static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint3
     PCC_TRY(ix->scratch_d.reserve((size_t)n * 4));
     PCC_TRY(ix->scratch_e.reserve((size_t)n * 4));
     PCC_TRY(ix->scratch_f.reserve((size_t)n * 4));
-    PCC_TRY(ix->scratch_b.reserve((size_t)cap * sizeof(uint4) + 16));
+    const size_t sizes_at = rank_sizes_offset((size_t)cap * sizeof(uint4));
+    PCC_TRY(ix->scratch_b.reserve(device_rank ? sizes_at + EC_RANK_MAX * sizeof(unsigned int) : (size_t)cap * sizeof(uint4) + 16));
     unsigned int* cparent = ix->scratch_c.as<unsigned int>();
     unsigned int* size = ix->scratch_d.as<unsigned int>();
     int* id_of_root = ix->scratch_e.as<int>();
@@ -630,6 +680,17 @@ static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint3
     unsigned int ncl;
     PCC_TRY(read_back(ix, d_count, &ncl));
     if (ncl > cap) { set_error("cluster list overflow (%u > %u)", ncl, cap); return PCC_ERR_OVERFLOW; }
+    if (device_rank && ncl <= EC_RANK_MAX) {
+        unsigned int* sizes_dev = reinterpret_cast<unsigned int*>(static_cast<char*>(ix->scratch_b.p) + sizes_at);
+        if (ncl) {
+            PCC_TRY(rank_on_device<true>(ix, list, ncl, id_of_root, sizes_dev));
+            hipLaunchKernelGGL(k_ecc_label, gp, blk, 0, s, cr2, cs2, gd2, cparent, id_of_root, labels_dev);
+            PCC_HIP(hipGetLastError());
+        }
+        ev_mark(ix, EV_MAIN1);
+        if (n_clusters) *n_clusters = (int32_t)ncl;
+        return rank_sizes_to_host(ix, sizes_dev, ncl, sizes, max_sizes);
+    }
     std::vector<uint4> host_list(ncl);
     if (ncl) {
         PCC_HIP(hipMemcpyAsync(host_list.data(), list, (size_t)ncl * sizeof(uint4), hipMemcpyDeviceToHost, s));
@@ -654,7 +715,7 @@ static int grid_clusters_cells(pcc_index* ix, float r2, uint32_t min_size, uint3
 }
 
 int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t max_size,
-                  int32_t* labels_dev, int32_t* n_clusters, int32_t* sizes, int max_sizes) {
+                  int32_t* labels_dev, int32_t* n_clusters, int32_t* sizes, int max_sizes, bool device_rank) {
     hipStream_t s = ix->stream;
     const unsigned int n = (unsigned int)ix->n_orig;
     // (built first: the cell sort uses the scratch buffers the union-find arrays live in afterwards)
@@ -705,13 +766,14 @@ int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t 
         }
     }
     if (cells_ok && ix->opt.ec_cells >= 3)
-        return grid_clusters_cells(ix, r2, min_size, max_size, labels_dev, n_clusters, sizes, max_sizes);
+        return grid_clusters_cells(ix, r2, min_size, max_size, labels_dev, n_clusters, sizes, max_sizes, device_rank);
     // scratch: parent[n] | size[n] | id_of_root[n] | list[cap]
     const unsigned int cap = min_size > 0 ? n / min_size + 1 : n;
     PCC_TRY(ix->scratch_c.reserve((size_t)n * 4));
     PCC_TRY(ix->scratch_d.reserve((size_t)n * 4));
     PCC_TRY(ix->scratch_e.reserve((size_t)n * 4));
-    PCC_TRY(ix->scratch_b.reserve((size_t)cap * sizeof(uint2) + 16));
+    const size_t sizes_at = rank_sizes_offset((size_t)cap * sizeof(uint2));
+    PCC_TRY(ix->scratch_b.reserve(device_rank ? sizes_at + EC_RANK_MAX * sizeof(unsigned int) : (size_t)cap * sizeof(uint2) + 16));
     unsigned int* parent = ix->scratch_c.as<unsigned int>();
     unsigned int* size = ix->scratch_d.as<unsigned int>();
     int* id_of_root = ix->scratch_e.as<int>();
@@ -744,6 +806,15 @@ int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t 
     unsigned int ncl;
     PCC_TRY(read_back(ix, d_count, &ncl));
     if (ncl > cap) { set_error("cluster list overflow (%u > %u)", ncl, cap); return PCC_ERR_OVERFLOW; }
+    if (device_rank && ncl <= EC_RANK_MAX) {
+        unsigned int* sizes_dev = reinterpret_cast<unsigned int*>(static_cast<char*>(ix->scratch_b.p) + sizes_at);
+        if (ncl) PCC_TRY(rank_on_device<false>(ix, list, ncl, id_of_root, sizes_dev));
+        hipLaunchKernelGGL(k_uf_label, dim3(g1(n)), dim3(256), 0, s, ix->refs.as<float4>(), parent, id_of_root, n, labels_dev);
+        PCC_HIP(hipGetLastError());
+        ev_mark(ix, EV_MAIN1);
+        if (n_clusters) *n_clusters = (int32_t)ncl;
+        return rank_sizes_to_host(ix, sizes_dev, ncl, sizes, max_sizes);
+    }
     std::vector<uint2> host_list(ncl);
     if (ncl) {
         PCC_HIP(hipMemcpyAsync(host_list.data(), list, (size_t)ncl * sizeof(uint2), hipMemcpyDeviceToHost, s));

@@ -580,6 +580,37 @@ int grid_radius(pcc_index* ix, const float4* q, size_t nq, float r, float r2, in
                 const int64_t* offsets, unsigned long long* keys, int sorted, size_t total = 0, int32_t* idx_out = nullptr,
                 float* d2_out = nullptr, bool* delivered = nullptr);
 constexpr int PCC_ERR_RETRY_HOST = -1000;  // sac_plane without a host array met a degenerate sample: repeat with one (internal)
+// sac.hip: the loop of pcc_plane_removal over a cloud's records (arguments checked, n > 0).  It stages the cloud in q_packed and
+// ping-pongs it with vox_a, the original indices between vox_b and vox_c; waits only where sac_plane() waits.  PCC_ERR_OVERFLOW
+// (more than max_planes planes) leaves the counts of the planes found.
+struct PlaneLoop {
+    const void* pts = nullptr;  // records in space `mem`; a host array is read on turn 0 (single points)
+    size_t n = 0, stride = 0;
+    int mem = 0;
+    double stop_fraction = 0, threshold = 0, probability = 0;
+    int max_iterations = 0, optimize = 0;
+    size_t max_planes = 0;
+    float* out_coefficients = nullptr;     // host tables, as pcc_plane_removal's
+    uint32_t* out_plane_sizes = nullptr;
+    int* out_iterations = nullptr;         // nullable
+    int* ended_without_model = nullptr;    // nullable
+    int32_t* plane_of_point = nullptr;     // device, nullable
+    // results
+    size_t planes = 0, remaining = 0;
+    uint64_t host_copies = 0;              // turns that took a host copy of the current cloud (a degenerate sample)
+    const int32_t* remaining_index = nullptr;  // device: the original indices of the points that remain, ascending (vox_b or vox_c)
+};
+int plane_loop(pcc_index* ix, PlaneLoop& L);
+int check_plane_loop(double stop_fraction, int max_iterations, double threshold, double probability, size_t max_planes,
+                     const float* out_coefficients, const uint32_t* out_plane_sizes, const void* n_planes, const void* n_remaining);
+// out record j = the first record_bytes of input record idx[j] (k_planes_records), both on the device
+int launch_plane_records(hipStream_t s, const void* in, size_t stride, const int32_t* idx, size_t m, size_t record_bytes, void* out,
+                         size_t out_stride);
+// cluster.hip: pcl::EuclideanClusterExtraction over the indexed cloud, labels_dev[n_orig].  device_rank: up to EC_RANK_MAX clusters
+// are numbered by k_ec_rank instead of the host sort (one wait, for the count)
+constexpr unsigned int EC_RANK_MAX = 2048;
+int grid_clusters(pcc_index* ix, float r, float r2, uint32_t min_size, uint32_t max_size, int32_t* labels_dev, int32_t* n_clusters,
+                  int32_t* sizes, int max_sizes, bool device_rank = false);
 // the two halves of pcc_normals_radius (normals.hip): the sorted self radius rows of the indexed cloud as a CSR (keys: d2 bits << 32 | point
 // index; offsets[n + 1]; both stay valid until the next radius search on the handle), and the plane fit over such rows
 int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys, const unsigned int** offsets);

@@ -458,17 +458,100 @@ int pcc_sac_plane(pcc_index* ix, const void* pts, size_t n, size_t stride, int m
     return PCC_OK;
 }
 
+}  // extern "C"
+
 // The plane-removal loop of the -e path (reference src/segmentation.cpp:79-117) with the cloud staged ONCE: every turn is a
 // fresh sac_plane() on the current device cloud, then k_planes_partition moves what stays into the other ping-pong buffer.
 // The staged float4 holds bits(original index) in w for a finite point and -1 for a non-finite one; sac_plane's kernels read
 // only its sign, and the partition copies it verbatim, so a compacted cloud differs from a restaged one in no bit that is read.
 // A turn waits for nothing beyond sac_plane()'s own waits: the inlier count it returns decides the loop.
-int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, double stop_fraction, int max_iterations,
-                      double threshold, double probability, int optimize, size_t max_planes, float* out_coefficients,
-                      uint32_t* out_plane_sizes, int* out_iterations, size_t* n_planes, int* ended_without_model,
-                      int32_t* out_plane_of_point, int32_t* out_remaining_index, size_t* n_remaining, void* out_points,
-                      size_t out_stride, size_t record_bytes) {
-    PCC_TRY(check_points(pts, n, stride, mem));
+// The loop itself, shared by pcc_plane_removal and pcc_euclidean_cluster_segmentation (segment.hip): arguments checked, n > 0.
+namespace pcc {
+int plane_loop(pcc_index* ix, PlaneLoop& L) {
+    hipStream_t s = ix->stream;
+    const size_t n = L.n;
+    const double stop_size = L.stop_fraction * (double)n;  // (:91: size() > 0.3 * nr_points, in double)
+    const bool any_turn = (double)n > stop_size;
+    // every buffer before any pointer into one is taken (a DevBuf that grows moves)
+    if (any_turn) PCC_TRY(stage_queries(ix, L.pts, n, L.stride, L.mem));
+    PCC_TRY(ix->vox_a.reserve(n * sizeof(float4)));
+    PCC_TRY(ix->vox_b.reserve(n * sizeof(int32_t)));
+    PCC_TRY(ix->vox_c.reserve(n * sizeof(int32_t)));
+    PCC_TRY(ix->out_idx.reserve(n * sizeof(int32_t)));
+    const float4* cur = ix->q_packed.as<float4>();
+    float4* other = ix->vox_a.as<float4>();
+    int32_t* orig = ix->vox_b.as<int32_t>();
+    int32_t* other_orig = ix->vox_c.as<int32_t>();
+    hipLaunchKernelGGL(k_planes_begin, dim3(g1(n)), dim3(256), 0, s, (unsigned int)n, orig, L.plane_of_point);
+    PCC_HIP(hipGetLastError());
+
+    size_t cur_n = n, planes = 0;
+    uint64_t host_copies = 0;
+    int status = PCC_OK;
+    while ((double)cur_n > stop_size) {
+        if (planes == L.max_planes) { set_error("more than max_planes = %zu planes", L.max_planes); status = PCC_ERR_OVERFLOW; break; }
+        size_t m = 0;
+        float coeff[4];
+        int its = 0;
+        // turn 0 of a host cloud reads single points from the caller's own array, as pcc_sac_plane does; every other turn
+        // gathers the few points the host needs on the device
+        const char* own = (planes == 0 && L.mem == PCC_MEM_HOST) ? static_cast<const char*>(L.pts) : nullptr;
+        int st = sac_plane(ix, cur, cur_n, own, L.stride, L.max_iterations, L.threshold, L.probability, L.optimize,
+                           ix->out_idx.as<int32_t>(), &m, coeff, &its);
+        if (st == PCC_ERR_RETRY_HOST) {
+            // a degenerate sample (pcc_sac_plane above): this turn alone with a host copy of the CURRENT cloud
+            PCC_TRY(ix->host_b.reserve(cur_n * sizeof(float4)));
+            float4* hp = ix->host_b.as<float4>();
+            PCC_HIP(hipMemcpyAsync(hp, cur, cur_n * sizeof(float4), hipMemcpyDeviceToHost, s));
+            PCC_HIP(hipStreamSynchronize(s));
+            const float qnan = std::nanf("");
+            for (size_t i = 0; i < cur_n; ++i)
+                if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
+            ++host_copies;
+            st = sac_plane(ix, cur, cur_n, reinterpret_cast<const char*>(hp), sizeof(float4), L.max_iterations, L.threshold,
+                           L.probability, L.optimize, ix->out_idx.as<int32_t>(), &m, coeff, &its);
+        }
+        PCC_TRY(st);
+        if (m == 0) {  // :95-100 "Could not estimate a planar model for the given dataset."
+            if (L.ended_without_model) *L.ended_without_model = 1;
+            break;
+        }
+        std::memcpy(L.out_coefficients + 4 * planes, coeff, sizeof(coeff));
+        L.out_plane_sizes[planes] = (uint32_t)m;
+        if (L.out_iterations) L.out_iterations[planes] = its;
+        hipLaunchKernelGGL(k_planes_partition, dim3(g1(cur_n)), dim3(256), 0, s, cur, orig, (unsigned int)cur_n,
+                           ix->scratch_c.as<unsigned int>(), (int32_t)planes, other, other_orig, L.plane_of_point);
+        PCC_HIP(hipGetLastError());
+        float4* freed = const_cast<float4*>(cur);  // (turn 0 frees q_packed: the staged cloud is not needed again)
+        cur = other;
+        other = freed;
+        std::swap(orig, other_orig);
+        cur_n -= m;
+        ++planes;
+    }
+    L.planes = planes;
+    L.remaining = cur_n;
+    L.host_copies = host_copies;
+    L.remaining_index = orig;
+    return status;
+}
+
+int launch_plane_records(hipStream_t s, const void* in, size_t stride, const int32_t* idx, size_t m, size_t record_bytes, void* out,
+                         size_t out_stride) {
+    if (m == 0) return PCC_OK;
+    const bool vec = record_bytes % 16 == 0 && stride % 16 == 0 && out_stride % 16 == 0 && reinterpret_cast<uintptr_t>(in) % 16 == 0 &&
+                     reinterpret_cast<uintptr_t>(out) % 16 == 0;
+    const unsigned int words = (unsigned int)(record_bytes / (vec ? 16 : 4));
+    auto kernel = vec ? k_planes_records<uint4> : k_planes_records<unsigned int>;
+    hipLaunchKernelGGL(kernel, dim3(g1(m * words)), dim3(256), 0, s, static_cast<const char*>(in), stride, idx, m, words,
+                       static_cast<char*>(out), out_stride);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+// what pcc_plane_removal refuses about its own parameters and tables
+int check_plane_loop(double stop_fraction, int max_iterations, double threshold, double probability, size_t max_planes,
+                     const float* out_coefficients, const uint32_t* out_plane_sizes, const void* n_planes, const void* n_remaining) {
     if (max_iterations < 0 || !(threshold >= 0) || !(probability > 0 && probability < 1)) {
         set_error("bad RANSAC parameters");
         return PCC_ERR_INVALID;
@@ -481,6 +564,19 @@ int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, i
         set_error("null output");
         return PCC_ERR_INVALID;
     }
+    return PCC_OK;
+}
+}  // namespace pcc
+
+extern "C" {
+int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, double stop_fraction, int max_iterations,
+                      double threshold, double probability, int optimize, size_t max_planes, float* out_coefficients,
+                      uint32_t* out_plane_sizes, int* out_iterations, size_t* n_planes, int* ended_without_model,
+                      int32_t* out_plane_of_point, int32_t* out_remaining_index, size_t* n_remaining, void* out_points,
+                      size_t out_stride, size_t record_bytes) {
+    PCC_TRY(check_points(pts, n, stride, mem));
+    PCC_TRY(check_plane_loop(stop_fraction, max_iterations, threshold, probability, max_planes, out_coefficients, out_plane_sizes,
+                             n_planes, n_remaining));
     if (out_points && (record_bytes < 12 || record_bytes % 4 || record_bytes > stride || record_bytes > out_stride || out_stride % 4)) {
         set_error("record_bytes %zu must be a multiple of 4, >= 12 and at most both strides (%zu, %zu, the output's a multiple of 4)",
                   record_bytes, stride, out_stride);
@@ -496,71 +592,23 @@ int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, i
     hipStream_t s = ix->stream;
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    const double stop_size = stop_fraction * (double)n;  // (:91: size() > 0.3 * nr_points, in double)
-    const bool any_turn = (double)n > stop_size;
-    // every buffer before any pointer into one is taken (a DevBuf that grows moves)
-    if (any_turn) PCC_TRY(stage_queries(ix, pts, n, stride, mem));
-    PCC_TRY(ix->vox_a.reserve(n * sizeof(float4)));
-    PCC_TRY(ix->vox_b.reserve(n * sizeof(int32_t)));
-    PCC_TRY(ix->vox_c.reserve(n * sizeof(int32_t)));
-    PCC_TRY(ix->out_idx.reserve(n * sizeof(int32_t)));
     Out<int32_t> plane_of;
     PCC_TRY(plane_of.stage(out_plane_of_point, n, mem, ix->scratch_g));
-    const float4* cur = ix->q_packed.as<float4>();
-    float4* other = ix->vox_a.as<float4>();
-    int32_t* orig = ix->vox_b.as<int32_t>();
-    int32_t* other_orig = ix->vox_c.as<int32_t>();
-    hipLaunchKernelGGL(k_planes_begin, dim3(g1(n)), dim3(256), 0, s, (unsigned int)n, orig, plane_of.dev);
-    PCC_HIP(hipGetLastError());
-
-    size_t cur_n = n, planes = 0;
-    uint64_t host_copies = 0;
-    int status = PCC_OK;
-    while ((double)cur_n > stop_size) {
-        if (planes == max_planes) { set_error("more than max_planes = %zu planes", max_planes); status = PCC_ERR_OVERFLOW; break; }
-        size_t m = 0;
-        float coeff[4];
-        int its = 0;
-        // turn 0 of a host cloud reads single points from the caller's own array, as pcc_sac_plane does; every other turn
-        // gathers the few points the host needs on the device
-        const char* own = (planes == 0 && mem == PCC_MEM_HOST) ? static_cast<const char*>(pts) : nullptr;
-        int st = sac_plane(ix, cur, cur_n, own, stride, max_iterations, threshold, probability, optimize, ix->out_idx.as<int32_t>(), &m,
-                           coeff, &its);
-        if (st == PCC_ERR_RETRY_HOST) {
-            // a degenerate sample (pcc_sac_plane above): this turn alone with a host copy of the CURRENT cloud
-            PCC_TRY(ix->host_b.reserve(cur_n * sizeof(float4)));
-            float4* hp = ix->host_b.as<float4>();
-            PCC_HIP(hipMemcpyAsync(hp, cur, cur_n * sizeof(float4), hipMemcpyDeviceToHost, s));
-            PCC_HIP(hipStreamSynchronize(s));
-            const float qnan = std::nanf("");
-            for (size_t i = 0; i < cur_n; ++i)
-                if (__builtin_bit_cast(int, hp[i].w) < 0) hp[i].x = hp[i].y = hp[i].z = qnan;
-            ++host_copies;
-            st = sac_plane(ix, cur, cur_n, reinterpret_cast<const char*>(hp), sizeof(float4), max_iterations, threshold, probability,
-                           optimize, ix->out_idx.as<int32_t>(), &m, coeff, &its);
-        }
-        PCC_TRY(st);
-        if (m == 0) {  // :95-100 "Could not estimate a planar model for the given dataset."
-            if (ended_without_model) *ended_without_model = 1;
-            break;
-        }
-        std::memcpy(out_coefficients + 4 * planes, coeff, sizeof(coeff));
-        out_plane_sizes[planes] = (uint32_t)m;
-        if (out_iterations) out_iterations[planes] = its;
-        hipLaunchKernelGGL(k_planes_partition, dim3(g1(cur_n)), dim3(256), 0, s, cur, orig, (unsigned int)cur_n,
-                           ix->scratch_c.as<unsigned int>(), (int32_t)planes, other, other_orig, plane_of.dev);
-        PCC_HIP(hipGetLastError());
-        float4* freed = const_cast<float4*>(cur);  // (turn 0 frees q_packed: the staged cloud is not needed again)
-        cur = other;
-        other = freed;
-        std::swap(orig, other_orig);
-        cur_n -= m;
-        ++planes;
-    }
-    *n_planes = planes;
+    PlaneLoop L;
+    L.pts = pts; L.n = n; L.stride = stride; L.mem = mem;
+    L.stop_fraction = stop_fraction; L.max_iterations = max_iterations; L.threshold = threshold; L.probability = probability;
+    L.optimize = optimize; L.max_planes = max_planes;
+    L.out_coefficients = out_coefficients; L.out_plane_sizes = out_plane_sizes; L.out_iterations = out_iterations;
+    L.ended_without_model = ended_without_model;
+    L.plane_of_point = plane_of.dev;
+    const int status = plane_loop(ix, L);
+    if (status != PCC_OK && status != PCC_ERR_OVERFLOW) return status;
+    const size_t cur_n = L.remaining;
+    const int32_t* orig = L.remaining_index;
+    *n_planes = L.planes;
     *n_remaining = cur_n;
-    ix->stats[0] = planes;
-    ix->stats[1] = host_copies;
+    ix->stats[0] = L.planes;
+    ix->stats[1] = L.host_copies;
     if (status != PCC_OK) {
         PCC_HIP(hipStreamSynchronize(s));  // (the arrays in space `mem` are unspecified, but nothing is in flight at the return)
         return status;
@@ -570,20 +618,12 @@ int pcc_plane_removal(pcc_index* ix, const void* pts, size_t n, size_t stride, i
     // the remaining points' original indices, and their records
     Out<int32_t> remaining;
     remaining.user = out_remaining_index;
-    remaining.dev = orig;
+    remaining.dev = const_cast<int32_t*>(orig);
     remaining.count = cur_n;
     if (mem == PCC_MEM_DEVICE) {
         if (out_remaining_index && cur_n)
             PCC_HIP(hipMemcpyAsync(out_remaining_index, orig, cur_n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        if (out_points && cur_n) {
-            const bool vec = record_bytes % 16 == 0 && stride % 16 == 0 && out_stride % 16 == 0 &&
-                             reinterpret_cast<uintptr_t>(pts) % 16 == 0 && reinterpret_cast<uintptr_t>(out_points) % 16 == 0;
-            const unsigned int words = (unsigned int)(record_bytes / (vec ? 16 : 4));
-            auto kernel = vec ? k_planes_records<uint4> : k_planes_records<unsigned int>;
-            hipLaunchKernelGGL(kernel, dim3(g1(cur_n * words)), dim3(256), 0, s, static_cast<const char*>(pts), stride, orig, cur_n,
-                               words, static_cast<char*>(out_points), out_stride);
-            PCC_HIP(hipGetLastError());
-        }
+        if (out_points) PCC_TRY(launch_plane_records(s, pts, stride, orig, cur_n, record_bytes, out_points, out_stride));
         return PCC_OK;
     }
     // host memory: the records are the caller's own, copied on the host in the order of the index list

@@ -20,6 +20,9 @@
 // pcc_region_growing_segmentation: region_growing_segmentation (src/segmentation.cpp:218-327): VoxelGrid -> NormalEstimation ->
 // RegionGrowing -> one cloud per cluster, the filtered cloud, its index, its rows, its normals and its labels on the device
 // from the raw cloud to the cluster clouds.
+//
+// pcc_euclidean_cluster_segmentation: euclidean_cluster_segmentation (src/segmentation.cpp:64-156): VoxelGrid -> the plane-removal
+// loop -> EuclideanClusterExtraction -> one cloud per cluster, the same way.
 #include "entry.hpp"
 #include <algorithm>
 #include <cmath>
@@ -31,7 +34,8 @@ namespace pcc {
 struct SegmentScratch {
     pcc_index* work = nullptr;       // the handle the filtered cloud is indexed on (the caller's stream and options, scratch of its own)
     DevBuf cloud, normals, labels;   // the filtered cloud's records, float4[nv], int32[nv]: nothing voxel_grid, the k-NN rows, the
-                                     // plane fit or grid_region_growing reserves
+                                     // plane fit, the plane loop, grid_region_growing or grid_clusters reserves
+    DevBuf remain;                   // pcc_euclidean_cluster_segmentation: the records that remain after the planes (a caller in host memory)
     DevBuf lab_in;                   // pcc_extract_clusters: the caller's labels, staged (host memory)
     DevBuf order_a, order_b;         // uint32[n]: the order going into a pass and coming out of it
     DevBuf table, scan_tmp;          // uint32[256][blocks]; the scan's block totals
@@ -39,7 +43,7 @@ struct SegmentScratch {
     DevBuf out_rec;                  // the cluster records of a caller in host memory
     ~SegmentScratch() {
         if (work) (void)pcc_index_destroy(work);
-        DevBuf* bufs[] = {&cloud, &normals, &labels, &lab_in, &order_a, &order_b, &table, &scan_tmp, &offsets, &out_rec};
+        DevBuf* bufs[] = {&cloud, &normals, &labels, &remain, &lab_in, &order_a, &order_b, &table, &scan_tmp, &offsets, &out_rec};
         for (DevBuf* b : bufs) b->release();
     }
 };
@@ -416,6 +420,142 @@ int pcc_region_growing_segmentation(pcc_index* ix, const void* pts, size_t n, si
                 dst = sg->out_rec.p;
             }
             PCC_TRY(launch_records(s, sg->cloud.p, out_stride, order, m, out_stride, dst, out_stride));
+            if (mem == PCC_MEM_HOST) PCC_TRY(give(ix, mem, out_cluster_points, dst, m * out_stride));
+        }
+    }
+    if (mem == PCC_MEM_HOST) PCC_HIP(hipStreamSynchronize(s));
+    if (!fits) {
+        set_error("%d clusters, more than max_clusters = %zu", ncl, max_clusters);
+        return PCC_ERR_OVERFLOW;
+    }
+    return PCC_OK;
+}
+int pcc_euclidean_cluster_segmentation(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem, float leaf, int has_rgb,
+                                       double stop_fraction, int max_iterations, double distance_threshold, double probability,
+                                       int optimize, size_t max_planes, float* out_coefficients, uint32_t* out_plane_sizes,
+                                       int* out_iterations, size_t* n_planes, int* ended_without_model, double tolerance,
+                                       uint32_t min_size, uint32_t max_size, void* out_points, size_t out_stride, size_t* n_filtered,
+                                       size_t* n_remaining, int32_t* out_labels, size_t max_clusters, int32_t* n_clusters,
+                                       size_t* out_offsets, void* out_cluster_points, int32_t* out_cluster_index) {
+    // what pcc_voxel_grid refuses, with its messages
+    PCC_TRY(check_points(pts, n, stride, mem));
+    if (!out_points) { set_error("null output"); return PCC_ERR_INVALID; }
+    if (out_stride < 12 || out_stride % 4) { set_error("bad output stride"); return PCC_ERR_INVALID; }
+    if (has_rgb && (stride < 20 || out_stride < 20)) { set_error("rgb needs a stride of at least 20 bytes"); return PCC_ERR_INVALID; }
+    if (!(leaf > 0.f)) { set_error("leaf size must be positive"); return PCC_ERR_INVALID; }
+    // what pcc_plane_removal refuses about its own parameters and tables (its records are whole voxel-grid records; n_remaining
+    // has its turn below: n_planes stands in for it here)
+    PCC_TRY(check_plane_loop(stop_fraction, max_iterations, distance_threshold, probability, max_planes, out_coefficients, out_plane_sizes,
+                             n_planes, n_planes));
+    if (!(tolerance >= 0)) { set_error("bad tolerance"); return PCC_ERR_INVALID; }
+    if (!n_filtered || !n_remaining || !n_clusters || !out_offsets) { set_error("null output"); return PCC_ERR_INVALID; }
+    if ((out_cluster_points || out_cluster_index) && max_clusters == 0) {
+        set_error("cluster outputs given without room: max_clusters is 0");
+        return PCC_ERR_INVALID;
+    }
+    PCC_ENTER(ix);
+    *n_filtered = 0;
+    *n_remaining = 0;
+    *n_planes = 0;
+    *n_clusters = 0;
+    if (ended_without_model) *ended_without_model = 0;
+    out_offsets[0] = 0;
+    PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
+    ix->stats[0] = ix->stats[1] = ix->stats[2] = ix->stats[3] = ix->stats[4] = 0;
+    ix->stats_pending = false;
+    if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
+    hipStream_t s = ix->stream;
+    ev_next(ix);
+    ev_mark(ix, EV_CALL0);
+    segment_scratch(ix);
+    SegmentScratch* sg = ix->segment;
+
+    // 1. the voxel grid, on `ix`, into a zeroed buffer of this call's own (as pcc_region_growing_segmentation)
+    const void* src = pts;
+    if (mem == PCC_MEM_HOST) {
+        PCC_TRY(ix->q_raw.reserve(n * stride));
+        PCC_HIP(hipMemcpyAsync(ix->q_raw.p, pts, (n - 1) * stride + (has_rgb ? 20 : 12), hipMemcpyHostToDevice, s));
+        src = ix->q_raw.p;
+    }
+    PCC_TRY(sg->cloud.reserve(n * out_stride));
+    PCC_HIP(hipMemsetAsync(sg->cloud.p, 0, n * out_stride, s));
+    size_t nv = 0;
+    PCC_TRY(voxel_grid(ix, src, n, stride, PCC_MEM_DEVICE, leaf, has_rgb, sg->cloud.p, out_stride, &nv));
+    *n_filtered = nv;
+    ix->stats[0] = nv;
+    if (nv == 0) return PCC_OK;  // (no finite point; voxel_grid has waited: nothing is in flight)
+
+    // 2. the plane loop over the filtered cloud where it lies.  voxel_grid has waited for its last kernel, so vox_a/b/c are
+    // free; the loop packs sg->cloud into q_packed (q_raw, the raw cloud of a host caller, is not needed again) and reads single
+    // points by gathering them on the device -- turn 0 included: the filtered cloud has no host copy
+    PlaneLoop L;
+    L.pts = sg->cloud.p; L.n = nv; L.stride = out_stride; L.mem = PCC_MEM_DEVICE;
+    L.stop_fraction = stop_fraction; L.max_iterations = max_iterations; L.threshold = distance_threshold; L.probability = probability;
+    L.optimize = optimize; L.max_planes = max_planes;
+    L.out_coefficients = out_coefficients; L.out_plane_sizes = out_plane_sizes; L.out_iterations = out_iterations;
+    L.ended_without_model = ended_without_model;
+    const int plane_status = plane_loop(ix, L);
+    if (plane_status != PCC_OK && plane_status != PCC_ERR_OVERFLOW) return plane_status;
+    const size_t nr = L.remaining;
+    *n_planes = L.planes;
+    *n_remaining = nr;
+    ix->stats[3] = L.planes;
+    ix->stats[4] = L.host_copies;
+    if (plane_status != PCC_OK) {
+        PCC_HIP(hipStreamSynchronize(s));  // (the arrays in space `mem` are unspecified, but nothing is in flight at the return)
+        return plane_status;
+    }
+    if (nr == 0) {  // nothing remains: no cluster, nothing to hand over
+        ev_mark(ix, EV_CALL1);
+        return PCC_OK;
+    }
+    // the records that remain: into the caller's array in device memory, else into a buffer of this call's
+    void* rem = out_points;
+    if (mem == PCC_MEM_HOST) {
+        PCC_TRY(sg->remain.reserve(nr * out_stride));
+        rem = sg->remain.p;
+    }
+    PCC_TRY(launch_plane_records(s, sg->cloud.p, out_stride, L.remaining_index, nr, out_stride, rem, out_stride));
+
+    // 3. the remaining cloud indexed on the work handle, 4. clustered there, the labels in a buffer of this call's
+    WorkLease lease;
+    PCC_TRY(lease.take(ix, &sg->work, true));
+    pcc_index* w = lease.w;
+    PCC_TRY(set_input(w, rem, nr, out_stride, PCC_MEM_DEVICE));
+    entered(w);
+    PCC_TRY(ensure_grid(w));
+    PCC_TRY(sg->labels.reserve(nr * sizeof(int32_t)));
+    const float tol_f = (float)tolerance;  // (pcc_euclidean_clusters: r2 = float(double(float(tol))^2))
+    int32_t ncl = 0;
+    PCC_TRY(grid_clusters(w, tol_f, radius2((double)tol_f), min_size, max_size, sg->labels.as<int32_t>(), &ncl, nullptr, 0, true));
+    *n_clusters = ncl;
+    ix->stats[1] = (uint64_t)ncl;
+
+    // 5. labels -> cluster clouds, on `ix` again
+    const bool fits = (size_t)ncl <= max_clusters;
+    const unsigned int *order = nullptr, *d_offsets = nullptr;
+    size_t m = 0;
+    if (fits && ncl > 0) {
+        PCC_TRY(extract_order(ix, sg->labels.as<int32_t>(), nr, ncl, &order, &d_offsets));
+        PCC_TRY(offsets_to_host(ix, d_offsets, ncl));
+        PCC_HIP(hipStreamSynchronize(s));
+        PCC_TRY(offsets_arrived(ix, ncl, out_offsets));
+        m = out_offsets[ncl];
+        ix->stats[2] = m;
+    }
+    ev_mark(ix, EV_CALL1);
+    // the caller's arrays: each once (host memory: through deliver, then the call's last wait)
+    if (mem == PCC_MEM_HOST) PCC_TRY(give(ix, mem, out_points, rem, nr * out_stride));
+    PCC_TRY(give(ix, mem, out_labels, sg->labels.p, nr * sizeof(int32_t)));
+    if (m) {
+        PCC_TRY(give(ix, mem, out_cluster_index, order, m * sizeof(int32_t)));
+        if (out_cluster_points) {
+            void* dst = out_cluster_points;
+            if (mem == PCC_MEM_HOST) {
+                PCC_TRY(sg->out_rec.reserve(m * out_stride));
+                dst = sg->out_rec.p;
+            }
+            PCC_TRY(launch_records(s, rem, out_stride, order, m, out_stride, dst, out_stride));
             if (mem == PCC_MEM_HOST) PCC_TRY(give(ix, mem, out_cluster_points, dst, m * out_stride));
         }
     }
