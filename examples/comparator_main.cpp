@@ -29,6 +29,7 @@
 #include "pcc/multi_device.hpp"
 #include "pcc/rift.hpp"
 #include "pcc/sift.hpp"
+#include "pcc/descriptors.hpp"
 #include "ply_io.hpp"
 #include "report.hpp"
 
@@ -41,6 +42,7 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --rift (clusters of a scene without a descriptor file get their descriptors from pcc::processRIFT),
 // --sift (with --rift: clusters above 700 points take pcc::processRIFTwithSIFT, the reference's own choice),
 // --rift-loop (with --rift: one call per cluster as in the reference, :1224-1272, instead of one pcc::processRIFTBatch for all),
+// --descriptors-device (with --rift: the whole descriptor loop of both scenes in one pcc::clusterDescriptors call),
 // --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read),
 // --descriptor-dims N (the bins of a descriptor the cluster matching searches on),
 // --rgb-device (the colour segmentation of matched clusters, :1456-1495, as one pcc_region_growing_rgb call each: same report),
@@ -56,6 +58,9 @@ static bool segment_device = false;
 // euclideanClusterSegmentation): same lines, same clusters
 static bool euclidean_device = false;
 static bool rift = false, sift = false, rift_loop = false;
+// --descriptors-device (with --rift): the descriptor loop over the clusters of BOTH scenes runs in one library call
+// (pcc_cluster_descriptors through clusterDescriptors; without --sift its gate is "never"): same lines, same descriptors
+static bool descriptors_device = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
 static void printUsage() {
@@ -78,6 +83,9 @@ static void printUsage() {
               << "                   within 0.05, RIFT descriptors of the snapped cloud\n"
               << "--rift-loop        (this build, with --rift) one library call per cluster, as the reference's loop does; without it\n"
               << "                   every cluster of both scenes goes through ONE processRIFTBatch call (same descriptors)\n"
+              << "--descriptors-device  (this build, with --rift) the descriptor loop -- SIFT keypoints and their snap for the clusters\n"
+              << "                   above 700 points (with --sift), RIFT for every cluster -- runs in ONE library call for both scenes\n"
+              << "                   (pcc_cluster_descriptors: keypoints and snapped clouds stay on the GPU): the same descriptors\n"
               << "--dump-descriptors P  (this build) write the descriptors in use as P_<scene>.txt (the format of --descriptors1/2)\n"
               << "--descriptor-dims N  (this build) the cluster matching searches on the first N bins of every descriptor, 1 ... 32\n"
               << "                   (default 3: what the reference's PCL does with a 32-bin histogram -- recalled, not re-checked;\n"
@@ -305,7 +313,22 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
     std::vector<PointCloud<PointXYZRGB>::Ptr> sift_snapped;
     std::vector<size_t> sift_found;
     size_t sift_at = 0;
-    if (rift && sift && !rift_loop) {
+    if (rift && descriptors_device) {
+        // every cluster of the scenes without a descriptor file through ONE clusterDescriptors call
+        std::vector<PointCloud<PointXYZRGB>::Ptr> all;
+        for (int k = 0; k < 2; ++k)
+            if (descriptors_path[k].empty()) all.insert(all.end(), clusters[k].begin(), clusters[k].end());
+        const ClusterDescriptors cd = clusterDescriptors(all, sift ? SIFT_ABOVE : SIFT_NEVER);
+        size_t at = 0;
+        for (int k = 0; k < 2; ++k) {
+            if (!descriptors_path[k].empty()) continue;
+            for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
+                if (sift && c->points.size() > SIFT_ABOVE) std::cout << "Computed " << cd.n_keypoints[at] << " SIFT Keypoints\n";  // reference :467
+                des[k].push_back(cd.descriptors[at++]);
+            }
+        }
+    }
+    if (rift && sift && !rift_loop && !descriptors_device) {
         std::vector<PointCloud<PointXYZRGB>::Ptr> large;
         for (int k = 0; k < 2; ++k)
             if (descriptors_path[k].empty())
@@ -314,7 +337,9 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
         if (!large.empty()) sift_snapped = siftSnappedCloudBatch(large, &sift_found);
     }
     for (int k = 0; k < 2; ++k) {
-        if (descriptors_path[k].empty() && rift && !rift_loop) {
+        if (descriptors_path[k].empty() && rift && descriptors_device) {
+            // (filled above)
+        } else if (descriptors_path[k].empty() && rift && !rift_loop) {
             // the clouds the RIFT pipeline runs over, in cluster order; one processRIFTBatch call for both scenes below
             for (const PointCloud<PointXYZRGB>::Ptr& c : clusters[k]) {
                 if (sift && c->points.size() > 700) {
@@ -425,6 +450,7 @@ int main(int argc, char** argv) {
         else if (a == "--rift") rift = true;
         else if (a == "--sift") sift = true;
         else if (a == "--rift-loop") rift_loop = true;
+        else if (a == "--descriptors-device") descriptors_device = true;
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a == "--descriptor-dims" && i + 1 < argc) descriptor_dims = std::atoi(argv[++i]);
         else if (a == "--rgb-device") rgb_device = true;
@@ -436,6 +462,7 @@ int main(int argc, char** argv) {
     }
     if (help) { printUsage(); return 1; }
     if (sift && !rift) { std::cerr << "--sift needs --rift\n"; printUsage(); return 1; }
+    if (descriptors_device && !rift) { std::cerr << "--descriptors-device needs --rift\n"; printUsage(); return 1; }
     if (descriptor_dims < 1 || descriptor_dims > 32) { std::cerr << "--descriptor-dims takes 1 ... 32\n"; printUsage(); return 1; }
     std::cout << (seeClusters ? "Visualization of clusters is on." : "Visualization of clusters is off.") << std::endl;
     std::cout << (noise ? "Noise analysis is on." : "Noise analysis is off.") << std::endl;

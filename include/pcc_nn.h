@@ -727,6 +727,50 @@ int pcc_sift_keypoints_batch(pcc_index *ctx, size_t n_clouds,
                              double snap_radius,
                              float *out_keypoints /* [capacity][4] */, int32_t *out_snap_index /* [capacity], nullable */,
                              size_t capacity, size_t *out_offsets /* [n_clouds + 1] */);
+/* The per-cluster descriptor loop of a comparison in one call -- replaces the loop of src/comparator.cpp:1224-1290: a cluster
+ *   above 700 points takes processRIFTwithSIFT (:686-822), the others processRIFT (:590-684), and every cluster's centroid is
+ *   taken on the way (:1235-1247).  The clusters are staged once and stay on the device: the SIFT rounds, the keypoint snap, the
+ *   gather of the snapped clouds, RIFT and the centroids; neither keypoints nor snap indices nor snapped clouds cross to the host.
+ *   ctx: any index handle, as for the other batch calls: it supplies device, stream and scratch; its cloud, tie order and kept
+ *     rows are neither read nor changed.
+ *   Cluster c is points offsets[c] .. offsets[c + 1] of pts / rgb (records stride_bytes apart, x, y, z first; colour words
+ *     rgb_stride_bytes apart), both in memory space `mem`, PCC_MEM_HOST or PCC_MEM_DEVICE -- what
+ *     pcc_region_growing_segmentation and pcc_euclidean_cluster_segmentation write as out_cluster_points / out_offsets (32-byte
+ *     records: rgb = pts + 16, same stride).  offsets (HOST, n_clusters + 1) is non-decreasing and spans fewer than 2^31 points.
+ *   Its slice, rows out_offsets[c] .. out_offsets[c + 1] of out_histograms / out_point_index, bit for bit and in order:
+ *     n_c <= sift_above (the dense route): what pcc_rift_descriptors_batch returns for that cluster alone.
+ *     n_c > sift_above (the SIFT route): K = the cluster's keypoints from pcc_sift_keypoints_batch with the four SIFT parameters
+ *       and snap_radius; S = their snap indices >= 0 in keypoint order, duplicates kept (:696-713); Q = the cluster's points and
+ *       colours at S; (H, J) = what pcc_rift_descriptors_batch returns for Q.  The slice is H with point indices S[J]: the
+ *       cluster-local index of the snapped point each descriptor was computed at.  No keypoints, or none snapped: empty.
+ *     sift_above = SIZE_MAX sends every cluster the dense route.  No point of another cluster enters a voxel, a row or a
+ *     neighbourhood.
+ *   out_n_keypoints[c] (nullable): |K|; 0 on the dense route.
+ *   out_centroids[c] (nullable): three float accumulators from 0.0f, += x / y / z of every point of the cluster in index order
+ *     (non-finite points included), each divided by float(n_c); an empty cluster gives NaN.  The order of the additions is part
+ *     of the result (pointcloudcomparator_amd/host/report.hpp: centroidOf).
+ *   out_histograms[capacity][32], out_point_index[capacity], out_offsets[n_clusters + 1], out_n_keypoints[n_clusters],
+ *     out_centroids[n_clusters][3]: HOST arrays.  More than capacity descriptors: PCC_ERR_OVERFLOW, out_offsets holds the offsets
+ *     that would have been returned, nothing else is written.  n_clusters == 0: PCC_OK, out_offsets[0] = 0, no device is touched.
+ *   SIFT-route clusters above PCC_OPT_SIFT_BATCH_BRUTE_MAX points take pcc_sift_keypoints' path and pcc_first_within on a work
+ *     handle; dense clusters or snapped clouds above PCC_OPT_RIFT_BATCH_BRUTE_MAX take pcc_rift_descriptors on it (same bits).
+ *     Launches and host waits depend on nr_octaves, on the clusters above the limits and on buffer growth, never on n_clusters.
+ *     pcc_index_stats afterwards: [0] dense-route points, [1] SIFT-route points, [2] octave rounds, [3] keypoints, [4] snapped
+ *     points, [5] points sent through the work handle.
+ *   Refused before the handle is looked at, in this order: 1. a bad memory space; 2. null arrays; 3. a bad stride or alignment;
+ *     4. offsets that decrease (PCC_ERR_INVALID) or span 2^31 points and more (PCC_ERR_UNSUPPORTED); 5. the SIFT parameters
+ *     (pcc_sift_keypoints' checks); 6. the radii and bins (pcc_rift_descriptors' checks); 7. a snap_radius that is not positive
+ *     and finite; 8. a null handle. */
+int pcc_cluster_descriptors(pcc_index *ctx,
+                            const void *pts, size_t stride_bytes, const void *rgb, size_t rgb_stride_bytes,
+                            const size_t *offsets /* HOST [n_clusters + 1] */, size_t n_clusters, int mem,
+                            size_t sift_above,
+                            float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, double snap_radius,
+                            double normal_radius, double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins,
+                            float *out_histograms /* HOST [capacity][32] */, int32_t *out_point_index /* HOST [capacity] */, size_t capacity,
+                            size_t *out_offsets /* HOST [n_clusters + 1] */,
+                            uint32_t *out_n_keypoints /* HOST [n_clusters], nullable */,
+                            float *out_centroids /* HOST [n_clusters][3], nullable */);
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);
@@ -869,6 +913,8 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX).
  *  After pcc_sift_keypoints_batch on the handle: [0] points that went through the batch kernels, [1] points of the clouds sent
  *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
+ *  After pcc_cluster_descriptors on the handle: [0] dense-route points, [1] SIFT-route points, [2] octave rounds, [3] keypoints,
+ *  [4] snapped points, [5] points sent through the work handle (above either batch limit).
  *  After pcc_region_growing_rgb on the handle: [0] grown colour segments, [1] distinct ordered segment pairs (s, t) with a row
  *  entry leading from s to t, [7] label sweeps of the growing stage.
  *  After pcc_region_growing_rgb_batch on the handle: [0] grown colour segments, [1] distinct ordered segment pairs and [7] label

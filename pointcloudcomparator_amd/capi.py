@@ -37,7 +37,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_euclidean_cluster_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -115,6 +115,8 @@ def _load() -> C.CDLL:
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_sift_keypoints_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, C.c_double, vp, vp, sz, vp]
+    lib.pcc_cluster_descriptors.argtypes = [vp, vp, sz, vp, sz, vp, sz, i32, sz, C.c_float, i32, i32, C.c_float, C.c_double, C.c_double, C.c_double,
+                                            C.c_double, i32, i32, vp, vp, sz, vp, vp, vp]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
                                            C.POINTER(C.c_int32)]
@@ -946,6 +948,58 @@ class Index:
         m = int(off[n])
         offsets = off.astype(np.int64)
         return (kp[:m], offsets) if snap is None else (kp[:m], offsets, snap[:m])
+
+    def cluster_descriptors(self, points, rgb=None, offsets=None, sift_above: int | None = 700, min_scale: float = 0.005, nr_octaves: int = 5,
+                            nr_scales_per_octave: int = 5, min_contrast: float = 0.001, snap_radius: float = 0.05,
+                            normal_radius: float = 0.03, gradient_radius: float = 0.03, rift_radius: float = 0.05,
+                            nr_distance_bins: int = 4, nr_gradient_bins: int = 8, capacity: int | None = None):
+        """pcc_cluster_descriptors with this handle as the context: the reference's per-cluster descriptor loop
+        (src/comparator.cpp:1224-1290) in one call.  points: (n, >= 3) float32 numpy array or torch tensor (host or CUDA); rgb: one
+        colour per point in any of rift_descriptors' three forms, in the memory space of `points`, or None when `points` are
+        pcl::PointXYZRGB records (the colour word is read in place); offsets: (n_clusters + 1,) non-decreasing, cluster c is
+        points[offsets[c]:offsets[c + 1]] -- what region_growing_segmentation / euclidean_cluster_segmentation return as
+        cluster_points / offsets.  Clusters above sift_above points take SIFT keypoints, their snap and RIFT over the snapped
+        points; the others RIFT over all their points (sift_above=None: every cluster).  Returns a dict: histograms (m, 32) float32,
+        point_index (m,) int32 local to the cluster, offsets (n_clusters + 1,) int64 -- cluster c owns rows offsets[c] ..
+        offsets[c + 1] --, n_keypoints (n_clusters,) uint32, centroids (n_clusters, 3) float32.  Too little capacity is retried
+        once with the room the call asks for."""
+        ptr, n, stride, mem = _points(points)
+        if rgb is None:
+            assert points.shape[1] >= 5, "PointXYZRGB records have their colour word in column 4"
+            words, cptr, cstride, cmem = points, (ptr + 16 if n else ptr), stride, mem
+        else:
+            assert len(rgb) == n, "one colour per point"
+            words, cptr, cstride, cmem = _colour_words(rgb) if n else (rgb, None, 4, mem)
+        assert cmem == mem, "points and colours live in the same memory space"
+        assert offsets is not None, "offsets: the clusters' bounds"
+        off_in = np.ascontiguousarray(np.asarray(offsets), dtype=np.uintp)
+        assert off_in.ndim == 1 and len(off_in) >= 1, "offsets holds n_clusters + 1 entries"
+        n_clusters = len(off_in) - 1
+        assert n_clusters == 0 or int(off_in.max()) <= n, "offsets reach beyond the points"
+        gate = (2 ** (8 * C.sizeof(C.c_size_t)) - 1) if sift_above is None else int(sift_above)
+        assert gate >= 0, "sift_above must not be negative"
+        off = np.zeros(n_clusters + 1, dtype=np.uintp)
+        nkp = np.zeros(max(n_clusters, 1), dtype=np.uint32)
+        cent = np.zeros((max(n_clusters, 1), 3), dtype=np.float32)
+        capacity = max(256, n) if capacity is None else int(capacity)
+        for attempt in range(2):
+            hist = np.empty((max(capacity, 1), 32), dtype=np.float32)
+            index = np.empty(max(capacity, 1), dtype=np.int32)
+            st = self._before(points, words)
+            status = LIB.pcc_cluster_descriptors(self._h, ptr if n else None, stride, cptr if n else None, cstride, off_in.ctypes.data, n_clusters,
+                                                 mem, gate, float(min_scale), int(nr_octaves), int(nr_scales_per_octave), float(min_contrast),
+                                                 float(snap_radius), float(normal_radius), float(gradient_radius), float(rift_radius),
+                                                 int(nr_distance_bins), int(nr_gradient_bins), hist.ctypes.data, index.ctypes.data, capacity,
+                                                 off.ctypes.data, nkp.ctypes.data, cent.ctypes.data)
+            self._after(st)
+            if status == -6 and attempt == 0:  # PCC_ERR_OVERFLOW: once more with the room it asks for
+                capacity = int(off[n_clusters])
+                continue
+            _check(status)
+            break
+        m = int(off[n_clusters])
+        return dict(histograms=hist[:m], point_index=index[:m], offsets=off.astype(np.int64), n_keypoints=nkp[:n_clusters],
+                    centroids=cent[:n_clusters])
 
     def region_growing(self, normals, k: int = 100, smoothness: float = 3.0 / 180.0 * np.pi,
                        curvature_threshold: float = 1.0, min_size: int = 50, max_size: int = 1000000):

@@ -510,6 +510,7 @@ int pcc_index_destroy(pcc_index* ix) {
     match_batch_release(ix);
     rift_batch_release(ix);
     sift_batch_release(ix);
+    cluster_desc_release(ix);
     rgb_batch_release(ix);
     segment_release(ix);
     rift_release(ix);

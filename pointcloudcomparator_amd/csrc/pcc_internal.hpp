@@ -299,6 +299,7 @@ struct BatchStaging {
 struct RiftBatchScratch;   // rift_batch.hip: BatchStaging and the CSR of pcc_rift_descriptors_batch
 struct SiftBatchScratch;   // sift_batch.hip: BatchStaging and the voxel keys, tables and CSR of pcc_sift_keypoints_batch
 struct RgbBatchScratch;    // region_rgb_batch.hip: BatchStaging and the rows of pcc_region_growing_rgb_batch
+struct ClusterDescScratch; // cluster_desc.hip: BatchStaging, the staged clusters, snap indices and RIFT clouds of pcc_cluster_descriptors
 struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
                            // and the orders and tables of pcc_extract_clusters
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
@@ -391,6 +392,7 @@ struct pcc_index {
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
     pcc::RgbBatchScratch* rgb_batch = nullptr;    // made at the first pcc_region_growing_rgb_batch with this handle as its context (region_rgb_batch.hip)
+    pcc::ClusterDescScratch* cluster_desc = nullptr;  // made at the first pcc_cluster_descriptors with this handle as its context (cluster_desc.hip)
     pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -650,6 +652,8 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
 // sift_batch.hip: pcc_sift_keypoints_batch behind its argument checks
 void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work handle
+// cluster_desc.hip: pcc_cluster_descriptors
+void cluster_desc_release(pcc_index* ix);  // frees ix->cluster_desc and its work handle
 // region_rgb_batch.hip: pcc_region_growing_rgb_batch behind its argument checks
 void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work handle
 // segment.hip: pcc_extract_clusters and pcc_region_growing_segmentation

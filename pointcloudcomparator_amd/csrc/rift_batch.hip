@@ -28,6 +28,7 @@
 #include "grid_device.hpp"
 #include "rift_math.hpp"
 #include "rift_batch_plan.hpp"
+#include "desc_batch.hpp"
 
 namespace pcc {
 
@@ -145,6 +146,54 @@ void rift_batch_release(pcc_index* ix) {
     ix->rift_batch = nullptr;
 }
 
+// ---- the half over a device-resident concatenation (desc_batch.hpp): shared with cluster_desc.hip ---------------------------
+void rift_batch_scratch(pcc_index* ix) {
+    if (!ix->rift_batch) ix->rift_batch = new RiftBatchScratch();
+    if (!ix->rift) ix->rift = new RiftScratch();
+}
+
+int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius, double gradient_radius, double rift_radius,
+                   const unsigned int** d_slice) {
+    hipStream_t s = ix->stream;
+    RiftBatchScratch* b = ix->rift_batch;
+    const size_t total = in.total, n_clouds = in.n_clouds;
+    // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
+    const RiftRows rows = [&](double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) -> int {
+        return batch_radius_rows(ix, in.d_items, in.n_items, in.d_pts, total, (float)(radius * radius), b->offs, b->keys, keys_out, offsets_out);
+    };
+    // ---- the stages of the single call, once over the concatenation -------------------------------------------------------
+    RiftScratch* r = ix->rift;
+    PCC_TRY(r->out_hist.reserve(total * RIFT_BINS * sizeof(float)));
+    PCC_TRY(r->out_index.reserve(total * sizeof(int32_t)));
+    PCC_TRY(rift_stages(ix, in.d_pts, in.d_pts, in.gd, total, rows, in.d_rgb, sizeof(uint32_t), normal_radius, gradient_radius, rift_radius,
+                        r->out_hist.as<float>(), r->out_index.as<int32_t>()));
+    PCC_TRY(b->slice.reserve((n_clouds + 1) * sizeof(unsigned int)));
+    const unsigned int fb = (unsigned int)std::min<size_t>((std::max(total, n_clouds + 1) + 255) / 256, 2048);
+    hipLaunchKernelGGL(k_rift_batch_finish, dim3(fb), dim3(256), 0, s, r->keep.as<unsigned int>(), in.d_bases, (unsigned int)n_clouds,
+                       (unsigned int)total, b->slice.as<unsigned int>(), r->out_index.as<int32_t>());
+    PCC_HIP(hipGetLastError());
+    *d_slice = b->slice.as<unsigned int>();
+    return PCC_OK;
+}
+
+int rift_batch_slices(pcc_index* ix, size_t n_clouds, const unsigned int** h_slice) {
+    RiftBatchScratch* b = ix->rift_batch;
+    PCC_TRY(b->down.reserve((n_clouds + 1) * sizeof(unsigned int)));
+    PCC_HIP(hipMemcpyAsync(b->down.p, b->slice.p, (n_clouds + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    *h_slice = b->down.as<unsigned int>();
+    return PCC_OK;
+}
+
+int rift_batch_fetch(pcc_index* ix, size_t kept, float* out_hist, int32_t* out_index) {
+    if (!kept) return PCC_OK;
+    RiftScratch* r = ix->rift;
+    PCC_HIP(hipMemcpyAsync(out_hist, r->out_hist.p, kept * RIFT_BINS * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipMemcpyAsync(out_index, r->out_index.p, kept * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipStreamSynchronize(ix->stream));
+    return PCC_OK;
+}
+
 // every cloud of the call through the exhaustive builder: out_hist / out_index / offsets (n_clouds + 1) are host arrays
 static int rift_batch_brute(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
                             float* out_hist, int32_t* out_index, size_t* out_offsets) {
@@ -176,36 +225,22 @@ static int rift_batch_brute(pcc_index* ix, const CloudBatch& batch, double norma
     const float4* d_pts = reinterpret_cast<const float4*>(d + up.pts_at);
     const unsigned char* d_rgb = reinterpret_cast<const unsigned char*>(d + up.rgb_at);
 
-    // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
-    const unsigned int n_items = (unsigned int)items.size();
-    const RiftRows rows = [&](double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) -> int {
-        return batch_radius_rows(ix, d_items, n_items, d_pts, total, (float)(radius * radius), b->offs, b->keys, keys_out, offsets_out);
-    };
-
-    // ---- the stages of the single call, once over the concatenation -------------------------------------------------------
-    RiftScratch* r = ix->rift;
-    PCC_TRY(r->out_hist.reserve(total * RIFT_BINS * sizeof(float)));
-    PCC_TRY(r->out_index.reserve(total * sizeof(int32_t)));
-    PCC_TRY(rift_stages(ix, d_pts, d_pts, gd, total, rows, d_rgb, sizeof(uint32_t), normal_radius, gradient_radius, rift_radius,
-                        r->out_hist.as<float>(), r->out_index.as<int32_t>()));
-    PCC_TRY(b->slice.reserve((n_clouds + 1) * sizeof(unsigned int)));
-    PCC_TRY(b->down.reserve((n_clouds + 1) * sizeof(unsigned int)));
-    const unsigned int fb = (unsigned int)std::min<size_t>((std::max(total, n_clouds + 1) + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_rift_batch_finish, dim3(fb), dim3(256), 0, s, r->keep.as<unsigned int>(), d_bases, (unsigned int)n_clouds,
-                       (unsigned int)total, b->slice.as<unsigned int>(), r->out_index.as<int32_t>());
-    PCC_HIP(hipGetLastError());
+    RiftBatchInput in;
+    in.n_clouds = n_clouds;
+    in.total = total;
+    in.gd = gd;
+    in.d_bases = d_bases;
+    in.d_items = d_items;
+    in.n_items = (unsigned int)items.size();
+    in.d_pts = d_pts;
+    in.d_rgb = d_rgb;
+    const unsigned int* d_slice = nullptr;
+    PCC_TRY(rift_batch_run(ix, in, normal_radius, gradient_radius, rift_radius, &d_slice));
     // the slice bounds in one copy, then the rows that were written in one copy each
-    PCC_HIP(hipMemcpyAsync(b->down.p, b->slice.p, (n_clouds + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
-    PCC_HIP(hipStreamSynchronize(s));
-    const unsigned int* h_slice = b->down.as<unsigned int>();
+    const unsigned int* h_slice = nullptr;
+    PCC_TRY(rift_batch_slices(ix, n_clouds, &h_slice));
     for (size_t c = 0; c <= n_clouds; ++c) out_offsets[c] = h_slice[c];
-    const size_t kept = h_slice[n_clouds];
-    if (kept) {
-        PCC_HIP(hipMemcpyAsync(out_hist, r->out_hist.p, kept * RIFT_BINS * sizeof(float), hipMemcpyDeviceToHost, s));
-        PCC_HIP(hipMemcpyAsync(out_index, r->out_index.p, kept * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        PCC_HIP(hipStreamSynchronize(s));
-    }
-    return PCC_OK;
+    return rift_batch_fetch(ix, h_slice[n_clouds], out_hist, out_index);
 }
 
 int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,

@@ -37,6 +37,7 @@
 #include "grid_device.hpp"
 #include "sift_stages.hpp"
 #include "sift_batch_plan.hpp"
+#include "desc_batch.hpp"
 
 namespace pcc {
 
@@ -301,70 +302,29 @@ void sift_batch_release(pcc_index* ix) {
     ix->sift_batch = nullptr;
 }
 
-namespace {
+// ---- the half over a device-resident first concatenation (desc_batch.hpp): shared with cluster_desc.hip ---------------------
+void sift_batch_scratch(pcc_index* ix) {
+    if (!ix->sift_batch) ix->sift_batch = new SiftBatchScratch();
+    if (!ix->sift) ix->sift = new SiftScratch();
+}
 
-// What the batch route leaves behind: the keypoints of every round on the device (ix->sift->kp, round-major) and, on the host,
-// how many each round found in each cloud.
-struct BatchResult {
-    std::vector<std::vector<uint32_t>> counts;  // [round][cloud]
-    std::vector<uint32_t> bases0;               // the first concatenation's bases (the snap's clouds)
-    const unsigned int* d_bases0 = nullptr;
-    const SiftRec* d_rec0 = nullptr;
-    size_t total = 0;                           // keypoints on the device
-    unsigned int rounds = 0;
-};
-
-// the clouds of sizes batch.n[] (0: not part of the batch) through the octave rounds
-int sift_batch_rounds(pcc_index* ix, const CloudBatch& batch, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
-                      BatchResult* res) {
+int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const SiftBatchInput& in, float min_scale, SiftBatchResult* res) {
     hipStream_t s = ix->stream;
-    const size_t n_clouds = batch.n_clouds;
     SiftBatchScratch* b = ix->sift_batch;
     SiftScratch* r = ix->sift;
-    SiftBatchRound cur, next;
-    sift_batch_round(batch.n, n_clouds, 0, &cur);
-    res->bases0 = cur.bases;
-    if (cur.total == 0) return PCC_OK;
-    // (a float doubles fewer than 300 times before it is +inf: the 25-point gate has ended every cloud long before)
-    nr_octaves = std::min(nr_octaves, 300);
+    SiftBatchRound next;
+    const std::vector<SiftOctave>& h_octaves = *in.h_octaves;
+    const SiftOctave* d_octaves = in.d_octaves;
+    const int nr_octaves = (int)h_octaves.size();
+    res->bases0 = in.round0->bases;
+    res->d_bases0 = in.d_bases0;
+    res->d_rec0 = in.d_rec0;
+    size_t cur_total = in.round0->total;
+    if (cur_total == 0) return PCC_OK;
 
-    // ---- one pinned buffer, one copy: the octaves' scales, the first table, 32 bytes a point ---------------------------------
-    const size_t oct_bytes = align_up((size_t)nr_octaves * sizeof(SiftOctave), 16);
-    const TableLayout t0(n_clouds, 0, oct_bytes);  // (the first round needs no items: the voxel stage works by cloud)
-    const size_t rec_at = align_up(t0.bytes, 32), up_bytes = rec_at + cur.total * sizeof(SiftRec);
-    PCC_TRY(b->up.reserve(up_bytes));
-    PCC_TRY(b->dev.reserve(up_bytes));
-    char* u = b->up.as<char>();
-    std::vector<SiftOctave> h_octaves((size_t)nr_octaves);
-    {
-        float sc = min_scale;
-        for (int o = 0; o < nr_octaves; ++o, sc *= 2.0f) sift_octave_scales(sc, nr_scales_per_octave, min_contrast, &h_octaves[(size_t)o]);
-    }
-    memcpy(u, h_octaves.data(), h_octaves.size() * sizeof(SiftOctave));
-    cur.items.clear();
-    t0.fill(u, cur);
-    SiftRec* rec = reinterpret_cast<SiftRec*>(u + rec_at);
-    for (size_t c = 0; c < n_clouds; ++c) {
-        if (!cur.n[c]) continue;
-        const char* src = static_cast<const char*>(batch.pts[c]);
-        const char* col = static_cast<const char*>(batch.rgb[c]);
-        for (size_t i = 0; i < cur.n[c]; ++i) {
-            SiftRec& p = rec[cur.bases[c] + i];
-            memcpy(&p.x, src + i * batch.stride, 12);
-            p.w = 1.0f;
-            memcpy(&p.rgb, col + i * batch.rgb_stride, 4);
-            p.pad[0] = p.pad[1] = p.pad[2] = 0u;
-        }
-    }
-    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
-    const char* d0 = b->dev.as<char>();
-    const SiftOctave* d_octaves = reinterpret_cast<const SiftOctave*>(d0);
-    res->d_bases0 = reinterpret_cast<const unsigned int*>(d0 + t0.bases_at);
-    res->d_rec0 = reinterpret_cast<const SiftRec*>(d0 + rec_at);
-
-    const unsigned int* d_bases_in = res->d_bases0;
-    const int64_t* d_bases64_in = reinterpret_cast<const int64_t*>(d0 + t0.bases64_at);
-    const SiftRec* d_in = res->d_rec0;
+    const unsigned int* d_bases_in = in.d_bases0;
+    const int64_t* d_bases64_in = in.d_bases64_0;
+    const SiftRec* d_in = in.d_rec0;
     PCC_TRY(b->words.reserve((n_clouds + 2) * sizeof(unsigned int)));
     PCC_TRY(b->down.reserve((n_clouds + 2) * sizeof(unsigned int)));
     unsigned int* d_status = b->words.as<unsigned int>();
@@ -374,7 +334,7 @@ int sift_batch_rounds(pcc_index* ix, const CloudBatch& batch, float min_scale, i
     int flip = 0;
     float scale = min_scale;
     for (int o = 0; o < nr_octaves; ++o, scale *= 2.0f) {
-        const size_t n_in = cur.total;
+        const size_t n_in = cur_total;
         ++res->rounds;
         // ---- 1. the voxel grid of every cloud at leaf = the octave's scale ----------------------------------------------------
         PCC_TRY(b->vkeys.reserve(n_in * sizeof(unsigned long long)));
@@ -443,13 +403,84 @@ int sift_batch_rounds(pcc_index* ix, const CloudBatch& batch, float min_scale, i
         PCC_TRY(sift_write_stage(ix, d_cloud, n_oct, oc, res->total, found));
         res->total += found;
         // the next round reads what this one wrote
-        cur = next;
+        cur_total = next.total;
         d_bases_in = d_bases_out;
         d_bases64_in = reinterpret_cast<const int64_t*>(dt + tl.bases64_at);
         d_in = d_cloud;
         flip ^= 1;
     }
     return PCC_OK;
+}
+
+// d_snap[k] for the keypoints of the rounds (round-major): the cloud of every keypoint goes up, then a wave per keypoint
+int sift_batch_snap(pcc_index* ix, const SiftBatchResult& res, size_t n_clouds, double snap_radius, int32_t* d_snap) {
+    hipStream_t s = ix->stream;
+    SiftBatchScratch* b = ix->sift_batch;
+    const size_t m = res.total;
+    if (!m) return PCC_OK;
+    // the cloud of every keypoint, in the device's (round, cloud) order
+    PCC_TRY(b->up.reserve(m * sizeof(uint32_t)));
+    PCC_TRY(b->kp_cloud.reserve(m * sizeof(uint32_t)));
+    uint32_t* kc = b->up.as<uint32_t>();
+    size_t at = 0;
+    for (const std::vector<uint32_t>& round : res.counts)
+        for (size_t c = 0; c < n_clouds; ++c)
+            for (uint32_t i = 0; i < round[c]; ++i) kc[at++] = (uint32_t)c;
+    PCC_HIP(hipMemcpyAsync(b->kp_cloud.p, kc, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    const unsigned int wb = (unsigned int)std::min<size_t>((m + 3) / 4, 8192);
+    hipLaunchKernelGGL(k_sb_snap, dim3(wb), dim3(256), 0, s, ix->sift->kp.as<float4>(), b->kp_cloud.as<unsigned int>(), res.d_bases0, res.d_rec0,
+                       snap_radius, (unsigned int)m, d_snap);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
+namespace {
+
+// the host clouds of sizes batch.n[] (0: not part of the batch) staged as the first concatenation, then through the rounds
+int sift_batch_rounds_host(pcc_index* ix, const CloudBatch& batch, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
+                           SiftBatchResult* res) {
+    hipStream_t s = ix->stream;
+    const size_t n_clouds = batch.n_clouds;
+    SiftBatchScratch* b = ix->sift_batch;
+    SiftBatchRound cur;
+    sift_batch_round(batch.n, n_clouds, 0, &cur);
+    res->bases0 = cur.bases;
+    if (cur.total == 0) return PCC_OK;
+    const std::vector<SiftOctave> h_octaves = sift_batch_octaves(min_scale, nr_octaves, nr_scales_per_octave, min_contrast);
+
+    // ---- one pinned buffer, one copy: the octaves' scales, the first table, 32 bytes a point ---------------------------------
+    const size_t oct_bytes = align_up(h_octaves.size() * sizeof(SiftOctave), 16);
+    const TableLayout t0(n_clouds, 0, oct_bytes);  // (the first round needs no items: the voxel stage works by cloud)
+    const size_t rec_at = align_up(t0.bytes, 32), up_bytes = rec_at + cur.total * sizeof(SiftRec);
+    PCC_TRY(b->up.reserve(up_bytes));
+    PCC_TRY(b->dev.reserve(up_bytes));
+    char* u = b->up.as<char>();
+    memcpy(u, h_octaves.data(), h_octaves.size() * sizeof(SiftOctave));
+    cur.items.clear();
+    t0.fill(u, cur);
+    SiftRec* rec = reinterpret_cast<SiftRec*>(u + rec_at);
+    for (size_t c = 0; c < n_clouds; ++c) {
+        if (!cur.n[c]) continue;
+        const char* src = static_cast<const char*>(batch.pts[c]);
+        const char* col = static_cast<const char*>(batch.rgb[c]);
+        for (size_t i = 0; i < cur.n[c]; ++i) {
+            SiftRec& p = rec[cur.bases[c] + i];
+            memcpy(&p.x, src + i * batch.stride, 12);
+            p.w = 1.0f;
+            memcpy(&p.rgb, col + i * batch.rgb_stride, 4);
+            p.pad[0] = p.pad[1] = p.pad[2] = 0u;
+        }
+    }
+    PCC_HIP(hipMemcpyAsync(b->dev.p, u, up_bytes, hipMemcpyHostToDevice, s));
+    const char* d0 = b->dev.as<char>();
+    SiftBatchInput in;
+    in.round0 = &cur;
+    in.h_octaves = &h_octaves;
+    in.d_octaves = reinterpret_cast<const SiftOctave*>(d0);
+    in.d_bases0 = reinterpret_cast<const unsigned int*>(d0 + t0.bases_at);
+    in.d_bases64_0 = reinterpret_cast<const int64_t*>(d0 + t0.bases64_at);
+    in.d_rec0 = reinterpret_cast<const SiftRec*>(d0 + rec_at);
+    return sift_batch_rounds(ix, n_clouds, in, min_scale, res);
 }
 
 // the single path for cloud c, which is above the brute limit, on the work handle: its keypoints into kp (host)
@@ -486,8 +517,8 @@ int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale
     const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
     CloudBatch small = batch;
     small.n = routes.small_n.data();
-    BatchResult res;
-    PCC_TRY(sift_batch_rounds(ix, small, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &res));
+    SiftBatchResult res;
+    PCC_TRY(sift_batch_rounds_host(ix, small, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &res));
     ix->stats[0] = routes.n_brute;
     ix->stats[1] = routes.n_large;
     ix->stats[2] = res.rounds;
@@ -520,20 +551,8 @@ int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale
         const size_t snap_at = align_up(m * sizeof(float4), 16);
         PCC_TRY(b->down.reserve(snap_at + m * sizeof(int32_t)));
         if (out_snap) {
-            // the cloud of every keypoint, in the device's (round, cloud) order
-            PCC_TRY(b->up.reserve(m * sizeof(uint32_t)));
-            PCC_TRY(b->kp_cloud.reserve(m * sizeof(uint32_t)));
             PCC_TRY(b->snap.reserve(m * sizeof(int32_t)));
-            uint32_t* kc = b->up.as<uint32_t>();
-            size_t at = 0;
-            for (const std::vector<uint32_t>& round : res.counts)
-                for (size_t c = 0; c < n_clouds; ++c)
-                    for (uint32_t i = 0; i < round[c]; ++i) kc[at++] = (uint32_t)c;
-            PCC_HIP(hipMemcpyAsync(b->kp_cloud.p, kc, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-            const unsigned int wb = (unsigned int)std::min<size_t>((m + 3) / 4, 8192);
-            hipLaunchKernelGGL(k_sb_snap, dim3(wb), dim3(256), 0, s, ix->sift->kp.as<float4>(), b->kp_cloud.as<unsigned int>(), res.d_bases0, res.d_rec0,
-                               snap_radius, (unsigned int)m, b->snap.as<int32_t>());
-            PCC_HIP(hipGetLastError());
+            PCC_TRY(sift_batch_snap(ix, res, n_clouds, snap_radius, b->snap.as<int32_t>()));
             PCC_HIP(hipMemcpyAsync(b->down.as<char>() + snap_at, b->snap.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
         PCC_HIP(hipMemcpyAsync(b->down.p, ix->sift->kp.p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
