@@ -8,7 +8,7 @@ ARCH       ?= gfx950
 HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 -fPIC -Iinclude -Ipointcloudcomparator_amd/csrc
 CSRC       := pointcloudcomparator_amd/csrc
 LIBDIR     := pointcloudcomparator_amd/lib
-HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/sor.hip $(CSRC)/segment.hip)
+HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/cluster_match.hip $(CSRC)/sor.hip $(CSRC)/segment.hip)
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/pcc_nn.h
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 
@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -70,11 +70,11 @@ build/comparator: examples/comparator_main.cpp pointcloudcomparator_amd/host/ply
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
-build/test_report: tests/cpp/test_report.cpp pointcloudcomparator_amd/host/report.hpp include/pcc/comparator_nn.hpp include/pcc/search.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+build/test_report: tests/cpp/test_report.cpp pointcloudcomparator_amd/host/report.hpp include/pcc/comparator_nn.hpp include/pcc/descriptors.hpp include/pcc/rift.hpp include/pcc/sift.hpp include/pcc/search.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
-build/test_match_batch: tests/cpp/test_match_batch.cpp pointcloudcomparator_amd/host/report.hpp include/pcc/comparator_nn.hpp include/pcc/region_growing_rgb.hpp include/pcc/search.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+build/test_match_batch: tests/cpp/test_match_batch.cpp pointcloudcomparator_amd/host/report.hpp include/pcc/comparator_nn.hpp include/pcc/descriptors.hpp include/pcc/rift.hpp include/pcc/sift.hpp include/pcc/region_growing_rgb.hpp include/pcc/search.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
@@ -183,6 +183,11 @@ build/cluster_desc_driver: tests/cpp/cluster_desc_driver.cpp include/pcc/descrip
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
+# the candidates, gates, acceptance and work-item table of pcc_cluster_matching on the CPU (no library, no GPU)
+build/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
+
 # the host scaffold the batch calls share (route split, pack, upload layouts) on the CPU (no library, no GPU)
 build/test_cloud_batch: tests/cpp/test_cloud_batch.cpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/sift_batch_plan.hpp
 	@mkdir -p build
@@ -220,7 +225,7 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
@@ -229,6 +234,7 @@ asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host bui
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_rgb_batch_split
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_cloud_batch
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_cluster_desc_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_cluster_match_plan
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -263,6 +269,10 @@ build/asan/test_cloud_batch: tests/cpp/test_cloud_batch.cpp $(CSRC)/cloud_batch.
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
 build/asan/test_cluster_desc_plan: tests/cpp/test_cluster_desc_plan.cpp $(CSRC)/cluster_desc_plan.hpp $(CSRC)/sift_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp $(CSRC)/cloud_batch.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
+
+build/asan/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 

@@ -61,6 +61,9 @@ static bool rift = false, sift = false, rift_loop = false;
 // --descriptors-device (with --rift): the descriptor loop over the clusters of BOTH scenes runs in one library call
 // (pcc_cluster_descriptors through clusterDescriptors; without --sift its gate is "never"): same lines, same descriptors
 static bool descriptors_device = false;
+// --matching-device: the cluster-matching loop (:1296-1366) runs in one library call (pcc_cluster_matching through matchClusters):
+// same lines, same matches
+static bool matching_device = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
 
 static void printUsage() {
@@ -90,6 +93,9 @@ static void printUsage() {
               << "--descriptor-dims N  (this build) the cluster matching searches on the first N bins of every descriptor, 1 ... 32\n"
               << "                   (default 3: what the reference's PCL does with a 32-bin histogram -- recalled, not re-checked;\n"
               << "                   32 matches on the whole histogram; exact ties then go to the lowest index)\n"
+              << "--matching-device  (this build) the cluster-matching loop -- three nearest centroids, the two gates, the descriptor\n"
+              << "                   search of every gated pair, the acceptance rule -- runs in ONE library call (pcc_cluster_matching:\n"
+              << "                   every cluster packed once, only the correspondence counts come back): the same lines, the same matches\n"
               << "--rgb-device       (this build) the colour segmentation of every matched cluster runs in the library, rows and growing on\n"
               << "                   the GPU (pcc_region_growing_rgb), instead of on the host over downloaded rows: the same report\n"
               << "--rgb-batch        (this build) the colour segmentations of ALL accepted matches run in one library call\n"
@@ -392,7 +398,8 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
             }
         }
     std::vector<int> matches;
-    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims, rgb_device, rgb_batch);
+    const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims, rgb_device, rgb_batch,
+                                                          matching_device);
 
     if (noise) {
         PointCloud<PointXYZRGB> nonoise[2];
@@ -453,6 +460,7 @@ int main(int argc, char** argv) {
         else if (a == "--descriptors-device") descriptors_device = true;
         else if (a == "--dump-descriptors" && i + 1 < argc) dump_descriptors_prefix = argv[++i];
         else if (a == "--descriptor-dims" && i + 1 < argc) descriptor_dims = std::atoi(argv[++i]);
+        else if (a == "--matching-device") matching_device = true;
         else if (a == "--rgb-device") rgb_device = true;
         else if (a == "--rgb-batch") rgb_batch = true;
         else if (a == "--planes-device") planes_device = true;

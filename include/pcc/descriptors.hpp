@@ -2,7 +2,9 @@
 // library call (pcc_cluster_descriptors).  A cluster above `sift_above` points (700 in the reference, :1228-1231, :1264-1265)
 // gets what pcc::processRIFTwithSIFT returns for it, the others what pcc::processRIFT returns; every cluster's centroid
 // (:1235-1247) comes with them.  Neither keypoints nor snapped clouds visit the host in between.
+// pcc::matchClusters: the cluster-matching loop that follows it (:1296-1366) in ONE library call (pcc_cluster_matching).
 #pragma once
+#include <array>
 #include <cstdint>
 #include <limits>
 #include <vector>
@@ -74,6 +76,52 @@ inline ClusterDescriptors clusterDescriptors(const std::vector<PointCloud<PointX
         out.centroids[c].y = centroids[c * 3 + 1];
         out.centroids[c].z = centroids[c * 3 + 2];
     }
+    return out;
+}
+
+// ---- the cluster-matching loop (src/comparator.cpp:1296-1366) in one call ------------------------------------------------------
+// Per cluster i of scene 1 (pcc_nn.h: pcc_cluster_matching): the three nearest free clusters of scene 2 by centroid (-1: none),
+// what became of each (0 no candidate, 1 gated out by the descriptor counts, 2 gated out by size, 3 searched), the length of the
+// row matchRIFTFeaturesKnn would return for a searched pair (else 0), and the accepted match (-1: none).
+struct ClusterMatches {
+    std::vector<std::array<int, 3> > candidates, state;
+    std::vector<std::array<uint32_t, 3> > correspondences;
+    std::vector<int> matches;
+};
+
+// des_s[c]: the descriptors of cluster c of scene s (null: none); centroids_s and points_s: its centroid and its number of
+// points.  dims: the bins the search reads (3 = the reference's PCL, 32 = the whole histogram).  ctx (nullable): as above.
+inline ClusterMatches matchClusters(const std::vector<PointCloud<RIFT32>::Ptr>& des1, const std::vector<PointCloud<RIFT32>::Ptr>& des2,
+                                    const std::vector<std::array<float, 3> >& centroids1, const std::vector<std::array<float, 3> >& centroids2,
+                                    const std::vector<size_t>& points1, const std::vector<size_t>& points2, int dims = 3, float threshold = 0.05f,
+                                    search::KdTree<PointXYZRGB>* ctx = nullptr) {
+    const size_t nc1 = des1.size(), nc2 = des2.size();
+    if (centroids1.size() != nc1 || points1.size() != nc1 || centroids2.size() != nc2 || points2.size() != nc2)
+        throw Error(PCC_ERR_INVALID, "matchClusters: one centroid and one point count per cluster");
+    ClusterMatches out;
+    out.candidates.resize(nc1);
+    out.state.resize(nc1);
+    out.correspondences.resize(nc1);
+    out.matches.assign(nc1, -1);
+    if (nc1 == 0) return out;  // (no library call)
+    std::vector<RIFT32> all[2];
+    std::vector<size_t> offsets[2];
+    for (int s = 0; s < 2; ++s) {
+        const std::vector<PointCloud<RIFT32>::Ptr>& des = s ? des2 : des1;
+        offsets[s].assign(des.size() + 1, 0);
+        for (size_t c = 0; c < des.size(); ++c) offsets[s][c + 1] = offsets[s][c] + (des[c] ? des[c]->size() : 0);
+        all[s].reserve(offsets[s].back());
+        for (size_t c = 0; c < des.size(); ++c)
+            if (des[c]) all[s].insert(all[s].end(), des[c]->points.begin(), des[c]->points.end());
+    }
+    std::vector<int32_t> matches(nc1);
+    static_assert(sizeof(std::array<int, 3>) == 3 * sizeof(int32_t) && sizeof(std::array<float, 3>) == 3 * sizeof(float), "rows of three");
+    check(pcc_cluster_matching(detail::batchContext<PointXYZRGB>(ctx ? ctx->handle() : nullptr), all[0].empty() ? nullptr : all[0].data(),
+                               offsets[0].data(), nc1, all[1].empty() ? nullptr : all[1].data(), offsets[1].data(), nc2, sizeof(RIFT32), dims,
+                               PCC_MEM_HOST, centroids1[0].data(), nc2 ? centroids2[0].data() : nullptr, points1.data(),
+                               nc2 ? points2.data() : nullptr, threshold, out.candidates[0].data(), out.state[0].data(),
+                               out.correspondences[0].data(), matches.data()));
+    out.matches.assign(matches.begin(), matches.end());
     return out;
 }
 

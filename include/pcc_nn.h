@@ -771,6 +771,54 @@ int pcc_cluster_descriptors(pcc_index *ctx,
                             size_t *out_offsets /* HOST [n_clusters + 1] */,
                             uint32_t *out_n_keypoints /* HOST [n_clusters], nullable */,
                             float *out_centroids /* HOST [n_clusters][3], nullable */);
+/* The cluster-matching loop of a comparison in one call -- replaces the loop of src/comparator.cpp:1296-1366: per cluster of
+ *   scene 1 the three nearest free centroids of scene 2 (closestCentroid, :1069-1087), two gates, matchRIFTFeaturesKnn
+ *   (:560-588) for every pair that passes them, and the acceptance rule on the NUMBER of correspondences (:1327-1357; the
+ *   indices are never read).  The result is bit for bit what report::clusterSections (pointcloudcomparator_amd/host/report.hpp)
+ *   computes with pcc_match_knn_batch_dims.  Candidates, gates and acceptance are host arithmetic; the searches of all pairs are
+ *   one pass on the device that tracks the smallest distance per (pair, query) alone: every cluster that takes part is packed
+ *   once, no index, no second minimum, no tie order, no FLANN tree.  One upload, one wait and one read-back of
+ *   3 * n_clusters1 words per call, whatever the number of clusters or pairs; device memory adds none.
+ *   ctx: any index handle, as for the other batch calls: it supplies device, stream and scratch; its cloud, tie order and kept
+ *     rows are neither read nor changed.
+ *   The descriptors of cluster c of scene s are records offsets_s[c] .. offsets_s[c + 1] of des_s, stride_bytes apart; both
+ *     arrays in memory space `mem`, PCC_MEM_HOST or PCC_MEM_DEVICE.  With stride 128 that is what pcc_cluster_descriptors writes
+ *     as out_histograms / out_offsets; centroids and point counts are what it and the segmentation calls return.  The first
+ *     `dim` = 1 ... 32 floats of every record are read, as in pcc_match_knn_batch_dims.  offsets_s (HOST, n_clusters_s + 1) is
+ *     non-decreasing and spans fewer than 2^31 records.
+ *   out_candidates[i][k], k = 0, 1, 2: the nearest centroid of scene 2 not among candidates 0 .. k - 1 of i: differences
+ *     in float, squares and their sum in double, the sum rounded to float, a float square root, strict < against a start value
+ *     of 1e12f.  -1 when nothing qualifies (fewer than three clusters, a NaN centroid, a distance of 1e12 or more); among equal
+ *     distances the lowest index.
+ *   out_state[i][k]: 0 no candidate; 1 gated out by the descriptor counts (both must exceed 3; evaluated first); 2 gated out by
+ *     size (the pair passes only when points2[j] / points1[i] == 1 as size_t division; points1[i] == 0 is gated out, not divided
+ *     by); 3 searched.
+ *   out_correspondences[i][k]: in state 3, 1 + the number of valid records q of scene-2 cluster j whose smallest distance to a
+ *     valid record of scene-1 cluster i is a neighbour and < threshold (strict); else 0.  That is the length of the row
+ *     pcc_match_knn_batch_dims returns for (des1 = cluster i, des2 = cluster j) with the same dim and threshold, under either
+ *     tie order.  Distance: FLANN's L2_Simple in index order, every operation rounded on its own; a record is valid when its
+ *     first dim floats are all finite; an overflowed distance is no neighbour; a cluster without a valid reference gives 1.
+ *   out_matches[i]: -1 and best = 0 to start with; for k = 0, 1, 2 in state 3, corr = out_correspondences[i][k] and denom = the
+ *     larger of the two descriptor counts: accepted when corr / denom >= 1 in integer division and corr > best; then best = corr
+ *     and out_matches[i] = j.
+ *   All four outputs, offsets, centroids and point counts are HOST arrays.  n_clusters1 == 0: PCC_OK without a handle or a
+ *     device.  No pair in state 3: the tables are filled, PCC_OK, no device is touched.  pcc_index_stats afterwards: [0] the
+ *     searched pairs, [1] the queries over all searched pairs.
+ *   Refused before the handle is looked at, in this order: 1. dim outside 1 ... 32 (PCC_ERR_UNSUPPORTED); 2. a bad memory space;
+ *     3. null arrays (a scene's arrays may be null while it has no cluster -- the outputs go with scene 1 --, its descriptor
+ *     array while none of its clusters holds a record); 4. a stride that is not a multiple of 4 or below 4 * dim, or a
+ *     descriptor pointer that is not 4-byte aligned; 5. offsets that decrease (PCC_ERR_INVALID) or span 2^31 records and more
+ *     (PCC_ERR_UNSUPPORTED); 6. what pcc_match_knn_batch_dims refuses about the threshold (nothing: a NaN threshold counts
+ *     nothing); 7. a null handle.  A refused call writes nothing. */
+int pcc_cluster_matching(pcc_index *ctx,
+                         const void *des1, const size_t *offsets1 /* HOST [n_clusters1 + 1] */, size_t n_clusters1,
+                         const void *des2, const size_t *offsets2 /* HOST [n_clusters2 + 1] */, size_t n_clusters2,
+                         size_t stride_bytes, int dim, int mem,
+                         const float *centroids1 /* HOST [n_clusters1][3] */, const float *centroids2 /* HOST [n_clusters2][3] */,
+                         const size_t *points1 /* HOST [n_clusters1] */, const size_t *points2 /* HOST [n_clusters2] */,
+                         float threshold,
+                         int32_t *out_candidates /* HOST [n_clusters1][3] */, int32_t *out_state /* HOST [n_clusters1][3] */,
+                         uint32_t *out_correspondences /* HOST [n_clusters1][3] */, int32_t *out_matches /* HOST [n_clusters1] */);
 int pcc_region_growing(pcc_index *index, const float *normals, int mem, int k, float smoothness,
                        float curvature_threshold, uint32_t min_size, uint32_t max_size,
                        int32_t *labels, int32_t *n_clusters);
@@ -915,6 +963,7 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
  *  After pcc_cluster_descriptors on the handle: [0] dense-route points, [1] SIFT-route points, [2] octave rounds, [3] keypoints,
  *  [4] snapped points, [5] points sent through the work handle (above either batch limit).
+ *  After pcc_cluster_matching on the handle: [0] searched pairs, [1] queries over all searched pairs.
  *  After pcc_region_growing_rgb on the handle: [0] grown colour segments, [1] distinct ordered segment pairs (s, t) with a row
  *  entry leading from s to t, [7] label sweeps of the growing stage.
  *  After pcc_region_growing_rgb_batch on the handle: [0] grown colour segments, [1] distinct ordered segment pairs and [7] label

@@ -37,7 +37,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_euclidean_cluster_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_cluster_matching", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -117,6 +117,7 @@ def _load() -> C.CDLL:
     lib.pcc_sift_keypoints_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, C.c_double, vp, vp, sz, vp]
     lib.pcc_cluster_descriptors.argtypes = [vp, vp, sz, vp, sz, vp, sz, i32, sz, C.c_float, i32, i32, C.c_float, C.c_double, C.c_double, C.c_double,
                                             C.c_double, i32, i32, vp, vp, sz, vp, vp, vp]
+    lib.pcc_cluster_matching.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
                                            C.POINTER(C.c_int32)]
@@ -1000,6 +1001,64 @@ class Index:
         m = int(off[n_clusters])
         return dict(histograms=hist[:m], point_index=index[:m], offsets=off.astype(np.int64), n_keypoints=nkp[:n_clusters],
                     centroids=cent[:n_clusters])
+
+    def cluster_matching(self, des1, offsets1, des2, offsets2, centroids1, centroids2, points1, points2, threshold: float = 0.05, dim: int = 3):
+        """pcc_cluster_matching with this handle as the context: the reference's cluster-matching loop (src/comparator.cpp:1296-1366)
+        in one call.  des1 / des2: the descriptors of all clusters of a scene one behind the other, (n, >= dim) float32 numpy arrays
+        or torch CUDA tensors (both in the same memory space; rows may be strided) -- with offsets what cluster_descriptors returns
+        as histograms / offsets; offsets_s: (n_clusters_s + 1,) non-decreasing, cluster c of scene s owns rows offsets_s[c] ..
+        offsets_s[c + 1]; centroids_s: (n_clusters_s, 3) float32; points_s: (n_clusters_s,) the clusters' point counts.  The first
+        `dim` floats of every record are searched.  Returns a dict: candidates (n_clusters1, 3) int32 -- the three nearest free
+        clusters of scene 2 by centroid, -1: none --, state (n_clusters1, 3) int32 -- 0 no candidate, 1 gated out by the descriptor
+        counts, 2 gated out by size, 3 searched --, correspondences (n_clusters1, 3) uint32 -- the length of the row match_knn_batch
+        returns for a searched pair, else 0 --, matches (n_clusters1,) int32 -- the accepted cluster of scene 2, or -1."""
+        sides = []
+        for des in (des1, des2):
+            if _is_torch(des):
+                assert des.dtype.is_floating_point and des.element_size() == 4 and des.dim() == 2, "descriptors: (n, >= dim) float32"
+                assert des.shape[0] == 0 or des.stride(1) == 1
+                stride = des.stride(0) * 4 if des.shape[0] > 1 else des.shape[1] * 4
+                sides.append((des.data_ptr() if des.shape[0] else None, des.shape[0], des.shape[1], stride, MEM_DEVICE if des.is_cuda else MEM_HOST))
+            else:
+                assert isinstance(des, np.ndarray) and des.dtype == np.float32 and des.ndim == 2, "descriptors: (n, >= dim) float32"
+                assert des.shape[0] == 0 or des.strides[1] == 4
+                stride = des.strides[0] if des.shape[0] > 1 else des.shape[1] * 4
+                sides.append((des.ctypes.data if des.shape[0] else None, des.shape[0], des.shape[1], stride, MEM_HOST))
+        (p1, n1, w1, s1, m1), (p2, n2, w2, s2, m2) = sides
+        if n1 == 0 or n2 == 0:  # (an empty side has no memory space and no stride of its own)
+            if n1 == 0:
+                s1, m1, w1 = s2, m2, w2
+            if n2 == 0:
+                s2, m2, w2 = s1, m1, w1
+        assert m1 == m2, "both descriptor arrays live in the same memory space"
+        assert s1 == s2, "both descriptor arrays have the same row stride"
+        offs = []
+        for off, n in ((offsets1, n1), (offsets2, n2)):
+            assert off is not None, "offsets: the clusters' bounds"
+            o = np.ascontiguousarray(np.asarray(off), dtype=np.uintp)
+            assert o.ndim == 1 and len(o) >= 1, "offsets holds n_clusters + 1 entries"
+            assert len(o) == 1 or int(o.max()) <= n, "offsets reach beyond the descriptors"
+            offs.append(o)
+        nc1, nc2 = len(offs[0]) - 1, len(offs[1]) - 1
+        cents, pts = [], []
+        for c, p, nc in ((centroids1, points1, nc1), (centroids2, points2, nc2)):
+            c = np.ascontiguousarray(np.asarray(c, dtype=np.float32).reshape(-1, 3))
+            p = np.ascontiguousarray(np.asarray(p), dtype=np.uintp).reshape(-1)
+            assert len(c) == nc and len(p) == nc, "one centroid and one point count per cluster"
+            cents.append(c)
+            pts.append(p)
+        cand = np.full((max(nc1, 1), 3), -1, dtype=np.int32)
+        state = np.zeros((max(nc1, 1), 3), dtype=np.int32)
+        corr = np.zeros((max(nc1, 1), 3), dtype=np.uint32)
+        matches = np.full(max(nc1, 1), -1, dtype=np.int32)
+        st = self._before(des1, des2)
+        status = LIB.pcc_cluster_matching(self._h, p1, offs[0].ctypes.data, nc1, p2, offs[1].ctypes.data, nc2, s1, int(dim), m1,
+                                          cents[0].ctypes.data if nc1 else None, cents[1].ctypes.data if nc2 else None,
+                                          pts[0].ctypes.data if nc1 else None, pts[1].ctypes.data if nc2 else None, float(threshold),
+                                          cand.ctypes.data, state.ctypes.data, corr.ctypes.data, matches.ctypes.data)
+        self._after(st)
+        _check(status)
+        return dict(candidates=cand[:nc1], state=state[:nc1], correspondences=corr[:nc1], matches=matches[:nc1])
 
     def region_growing(self, normals, k: int = 100, smoothness: float = 3.0 / 180.0 * np.pi,
                        curvature_threshold: float = 1.0, min_size: int = 50, max_size: int = 1000000):

@@ -5,7 +5,8 @@
 // :1570-1615 scores and ratios, :1617-1635 verdict).
 //
 // What feeds it is the nearest-neighbour path of this repository: cluster sizes from the segmentation,
-// matchRIFTFeaturesKnnBatch() (one pcc_match_knn_batch for all candidate pairs of a comparison) for the correspondences.  The descriptors
+// matchRIFTFeaturesKnnBatch() (one pcc_match_knn_batch for all candidate pairs of a comparison) for the correspondences -- or, with
+// matching_device, matchClusters() (one pcc_cluster_matching call for the whole matching loop: the same numbers).  The descriptors
 // themselves (SIFT keypoints + RIFT histograms) are NOT computed here -- SURVEY.md section 2 keeps that pipeline
 // out of scope -- they are read from files a caller provides (descriptors_io below); without them every
 // cluster has 0 descriptors, nothing can match and no verdict is given.  The colour-based element count of a match
@@ -21,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "pcc/comparator_nn.hpp"
+#include "pcc/descriptors.hpp"
 #include "pcc/region_growing_rgb.hpp"
 
 namespace pcc {
@@ -127,9 +129,11 @@ private:
 
 // Sections "Information of clusters of PCL2 / PCL 1", the cluster matching between them and "Information of
 // matches ...".  Returns the scores; matches[i] = cluster of PCL 2 matched to cluster i of PCL 1, or -1.
+// matching_device: candidates, gates, correspondence counts and matches come from ONE pcc_cluster_matching call
+// (pcc::matchClusters) instead of the first pass below and matchRIFTFeaturesKnnBatch: the same lines in the same order.
 inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1, const std::vector<CloudPtr>& clusters2,
                               const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches,
-                              int descriptor_dims = 3, bool rgb_device = false, bool rgb_batch = false) {
+                              int descriptor_dims = 3, bool rgb_device = false, bool rgb_batch = false, bool matching_device = false) {
     std::ofstream& f = w.file();
     std::vector<std::vector<float> > centroids2;
     w.sectionTitle("Information of clusters of PCL2:");
@@ -147,8 +151,17 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
     std::vector<std::array<int, 3> > candidates(clusters1.size());
     std::vector<std::array<int, 3> > call_of(clusters1.size());  // position of (i, candidate k) among the gated pairs, -1: gated out
     std::vector<std::pair<DescPtr, DescPtr> > gated;
-    for (size_t i = 0; i < clusters1.size(); ++i) {
-        centroidOf(*clusters1[i], centroids1[i].data());
+    for (size_t i = 0; i < clusters1.size(); ++i) centroidOf(*clusters1[i], centroids1[i].data());
+    ClusterMatches device;
+    if (matching_device) {
+        std::vector<std::array<float, 3> > c2(clusters2.size());
+        for (size_t j = 0; j < clusters2.size(); ++j) std::copy(centroids2[j].begin(), centroids2[j].end(), c2[j].begin());
+        std::vector<size_t> points1(clusters1.size()), points2(clusters2.size());
+        for (size_t i = 0; i < clusters1.size(); ++i) points1[i] = clusters1[i]->points.size();
+        for (size_t j = 0; j < clusters2.size(); ++j) points2[j] = clusters2[j]->points.size();
+        device = matchClusters(des1, des2, centroids1, c2, points1, points2, descriptor_dims);
+    }
+    for (size_t i = 0; !matching_device && i < clusters1.size(); ++i) {
         std::set<int> taken;
         for (int k = 0; k < 3; ++k) {
             candidates[i][k] = nearestFreeCentroid(centroids1[i].data(), centroids2, taken);
@@ -178,12 +191,13 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
         size_t best_corr = 0;
         const size_t n1 = des1[i]->points.size();
         for (int k = 0; k < 3; ++k) {
-            const int j = candidates[i][k];
+            const int j = matching_device ? device.candidates[i][k] : candidates[i][k];
             if (j == -1) { std::cout << "No closer centroid found" << std::endl; continue; }
-            if (call_of[i][k] < 0) continue;  // gated out above
+            if (matching_device ? device.state[i][k] != 3 : call_of[i][k] < 0) continue;  // gated out above
             const size_t n2 = des2[j]->points.size();
             std::cout << "Des pcl 1: " << n1 << std::endl << "Des pcl 2: " << n2 << std::endl;
-            const size_t corr = correspondences[call_of[i][k]].size();  // matches + the dummy first element
+            // matches + the dummy first element
+            const size_t corr = matching_device ? device.correspondences[i][k] : correspondences[call_of[i][k]].size();
             // percentage and acceptance use integer division by the LARGER descriptor count
             const bool first_larger = n1 > n2;
             const size_t denom = first_larger ? n1 : n2;
@@ -195,6 +209,7 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
                 if (first_larger) std::cout << "Match accepted" << std::endl;  // (the reference prints it in this branch only)
             }
         }
+        if (matching_device) matches[i] = device.matches[i];  // (the call's own acceptance: the same rule, bit for bit)
     }
     w.sectionTitle("Information of matches of clusters of PCL 1 and PCL 2:");
     // rgb_batch: every match is known here and no colour segmentation depends on another (reference :1456-1495), so the clusters
