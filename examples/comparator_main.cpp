@@ -46,9 +46,10 @@ static bool seeClusters = false, noise = false, euclidean = false, icp = false;
 // --dump-descriptors PREFIX (the descriptors in use, as PREFIX_<scene>.txt in the format --descriptors1/2 read),
 // --descriptor-dims N (the bins of a descriptor the cluster matching searches on),
 // --rgb-device (the colour segmentation of matched clusters, :1456-1495, as one pcc_region_growing_rgb call each: same report),
-// --rgb-batch (the same for the clusters of ALL accepted matches in one pcc_region_growing_rgb_batch call: same report)
+// --rgb-batch (the same for the clusters of ALL accepted matches in one pcc_region_growing_rgb_batch call: same report),
+// --colours-device (the colour-element counts of ALL accepted matches from one pcc_match_colour_elements call: same report)
 static int n_gpus = 1, descriptor_dims = 3;
-static bool rgb_device = false, rgb_batch = false;
+static bool rgb_device = false, rgb_batch = false, colours_device = false;
 // --planes-device (with -e): the plane-removal loop runs in one library call (pcc_plane_removal through removePlanes): same lines
 static bool planes_device = false;
 // --segment-device (without -e): the whole default segmentation runs in one library call (pcc_region_growing_segmentation through
@@ -100,6 +101,9 @@ static void printUsage() {
               << "                   the GPU (pcc_region_growing_rgb), instead of on the host over downloaded rows: the same report\n"
               << "--rgb-batch        (this build) the colour segmentations of ALL accepted matches run in one library call\n"
               << "                   (pcc_region_growing_rgb_batch) before the match sections are written: the same report\n"
+              << "--colours-device   (this build) the colour-element counts of ALL accepted matches come from one library call\n"
+              << "                   (pcc_match_colour_elements: the clusters of both scenes and the match table go in, every distinct\n"
+              << "                   cluster is segmented once, only the counts come back): the same report\n"
               << "--planes-device    (this build, with -e) the plane-removal loop in front of the clustering runs in ONE library call\n"
               << "                   (pcc_plane_removal: the cloud uploaded once, compacted on the GPU) instead of one call and one\n"
               << "                   host compaction per plane: the same lines, the same clusters\n"
@@ -399,7 +403,7 @@ static double computeSimilarity(const std::string& file1, const std::string& fil
         }
     std::vector<int> matches;
     const report::Scores scores = report::clusterSections(w, clusters_pcl_1, clusters_pcl_2, des[0], des[1], matches, descriptor_dims, rgb_device, rgb_batch,
-                                                          matching_device);
+                                                          matching_device, colours_device);
 
     if (noise) {
         PointCloud<PointXYZRGB> nonoise[2];
@@ -463,6 +467,7 @@ int main(int argc, char** argv) {
         else if (a == "--matching-device") matching_device = true;
         else if (a == "--rgb-device") rgb_device = true;
         else if (a == "--rgb-batch") rgb_batch = true;
+        else if (a == "--colours-device") colours_device = true;
         else if (a == "--planes-device") planes_device = true;
         else if (a == "--segment-device") segment_device = true;
         else if (a == "--euclidean-device") euclidean_device = true;

@@ -26,8 +26,13 @@
 //
 // color_growing_segmentation_batch does the same for MANY clouds in one pcc_region_growing_rgb_batch call -- the two
 // segmentations of every accepted match of a comparison, none of which depends on another.
+//
+// matchColourElements goes one step further for the match loop (src/comparator.cpp:1379-1509), which keeps only the NUMBER of
+// colour segments of either cluster: the clusters of both scenes and the match table in ONE pcc_match_colour_elements call, every
+// distinct cluster segmented once, nothing but the counts coming back.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <limits>
 #include <queue>
 #include <stdexcept>
@@ -358,6 +363,39 @@ inline std::vector<std::vector<typename PointCloud<PointT>::Ptr> > color_growing
         for (size_t i = 0; i < sent[c]->size(); ++i)
             if (l[i] >= 0) out[c][(size_t)l[i]]->push_back(sent[c]->points[i]);
     }
+    return out;
+}
+
+// The colour-element counts of the match loop in ONE library call (pcc_match_colour_elements): element i is {-1, -1} when
+// matches[i] == -1, else {color_growing_segmentation(clusters1[i]).size(), color_growing_segmentation(clusters2[matches[i]]).size()}
+// -- the same gate of more than 10 finite points, the reference's thresholds 10 / 6 / 5, minimum cluster size 200, PCL's 30 and
+// 100 neighbours.  The clusters of a scene (null: an empty one) are concatenated once into one record array with offsets; a
+// cluster of scene 2 that several matches name is segmented once.  ctx (nullable): any handle to lend device, stream and scratch.
+// No match at all: no library call.
+inline std::vector<std::array<int, 2> > matchColourElements(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clusters1,
+                                                            const std::vector<PointCloud<PointXYZRGB>::Ptr>& clusters2,
+                                                            const std::vector<int>& matches, pcc_index* ctx = nullptr) {
+    const size_t nc1 = clusters1.size(), nc2 = clusters2.size();
+    if (matches.size() != nc1) throw Error(PCC_ERR_INVALID, "matchColourElements: one match per cluster of the first scene");
+    std::vector<std::array<int, 2> > out(nc1, std::array<int, 2>{{-1, -1}});
+    if (std::all_of(matches.begin(), matches.end(), [](int m) { return m == -1; })) return out;
+    std::vector<PointXYZRGB> all[2];
+    std::vector<size_t> offsets[2];
+    for (int s = 0; s < 2; ++s) {
+        const std::vector<PointCloud<PointXYZRGB>::Ptr>& clusters = s ? clusters2 : clusters1;
+        offsets[s].assign(clusters.size() + 1, 0);
+        for (size_t c = 0; c < clusters.size(); ++c) offsets[s][c + 1] = offsets[s][c] + (clusters[c] ? clusters[c]->size() : 0);
+        all[s].reserve(offsets[s].back());
+        for (size_t c = 0; c < clusters.size(); ++c)
+            if (clusters[c]) all[s].insert(all[s].end(), clusters[c]->points.begin(), clusters[c]->points.end());
+    }
+    const std::vector<int32_t> table(matches.begin(), matches.end());
+    static_assert(sizeof(std::array<int, 2>) == 2 * sizeof(int32_t), "rows of two");
+    const void* pts[2] = {all[0].empty() ? nullptr : &all[0][0].x, all[1].empty() ? nullptr : &all[1][0].x};
+    const void* rgb[2] = {all[0].empty() ? nullptr : &all[0][0].rgba, all[1].empty() ? nullptr : &all[1][0].rgba};
+    check(pcc_match_colour_elements(detail::batchContext<PointXYZRGB>(ctx), pts[0], rgb[0], offsets[0].data(), nc1, pts[1], rgb[1], offsets[1].data(), nc2,
+                                    sizeof(PointXYZRGB), sizeof(PointXYZRGB), PCC_MEM_HOST, table.data(), 10, 10.f, 6.f, 5.f, 200u,
+                                    (uint32_t)std::numeric_limits<int>::max(), 30u, 100u, out[0].data()));
     return out;
 }
 

@@ -888,6 +888,57 @@ int pcc_region_growing_rgb_batch(pcc_index *ctx, size_t n_clouds,
                                  uint32_t min_size, uint32_t max_size,
                                  unsigned int nr_neighbours, unsigned int nr_region_neighbours,
                                  int32_t *out_labels /* [sum(n)] */, int32_t *out_n_clusters /* [n_clouds] */);
+/* The colour counts of a comparison's match loop in one call -- replaces, for all accepted matches at once, the two
+ *   color_growing_segmentation calls of the match loop (src/comparator.cpp:1379-1509; the calls :1456-1495, the body
+ *   src/segmentation.cpp:161-216), of which the loop keeps colors_segments_pcl1.size() and colors_segments_pcl2.size() alone.
+ *   Where pcc_region_growing_rgb_batch takes one host pointer per cloud and brings every label back, this call takes the
+ *   clusters as the segmentation calls write them -- records behind one another with offsets, in host or device memory -- and
+ *   the match table pcc_cluster_matching writes, and returns the counts.  Every distinct (scene, cluster) the table names is
+ *   segmented ONCE, however many matches name it (closestCentroid's exclusion set is per cluster of scene 1, so several
+ *   clusters of scene 1 can be matched to one cluster of scene 2).  The named clusters are packed on the device into one
+ *   concatenation (one launch, which also counts the finite points of every cluster) and pcc_region_growing_rgb_batch's row
+ *   kernel and stages run once over it, without their label half.  Launches and waits depend on the label sweeps, not on the
+ *   number of clusters or matches.
+ *   ctx: any index handle, as for the other batch calls: it supplies device, stream and scratch; its cloud, tie order and kept
+ *     rows are neither read nor changed.
+ *   Cluster c of scene s is records offsets_s[c] .. offsets_s[c + 1] of pts_s, stride_bytes apart with x, y, z first; PCL's
+ *     packed colour word of record i sits at rgb_s + i * rgb_stride_bytes.  All four arrays are in memory space `mem`,
+ *     PCC_MEM_HOST or PCC_MEM_DEVICE: what pcc_region_growing_segmentation and pcc_euclidean_cluster_segmentation write as
+ *     out_cluster_points / out_offsets (32-byte records: rgb = pts + 16, the same stride).  offsets_s (HOST, n_clusters_s + 1)
+ *     is non-decreasing and spans fewer than 2^31 records.
+ *   matches[i] (HOST): the cluster of scene 2 matched to cluster i of scene 1, or -1: pcc_cluster_matching's out_matches.
+ *   out_elements[i] (HOST): {-1, -1} when matches[i] == -1; else [0] the colour-element count of cluster i of scene 1 and [1]
+ *     that of cluster matches[i] of scene 2.  The count of a cluster with at most min_points finite points is 0 -- the
+ *     reference's gate, size() > 10 after removeNaNFromPointCloud (src/segmentation.cpp:164-167); an empty cluster and one
+ *     without a finite point fall under it.  Otherwise it is, bit for bit, the *n_clusters that pcc_index_create(cluster) +
+ *     pcc_region_growing_rgb(...) give on a fresh handle with the same seven parameters.  Non-finite points take part in
+ *     nothing; no point of another cluster enters a row, a segment or a segment pair.
+ *   To the host cross, inside the call: what the stages of pcc_region_growing_rgb bring (three words per label sweep, the
+ *     segment records, the pair list, the clusters' first segment ids) and one finite count per segmented cluster, in the first
+ *     sweep's wait.  No label is downloaded.  From PCC_MEM_DEVICE no point or colour crosses in either direction; from
+ *     PCC_MEM_HOST the records of the named clusters go up once, in the copy that carries the tables.
+ *   Clusters above PCC_OPT_RGB_BATCH_BRUTE_MAX records, and every cluster when nr_region_neighbours > 128, take
+ *     pcc_index_set_input + pcc_region_growing_rgb on a work handle kept in ctx (reused across calls, freed with ctx; same
+ *     bits), one by one, straight from the device array (host memory: from what went up), their labels to device scratch.
+ *   pcc_index_stats afterwards: [0] grown colour segments, [1] distinct ordered segment pairs and [7] label sweeps of the
+ *     batch route; [2] points through the batch kernels, [3] points through the work handle, [4] distinct clusters segmented,
+ *     [5] segmentations the deduplication saved.
+ *   Refused before the handle is looked at, in this order: 1. a bad memory space; 2. null arrays (offsets_2 may be null while
+ *     scene 2 has no cluster; matches and out_elements go with scene 1; a scene's pts and rgb may be null while no matched
+ *     cluster of it holds a record); 3. a bad stride or alignment, by pcc_region_growing_rgb_batch's rules and messages;
+ *     4. offsets that decrease (PCC_ERR_INVALID) or span 2^31 records and more (PCC_ERR_UNSUPPORTED); 5. a matches[i] outside
+ *     [-1, n_clusters2) (PCC_ERR_INVALID; the message names i); 6. what pcc_region_growing_rgb refuses about thresholds and
+ *     neighbour counts; 7. a null handle.  A refused call writes nothing.  n_clusters1 == 0, and a table without an entry
+ *     >= 0 (out_elements is then -1 throughout), are PCC_OK without a handle or a device.  A batch route of 2^31 points and
+ *     more, or one whose rows would hold 2^32 entries and more, is PCC_ERR_UNSUPPORTED: split the call. */
+int pcc_match_colour_elements(pcc_index *ctx,
+                              const void *pts1, const void *rgb1, const size_t *offsets1 /* HOST [n_clusters1 + 1] */, size_t n_clusters1,
+                              const void *pts2, const void *rgb2, const size_t *offsets2 /* HOST [n_clusters2 + 1] */, size_t n_clusters2,
+                              size_t stride_bytes, size_t rgb_stride_bytes, int mem,
+                              const int32_t *matches /* HOST [n_clusters1] */, size_t min_points,
+                              float distance_threshold, float point_color_threshold, float region_color_threshold,
+                              uint32_t min_size, uint32_t max_size, unsigned int nr_neighbours, unsigned int nr_region_neighbours,
+                              int32_t *out_elements /* HOST [n_clusters1][2] */);
 
 /* ---- first point within a radius ----------------------------------------------------------------
  * replaces: the O(S*N) linear scan in processRIFTwithSIFT (src/comparator.cpp:696-713) that snaps
@@ -968,7 +1019,10 @@ int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count
  *  entry leading from s to t, [7] label sweeps of the growing stage.
  *  After pcc_region_growing_rgb_batch on the handle: [0] grown colour segments, [1] distinct ordered segment pairs and [7] label
  *  sweeps of the batch route (all its clouds together), [2] points that went through the batch kernels, [3] points of the
- *  clouds sent through the work handle (above PCC_OPT_RGB_BATCH_BRUTE_MAX, or nr_region_neighbours > 128). */
+ *  clouds sent through the work handle (above PCC_OPT_RGB_BATCH_BRUTE_MAX, or nr_region_neighbours > 128).
+ *  After pcc_match_colour_elements on the handle: [0], [1], [7] as after pcc_region_growing_rgb_batch, [2] points that went through
+ *  the batch kernels, [3] points of the clusters sent through the work handle, [4] distinct clusters segmented (the profiling
+ *  build reports its pair counter there instead), [5] segmentations the deduplication saved. */
 int pcc_index_stats(const pcc_index *index, uint64_t stats[8]);
 /* 1 when this library was built with the pair counter (-DPCC_COUNT_PAIRS: the profiling build), else 0 */
 int pcc_counts_pairs(void);

@@ -37,7 +37,7 @@ SYMBOLS = [
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_euclidean_cluster_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
-    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_cluster_matching", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
+    "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_cluster_matching", "pcc_match_colour_elements", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
@@ -118,6 +118,8 @@ def _load() -> C.CDLL:
     lib.pcc_cluster_descriptors.argtypes = [vp, vp, sz, vp, sz, vp, sz, i32, sz, C.c_float, i32, i32, C.c_float, C.c_double, C.c_double, C.c_double,
                                             C.c_double, i32, i32, vp, vp, sz, vp, vp, vp]
     lib.pcc_cluster_matching.argtypes = [vp, vp, vp, sz, vp, vp, sz, sz, i32, i32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp]
+    lib.pcc_match_colour_elements.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, sz, sz, sz, i32, vp, sz, C.c_float, C.c_float, C.c_float, C.c_uint32,
+                                              C.c_uint32, C.c_uint, C.c_uint, vp]
     lib.pcc_region_growing.argtypes = [vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint32, C.c_uint32, vp, vp]
     lib.pcc_region_growing_rgb.argtypes = [vp, vp, sz, i32, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, C.c_uint, C.c_uint, vp,
                                            C.POINTER(C.c_int32)]
@@ -178,7 +180,7 @@ def _points(x):
     """(pointer, n, stride_bytes, mem) of an (n, >=3) float32 numpy array or torch tensor."""
     if _is_torch(x):
         assert x.dtype.is_floating_point and x.element_size() == 4 and x.dim() == 2 and x.shape[1] >= 3
-        assert x.stride(1) == 1
+        assert x.shape[0] == 0 or x.stride(1) == 1  # (an empty tensor made from an empty array has no strides to speak of)
         mem = MEM_DEVICE if x.is_cuda else MEM_HOST
         return x.data_ptr(), x.shape[0], x.stride(0) * 4 if x.shape[0] > 1 else x.shape[1] * 4, mem
     a = x
@@ -1059,6 +1061,61 @@ class Index:
         self._after(st)
         _check(status)
         return dict(candidates=cand[:nc1], state=state[:nc1], correspondences=corr[:nc1], matches=matches[:nc1])
+
+    def match_colour_elements(self, points1, offsets1, points2, offsets2, matches, rgb1=None, rgb2=None, min_points: int = 10,
+                              distance: float = 10.0, point_colour: float = 6.0, region_colour: float = 5.0, min_size: int = 200,
+                              max_size: int | None = None, nn: int = 30, region_nn: int = 100):
+        """pcc_match_colour_elements with this handle as the context: the colour-element counts of the reference's match loop
+        (src/comparator.cpp:1379-1509) in one call.  points_s: the clusters of scene s one behind the other, (n, >= 3) float32 numpy
+        arrays (host) or torch CUDA tensors (device), both in the same memory space with the same row stride; offsets_s:
+        (n_clusters_s + 1,) non-decreasing, cluster c owns rows offsets_s[c] .. offsets_s[c + 1] -- what
+        region_growing_segmentation / euclidean_cluster_segmentation return as cluster_points / offsets; rgb_s: one colour per
+        point in any of rift_descriptors' three forms, in the memory space of the points, or None when the points are (n, 8)
+        pcl::PointXYZRGB records (rgb = pts + 16).  matches: (n_clusters1,) the matched cluster of scene 2 or -1, what
+        cluster_matching returns.  Returns an (n_clusters1, 2) int32 array: row i is (-1, -1) without a match, else the counts of
+        cluster i of scene 1 and of cluster matches[i] of scene 2; a cluster with at most min_points finite points counts 0, any
+        other what Index(cluster).region_growing_rgb(...) counts.  Every distinct cluster is segmented once."""
+        sides = []
+        for points, rgb in ((points1, rgb1), (points2, rgb2)):
+            ptr, n, stride, mem = _points(points)
+            if rgb is None:
+                assert points.shape[1] >= 5, "PointXYZRGB records have their colour word in column 4"
+                words, cptr, cstride, cmem = points, ptr + 16, stride, mem
+            else:
+                assert len(rgb) == n, "one colour per point"
+                words, cptr, cstride, cmem = _colour_words(rgb) if n else (rgb, None, 4, mem)
+            assert cmem == mem, "points and colours live in the same memory space"
+            sides.append([ptr if n else None, cptr if n else None, n, stride, cstride, mem, words])
+        a, b = sides
+        for x, y in ((a, b), (b, a)):  # (an empty side has no memory space and no strides of its own)
+            if x[2] == 0:
+                x[3:6] = y[3:6]
+            elif x[2] == 1 and y[2] > 1:
+                x[3:5] = y[3:5]
+        assert a[5] == b[5], "both scenes live in the same memory space"
+        assert a[3] == b[3] and a[4] == b[4], "both scenes have the same row stride, and so both colour arrays"
+        offs = []
+        for off, side in ((offsets1, a), (offsets2, b)):
+            assert off is not None, "offsets: the clusters' bounds"
+            o = np.ascontiguousarray(np.asarray(off), dtype=np.uintp)
+            assert o.ndim == 1 and len(o) >= 1, "offsets holds n_clusters + 1 entries"
+            assert len(o) == 1 or int(o.max()) <= side[2], "offsets reach beyond the points"
+            offs.append(o)
+        nc1, nc2 = len(offs[0]) - 1, len(offs[1]) - 1
+        m = np.ascontiguousarray(np.asarray(matches), dtype=np.int32).reshape(-1)
+        assert len(m) == nc1, "one match per cluster of scene 1"
+        out = np.zeros((max(nc1, 1), 2), dtype=np.int32)
+        st = self._before(points1, points2, a[6], b[6])
+        if a[5] == MEM_DEVICE and st is None:
+            import torch
+            torch.cuda.current_stream((points1 if a[2] else points2).device).synchronize()
+        status = LIB.pcc_match_colour_elements(self._h, a[0], a[1], offs[0].ctypes.data, nc1, b[0], b[1], offs[1].ctypes.data, nc2, a[3], a[4], a[5],
+                                               m.ctypes.data if nc1 else None, int(min_points), np.float32(distance), np.float32(point_colour),
+                                               np.float32(region_colour), int(min_size), 2**31 - 1 if max_size is None else int(max_size),
+                                               int(nn), int(region_nn), out.ctypes.data)
+        self._after(st)
+        _check(status)
+        return out[:nc1]
 
     def region_growing(self, normals, k: int = 100, smoothness: float = 3.0 / 180.0 * np.pi,
                        curvature_threshold: float = 1.0, min_size: int = 50, max_size: int = 1000000):

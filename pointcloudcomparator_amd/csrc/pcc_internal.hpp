@@ -299,6 +299,7 @@ struct BatchStaging {
 struct RiftBatchScratch;   // rift_batch.hip: BatchStaging and the CSR of pcc_rift_descriptors_batch
 struct SiftBatchScratch;   // sift_batch.hip: BatchStaging and the voxel keys, tables and CSR of pcc_sift_keypoints_batch
 struct RgbBatchScratch;    // region_rgb_batch.hip: BatchStaging and the rows of pcc_region_growing_rgb_batch
+struct MatchColourScratch; // match_colour.hip: BatchStaging, the packed concatenation, rows and finite counts of pcc_match_colour_elements
 struct ClusterDescScratch; // cluster_desc.hip: BatchStaging, the staged clusters, snap indices and RIFT clouds of pcc_cluster_descriptors
 struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
                            // and the orders and tables of pcc_extract_clusters
@@ -392,6 +393,7 @@ struct pcc_index {
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
     pcc::RgbBatchScratch* rgb_batch = nullptr;    // made at the first pcc_region_growing_rgb_batch with this handle as its context (region_rgb_batch.hip)
+    pcc::MatchColourScratch* match_colour = nullptr;  // made at the first pcc_match_colour_elements with this handle as its context (match_colour.hip)
     pcc::ClusterDescScratch* cluster_desc = nullptr;  // made at the first pcc_cluster_descriptors with this handle as its context (cluster_desc.hip)
     pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
@@ -656,6 +658,8 @@ void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work ha
 void cluster_desc_release(pcc_index* ix);  // frees ix->cluster_desc and its work handle
 // region_rgb_batch.hip: pcc_region_growing_rgb_batch behind its argument checks
 void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work handle
+// match_colour.hip: pcc_match_colour_elements
+void match_colour_release(pcc_index* ix);  // frees ix->match_colour and its work handle
 // segment.hip: pcc_extract_clusters and pcc_region_growing_segmentation
 void segment_release(pcc_index* ix);  // frees ix->segment and its work handle
 // normals.hip: the plane fit over the self k-NN rows `keys` (n x K) of a packed cloud

@@ -445,19 +445,23 @@ int rgb_stages_in(pcc_index* ix, const RgbRun& run, const Order& order, const Rg
     std::vector<int32_t> cluster_of_segment;
     PCC_TRY(host_half(h_stats, ns, h_pairs, np, cluster_of_segment));
     if (cluster_of_segment.size() != ns) { set_error("colour region growing: %zu cluster ids for %u segments", cluster_of_segment.size(), ns); return PCC_ERR_DEVICE; }
-    int32_t* d_ids = nullptr;
-    if (ns) {
-        int32_t* h_ids = ix->host_a.as<int32_t>();  // (the records are used up; ns x 16 bytes hold ns ids)
-        std::copy(cluster_of_segment.begin(), cluster_of_segment.end(), h_ids);
-        PCC_TRY(ix->rows_d2.reserve((size_t)ns * sizeof(int32_t)));
-        d_ids = ix->rows_d2.as<int32_t>();
-        PCC_HIP(hipMemcpyAsync(d_ids, h_ids, (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (run.labels_dev) {
+        int32_t* d_ids = nullptr;
+        if (ns) {
+            int32_t* h_ids = ix->host_a.as<int32_t>();  // (the records are used up; ns x 16 bytes hold ns ids)
+            std::copy(cluster_of_segment.begin(), cluster_of_segment.end(), h_ids);
+            PCC_TRY(ix->rows_d2.reserve((size_t)ns * sizeof(int32_t)));
+            d_ids = ix->rows_d2.as<int32_t>();
+            PCC_HIP(hipMemcpyAsync(d_ids, h_ids, (size_t)ns * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        }
+        hipLaunchKernelGGL(k_rgb_label, dim3(g1(n)), dim3(256), 0, s, seg, d_ids, n, ns, run.labels_dev);
+        PCC_HIP(hipGetLastError());
+        if (run.labels_host) PCC_HIP(hipMemcpyAsync(run.labels_host, run.labels_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        ev_mark(ix, EV_MAIN1);
+        PCC_HIP(hipStreamSynchronize(s));  // h_ids may be rewritten by the next call
+    } else {
+        ev_mark(ix, EV_MAIN1);  // (counts only: nothing has been enqueued since the wait for the pair list)
     }
-    hipLaunchKernelGGL(k_rgb_label, dim3(g1(n)), dim3(256), 0, s, seg, d_ids, n, ns, run.labels_dev);
-    PCC_HIP(hipGetLastError());
-    if (run.labels_host) PCC_HIP(hipMemcpyAsync(run.labels_host, run.labels_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    ev_mark(ix, EV_MAIN1);
-    PCC_HIP(hipStreamSynchronize(s));  // h_ids may be rewritten by the next call
     ix->stats[0] = ns;
     ix->stats[1] = np;
     ix->stats[7] = sweeps;

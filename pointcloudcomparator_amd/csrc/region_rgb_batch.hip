@@ -39,8 +39,6 @@ namespace pcc {
 
 namespace {
 
-constexpr unsigned int RGB_BATCH_MAX_K = 128;  // the longest row the batch kernel builds (two registers of top list per lane)
-
 // register r of a top list, r wave-uniform: selects, so that the list is never indexed by a variable
 template <int KR>
 __device__ __forceinline__ unsigned long long top_reg(const unsigned long long (&top)[KR], int r) {
@@ -133,6 +131,15 @@ k_rgb_batch_knn(const RiftBatchItem* __restrict__ items, const float4* __restric
 
 }  // namespace
 
+int rgb_batch_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, int K, unsigned long long* keys) {
+    if (K <= 64)
+        hipLaunchKernelGGL(k_rgb_batch_knn<1>, dim3(n_items), dim3(256), 0, ix->stream, d_items, d_pts, K, keys);
+    else
+        hipLaunchKernelGGL(k_rgb_batch_knn<2>, dim3(n_items), dim3(256), 0, ix->stream, d_items, d_pts, K, keys);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
+
 struct RgbBatchScratch : BatchStaging {  // (up: bases + table + points + colour words; down: the clouds' first ids + labels)
     DevBuf keys;              // u64[total][K]: the rows
     DevBuf id_bases, labels;  // uint32[n_clouds + 1]; int32[total]
@@ -184,12 +191,7 @@ int rgb_batch_route(pcc_index* ix, const CloudBatch& batch, const RgbParams& par
     // ---- the rows ------------------------------------------------------------------------------------------------------------
     PCC_TRY(b->keys.reserve(total * (size_t)K * sizeof(unsigned long long)));
     unsigned long long* keys = b->keys.as<unsigned long long>();
-    const unsigned int n_items = (unsigned int)items.size();
-    if (K <= 64)
-        hipLaunchKernelGGL(k_rgb_batch_knn<1>, dim3(n_items), dim3(256), 0, s, d_items, d_pts, K, keys);
-    else
-        hipLaunchKernelGGL(k_rgb_batch_knn<2>, dim3(n_items), dim3(256), 0, s, d_items, d_pts, K, keys);
-    PCC_HIP(hipGetLastError());
+    PCC_TRY(rgb_batch_rows(ix, d_items, (unsigned int)items.size(), d_pts, K, keys));
 
     // ---- the stages of the single call, once over the concatenation -------------------------------------------------------
     const size_t ids_bytes = align_up((n_clouds + 1) * sizeof(unsigned int), 16);

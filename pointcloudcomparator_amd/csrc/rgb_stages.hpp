@@ -32,7 +32,8 @@ struct RgbRun {
     unsigned int n_clouds = 0;
     unsigned int* d_id_bases = nullptr;
     unsigned int* h_id_bases = nullptr;
-    int32_t* labels_dev = nullptr;   // labels[n] (device)
+    int32_t* labels_dev = nullptr;   // labels[n] (device).  Null: counts only -- the host half's result is all the caller wants, so
+                                     // no cluster id goes up, no label is written and the last wait falls away
     int32_t* labels_host = nullptr;  // nullable, pinned: the labels are copied there in front of the last wait
 };
 
@@ -49,5 +50,10 @@ int check_rgb_params(float distance_threshold, float point_color_threshold, floa
 // Waits: one per label sweep, one for the segment count (and the clouds' first ids), one for the pair count, one for the pair
 // list (a second one beyond 2^18 pairs), one at the end.  Leaves segments, pairs and sweeps in ix->stats[0], [1], [7].
 int rgb_stages(pcc_index* ix, const RgbRun& run, const RgbHostHalf& host_half);
+
+// region_rgb_batch.hip: the rows of a concatenation, keys[total][K], for whoever brings its points (w = bits(concatenated index),
+// negative for a non-finite point) and rift_batch_plan.hpp's items on the device: k_rgb_batch_knn, one launch.  K <= RGB_BATCH_MAX_K.
+constexpr unsigned int RGB_BATCH_MAX_K = 128;  // the longest row the batch kernel builds (two registers of top list per lane)
+int rgb_batch_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, int K, unsigned long long* keys);
 
 }  // namespace pcc

@@ -131,9 +131,12 @@ private:
 // matches ...".  Returns the scores; matches[i] = cluster of PCL 2 matched to cluster i of PCL 1, or -1.
 // matching_device: candidates, gates, correspondence counts and matches come from ONE pcc_cluster_matching call
 // (pcc::matchClusters) instead of the first pass below and matchRIFTFeaturesKnnBatch: the same lines in the same order.
+// colours_device: the colour-element counts of all matches come from ONE pcc_match_colour_elements call
+// (pcc::matchColourElements) before the first match section is written: the same report.
 inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1, const std::vector<CloudPtr>& clusters2,
                               const std::vector<DescPtr>& des1, const std::vector<DescPtr>& des2, std::vector<int>& matches,
-                              int descriptor_dims = 3, bool rgb_device = false, bool rgb_batch = false, bool matching_device = false) {
+                              int descriptor_dims = 3, bool rgb_device = false, bool rgb_batch = false, bool matching_device = false,
+                              bool colours_device = false) {
     std::ofstream& f = w.file();
     std::vector<std::vector<float> > centroids2;
     w.sectionTitle("Information of clusters of PCL2:");
@@ -215,12 +218,16 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
     // rgb_batch: every match is known here and no colour segmentation depends on another (reference :1456-1495), so the clusters
     // of all accepted matches go through ONE pcc_region_growing_rgb_batch call before the first match section is written
     std::vector<size_t> colour_counts;
-    if (rgb_batch) {
+    if (rgb_batch && !colours_device) {
         std::vector<CloudPtr> both;
         for (size_t i = 0; i < matches.size(); ++i)
             if (matches[i] != -1) { both.push_back(clusters1[i]); both.push_back(clusters2[(size_t)matches[i]]); }
         for (const std::vector<CloudPtr>& segments : color_growing_segmentation_batch<PointXYZRGB>(both)) colour_counts.push_back(segments.size());
     }
+    // colours_device: the same, from the clusters of both scenes and the match table in ONE pcc_match_colour_elements call -- only
+    // the counts come back, and a cluster of PCL 2 that several matches name is segmented once
+    std::vector<std::array<int, 2> > colour_elements;
+    if (colours_device) colour_elements = matchColourElements(clusters1, clusters2, matches);
     size_t next_count = 0;
     Scores s;
     for (size_t i = 0; i < matches.size(); ++i) {
@@ -236,9 +243,13 @@ inline Scores clusterSections(Writer& w, const std::vector<CloudPtr>& clusters1,
             s.des1 += d1; s.des2 += d2;
             // colour based segmentation of both clusters: which one has more elements of different colours
             // (rgb_device: the whole segmentation in the library, pcc_region_growing_rgb -- the same segments)
-            // (rgb_batch: the counts of the one batch call above, in match order)
-            const size_t c1 = rgb_batch ? colour_counts[next_count] : color_growing_segmentation<PointXYZRGB>(clusters1[i], rgb_device).size();
-            const size_t c2 = rgb_batch ? colour_counts[next_count + 1] : color_growing_segmentation<PointXYZRGB>(clusters2[j], rgb_device).size();
+            // (rgb_batch: the counts of the one batch call above, in match order; colours_device: row i of the one call's table)
+            const size_t c1 = colours_device ? (size_t)colour_elements[i][0]
+                              : rgb_batch    ? colour_counts[next_count]
+                                             : color_growing_segmentation<PointXYZRGB>(clusters1[i], rgb_device).size();
+            const size_t c2 = colours_device ? (size_t)colour_elements[i][1]
+                              : rgb_batch    ? colour_counts[next_count + 1]
+                                             : color_growing_segmentation<PointXYZRGB>(clusters2[j], rgb_device).size();
             next_count += 2;
             w.compareColour(c1, c2);
             s.colour1 += c1; s.colour2 += c2;
