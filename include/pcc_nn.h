@@ -598,6 +598,84 @@ int pcc_euclidean_cluster_segmentation(pcc_index *ctx, const void *pts, size_t n
                                        int32_t *out_labels,
                                        size_t max_clusters, int32_t *n_clusters, size_t *out_offsets,
                                        void *out_cluster_points, int32_t *out_cluster_index);
+/* ---- the morphological ground filter ------------------------------------------------------------------
+ * replaces: ground_segmentation (src/segmentation.cpp:330-387): pcl::VoxelGrid<PointXYZ> (leaf 0.01) ->
+ *   pcl::ProgressiveMorphologicalFilter (max window 20, slope 1, initial distance 0.5, max distance 3; PCL's defaults cell
+ *   size 1, base 2, exponential) -> pcl::ExtractIndices, positive and negative.  PCL 1.7's filter and its
+ *   applyMorphologicalOperator are restated from the published source as recalled; parity with PCL itself is unpinned.
+ * All arithmetic is float32, every operation rounded on its own, unless it says double. */
+enum pcc_morph_op { PCC_MORPH_DILATE = 0, PCC_MORPH_ERODE = 1, PCC_MORPH_OPEN = 2, PCC_MORPH_CLOSE = 3 };
+#define PCC_PMF_MAX_WINDOWS 64
+/* The window table of ProgressiveMorphologicalFilter::extract (src/segmentation.cpp:330-387 sets its parameters at :352-358).
+ * Host arithmetic, no handle:
+ *     it = 0; w = 0.0f
+ *     while (w < (float)max_window_size):
+ *         w = exponential ? float((double)cell_size * (2.0 * pow((double)base, it) + 1.0))
+ *                         : float((double)cell_size * (2.0 * (it + 1) * (double)base + 1.0))
+ *         h = it == 0 ? initial_distance : ((slope * (w - windows[it - 1])) * cell_size) + initial_distance
+ *         if (h > max_distance) h = max_distance
+ *         windows[it] = w; thresholds[it] = h; ++it
+ *   (the last window may exceed max_window_size: 3, 5, 9, 17, 33 for the reference's parameters).
+ * out_windows, out_thresholds: `capacity` floats each; *n_windows: the table's length.  A longer table than `capacity` or than
+ *   PCC_PMF_MAX_WINDOWS: PCC_ERR_OVERFLOW, *n_windows set (PCC_PMF_MAX_WINDOWS + 1 stands for any greater length), the first
+ *   min(capacity, PCC_PMF_MAX_WINDOWS) entries written.
+ * PCC_ERR_INVALID: a null output; a slope, distance, cell size or base that is not finite; cell_size <= 0; base <= 1 with
+ *   exponential; base <= 0 without (PCL loops forever on the last three). */
+int pcc_pmf_windows(int max_window_size, float slope, float initial_distance, float max_distance, float cell_size, float base,
+                    int exponential, size_t capacity, float *out_windows, float *out_thresholds, size_t *n_windows);
+/* pcl::applyMorphologicalOperator (the operator ground_segmentation's filter runs twice per window, src/segmentation.cpp:330-387)
+ * over all n points, with window `window`:
+ *   half = window / 2.0f; the box of point i is lo_x = x_i - half, hi_x = x_i + half and the same in y; point j lies in B(i) when
+ *   lo_x <= x_j && x_j <= hi_x && lo_y <= y_j && y_j <= hi_y -- both ends inclusive, the edges computed exactly as written; z
+ *   takes no part.  A point with a non-finite coordinate enters no box and its output is its input z.
+ *   PCC_MORPH_ERODE: out_i = min z_j over B(i); DILATE: max; OPEN: e = ERODE(z), out_i = max e_j over B(i); CLOSE: its dual.
+ *   The results are exact by value (a zero's sign is unspecified: min / max of floats depend on the order in nothing else).
+ * out_z[n]: space `mem`.  n == 0: PCC_OK.  Device memory: enqueued, no wait.  Host memory: one wait, at the end.
+ * How: the points are binned into an xy lattice (cell side window / 8, doubled until the table has at most max(16384, n) and
+ *   at most 2^20 cells), sorted by cell, and
+ *   every cell's min / max is reduced once; a point takes the aggregates of the cells strictly inside its cell range and tests
+ *   the points of the rim cells with the comparisons above.  The binning is monotone, so the result does not depend on the
+ *   lattice.  A window whose boxes all hold the whole cloud is one global min / max.
+ * Refused before any device is touched, in this order: a bad memory space, point pointer, stride or 2^31 points and more (as
+ *   everywhere); a null out_z with n > 0; an op outside pcc_morph_op; a window that is not finite and positive
+ *   (PCC_ERR_INVALID); a null handle last.
+ * `ctx` is any index handle: the cloud it indexes, its tie order and its kept rows are neither read nor changed. */
+int pcc_morphological_operator(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, float window, int op,
+                               float *out_z);
+/* pcl::ProgressiveMorphologicalFilter::extract (src/segmentation.cpp:330-387, the filter between the voxel grid and
+ * ExtractIndices): the window table of pcc_pmf_windows, then
+ *     ground = all indices, ascending
+ *     for each (w, h):  o = OPEN over the points of `ground` alone;  keep i when (z_i - o_i) < h  (strict);  the order stays
+ * One deviation from PCL: a point with a non-finite coordinate is never ground (PCL lets one with finite z through; the
+ *   reference's voxel grid drops such points first).
+ * out_ground[n] (space `mem`): the original indices of the ground points, ascending, *n_ground (HOST) of them.
+ * out_pass_sizes (HOST, may be NULL): the survivors after each window, min(windows, max_passes) entries.
+ * The cloud goes up once, the survivors are compacted on the device between windows, and the host waits once per window (for
+ *   the survivor count): launches and waits do not depend on n.  n == 0 or no finite point: PCC_OK, *n_ground = 0.
+ * Refused before any device is touched, in this order: what pcc_morphological_operator refuses about the cloud; a null
+ *   out_ground with n > 0 or a null n_ground; what pcc_pmf_windows refuses (a table longer than PCC_PMF_MAX_WINDOWS is
+ *   PCC_ERR_OVERFLOW); a null handle last. */
+int pcc_progressive_morphological_filter(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
+                                         int max_window_size, float slope, float initial_distance, float max_distance,
+                                         float cell_size, float base, int exponential,
+                                         int32_t *out_ground, size_t *n_ground, size_t *out_pass_sizes, size_t max_passes);
+/* ground_segmentation (src/segmentation.cpp:330-387) in one call.  Every output is, bit for bit, what this sequence gives:
+ *     pcc_voxel_grid(ctx, pts, n, stride_bytes, mem, leaf, has_rgb = 0, F, out_stride_bytes, &nv)      -> out_points, *n_filtered
+ *     pcc_progressive_morphological_filter(ctx, F, nv, out_stride_bytes, mem, ...)                      -> out_ground_index, *n_ground
+ *     out_ground_points = the records of F at out_ground_index; out_object_points = those of every other index, ascending
+ *   but the filtered cloud stays on the device throughout.
+ * out_points, out_ground_points, out_object_points (space `mem`; capacity n records of out_stride_bytes; the last two may be
+ *   NULL): whole voxel-grid records, the bytes pcc_voxel_grid does not write zero in both memory spaces; *n_ground of them in
+ *   out_ground_points (the reference's <name>_ground cloud), *n_filtered - *n_ground in out_object_points.  out_ground_index[n]
+ *   (space `mem`, may be NULL).  *n_filtered, *n_ground: HOST.
+ * n == 0 or no finite point: PCC_OK, both counts 0.
+ * Refused before any device is touched, in this order: what pcc_voxel_grid refuses (same messages); a null n_filtered or
+ *   n_ground; what pcc_pmf_windows refuses; a null handle last. */
+int pcc_ground_segmentation(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem, float leaf,
+                            int max_window_size, float slope, float initial_distance, float max_distance,
+                            float cell_size, float base, int exponential,
+                            void *out_points, size_t out_stride_bytes, size_t *n_filtered,
+                            int32_t *out_ground_index, size_t *n_ground, void *out_ground_points, void *out_object_points);
 /* ---- RIFT descriptors of the indexed cloud ---------------------------------------------------------
  * replaces: processRIFT (src/comparator.cpp:590-684) for one cloud: pcl::PointCloudXYZRGBtoXYZI, pcl::NormalEstimation
  *   (setRadiusSearch 0.03, :628-635), removeNaNNormalsFromPointCloud (:637-646), pcl::IntensityGradientEstimation

@@ -42,7 +42,11 @@ SYMBOLS = [
     "pcc_debug_fail_alloc",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
+    "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
 ]
+# enum pcc_morph_op
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
+PMF_MAX_WINDOWS = 64
 
 
 class PccError(RuntimeError):
@@ -150,6 +154,12 @@ def _load() -> C.CDLL:
     lib.pcc_sor_partial.argtypes = [vp, sz, sz, i32, i32, vp, C.POINTER(C.c_double)]
     lib.pcc_sor_threshold.argtypes = [C.POINTER(C.c_double), C.c_uint64, i32, C.c_double, C.POINTER(C.c_double), C.POINTER(i32)]
     lib.pcc_sor_sharded.argtypes = [vp, vp, sz, sz, i32, C.c_double, i32, vp, vp, C.POINTER(C.c_double), C.POINTER(sz)]
+    f32 = C.c_float
+    lib.pcc_pmf_windows.argtypes = [i32, f32, f32, f32, f32, f32, i32, sz, vp, vp, C.POINTER(sz)]
+    lib.pcc_morphological_operator.argtypes = [vp, vp, sz, sz, i32, f32, i32, vp]
+    lib.pcc_progressive_morphological_filter.argtypes = [vp, vp, sz, sz, i32, i32, f32, f32, f32, f32, f32, i32, vp, C.POINTER(sz), vp, sz]
+    lib.pcc_ground_segmentation.argtypes = [vp, vp, sz, sz, i32, f32, i32, f32, f32, f32, f32, f32, i32, vp, sz, C.POINTER(sz), vp,
+                                            C.POINTER(sz), vp, vp]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # raises AttributeError if the library lacks a declared symbol
         if name != "pcc_last_error":
@@ -275,6 +285,25 @@ def rigid_from_sums(sums, center=None):
         assert cc.shape == (3,)
         _check(LIB.pcc_rigid_from_sums_about(sm.ctypes.data, cc.ctypes.data, T.ctypes.data))
     return T.reshape(4, 4)
+
+
+def pmf_windows(max_window_size: int = 20, slope: float = 1.0, initial_distance: float = 0.5, max_distance: float = 3.0,
+                cell_size: float = 1.0, base: float = 2.0, exponential: bool = True, capacity: int = PMF_MAX_WINDOWS):
+    """pcc_pmf_windows: the window table of pcl::ProgressiveMorphologicalFilter (host arithmetic, no handle); the defaults are the
+    reference's parameters (src/segmentation.cpp:330-387).  Returns (windows, thresholds), float32 arrays.  A table longer than
+    `capacity` or than PMF_MAX_WINDOWS raises PccError (PCC_ERR_OVERFLOW) whose `n_windows` is the length needed."""
+    capacity = int(capacity)
+    assert capacity >= 0
+    w = np.zeros(max(capacity, 1), dtype=np.float32)
+    h = np.zeros(max(capacity, 1), dtype=np.float32)
+    nw = C.c_size_t(0)
+    status = LIB.pcc_pmf_windows(int(max_window_size), float(slope), float(initial_distance), float(max_distance), float(cell_size),
+                                 float(base), int(bool(exponential)), capacity, w.ctypes.data, h.ctypes.data, C.byref(nw))
+    if status != 0:
+        err = PccError(status, (LIB.pcc_last_error() or b"").decode())
+        err.n_windows = nw.value
+        raise err
+    return w[:nw.value], h[:nw.value]
 
 
 COMM_ID_BYTES = 128
@@ -830,6 +859,63 @@ class Index:
         res.update(offsets=offs, cluster_points=cpts[:m] if cpts is not None else None,
                    cluster_index=cidx[:m] if cidx is not None else None)
         return res
+
+    def morphological_operator(self, points, window: float, op: int):
+        """pcc_morphological_operator: pcl::applyMorphologicalOperator over `points` ((n, >= 3) float32 numpy array or torch
+        tensor; a CUDA tensor gives a CUDA result): min / max of z over every point's inclusive xy box of side `window`.
+        op: MORPH_ERODE, MORPH_DILATE, MORPH_OPEN or MORPH_CLOSE.  Returns the (n,) float32 heights."""
+        ptr, n, stride, mem = _points(points)
+        out, p_out = _out(points, (max(n, 1),), np.float32)
+        st = self._before(points)
+        status = LIB.pcc_morphological_operator(self._h, ptr, n, stride, mem, float(window), int(op), p_out)
+        self._after(st)
+        _check(status)
+        return out[:n]
+
+    def progressive_morphological_filter(self, points, max_window_size: int = 20, slope: float = 1.0, initial_distance: float = 0.5,
+                                         max_distance: float = 3.0, cell_size: float = 1.0, base: float = 2.0,
+                                         exponential: bool = True):
+        """pcc_progressive_morphological_filter: pcl::ProgressiveMorphologicalFilter::extract over `points` ((n, >= 3) float32
+        numpy array or torch tensor; a CUDA tensor gives a CUDA index array); the defaults are the reference's parameters
+        (src/segmentation.cpp:330-387).  Returns (ground, pass_sizes): the original indices of the ground points, ascending, and
+        the survivors after each window (int64 numpy array)."""
+        ptr, n, stride, mem = _points(points)
+        ground, p_g = _out(points, (max(n, 1),), np.int32)
+        sizes = np.zeros(PMF_MAX_WINDOWS, dtype=np.uintp)
+        ng = C.c_size_t(0)
+        args = (int(max_window_size), float(slope), float(initial_distance), float(max_distance), float(cell_size), float(base),
+                int(bool(exponential)))
+        st = self._before(points)
+        status = LIB.pcc_progressive_morphological_filter(self._h, ptr, n, stride, mem, *args, p_g, C.byref(ng), sizes.ctypes.data,
+                                                          PMF_MAX_WINDOWS)
+        self._after(st)
+        _check(status)
+        nw = len(pmf_windows(*args)[0])
+        return ground[:ng.value], sizes[:nw].astype(np.int64)
+
+    def ground_segmentation(self, points, leaf: float = 0.01, max_window_size: int = 20, slope: float = 1.0,
+                            initial_distance: float = 0.5, max_distance: float = 3.0, cell_size: float = 1.0, base: float = 2.0,
+                            exponential: bool = True):
+        """pcc_ground_segmentation: the reference's ground_segmentation (src/segmentation.cpp:330-387) in one call: VoxelGrid ->
+        ProgressiveMorphologicalFilter -> ExtractIndices, positive and negative, the filtered cloud staying on the device.
+        points: (n, >= 3) float32 numpy array or torch tensor (a CUDA tensor gives CUDA results).  Returns a dict: filtered
+        (nv, columns) records, ground_index (ng,), ground_points (ng, columns), object_points (nv - ng, columns)."""
+        ptr, n, stride, mem = _points(points)
+        cols = int(points.shape[1])
+        cap = max(n, 1)
+        filtered, p_f = _out(points, (cap, cols), np.float32)
+        gidx, p_gi = _out(points, (cap,), np.int32)
+        gpts, p_gp = _out(points, (cap, cols), np.float32)
+        opts, p_op = _out(points, (cap, cols), np.float32)
+        nv, ng = C.c_size_t(0), C.c_size_t(0)
+        st = self._before(points)
+        status = LIB.pcc_ground_segmentation(self._h, ptr, n, stride, mem, float(leaf), int(max_window_size), float(slope),
+                                             float(initial_distance), float(max_distance), float(cell_size), float(base),
+                                             int(bool(exponential)), p_f, cols * 4, C.byref(nv), p_gi, C.byref(ng), p_gp, p_op)
+        self._after(st)
+        _check(status)
+        return dict(filtered=filtered[:nv.value], ground_index=gidx[:ng.value], ground_points=gpts[:ng.value],
+                    object_points=opts[:nv.value - ng.value])
 
     def normals(self, k: int = 50, viewpoint=None, device=None):
         """pcl::NormalEstimation over the index's own points: (n, 4) = nx, ny, nz, curvature.

@@ -303,6 +303,7 @@ struct MatchColourScratch; // match_colour.hip: BatchStaging, the packed concate
 struct ClusterDescScratch; // cluster_desc.hip: BatchStaging, the staged clusters, snap indices and RIFT clouds of pcc_cluster_descriptors
 struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
                            // and the orders and tables of pcc_extract_clusters
+struct GroundScratch;      // ground.hip: the current points, lattice table and sorted copies of the morphological ground filter
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
@@ -396,6 +397,7 @@ struct pcc_index {
     pcc::MatchColourScratch* match_colour = nullptr;  // made at the first pcc_match_colour_elements with this handle as its context (match_colour.hip)
     pcc::ClusterDescScratch* cluster_desc = nullptr;  // made at the first pcc_cluster_descriptors with this handle as its context (cluster_desc.hip)
     pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
+    pcc::GroundScratch* ground = nullptr;         // made at the first pcc_morphological_operator / pcc_progressive_morphological_filter / pcc_ground_segmentation with this handle as its context (ground.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -662,6 +664,23 @@ void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work hand
 void match_colour_release(pcc_index* ix);  // frees ix->match_colour and its work handle
 // segment.hip: pcc_extract_clusters and pcc_region_growing_segmentation
 void segment_release(pcc_index* ix);  // frees ix->segment and its work handle
+// The partition machinery the segmentation calls share (segment.hip; ix->segment made by segment_scratch).  extract_order: labels[n]
+// on the device, n > 0, n_clusters > 0 -> *order (uint32[n]: the kept points key by key, ascending inside a key, then the points
+// left out (label -1)) and *offsets (uint32[n_clusters + 1]; offsets_out may be null: not computed), both in ix->segment; everything
+// enqueued, nothing waited for.
+// offsets_to_host / offsets_arrived: the offsets and the bad-label flag on their way to the host, and read after the caller's wait.
+// launch_records: out record j = the first record_bytes of input record order[j].  give: a result in a buffer of the library's into
+// the caller's array in either space (host: through deliver; the caller waits).
+void segment_scratch(pcc_index* ix);
+int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clusters, const unsigned int** order_out,
+                  const unsigned int** offsets_out);
+int offsets_to_host(pcc_index* ix, const unsigned int* d_offsets, int32_t n_clusters);
+int offsets_arrived(pcc_index* ix, int32_t n_clusters, size_t* out_offsets);
+int launch_records(hipStream_t s, const void* in, size_t stride, const unsigned int* order, size_t m, size_t record_bytes, void* out,
+                   size_t out_stride);
+int give(pcc_index* ix, int mem, void* user, const void* dev, size_t bytes);
+// ground.hip: pcc_morphological_operator, pcc_progressive_morphological_filter and pcc_ground_segmentation
+void ground_release(pcc_index* ix);  // frees ix->ground
 // normals.hip: the plane fit over the self k-NN rows `keys` (n x K) of a packed cloud
 int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n,
                    int K, const float vp[3], float4* out);

@@ -175,6 +175,10 @@ inline int g1(size_t n) {
     return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
 }
 
+}  // namespace
+
+// ---- what the other segmentation calls build on (pcc_internal.hpp: ground.hip) ------------------------------------------------
+
 void segment_scratch(pcc_index* ix) {
     if (!ix->segment) ix->segment = new SegmentScratch();
 }
@@ -196,7 +200,7 @@ int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clus
     PCC_TRY(sg->order_a.reserve(n * sizeof(unsigned int)));
     if (passes > 1) PCC_TRY(sg->order_b.reserve(n * sizeof(unsigned int)));
     PCC_TRY(sg->table.reserve(table_n * sizeof(unsigned int)));
-    PCC_TRY(sg->offsets.reserve(((size_t)n_clusters + 1) * sizeof(unsigned int)));
+    if (offsets_out) PCC_TRY(sg->offsets.reserve(((size_t)n_clusters + 1) * sizeof(unsigned int)));
     unsigned int* bad_word = ix->words()->op;
     PCC_HIP(hipMemsetAsync(bad_word, 0, sizeof(unsigned int), s));
     unsigned int* table = sg->table.as<unsigned int>();
@@ -214,9 +218,10 @@ int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clus
         PCC_HIP(hipGetLastError());
         in = out;
     }
+    *order_out = in;
+    if (!offsets_out) return PCC_OK;  // (ground.hip: a lattice's cells are mostly empty, and it looks their starts up itself)
     hipLaunchKernelGGL(k_seg_offsets, dim3(g1(n)), dim3(256), 0, s, labels, in, (unsigned int)n, n_clusters, sg->offsets.as<unsigned int>());
     PCC_HIP(hipGetLastError());
-    *order_out = in;
     *offsets_out = sg->offsets.as<unsigned int>();
     return PCC_OK;
 }
@@ -256,7 +261,6 @@ int give(pcc_index* ix, int mem, void* user, const void* dev, size_t bytes) {
     return PCC_OK;
 }
 
-}  // namespace
 }  // namespace pcc
 
 using namespace pcc;
