@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch build/ground_segments
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -184,9 +184,15 @@ build/cluster_desc_driver: tests/cpp/cluster_desc_driver.cpp include/pcc/descrip
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 # the candidates, gates, acceptance and work-item table of pcc_cluster_matching on the CPU (no library, no GPU)
-build/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp
+build/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp $(CSRC)/match_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
+
+# the plan the three descriptor searches share (slice rule, table of work items, shared reference clouds) against the tables its
+# users built before they shared it (tests/golden/match_plan_tables.txt), on the CPU (no library, no GPU)
+build/test_match_plan: tests/cpp/test_match_plan.cpp $(CSRC)/match_plan.hpp $(CSRC)/match_dims_plan.hpp $(CSRC)/cluster_match_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
 
 # the distinct clusters, routes, bases and the map back of pcc_match_colour_elements on the CPU (no library, no GPU)
 build/test_match_colour_plan: tests/cpp/test_match_colour_plan.cpp $(CSRC)/match_colour_plan.hpp $(CSRC)/rift_batch_plan.hpp
@@ -214,7 +220,7 @@ build/test_cloud_batch: tests/cpp/test_cloud_batch.cpp $(CSRC)/cloud_batch.hpp $
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
 
 # the record packing and work-item table of pcc_match_knn_batch_dims on the CPU (no library, no GPU)
-build/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/match_dims_plan.hpp
+build/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/match_dims_plan.hpp $(CSRC)/match_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
 
@@ -245,7 +251,7 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
@@ -257,6 +263,7 @@ asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host bui
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_cluster_match_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_colour_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_ground_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_plan
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -278,7 +285,11 @@ build/asan/sift_host: tests/cpp/sift_host.cpp $(CSRC)/sift_math.hpp $(CSRC)/libm
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@ -lm
 
-build/asan/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/match_dims_plan.hpp
+build/asan/test_match_dims_plan: tests/cpp/test_match_dims_plan.cpp $(CSRC)/match_dims_plan.hpp $(CSRC)/match_plan.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
+
+build/asan/test_match_plan: tests/cpp/test_match_plan.cpp $(CSRC)/match_plan.hpp $(CSRC)/match_dims_plan.hpp $(CSRC)/cluster_match_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
@@ -294,7 +305,7 @@ build/asan/test_cluster_desc_plan: tests/cpp/test_cluster_desc_plan.cpp $(CSRC)/
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
-build/asan/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp
+build/asan/test_cluster_match_plan: tests/cpp/test_cluster_match_plan.cpp $(CSRC)/cluster_match_plan.hpp $(CSRC)/match_dims_plan.hpp $(CSRC)/match_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 

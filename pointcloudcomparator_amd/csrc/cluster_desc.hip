@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "entry.hpp"
+#include "lane_ops.hpp"
 #include "rift_math.hpp"
 #include "desc_batch.hpp"
 #include "cluster_desc_plan.hpp"
@@ -34,17 +35,6 @@
 namespace pcc {
 
 namespace {
-
-// the last c in [0, n) with table[c] <= v (table: n + 1 non-decreasing entries, table[0] <= v < table[n]; an empty range
-// shares its start with the range behind it and is never the answer)
-__device__ __forceinline__ unsigned int range_of(const unsigned int* __restrict__ table, unsigned int n, unsigned int v) {
-    unsigned int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const unsigned int mid = (lo + hi) >> 1;
-        if (table[mid] <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // ---- 1. the pack from device memory ---------------------------------------------------------------------------------------------
 // Point e of the caller's range (cl_off[c] <= e < cl_off[c + 1] for its cluster c) -> record stage_base[c] + (e - cl_off[c]).
@@ -417,10 +407,7 @@ int cluster_descriptors(pcc_index* ix, const ClusterDescArgs& a) {
     ix->stats[2] = res.rounds;
     ix->stats[3] = kbase[n_clusters];
     ix->stats[4] = snapped;
-    ix->stats_pending = false;
-    ix->ties_pending = false;  // ([5] and [6] travel in these two)
-    ix->ties_flagged = work_points + clouds.n_single;
-    ix->ties_changed = 0;
+    own_counters(ix, work_points + clouds.n_single);
 
     const unsigned int* h_slice = nullptr;
     std::vector<unsigned int> no_slice(n_clusters + 1, 0u);
@@ -562,12 +549,7 @@ int pcc_cluster_descriptors(pcc_index* ctx, const void* pts, size_t stride_bytes
         return PCC_ERR_INVALID;
     }
     // 4. the offsets
-    for (size_t c = 0; c < n_clusters; ++c)
-        if (offsets[c + 1] < offsets[c]) { set_error("offsets must not decrease (cluster %zu)", c); return PCC_ERR_INVALID; }
-    if (n_clusters >= (1ull << 31) || (n_clusters && offsets[n_clusters] - offsets[0] >= (1ull << 31))) {
-        set_error("more than 2^31 - 1 points in one batch");
-        return PCC_ERR_UNSUPPORTED;
-    }
+    PCC_TRY(check_cluster_offsets({{offsets, n_clusters}}, "points in one batch"));
     // 5. to 7. the parameters
     PCC_TRY(check_sift_params(min_scale, nr_octaves, nr_scales_per_octave, min_contrast));
     PCC_TRY(check_rift_params(normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins));

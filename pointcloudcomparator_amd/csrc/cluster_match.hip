@@ -8,10 +8,11 @@
 //      16 or 32 floats, zero padding, an invalid record as (+inf, 0, ...)).  From host memory on the host into the pinned
 //      staging buffer (large scenes: by the host pipe's threads), one copy with the tables; from device memory by k_cm_pack
 //      from the strided records.
-//   2. k_cm_search: k_match_dims' shape (match_dims.hip) tracking the smallest distance alone -- one query per lane with its DP
-//      floats in VGPRs, the references through wave-uniform loads, the waves of a workgroup each taking a share of the slice,
-//      their minima meeting in LDS, the slices of a query block merging by a 32-bit atomicMin on the distance bits.  No index,
-//      no second minimum, no tie order: equal distances are equal bits whichever reference supplied them.
+//   2. k_cm_search: the shared search (match_plan.hpp's work items, match_search.hpp's workgroup) tracking the smallest distance
+//      alone -- one query per lane with its DP floats in VGPRs, the references through wave-uniform loads, the waves of a
+//      workgroup each taking a share of the slice, their minima meeting in LDS, the slices of a query block merging by a 32-bit
+//      atomicMin on the distance bits.  No index, no second minimum, no tie order: equal distances are equal bits whichever
+//      reference supplied them.
 //   3. k_cm_count: one wave per searched pair counts the queries whose minimum is a neighbour below the threshold.
 // One upload, one wait, one read-back of 3 * n_clusters1 words; launches and waits do not depend on the clusters or pairs.
 //
@@ -21,13 +22,14 @@
 
 #include "entry.hpp"
 #include "host_pipe.hpp"
+#include "lane_ops.hpp"
 #include "cluster_match_plan.hpp"
+#include "match_search.hpp"
 
 namespace pcc {
 
 namespace {
 
-constexpr int CM_WAVES = 16;  // waves of a workgroup: each takes a sixteenth of the slice for the same 64 queries
 constexpr size_t CM_PACK_CREW_MIN = 32768;  // records from which the host pack is shared out among threads (below: they cost more than they save)
 
 // ---- 1. the pack from device memory ---------------------------------------------------------------------------------------------
@@ -38,12 +40,7 @@ __global__ void __launch_bounds__(256)
 k_cm_pack(const unsigned char* __restrict__ des1, const unsigned char* __restrict__ des2, size_t stride, int dim,
           const ClusterMatchCloud* __restrict__ clouds, unsigned int n_clouds, unsigned int n_rec, float* __restrict__ out) {
     for (unsigned int t = blockIdx.x * blockDim.x + threadIdx.x; t < n_rec; t += gridDim.x * blockDim.x) {
-        unsigned int lo = 0, hi = n_clouds;
-        while (hi - lo > 1) {
-            const unsigned int mid = (lo + hi) >> 1;
-            if (clouds[mid].rec0 <= t) lo = mid; else hi = mid;
-        }
-        const ClusterMatchCloud cl = clouds[lo];
+        const ClusterMatchCloud cl = clouds[range_of_by(n_clouds, t, [clouds](unsigned int c) { return clouds[c].rec0; })];
         const unsigned char* base = cl.side ? des2 : des1;
         const float* __restrict__ src = reinterpret_cast<const float*>(base + (size_t)(cl.src0 + (t - cl.rec0)) * stride);
         float v[DP];
@@ -63,29 +60,20 @@ k_cm_pack(const unsigned char* __restrict__ des1, const unsigned char* __restric
 
 // ---- 2. the search ------------------------------------------------------------------------------------------------------------
 template <int DP>
-__global__ void __launch_bounds__(CM_WAVES * 64, 8)
-k_cm_search(const ClusterMatchItem* __restrict__ items, const float* __restrict__ rec, unsigned int* __restrict__ best) {
-    __shared__ unsigned int sk[CM_WAVES][64];
-    const unsigned int lane = threadIdx.x & 63;
-    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const ClusterMatchItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
-    const bool live = lane < it.nq;
-    // (a lane without a query computes with the item's first one and reports nothing)
-    const float4* __restrict__ qp = reinterpret_cast<const float4*>(rec + (size_t)(it.q0 + (live ? lane : 0u)) * DP);
+__global__ void __launch_bounds__(MATCH_WAVES * 64, 8)
+k_cm_search(const MatchItem* __restrict__ items, const float* __restrict__ rec, unsigned int* __restrict__ best) {
+    __shared__ unsigned int sk[MATCH_WAVES][64];
+    const MatchItem it = items[blockIdx.x];  // (block-uniform: scalar loads; ridx0 is not used: no index is reported)
+    const MatchLane me = match_lane(it);
     float q[DP];
-#pragma unroll
-    for (int k = 0; k < DP / 4; ++k) {
-        const float4 v = qp[k];
-        q[4 * k] = v.x; q[4 * k + 1] = v.y; q[4 * k + 2] = v.z; q[4 * k + 3] = v.w;
-    }
-    const unsigned int per = (it.nr + CM_WAVES - 1) / CM_WAVES;
-    const unsigned int b0 = min(it.nr, wave * per), b1 = min(it.nr, b0 + per);
+    match_load_query<DP>(rec, it, me, q);
+    const MatchShare share = match_share(it.nr, me.wave);
     const float* __restrict__ refs = rec + (size_t)it.r0 * DP;
     unsigned int kd = 0xffffffffu;  // this wave's smallest distance bits
     // (a plain minimum is a reduction the compiler would interleave four iterations deep: 65 VGPRs spilled at DP = 32 under
     // these launch bounds; two iterations in order keep every width within 64 registers)
 #pragma clang loop unroll_count(2) interleave(disable) vectorize(disable)
-    for (unsigned int j = b0; j < b1; ++j) {  // (wave-uniform: the record arrives by scalar loads)
+    for (unsigned int j = share.b0; j < share.b1; ++j) {  // (wave-uniform: the record arrives by scalar loads)
         const float* __restrict__ r = refs + (size_t)j * DP;
         const float t0 = q[0] - r[0];
         float d = t0 * t0;
@@ -98,12 +86,12 @@ k_cm_search(const ClusterMatchItem* __restrict__ items, const float* __restrict_
         // lie above every finite distance and are "no neighbour" to k_cm_count)
         kd = min(kd, __float_as_uint(d));
     }
-    sk[wave][lane] = kd;
+    sk[me.wave][me.lane] = kd;
     __syncthreads();
-    if (wave != 0) return;
+    if (me.wave != 0) return;
 #pragma unroll 4
-    for (int w = 1; w < CM_WAVES; ++w) kd = min(kd, sk[w][lane]);
-    if (live && kd != 0xffffffffu) atomicMin(best + it.qslot0 + lane, kd);
+    for (int w = 1; w < MATCH_WAVES; ++w) kd = min(kd, sk[w][me.lane]);
+    if (me.live && kd != 0xffffffffu) atomicMin(best + it.qslot0 + me.lane, kd);
 }
 
 // ---- 3. the count -------------------------------------------------------------------------------------------------------------
@@ -129,8 +117,6 @@ k_cm_count(const ClusterMatchPair* __restrict__ pairs, unsigned int n_pairs, con
     }
 }
 
-size_t cm_align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 struct ClusterMatchArgs {
     const unsigned char *des1, *des2;
     const size_t *offsets1, *offsets2;
@@ -146,20 +132,20 @@ int cluster_match_search(pcc_index* ix, const ClusterMatchArgs& a, const Cluster
     hipStream_t s = ix->stream;
     const bool host = a.mem == PCC_MEM_HOST;
     const size_t n_items = L.items.size(), n_pairs = L.pairs.size(), n_clouds = L.clouds.size(), n_out = 3 * a.n_clusters1;
-    const size_t pairs_at = cm_align16(n_items * sizeof(ClusterMatchItem)), clouds_at = pairs_at + cm_align16(n_pairs * sizeof(ClusterMatchPair));
-    const size_t rec_at = clouds_at + cm_align16(n_clouds * sizeof(ClusterMatchCloud));
+    const size_t pairs_at = align_up(n_items * sizeof(MatchItem), 16), clouds_at = pairs_at + align_up(n_pairs * sizeof(ClusterMatchPair), 16);
+    const size_t rec_at = clouds_at + align_up(n_clouds * sizeof(ClusterMatchCloud), 16);
     const size_t rec_bytes = L.n_rec * (size_t)dp * sizeof(float), all_bytes = rec_at + rec_bytes;
-    const size_t counts_at = cm_align16(L.n_slots * sizeof(unsigned int)), res_bytes = counts_at + n_out * sizeof(unsigned int);
+    const size_t counts_at = align_up(L.n_slots * sizeof(unsigned int), 16), res_bytes = counts_at + n_out * sizeof(unsigned int);
     PCC_TRY(mb->up.reserve((host ? all_bytes : rec_at) + 16));
     PCC_TRY(mb->dev.reserve(all_bytes + 16));
     PCC_TRY(mb->res.reserve(res_bytes + 16));
     PCC_TRY(mb->down.reserve(n_out * sizeof(unsigned int) + 16));
     char* u = mb->up.as<char>();
-    memcpy(u, L.items.data(), n_items * sizeof(ClusterMatchItem));
+    memcpy(u, L.items.data(), n_items * sizeof(MatchItem));
     memcpy(u + pairs_at, L.pairs.data(), n_pairs * sizeof(ClusterMatchPair));
     memcpy(u + clouds_at, L.clouds.data(), n_clouds * sizeof(ClusterMatchCloud));
     char* d0 = mb->dev.as<char>();
-    const ClusterMatchItem* d_items = reinterpret_cast<const ClusterMatchItem*>(d0);
+    const MatchItem* d_items = reinterpret_cast<const MatchItem*>(d0);
     const ClusterMatchPair* d_pairs = reinterpret_cast<const ClusterMatchPair*>(d0 + pairs_at);
     const ClusterMatchCloud* d_clouds = reinterpret_cast<const ClusterMatchCloud*>(d0 + clouds_at);
     float* d_rec = reinterpret_cast<float*>(d0 + rec_at);
@@ -188,25 +174,16 @@ int cluster_match_search(pcc_index* ix, const ClusterMatchArgs& a, const Cluster
         PCC_HIP(hipMemcpyAsync(d0, u, rec_at, hipMemcpyHostToDevice, s));
         const dim3 grid((unsigned int)std::min<size_t>((L.n_rec + 255) / 256, 2048)), wg(256);
         const unsigned int nc = (unsigned int)n_clouds, nr = (unsigned int)L.n_rec;
-        switch (dp) {
-            case 4: hipLaunchKernelGGL(k_cm_pack<4>, grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec); break;
-            case 8: hipLaunchKernelGGL(k_cm_pack<8>, grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec); break;
-            case 16: hipLaunchKernelGGL(k_cm_pack<16>, grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec); break;
-            default: hipLaunchKernelGGL(k_cm_pack<32>, grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec); break;
-        }
+        dispatch_dp(dp, [&](auto DP) {
+            hipLaunchKernelGGL((k_cm_pack<decltype(DP)::value>), grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec);
+        });
         PCC_HIP(hipGetLastError());
     }
     PCC_HIP(hipMemsetAsync(d_best, 0xff, L.n_slots * sizeof(unsigned int), s));
-    {
-        const dim3 grid((unsigned int)n_items), wg(CM_WAVES * 64);
-        switch (dp) {
-            case 4: hipLaunchKernelGGL(k_cm_search<4>, grid, wg, 0, s, d_items, d_rec, d_best); break;
-            case 8: hipLaunchKernelGGL(k_cm_search<8>, grid, wg, 0, s, d_items, d_rec, d_best); break;
-            case 16: hipLaunchKernelGGL(k_cm_search<16>, grid, wg, 0, s, d_items, d_rec, d_best); break;
-            default: hipLaunchKernelGGL(k_cm_search<32>, grid, wg, 0, s, d_items, d_rec, d_best); break;
-        }
-        PCC_HIP(hipGetLastError());
-    }
+    dispatch_dp(dp, [&](auto DP) {
+        hipLaunchKernelGGL((k_cm_search<decltype(DP)::value>), dim3((unsigned int)n_items), dim3(MATCH_WAVES * 64), 0, s, d_items, d_rec, d_best);
+    });
+    PCC_HIP(hipGetLastError());
     hipLaunchKernelGGL(k_cm_count, dim3((unsigned int)std::min<size_t>(n_pairs, 4096)), dim3(64), 0, s, d_pairs, (unsigned int)n_pairs, d_best,
                        a.threshold, d_counts);
     PCC_HIP(hipGetLastError());
@@ -220,9 +197,7 @@ int cluster_match_search(pcc_index* ix, const ClusterMatchArgs& a, const Cluster
 void cluster_match_stats(pcc_index* ix, const ClusterMatchLayout& L) {
     ix->stats[0] = L.pairs.size();
     ix->stats[1] = L.n_slots;
-    ix->stats_pending = false;
-    ix->ties_pending = false;
-    ix->ties_flagged = ix->ties_changed = 0;
+    own_counters(ix, 0);
 }
 
 }  // namespace
@@ -258,17 +233,7 @@ int pcc_cluster_matching(pcc_index* ctx, const void* des1, const size_t* offsets
     }
     if (reinterpret_cast<uintptr_t>(des1) % 4 || reinterpret_cast<uintptr_t>(des2) % 4) { set_error("descriptors must be 4-byte aligned"); return PCC_ERR_INVALID; }
     // 5. the offsets
-    for (int side = 0; side < 2; ++side) {
-        const size_t* off = side ? offsets2 : offsets1;
-        const size_t nc = side ? n_clusters2 : n_clusters1;
-        for (size_t c = 0; c < nc; ++c)
-            if (off[c + 1] < off[c]) { set_error("offsets must not decrease (scene %d, cluster %zu)", side + 1, c); return PCC_ERR_INVALID; }
-    }
-    for (int side = 0; side < 2; ++side) {
-        const size_t* off = side ? offsets2 : offsets1;
-        const size_t nc = side ? n_clusters2 : n_clusters1;
-        if (nc >= (1ull << 31) || (nc && off[nc] - off[0] >= (1ull << 31))) { set_error("more than 2^31 - 1 descriptors in one scene"); return PCC_ERR_UNSUPPORTED; }
-    }
+    PCC_TRY(check_cluster_offsets({{offsets1, n_clusters1}, {offsets2, n_clusters2}}, "descriptors in one scene"));
     // 6. the threshold: pcc_match_knn_batch_dims refuses none (a NaN threshold counts nothing)
     if (n_clusters1 == 0) return PCC_OK;  // (nothing to write, no device is touched: not even the handle's)
     // 7. the handle

@@ -10,9 +10,9 @@
 //
 // The search tables (cm_layout): every cluster of either scene that takes part in a searched pair is packed ONCE, as
 // match_dims_plan.hpp's record (DP floats, zero padding, an invalid record as (+inf, 0, ...)) -- a scene-2 cluster is typically a
-// candidate of several scene-1 clusters, and pcc_match_knn_batch packs it once per pair.  One work item = 64 consecutive queries
-// (scene-2 records) of ONE pair against one slice of that pair's references (scene-1 records); the slice is chosen as
-// match_dims_plan.hpp chooses it.  A (pair, query) owns one result slot: the bits of its smallest distance.
+// candidate of several scene-1 clusters, and pcc_match_knn_batch packs it once per pair.  The table of work items and its slice
+// are match_plan.hpp's: a pair's queries are its scene-2 records, its references its scene-1 records.  A (pair, query) owns one
+// result slot: the bits of its smallest distance.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -89,11 +89,6 @@ inline void cm_accept(const int32_t* candidates, const int32_t* state, const uin
     }
 }
 
-// queries rec[q0 .. q0 + nq) against references rec[r0 .. r0 + nr), in RECORDS of DP floats; the minimum of query q0 + i goes
-// to slot qslot0 + i
-struct ClusterMatchItem {
-    uint32_t q0, nq, r0, nr, qslot0, pad0, pad1, pad2;
-};
 // a searched pair: its nq result slots from slot0, its count to out[out] (out = 3 * i + k)
 struct ClusterMatchPair {
     uint32_t slot0, nq, out, pad;
@@ -107,7 +102,7 @@ struct ClusterMatchCloud {
 struct ClusterMatchLayout {
     std::vector<ClusterMatchCloud> clouds;  // scene 1's clusters that take part, in cluster order, then scene 2's
     std::vector<ClusterMatchPair> pairs;    // in (i, k) order
-    std::vector<ClusterMatchItem> items;
+    std::vector<MatchItem> items;           // (match_plan.hpp; the minimum of query q0 + i goes to slot qslot0 + i)
     size_t n_rec = 0, n_slots = 0;          // packed records; result slots (= queries over all searched pairs)
     unsigned int slice = 0;                 // references per item at most
 };
@@ -122,7 +117,6 @@ inline bool cm_layout(const int32_t* candidates, const int32_t* state, size_t n_
     L.items.clear();
     L.n_rec = L.n_slots = 0;
     L.slice = 0;
-    constexpr size_t LIMIT = 1ull << 31;
     std::vector<char> used1(n_clusters1, 0), used2(n_clusters2, 0);
     for (size_t e = 0; e < 3 * n_clusters1; ++e)
         if (state[e] == CM_SEARCHED) { used1[e / 3] = 1; used2[(size_t)candidates[e]] = 1; }
@@ -134,52 +128,23 @@ inline bool cm_layout(const int32_t* candidates, const int32_t* state, size_t n_
             if (!(side ? used2[c] : used1[c])) continue;
             const size_t n = off[c + 1] - off[c];
             (side ? rec2 : rec1)[c] = L.n_rec;
-            if (L.n_rec + n >= LIMIT) return false;
+            if (L.n_rec + n >= MATCH_LIMIT) return false;
             L.clouds.push_back({(uint32_t)L.n_rec, (uint32_t)n, (uint32_t)side, 0u, (uint64_t)off[c]});
             L.n_rec += n;
         }
     }
-    struct Pair { size_t i, j, n1, n2; };
-    std::vector<Pair> ps;
+    std::vector<MatchPair> ps;  // scene 2's records are the queries, scene 1's the references
     for (size_t e = 0; e < 3 * n_clusters1; ++e) {
         if (state[e] != CM_SEARCHED) continue;
         const size_t i = e / 3, j = (size_t)candidates[e];
         const size_t n2 = offsets2[j + 1] - offsets2[j];
-        if (L.n_slots + n2 >= LIMIT) return false;
+        if (L.n_slots + n2 >= MATCH_LIMIT) return false;
         L.pairs.push_back({(uint32_t)L.n_slots, (uint32_t)n2, (uint32_t)e, 0u});
-        ps.push_back({i, j, offsets1[i + 1] - offsets1[i], n2});
+        ps.push_back({rec2[j], n2, rec1[i], offsets1[i + 1] - offsets1[i], L.n_slots});
         L.n_slots += n2;
     }
-    auto items_at = [&](unsigned int slice) {
-        size_t c = 0;
-        for (const Pair& p : ps) c += ((p.n2 + 63) / 64) * ((p.n1 + slice - 1) / slice);
-        return c;
-    };
-    unsigned int slice = match_dims_slice_max(dp);
-    while (slice > MD_SLICE_MIN && items_at(slice) < MD_ITEMS_WANTED) slice /= 2;
-    L.slice = slice;
-    const size_t n_items = items_at(slice);
-    if (n_items >= LIMIT) return false;
-    L.items.reserve(n_items);
-    // (the widest pairs first: their many slices start while the short items fill the gaps behind them)
-    std::vector<size_t> order(ps.size());
-    for (size_t p = 0; p < ps.size(); ++p) order[p] = p;
-    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return ps[a].n1 > ps[b].n1; });
-    for (size_t p : order) {
-        const Pair& pr = ps[p];
-        for (size_t qb = 0; qb < pr.n2; qb += 64)
-            for (size_t rb = 0; rb < pr.n1; rb += slice) {
-                ClusterMatchItem it;
-                it.q0 = (uint32_t)(rec2[pr.j] + qb);
-                it.nq = (uint32_t)std::min<size_t>(64, pr.n2 - qb);
-                it.r0 = (uint32_t)(rec1[pr.i] + rb);
-                it.nr = (uint32_t)std::min<size_t>(slice, pr.n1 - rb);
-                it.qslot0 = (uint32_t)(L.pairs[p].slot0 + qb);
-                it.pad0 = it.pad1 = it.pad2 = 0;
-                L.items.push_back(it);
-            }
-    }
-    return true;
+    L.slice = match_slice(ps, match_dims_slice_max(dp));
+    return match_items(ps, L.slice, &L.items);
 }
 
 }  // namespace pcc

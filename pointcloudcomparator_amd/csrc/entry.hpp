@@ -1,7 +1,9 @@
 // entry.hpp -- the scaffold of a C-ABI entry point, included by every translation unit that defines one: the call prologue
-// (PCC_ENTER), the staging of caller arrays that are not point clouds (stage_in, Out, finish), and the batch calls' WorkLease and
-// check_cloud_batch.
+// (PCC_ENTER), the staging of caller arrays that are not point clouds (stage_in, Out, finish), the counters and cluster offsets
+// of the calls that work through a comparison's clusters, and the batch calls' WorkLease and check_cloud_batch.
 #pragma once
+#include <initializer_list>
+
 #include "pcc_internal.hpp"
 
 namespace pcc {
@@ -92,6 +94,41 @@ int finish(pcc_index* ix, int mem, const Out<T>&... outs) {
 // the host pipe, for the few calls whose results do not go through Out.  The caller waits.
 inline int copy_out(pcc_index* ix, void* user, const void* dev, size_t bytes, int mem) {
     PCC_HIP(hipMemcpyAsync(user, dev, bytes, mem == PCC_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, ix->stream));
+    return PCC_OK;
+}
+
+// A call that has written its own counters into ix->stats[0 ... 4]: nothing of an earlier search is still on its way into
+// them, and [5] and [6] are what the call says (they travel in the two tie words).
+inline void own_counters(pcc_index* ix, uint64_t ties_flagged) {
+    ix->stats_pending = false;
+    ix->ties_pending = false;
+    ix->ties_flagged = ties_flagged;
+    ix->ties_changed = 0;
+}
+
+// The cluster offsets of one or two scenes (offsets[c] .. offsets[c + 1]: the records of cluster c; nothing is read of a scene
+// without clusters).  Every scene's "must not decrease" comes before any scene's size: fewer than 2^31 clusters and records a
+// scene, `what` naming the records.
+struct ClusterOffsets {
+    const size_t* offsets;
+    size_t n_clusters;
+};
+inline int check_cluster_offsets(std::initializer_list<ClusterOffsets> scenes, const char* what) {
+    int side = 0;
+    for (const ClusterOffsets& s : scenes) {
+        ++side;
+        for (size_t c = 0; c < s.n_clusters; ++c) {
+            if (s.offsets[c + 1] >= s.offsets[c]) continue;
+            if (scenes.size() > 1) set_error("offsets must not decrease (scene %d, cluster %zu)", side, c);
+            else set_error("offsets must not decrease (cluster %zu)", c);
+            return PCC_ERR_INVALID;
+        }
+    }
+    for (const ClusterOffsets& s : scenes)
+        if (s.n_clusters >= (1ull << 31) || (s.n_clusters && s.offsets[s.n_clusters] - s.offsets[0] >= (1ull << 31))) {
+            set_error("more than 2^31 - 1 %s", what);
+            return PCC_ERR_UNSUPPORTED;
+        }
     return PCC_OK;
 }
 

@@ -3,7 +3,8 @@
 // bitonic network is a chain of dependent exchanges, so the k-NN merge spent its time waiting on them.
 // xor masks 1, 2, 8 are one DPP mov (quad_perm / row_ror:8), 4 is two row rotations and a select, 16 and 32
 // are the gfx950 row / half swaps (v_permlane16_swap, v_permlane32_swap) and a select.  Semantics checked
-// on the device for every lane.
+// on the device for every lane.  At the end: range_of, the one search a thread makes for itself and
+// several kernels share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -87,5 +88,23 @@ __device__ __forceinline__ unsigned int wave_incl_scan_max(unsigned int x) {
     return x;
 }
 #undef PCC_DPP_STEP
+
+// ---- which range a thread's element lies in (no lane exchange: every lane searches for itself) -----------------------------------
+// The last c in [0, n) with start(c) <= v: start is non-decreasing over [0, n) and start(0) <= v; an empty range shares its start
+// with the range behind it and is never the answer.  `start` reads the table as the caller's kernel lays it out (a field of a
+// record, say) and is called on [0, n) only.
+template <class Start>
+__device__ __forceinline__ unsigned int range_of_by(unsigned int n, unsigned int v, Start start) {
+    unsigned int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const unsigned int mid = (lo + hi) >> 1;
+        if (start(mid) <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// the same over a plain table of starts
+__device__ __forceinline__ unsigned int range_of(const unsigned int* __restrict__ table, unsigned int n, unsigned int v) {
+    return range_of_by(n, v, [table](unsigned int c) { return table[c]; });
+}
 
 }  // namespace pcc

@@ -9,8 +9,9 @@
 //
 // Shape of the search (k_match_batch): small.hip's workgroup -- 64 queries, 16 waves that share the references through
 // wave-uniform (scalar) loads, partial minima meeting in LDS -- driven by a host-built table of WORK ITEMS
-// (pair's query block of 64, slice of the pair's references).  Slices keep the workgroups of a 23 528-reference pair from
-// running fifty times longer than those of a 400-reference pair; the slices of a query block merge in device memory:
+// (pair's query block of 64, slice of the pair's references).  The table and its slice rule are match_plan.hpp's, the
+// workgroup's scaffold match_search.hpp's, both shared with match_dims.hip and cluster_match.hip; the slices of a query block
+// merge in device memory:
 //   best[q]   = atomicMin of (bits(d2) << 32 | index)           -- the smallest distance, the lowest index among equals
 //   second[q] = atomicMin of bits(d2) of every LOSER            -- the second-smallest distance, counted with multiplicity
 // A slice tracks its own minimum key and the second-smallest distance it saw; atomicMin returns the previous value, and of
@@ -22,37 +23,26 @@
 // (-ffp-contract=off); non-finite references never take part; non-finite queries find nothing; a distance that overflowed
 // is no neighbour (key_none).
 #include "entry.hpp"
+#include "match_search.hpp"
 #include <algorithm>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 namespace pcc {
 
-constexpr int MB_WAVES = 16;               // waves of a workgroup: each takes a sixteenth of the slice for the same 64 queries
-constexpr unsigned int MB_SLICE_MAX = 2048;  // references per work item at most (128 per wave)
-constexpr unsigned int MB_SLICE_MIN = 256;   // ... and at least, when the table would otherwise leave most of the chip idle
-constexpr size_t MB_ITEMS_WANTED = 1024;     // two workgroups of 1024 lanes per CU, 256 CUs, twice over
-
-// one workgroup's work: queries rec[q0 .. q0 + nq) against references rec[r0 .. r0 + nr), whose indices in their own cloud
-// are ridx0 ...; results for query q0 + i go to best / second [qslot0 + i]
-struct MatchItem {
-    unsigned int q0, nq, r0, nr, ridx0, qslot0, pad0, pad1;
-};
-
-__global__ void __launch_bounds__(MB_WAVES * 64, 8)  // (8 waves a SIMD: two workgroups a CU need at most 64 VGPRs)
+__global__ void __launch_bounds__(MATCH_WAVES * 64, 8)  // (8 waves a SIMD: two workgroups a CU need at most 64 VGPRs)
 k_match_batch(const MatchItem* __restrict__ items, const float4* __restrict__ rec, unsigned long long* __restrict__ best,
               unsigned int* __restrict__ second) {
-    __shared__ unsigned long long sk[MB_WAVES][64];
-    __shared__ unsigned int ss[MB_WAVES][64];
-    const unsigned int lane = threadIdx.x & 63;
-    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    __shared__ unsigned long long sk[MATCH_WAVES][64];
+    __shared__ unsigned int ss[MATCH_WAVES][64];
     const MatchItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
-    const bool live = lane < it.nq;
+    const MatchLane me = match_lane(it);
+    const unsigned int lane = me.lane, wave = me.wave;
+    const bool live = me.live;
     const float4 qv = live ? rec[it.q0 + lane] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));
     const float qx = qv.x, qy = qv.y, qz = qv.z;
-    const unsigned int per = (it.nr + MB_WAVES - 1) / MB_WAVES;
-    const unsigned int b0 = min(it.nr, wave * per), b1 = min(it.nr, b0 + per);
+    const MatchShare share = match_share(it.nr, wave);
+    const unsigned int b0 = share.b0, b1 = share.b1;
     const float4* __restrict__ refs = rec + it.r0;
     // this wave's minimum as (distance bits, position) and the second-smallest distance bits it met (with multiplicity)
     unsigned int kd = 0xffffffffu, ki = 0xffffffffu, s2 = 0xffffffffu;
@@ -79,7 +69,7 @@ k_match_batch(const MatchItem* __restrict__ items, const float4* __restrict__ re
     if (wave != 0) return;
     unsigned long long key = sk[0][lane];
 #pragma unroll 4
-    for (int w = 1; w < MB_WAVES; ++w) {
+    for (int w = 1; w < MATCH_WAVES; ++w) {
         const unsigned long long k = sk[w][lane];
         const unsigned long long lose = k < key ? key : k;
         s2 = min(min(s2, ss[w][lane]), (unsigned int)(lose >> 32));
@@ -154,97 +144,39 @@ static size_t pack_records(const void* raw, size_t n, size_t stride, float* out)
     return fin_n;
 }
 
-static size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-struct PtrLenHash {
-    size_t operator()(const std::pair<const void*, size_t>& k) const {
-        return std::hash<const void*>()(k.first) ^ (std::hash<size_t>()(k.second) * 0x9e3779b97f4a7c15ull);
-    }
-};
-
 int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                     const size_t* n2, size_t stride, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
     const bool flann = ix->tie_mode == PCC_TIES_FLANN;
     if (!ix->mb) ix->mb = new MatchBatchScratch();
     MatchBatchScratch* mb = ix->mb;
 
-    // ---- the clouds: every DISTINCT reference cloud once, every pair's queries ---------------------------------------
-    struct Cloud { const void* p; size_t n, rec0, finite; };
-    std::vector<Cloud> clouds;
-    std::vector<size_t> cloud_of(n_pairs), q_rec0(n_pairs), q_slot0(n_pairs + 1);
-    std::unordered_map<std::pair<const void*, size_t>, size_t, PtrLenHash> seen;
-    size_t n_rec = 0, n_slots = 0;
-    for (size_t p = 0; p < n_pairs; ++p) {
-        const auto key = std::make_pair(des1[p], n1[p]);
-        auto f = seen.find(key);
-        if (f == seen.end()) {
-            f = seen.emplace(key, clouds.size()).first;
-            clouds.push_back({des1[p], n1[p], n_rec, 0});
-            n_rec += n1[p];
-        }
-        cloud_of[p] = f->second;
+    // ---- the plan: every DISTINCT reference cloud once, every pair's queries, the table of work items (match_plan.hpp) --------
+    MatchPlan plan;
+    if (!match_plan(n_pairs, des1, n1, n2, match_slice_max_3d(), &plan)) {
+        set_error("more than 2^31 records or work items in one batch");
+        return PCC_ERR_UNSUPPORTED;
     }
-    for (size_t p = 0; p < n_pairs; ++p) {
-        q_rec0[p] = n_rec;
-        q_slot0[p] = n_slots;
-        n_rec += n2[p];
-        n_slots += n2[p];
-    }
-    q_slot0[n_pairs] = n_slots;
-    if (n_rec >= (1ull << 31)) { set_error("more than 2^31 records in one batch"); return PCC_ERR_UNSUPPORTED; }
+    const std::vector<MatchPlan::Cloud>& clouds = plan.clouds;
+    const std::vector<size_t>&cloud_of = plan.cloud_of, &q_rec0 = plan.q_rec0, &q_slot0 = plan.q_slot0;
+    const size_t n_rec = plan.n_rec, n_slots = plan.n_slots, n_items = plan.items.size();
 
-    // ---- the table of work items ---------------------------------------------------------------------------------------
-    auto items_at = [&](unsigned int slice) {
-        size_t c = 0;
-        for (size_t p = 0; p < n_pairs; ++p)
-            if (n2[p] && n1[p]) c += ((n2[p] + 63) / 64) * ((n1[p] + slice - 1) / slice);
-        return c;
-    };
-    unsigned int slice = MB_SLICE_MAX;
-    while (slice > MB_SLICE_MIN && items_at(slice) < MB_ITEMS_WANTED) slice /= 2;
-    const size_t n_items = items_at(slice);
-    if (n_items >= (1ull << 31)) { set_error("more than 2^31 work items in one batch"); return PCC_ERR_UNSUPPORTED; }
-
-    const size_t items_bytes = align16(n_items * sizeof(MatchItem));
+    const size_t items_bytes = align_up(n_items * sizeof(MatchItem), 16);
     const size_t up_bytes = items_bytes + n_rec * sizeof(float4);
-    const size_t best_bytes = align16(n_slots * sizeof(unsigned long long)), res_bytes = best_bytes + n_slots * sizeof(unsigned int);
+    const size_t best_bytes = align_up(n_slots * sizeof(unsigned long long), 16), res_bytes = best_bytes + n_slots * sizeof(unsigned int);
     PCC_TRY(mb->up.reserve(up_bytes + 16));
     PCC_TRY(mb->dev.reserve(up_bytes + 16));
     PCC_TRY(mb->down.reserve(res_bytes + 16));
     PCC_TRY(mb->res.reserve(res_bytes + 16));
-    MatchItem* items = mb->up.as<MatchItem>();
+    if (n_items) memcpy(mb->up.p, plan.items.data(), n_items * sizeof(MatchItem));
     float* rec = reinterpret_cast<float*>(mb->up.as<char>() + items_bytes);
-    for (Cloud& c : clouds) c.finite = pack_records(c.p, c.n, stride, rec + c.rec0 * 4);
+    std::vector<size_t> finite(clouds.size());  // per cloud: its finite records
+    for (size_t c = 0; c < clouds.size(); ++c) finite[c] = pack_records(clouds[c].p, clouds[c].n, stride, rec + clouds[c].rec0 * 4);
     for (size_t p = 0; p < n_pairs; ++p) pack_records(des2[p], n2[p], stride, rec + q_rec0[p] * 4);
-    {
-        size_t k = 0;
-        // (the widest pairs first: their many slices start while the short items fill the gaps behind them)
-        std::vector<size_t> order(n_pairs);
-        for (size_t p = 0; p < n_pairs; ++p) order[p] = p;
-        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return n1[a] > n1[b]; });
-        for (size_t p : order) {
-            const Cloud& c = clouds[cloud_of[p]];
-            if (!n2[p] || !n1[p]) continue;
-            for (size_t qb = 0; qb < n2[p]; qb += 64)
-                for (size_t rb = 0; rb < c.n; rb += slice) {
-                    MatchItem& it = items[k++];
-                    it.q0 = (unsigned int)(q_rec0[p] + qb);
-                    it.nq = (unsigned int)std::min<size_t>(64, n2[p] - qb);
-                    it.r0 = (unsigned int)(c.rec0 + rb);
-                    it.nr = (unsigned int)std::min<size_t>(slice, c.n - rb);
-                    it.ridx0 = (unsigned int)rb;
-                    it.qslot0 = (unsigned int)(q_slot0[p] + qb);
-                    it.pad0 = it.pad1 = 0;
-                }
-        }
-    }
 
     // ---- one upload, one launch, one read-back, one wait --------------------------------------------------------------------
     ix->stats[0] = 0;
     ix->stats[1] = n_slots;
-    ix->stats_pending = false;
-    ix->ties_pending = false;
-    ix->ties_flagged = ix->ties_changed = 0;
+    own_counters(ix, 0);
     const unsigned long long* h_best = mb->down.as<unsigned long long>();
     const unsigned int* h_second = reinterpret_cast<const unsigned int*>(mb->down.as<char>() + best_bytes);
     const float4* d_rec = reinterpret_cast<const float4*>(mb->dev.as<char>() + items_bytes);
@@ -253,7 +185,7 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
     if (n_items) {
         PCC_HIP(hipMemcpyAsync(mb->dev.p, mb->up.p, up_bytes, hipMemcpyHostToDevice, ix->stream));
         PCC_HIP(hipMemsetAsync(mb->res.p, 0xff, res_bytes, ix->stream));
-        hipLaunchKernelGGL(k_match_batch, dim3((unsigned int)n_items), dim3(MB_WAVES * 64), 0, ix->stream, mb->dev.as<MatchItem>(), d_rec,
+        hipLaunchKernelGGL(k_match_batch, dim3((unsigned int)n_items), dim3(MATCH_WAVES * 64), 0, ix->stream, mb->dev.as<MatchItem>(), d_rec,
                            d_best, d_second);
         PCC_HIP(hipGetLastError());
         PCC_HIP(hipMemcpyAsync(mb->down.p, mb->res.p, res_bytes, hipMemcpyDeviceToHost, ix->stream));
@@ -291,7 +223,7 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
             int deepest = 0;  // among the trees the device walks
             std::vector<MatchTree> mt(trees.size());
             for (size_t t = 0; t < trees.size(); ++t) {
-                const Cloud& c = clouds[tree_cloud[t]];
+                const MatchPlan::Cloud& c = clouds[tree_cloud[t]];
                 trees[t].build(rec + c.rec0 * 4, c.n, ix->opt.flann_split, c.n >= 50000 ? hw : (c.n >= 6000 ? std::min(hw, 4u) : 1u));
                 mt[t].node0 = (unsigned int)n_nodes;
                 mt[t].leaf0 = (unsigned int)n_leaf;
@@ -311,8 +243,8 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
             flann_idx.assign(n_slots, -1);
             const int32_t* found = nullptr;
             if (n_dev) {
-                const size_t tb = align16(mt.size() * sizeof(MatchTree)), nb = align16(n_nodes * sizeof(FlannNode));
-                const size_t lb = align16(n_leaf * sizeof(float)), wb = n_dev * sizeof(WalkItem);
+                const size_t tb = align_up(mt.size() * sizeof(MatchTree), 16), nb = align_up(n_nodes * sizeof(FlannNode), 16);
+                const size_t lb = align_up(n_leaf * sizeof(float), 16), wb = n_dev * sizeof(WalkItem);
                 PCC_TRY(mb->tree_up.reserve(tb + nb + lb + wb + 16));
                 PCC_TRY(mb->tree_dev.reserve(tb + nb + lb + wb + 16));
                 PCC_TRY(mb->tree_down.reserve(n_dev * sizeof(int32_t) + 16));
@@ -372,7 +304,7 @@ int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, cons
         out_offsets[p] = o;
         if (out_d2) out_d2[o] = 0.0f;
         out[o++] = 0;
-        if (!searched(p) || clouds[cloud_of[p]].finite == 0) continue;
+        if (!searched(p) || finite[cloud_of[p]] == 0) continue;
         const float* q = rec + q_rec0[p] * 4;
         for (size_t i = 0; i < n2[p]; ++i) {
             const size_t s = q_slot0[p] + i;

@@ -23,6 +23,7 @@
 
 #include "entry.hpp"
 #include "cloud_batch.hpp"
+#include "lane_ops.hpp"
 #include "match_colour_plan.hpp"
 #include "rgb_batch_split.hpp"
 #include "rgb_stages.hpp"
@@ -54,11 +55,7 @@ k_mc_pack(const unsigned char* __restrict__ pts1, const unsigned char* __restric
         unsigned int lo = 0;
         bool fin = false;
         if (live) {
-            unsigned int hi = n_clouds;
-            while (hi - lo > 1) {
-                const unsigned int mid = (lo + hi) >> 1;
-                if (clouds[mid].base <= t) lo = mid; else hi = mid;
-            }
+            lo = range_of_by(n_clouds, t, [clouds](unsigned int c) { return clouds[c].base; });
             const McCloud cl = clouds[lo];
             const size_t rec = (size_t)cl.src0 + (t - cl.base);
             const unsigned char* p = (cl.side ? pts2 : pts1) + rec * stride;
@@ -84,8 +81,6 @@ k_mc_pack(const unsigned char* __restrict__ pts1, const unsigned char* __restric
         }
     }
 }
-
-size_t mc_align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 }  // namespace
 
@@ -132,8 +127,8 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
     // The records of the named clusters follow one another at their stride, so a cluster's place is a record index as in the
     // caller's arrays.  Colour words inside the point records (rgb = pts + delta, the same stride) ride with them; else they
     // are staged the same way behind the points.
-    const size_t items_at = mc_align16((n_clouds + 1) * sizeof(uint32_t)), table_at = items_at + n_items * sizeof(RiftBatchItem);
-    const size_t rec_at = mc_align16(table_at + n_clouds * sizeof(McCloud));
+    const size_t items_at = align_up((n_clouds + 1) * sizeof(uint32_t), 16), table_at = items_at + n_items * sizeof(RiftBatchItem);
+    const size_t rec_at = align_up(table_at + n_clouds * sizeof(McCloud), 16);
     bool inside = host && a.rgb_stride == a.stride;
     size_t delta = 0;
     if (inside) {
@@ -151,7 +146,7 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
     size_t n_staged = 0;
     if (host)
         for (size_t e = 0; e < n_list; ++e) { staged0[e] = n_staged; n_staged += P.clusters[e].n; }
-    const size_t col_at = rec_at + mc_align16(n_staged * a.stride), up_bytes = !host ? rec_at : (inside ? col_at : col_at + mc_align16(n_staged * a.rgb_stride));
+    const size_t col_at = rec_at + align_up(n_staged * a.stride, 16), up_bytes = !host ? rec_at : (inside ? col_at : col_at + align_up(n_staged * a.rgb_stride, 16));
     PCC_TRY(sc->up.reserve(up_bytes + 16));
     PCC_TRY(sc->dev.reserve(up_bytes + 16));
     char* u = sc->up.as<char>();
@@ -190,7 +185,7 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
         PCC_TRY(sc->finite.reserve(n_clouds * sizeof(unsigned int)));
         PCC_TRY(sc->id_bases.reserve((n_clouds + 1) * sizeof(unsigned int)));
         PCC_TRY(sc->keys.reserve(total * (size_t)K * sizeof(unsigned long long)));
-        const size_t ids_bytes = mc_align16((n_clouds + 1) * sizeof(unsigned int));
+        const size_t ids_bytes = align_up((n_clouds + 1) * sizeof(unsigned int), 16);
         PCC_TRY(sc->down.reserve(ids_bytes + n_clouds * sizeof(unsigned int)));
         float4* d_cat = sc->cat.as<float4>();
         unsigned int* d_words = reinterpret_cast<unsigned int*>(sc->cat.as<char>() + words_at);
@@ -245,11 +240,8 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
     ix->stats[2] = P.n_batch_points;
     ix->stats[3] = P.n_work_points;
     ix->stats[4] = n_list;
-    ix->stats_pending = false;
     ix->open_pending = false;
-    ix->ties_pending = false;  // ([5] and [6] travel in these two)
-    ix->ties_flagged = P.n_saved;
-    ix->ties_changed = 0;
+    own_counters(ix, P.n_saved);
     if (P.n_work == 0) return PCC_OK;
 
     // ---- the other clusters: one by one on the work handle, from the device arrays, their labels to device scratch ----------------
@@ -311,17 +303,7 @@ int pcc_match_colour_elements(pcc_index* ctx, const void* pts1, const void* rgb1
             return PCC_ERR_INVALID;
         }
     // 4. the offsets
-    for (int side = 0; side < 2; ++side) {
-        const size_t* off = side ? offsets2 : offsets1;
-        const size_t nc = side ? n_clusters2 : n_clusters1;
-        for (size_t c = 0; c < nc; ++c)
-            if (off[c + 1] < off[c]) { set_error("offsets must not decrease (scene %d, cluster %zu)", side + 1, c); return PCC_ERR_INVALID; }
-    }
-    for (int side = 0; side < 2; ++side) {
-        const size_t* off = side ? offsets2 : offsets1;
-        const size_t nc = side ? n_clusters2 : n_clusters1;
-        if (nc >= (1ull << 31) || (nc && off[nc] - off[0] >= (1ull << 31))) { set_error("more than 2^31 - 1 points in one scene"); return PCC_ERR_UNSUPPORTED; }
-    }
+    PCC_TRY(check_cluster_offsets({{offsets1, n_clusters1}, {offsets2, n_clusters2}}, "points in one scene"));
     // 5. the match table
     bool any = false;
     for (size_t i = 0; i < n_clusters1; ++i) {

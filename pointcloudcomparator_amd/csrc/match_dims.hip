@@ -3,8 +3,8 @@
 // cluster-matching loop (:1296-1365); SURVEY 3.2 / 9.1 for why the reference's PCL searches three bins and what this is the
 // hedge for.
 //
-// k_match_batch's shape (match_batch.hip) with a wider record: a host-built table of work items (64 queries of one pair, a
-// slice of that pair's references; match_dims_plan.hpp), one query per lane with its DP floats in VGPRs for the length of the
+// The shared search (match_plan.hpp's table of work items: 64 queries of one pair, a slice of that pair's references;
+// match_search.hpp's workgroup) on a record of DP floats: one query per lane with its DP floats in VGPRs for the length of the
 // item, the references through wave-uniform (scalar) loads shared by the 64 lanes, the waves of a workgroup each taking a
 // share of the slice, partial minima meeting in LDS, the slices of a query block merging in device memory by
 //   best[q] = atomicMin of (bits(d2) << 32 | index),  second[q] = atomicMin of bits(d2) of every loser.
@@ -16,36 +16,28 @@
 // wins whatever tie order the handle has: FLANN's tree and the oracle's are 3-D, an N-D visit order could not be checked.
 #include "entry.hpp"
 #include "match_dims_plan.hpp"
+#include "match_search.hpp"
 
 namespace pcc {
 
-constexpr int MD_WAVES = 16;  // waves of a workgroup: each takes a sixteenth of the slice for the same 64 queries
-
 template <int DP>
-__global__ void __launch_bounds__(MD_WAVES * 64, 8)  // (8 waves a SIMD: two workgroups a CU need at most 64 VGPRs)
-k_match_dims(const MatchDimsItem* __restrict__ items, const float* __restrict__ rec, unsigned long long* __restrict__ best,
+__global__ void __launch_bounds__(MATCH_WAVES * 64, 8)  // (8 waves a SIMD: two workgroups a CU need at most 64 VGPRs)
+k_match_dims(const MatchItem* __restrict__ items, const float* __restrict__ rec, unsigned long long* __restrict__ best,
              unsigned int* __restrict__ second) {
-    __shared__ unsigned long long sk[MD_WAVES][64];
-    __shared__ unsigned int ss[MD_WAVES][64];
-    const unsigned int lane = threadIdx.x & 63;
-    const unsigned int wave = (unsigned int)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const MatchDimsItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
-    const bool live = lane < it.nq;
-    // (a lane without a query computes with the item's first one and reports nothing)
-    const float4* __restrict__ qp = reinterpret_cast<const float4*>(rec + (size_t)(it.q0 + (live ? lane : 0u)) * DP);
+    __shared__ unsigned long long sk[MATCH_WAVES][64];
+    __shared__ unsigned int ss[MATCH_WAVES][64];
+    const MatchItem it = items[blockIdx.x];  // (block-uniform: scalar loads)
+    const MatchLane me = match_lane(it);
+    const unsigned int lane = me.lane, wave = me.wave;
+    const bool live = me.live;
     float q[DP];
-#pragma unroll
-    for (int k = 0; k < DP / 4; ++k) {
-        const float4 v = qp[k];
-        q[4 * k] = v.x; q[4 * k + 1] = v.y; q[4 * k + 2] = v.z; q[4 * k + 3] = v.w;
-    }
-    const unsigned int per = (it.nr + MD_WAVES - 1) / MD_WAVES;
-    const unsigned int b0 = min(it.nr, wave * per), b1 = min(it.nr, b0 + per);
+    match_load_query<DP>(rec, it, me, q);
+    const MatchShare share = match_share(it.nr, wave);
     const float* __restrict__ refs = rec + (size_t)it.r0 * DP;
     // this wave's minimum as (distance bits, position) and the second-smallest distance bits it met (with multiplicity)
     unsigned int kd = 0xffffffffu, ki = 0xffffffffu, s2 = 0xffffffffu;
 #pragma unroll 2
-    for (unsigned int j = b0; j < b1; ++j) {  // (wave-uniform: the record arrives by scalar loads)
+    for (unsigned int j = share.b0; j < share.b1; ++j) {  // (wave-uniform: the record arrives by scalar loads)
         const float* __restrict__ r = refs + (size_t)j * DP;
         const float t0 = q[0] - r[0];
         float d = t0 * t0;
@@ -70,7 +62,7 @@ k_match_dims(const MatchDimsItem* __restrict__ items, const float* __restrict__ 
     if (wave != 0) return;
     unsigned long long key = sk[0][lane];
 #pragma unroll 4
-    for (int w = 1; w < MD_WAVES; ++w) {
+    for (int w = 1; w < MATCH_WAVES; ++w) {
         const unsigned long long k = sk[w][lane];
         const unsigned long long lose = k < key ? key : k;
         s2 = min(min(s2, ss[w][lane]), (unsigned int)(lose >> 32));
@@ -84,8 +76,6 @@ k_match_dims(const MatchDimsItem* __restrict__ items, const float* __restrict__ 
     if (s2 != 0xffffffffu) atomicMin(second + slot, s2);
 }
 
-static size_t md_align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                          const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
     if (!ix->mb) ix->mb = new MatchBatchScratch();
@@ -95,14 +85,14 @@ int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1,
     if (!match_dims_plan(n_pairs, des1, n1, n2, dp, &plan)) { set_error("more than 2^31 records or work items in one batch"); return PCC_ERR_UNSUPPORTED; }
     const size_t n_items = plan.items.size(), n_slots = plan.n_slots;
 
-    const size_t items_bytes = md_align16(n_items * sizeof(MatchDimsItem));
+    const size_t items_bytes = align_up(n_items * sizeof(MatchItem), 16);
     const size_t up_bytes = items_bytes + plan.n_rec * (size_t)dp * sizeof(float);
-    const size_t best_bytes = md_align16(n_slots * sizeof(unsigned long long)), res_bytes = best_bytes + n_slots * sizeof(unsigned int);
+    const size_t best_bytes = align_up(n_slots * sizeof(unsigned long long), 16), res_bytes = best_bytes + n_slots * sizeof(unsigned int);
     PCC_TRY(mb->up.reserve(up_bytes + 16));
     PCC_TRY(mb->dev.reserve(up_bytes + 16));
     PCC_TRY(mb->down.reserve(res_bytes + 16));
     PCC_TRY(mb->res.reserve(res_bytes + 16));
-    if (n_items) memcpy(mb->up.p, plan.items.data(), n_items * sizeof(MatchDimsItem));
+    if (n_items) memcpy(mb->up.p, plan.items.data(), n_items * sizeof(MatchItem));
     float* rec = reinterpret_cast<float*>(mb->up.as<char>() + items_bytes);
     for (const MatchDimsPlan::Cloud& c : plan.clouds) match_dims_pack(c.p, c.n, stride, dim, dp, rec + c.rec0 * dp);
     for (size_t p = 0; p < n_pairs; ++p) match_dims_pack(des2[p], n2[p], stride, dim, dp, rec + plan.q_rec0[p] * dp);
@@ -110,25 +100,20 @@ int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1,
     // ---- one upload, one launch, one read-back, one wait --------------------------------------------------------------------
     ix->stats[0] = 0;
     ix->stats[1] = n_slots;
-    ix->stats_pending = false;
-    ix->ties_pending = false;
-    ix->ties_flagged = ix->ties_changed = 0;
+    own_counters(ix, 0);
     const unsigned long long* h_best = mb->down.as<unsigned long long>();
     const unsigned int* h_second = reinterpret_cast<const unsigned int*>(mb->down.as<char>() + best_bytes);
     if (n_items) {
-        const MatchDimsItem* d_items = mb->dev.as<MatchDimsItem>();
+        const MatchItem* d_items = mb->dev.as<MatchItem>();
         const float* d_rec = reinterpret_cast<const float*>(mb->dev.as<char>() + items_bytes);
         unsigned long long* d_best = mb->res.as<unsigned long long>();
         unsigned int* d_second = reinterpret_cast<unsigned int*>(mb->res.as<char>() + best_bytes);
-        const dim3 grid((unsigned int)n_items), wg(MD_WAVES * 64);
+        const dim3 grid((unsigned int)n_items), wg(MATCH_WAVES * 64);
         PCC_HIP(hipMemcpyAsync(mb->dev.p, mb->up.p, up_bytes, hipMemcpyHostToDevice, ix->stream));
         PCC_HIP(hipMemsetAsync(mb->res.p, 0xff, res_bytes, ix->stream));
-        switch (dp) {
-            case 4: hipLaunchKernelGGL(k_match_dims<4>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
-            case 8: hipLaunchKernelGGL(k_match_dims<8>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
-            case 16: hipLaunchKernelGGL(k_match_dims<16>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
-            default: hipLaunchKernelGGL(k_match_dims<32>, grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second); break;
-        }
+        dispatch_dp(dp, [&](auto DP) {
+            hipLaunchKernelGGL((k_match_dims<decltype(DP)::value>), grid, wg, 0, ix->stream, d_items, d_rec, d_best, d_second);
+        });
         PCC_HIP(hipGetLastError());
         PCC_HIP(hipMemcpyAsync(mb->down.p, mb->res.p, res_bytes, hipMemcpyDeviceToHost, ix->stream));
         PCC_HIP(hipStreamSynchronize(ix->stream));

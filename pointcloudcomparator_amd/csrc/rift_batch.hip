@@ -95,12 +95,7 @@ k_rift_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __
     for (unsigned int row = t; row < kept; row += stride) {
         const unsigned int i = (unsigned int)out_index[row];
         // the last cloud whose base is <= i (empty clouds share a base with the cloud behind them: never the answer)
-        unsigned int lo = 0, hi = n_clouds;
-        while (hi - lo > 1) {
-            const unsigned int mid = (lo + hi) >> 1;
-            if (bases[mid] <= i) lo = mid; else hi = mid;
-        }
-        out_index[row] = (int32_t)(i - bases[lo]);
+        out_index[row] = (int32_t)(i - bases[range_of(bases, n_clouds, i)]);
     }
 }
 

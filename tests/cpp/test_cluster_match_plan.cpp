@@ -129,7 +129,7 @@ static void check_layout(const std::vector<size_t>& n1s, const std::vector<size_
     REQUIRE(n_pairs == L.pairs.size() && slots == L.n_slots);
     // the items: per pair, every (query, reference) exactly once
     std::vector<std::map<std::pair<size_t, size_t>, int> > seen(L.pairs.size());
-    for (const ClusterMatchItem& it : L.items) {
+    for (const MatchItem& it : L.items) {
         REQUIRE(it.nq >= 1 && it.nq <= 64 && it.nr >= 1 && it.nr <= L.slice);
         REQUIRE((size_t)it.q0 + it.nq <= L.n_rec && (size_t)it.r0 + it.nr <= L.n_rec && (size_t)it.qslot0 + it.nq <= L.n_slots);
         size_t p = 0;

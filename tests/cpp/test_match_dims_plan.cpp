@@ -96,7 +96,7 @@ static void check_plan(const std::vector<size_t>& n1, const std::vector<size_t>&
     for (size_t p = 0; p < np; ++p) des1[p] = arena + (shares[p] >= 0 ? shares[p] : (int)p) * 64;
     pcc::MatchDimsPlan pl;
     REQUIRE(pcc::match_dims_plan(np, des1.data(), n1.data(), n2.data(), dp, &pl));
-    REQUIRE(pl.slice >= pcc::MD_SLICE_MIN && pl.slice <= pcc::match_dims_slice_max(dp));
+    REQUIRE(pl.slice >= pcc::MATCH_SLICE_MIN && pl.slice <= pcc::match_dims_slice_max(dp));
     size_t want_clouds = 0, want_rec = 0, want_slots = 0;
     for (size_t p = 0; p < np; ++p) {
         if (shares[p] < 0) { ++want_clouds; want_rec += n1[p]; }
@@ -119,7 +119,7 @@ static void check_plan(const std::vector<size_t>& n1, const std::vector<size_t>&
     for (int o : owner_of_rec) REQUIRE(o >= 0);  // the layout has no hole and no overlap
     // per (slot, reference index of the pair's cloud): how many items cover it
     std::vector<std::map<uint32_t, int> > slices_of_slot(pl.n_slots);  // slot -> ridx0 -> count
-    for (const pcc::MatchDimsItem& it : pl.items) {
+    for (const pcc::MatchItem& it : pl.items) {
         REQUIRE(it.nq >= 1 && it.nq <= 64 && it.nr >= 1 && it.nr <= pl.slice);
         const int p = pair_of_slot[it.qslot0];
         REQUIRE(p >= 0);

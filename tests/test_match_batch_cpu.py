@@ -69,6 +69,26 @@ def test_argument_validation_needs_no_gpu():
     assert off.tolist() == [99, 99] and not out.any()         # nothing was written by any refused call
 
 
+def test_plan_header_alone():
+    """tests/cpp/test_match_plan.cpp compiles csrc/match_plan.hpp, the plan match_knn_batch() and the two other descriptor
+    searches build their tables with, on its own: the tables frozen in tests/golden/match_plan_tables.txt word for word, the
+    3-D plan equal to the frozen dp = 4 tables, 2^31 records or items refused without an allocation"""
+    subprocess.check_call(["make", "build/test_match_plan"], cwd=ROOT)
+    r = subprocess.run([str(ROOT / "build" / "test_match_plan"), str(ROOT / "tests" / "golden" / "match_plan_tables.txt")],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "test_match_plan: ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    csrc = ROOT / "pointcloudcomparator_amd" / "csrc"
+    batch = (csrc / "match_batch.hip").read_text()
+    assert "match_plan(n_pairs, des1, n1, n2, match_slice_max_3d()" in batch and "stable_sort" not in batch   # no planner of its own
+    for user in ("match_dims_plan.hpp", "cluster_match_plan.hpp"):
+        assert "stable_sort" not in (csrc / user).read_text()
+    mk = (ROOT / "Makefile").read_text()
+    assert re.search(r"^hosttest:.*build/test_match_plan\b", mk, flags=re.M)
+    assert re.search(r"^asan:.*build/asan/test_match_plan\b", mk, flags=re.M)
+    assert re.search(r"^build/asan/test_match_plan:.*\n.*\n\t\$\(CXX\).*\$\(SANFLAGS\)", mk, flags=re.M)
+    assert "build/asan/test_match_plan\n" in mk                                                             # ... and asan runs it
+
+
 def test_committed_workloads_match_the_recorded_runs():
     doc = json.loads(mbu.GOLDEN.read_text())
     assert "printed" in doc["note"].lower() and "six" in doc["note"]    # a replay of the PRINTED centroids

@@ -148,6 +148,56 @@ def test_edge_pairs(ix, stride, family, ties):
     assert n == 33 and all(len(got[p]) >= 61 for p in (30, 31, 32))
 
 
+def _check_both_entries(ix, pairs, ties):
+    """pcc_match_knn_batch against the per-pair loop (and the oracle), then pcc_match_knn_batch_dims at dim = 3: the same rows,
+    and beside each the squared distance the restated arithmetic gives"""
+    got, _ = check_batch(ix, pairs, ties)
+    rows, d2 = ix.match_knn_batch(pairs, dim=3, return_d2=True)
+    for p, (a, b) in enumerate(pairs):
+        assert np.array_equal(rows[p], got[p]), f"pair {p} ({len(a)} x {len(b)}): dim = 3 differs from pcc_match_knn_batch"
+        assert d2[p].dtype == np.float32 and d2[p][0] == 0
+        if 0 < len(a) * len(b) <= 1_000_000:   # (the distance matrix of a larger pair is left to the rows above)
+            t = b[:, None, :3] - a[None, :, :3]
+            t = t * t
+            best = ((t[..., 0] + t[..., 1]) + t[..., 2]).min(1)
+            assert np.array_equal(d2[p][1:].view(np.uint32), best[best < np.float32(0.05)].view(np.uint32)), p
+    return got
+
+
+@pytest.mark.parametrize("ties", sorted(TIES))
+@pytest.mark.parametrize("family", synth.DESCRIPTOR_FAMILIES)
+def test_slice_at_its_minimum(ix, family, ties):
+    """255, 256 and 257 references in one call: far fewer than 1024 items, so the slice falls to 256 and the 257 references
+    are a full slice and a slice of ONE; two pairs share one des1 (pointer and length), packed once.  Queries whose nearest
+    reference is the last one have their answer in the slice of one"""
+    pairs = []
+    for k, (n1, n2) in enumerate(((255, 63), (256, 64), (257, 65))):
+        a, b = synth.descriptor_cloud(n1, family, 400 + k), synth.descriptor_cloud(n2, family, 410 + k)
+        b[:8] = a[-1]                     # the last reference, at distance 0 ...
+        b[8:16] = a[n1 - 16:n1 - 8]       # ... and others of the last sixteenth
+        pairs.append((a, b))
+    shared = pairs[2][0]
+    q = synth.descriptor_cloud(70, family, 420)
+    q[:4] = shared[-1]
+    pairs.append((shared, q))             # the same array: the same pointer and length as pair 2's des1
+    got = _check_both_entries(ix, pairs, TIES[ties])
+    if ties == "lowest" and family == "uniform":
+        assert got[2][1:9].tolist() == [256] * 8 and got[3][1:5].tolist() == [256] * 4 and got[1][1:9].tolist() == [255] * 8
+
+
+@pytest.mark.parametrize("ties", sorted(TIES))
+@pytest.mark.parametrize("family", synth.DESCRIPTOR_FAMILIES)
+def test_slice_at_its_maximum(ix, family, ties):
+    """one pair of 2049 references and 32768 queries: 512 query blocks x 2 slices = 1024 items, just enough for the slice to
+    stay at 2048 -- the second slice holds ONE reference, and it is the answer of some queries in every part of the table"""
+    a, b = synth.descriptor_cloud(2049, family, 430), synth.descriptor_cloud(32768, family, 431)
+    b[1::101] = a[2047]
+    b[::97] = a[-1]
+    got = _check_both_entries(ix, [(a, b)], TIES[ties])
+    if ties == "lowest" and family == "uniform":
+        assert (got[0][1:] == 2048).sum() >= len(b[::97])
+
+
 def test_empty_batch_and_all_empty_pairs(ix):
     assert ix.match_knn_batch([]) == []
     e = np.zeros((0, 32), np.float32)
