@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan build/test_voxel_plan
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch build/ground_segments
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -204,6 +204,11 @@ build/test_ground_plan: tests/cpp/test_ground_plan.cpp $(CSRC)/ground_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
 
+# the leaf lattice of the voxel grid (origin, dimensions, the int32 and 2^26 refusals) on the CPU (no library, no GPU)
+build/test_voxel_plan: tests/cpp/test_voxel_plan.cpp $(CSRC)/voxel_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
+
 # pcc::groundSegmentation: a PLY in, <prefix>_ground.ply and <prefix>_object.ply out, as the reference's ground_segmentation writes them
 build/ground_segments: tests/cpp/ground_segments.cpp include/pcc/ground.hpp include/pcc/point_types.hpp pointcloudcomparator_amd/host/ply_io.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
@@ -251,7 +256,7 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan build/asan/test_voxel_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
@@ -264,6 +269,7 @@ asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host bui
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_colour_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_ground_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_voxel_plan
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -316,6 +322,11 @@ build/asan/test_match_colour_plan: tests/cpp/test_match_colour_plan.cpp $(CSRC)/
 build/asan/test_ground_plan: tests/cpp/test_ground_plan.cpp $(CSRC)/ground_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
+
+# (float-cast-overflow is not part of `undefined`: a conversion of a bound an int cannot hold must stop this one)
+build/asan/test_voxel_plan: tests/cpp/test_voxel_plan.cpp $(CSRC)/voxel_plan.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -fsanitize=float-cast-overflow -fno-sanitize-recover=float-cast-overflow -Wall -I$(CSRC) $< -o $@
 
 clean:
 	rm -rf build $(LIBDIR)/*.so oracle/_build

@@ -405,7 +405,21 @@ int pcc_match_knn_batch_dims(pcc_index *ctx, size_t n_pairs,
  *   Non-finite points are ignored.  `ctx` is any index handle (supplies device, stream, scratch).
  * out: caller-allocated, capacity n elements of out_stride bytes (x, y, z at 0 [, rgb at 16]);
  * *out_n (host) = number of voxels written.  Centroid coordinates are accumulated in double and
- * rounded once (PCL: float sums in sort order), i.e. equal to PCL's within float rounding. */
+ * rounded once (PCL: float sums in sort order), i.e. equal to PCL's within float rounding.
+ * What is written: rows 0 .. *out_n - 1, and of each x, y, z at 0, 1.0f at 12 when out_stride >= 16, the
+ *   colour word at 16 with has_rgb (its top byte 0).  Rows from *out_n on keep the caller's bytes.  The
+ *   other bytes of a written row (from 16 on without colour, from 20 on with it) keep the caller's bytes
+ *   when out is device memory and are ZERO when out is host memory (whole rows of a zeroed staging buffer
+ *   are copied).  A cloud without a finite point: PCC_OK, *out_n = 0, nothing written.
+ * Colour: channel sums are integers, exact up to 2^32 / 255 points in a voxel, divided in float as PCL
+ *   does.  PCL sums the channels in float: up to 65 793 points in a voxel (2^24 / 255) both are exact and
+ *   equal; beyond that PCL's own word depends on the order its sort left the points in.
+ * Refused with PCC_ERR_UNSUPPORTED ("leaf size %g too small for this cloud"), *out_n = 0 and out untouched:
+ *   more than 2^26 voxels in the lattice of the finite bounding box, or a bound of that box whose voxel
+ *   coordinate floor(bound * (1 / leaf)) is not finite or not below 2^31 in magnitude -- PCL converts it to
+ *   int, which is undefined there (a far cloud with a tiny leaf; a subnormal leaf, whose inverse is
+ *   infinite).  Decided on the host in floating point before anything is sorted.  The segmentation, ground
+ *   and SIFT entry points, which start with this step, refuse alike (pcc_sift_keypoints_batch names the cloud). */
 int pcc_voxel_grid(pcc_index *ctx, const void *pts, size_t n, size_t stride_bytes, int mem,
                    float leaf, int has_rgb, void *out, size_t out_stride, size_t *out_n);
 

@@ -37,19 +37,20 @@
 #include "grid_device.hpp"
 #include "sift_stages.hpp"
 #include "sift_batch_plan.hpp"
+#include "voxel_plan.hpp"
 #include "desc_batch.hpp"
 
 namespace pcc {
 
 namespace {
 
-constexpr unsigned int SB_MAX_CELLS = 1u << 26;   // voxel.hip's limit
+constexpr unsigned int SB_MAX_CELLS = VOXEL_MAX_CELLS;  // voxel.hip's limit
 constexpr unsigned int SB_NO_VOXEL = 0xffffffffu;  // the voxel of a non-finite point: behind every voxel of its cloud
 
 // ---- 1. segmented voxel grid ---------------------------------------------------------------------------------------------
-// A workgroup per cloud: bounding box of the finite points -> the lattice (voxel.hip:101-112: min_b = floor(lo * inv), dim =
-// max_b - min_b + 1, x fastest) -> a key per point.  A lattice above 2^26 voxels leaves the cloud's number + 1 in *status
-// (the largest such cloud) and the cloud without voxels.
+// A workgroup per cloud: bounding box of the finite points -> the lattice (voxel_plan.hpp, as voxel.hip: min_b = floor(lo * inv),
+// dim = max_b - min_b + 1, x fastest) -> a key per point.  A lattice above 2^26 voxels, or with a bound beyond int32, leaves the
+// cloud's number + 1 in *status (the largest such cloud) and the cloud without voxels.
 __global__ void __launch_bounds__(256)
 k_sb_voxel_keys(const unsigned int* __restrict__ bases, const SiftRec* __restrict__ in, float inv, unsigned long long* __restrict__ keys,
                 unsigned int* __restrict__ cloud_of, unsigned int* __restrict__ status) {
@@ -78,20 +79,19 @@ k_sb_voxel_keys(const unsigned int* __restrict__ bases, const SiftRec* __restric
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double cells = 1;
-        bool any = true;
+        float l[3], h[3];
         for (int a = 0; a < 3; ++a) {
-            const float l = fminf(fminf(s_lo[a][0], s_lo[a][1]), fminf(s_lo[a][2], s_lo[a][3]));
-            const float h = fmaxf(fmaxf(s_hi[a][0], s_hi[a][1]), fmaxf(s_hi[a][2], s_hi[a][3]));
-            if (!(l <= h)) { any = false; break; }  // no finite point
-            const int mn = (int)floorf(l * inv), mx = (int)floorf(h * inv);
-            s_org[a] = (float)mn;
-            s_dim[a] = mx - mn + 1;
-            cells *= (double)s_dim[a];
+            l[a] = fminf(fminf(s_lo[a][0], s_lo[a][1]), fminf(s_lo[a][2], s_lo[a][3]));
+            h[a] = fmaxf(fmaxf(s_hi[a][0], s_hi[a][1]), fmaxf(s_hi[a][2], s_hi[a][3]));
         }
-        if (any && cells > (double)SB_MAX_CELLS) {
-            atomicMax(status, c + 1u);
-            any = false;
+        bool any = l[0] <= h[0];  // (false: no finite point, on every axis alike)
+        if (any) {
+            const VoxelPlan vp = voxel_plan(l, h, inv);
+            if (vp.verdict != VOXEL_PLAN_OK) {  // (the host check of the entry point has refused the first octave's before)
+                atomicMax(status, c + 1u);
+                any = false;
+            }
+            for (int a = 0; a < 3; ++a) { s_org[a] = vp.org[a]; s_dim[a] = vp.dim[a]; }
         }
         if (!any) s_dim[0] = s_dim[1] = s_dim[2] = 0;
     }
@@ -601,7 +601,7 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
     PCC_TRY(check_sift_params(min_scale, nr_octaves, nr_scales_per_octave, min_contrast));
     if (out_snap_index && (!(snap_radius > 0) || !std::isfinite(snap_radius))) { set_error("bad radius"); return PCC_ERR_INVALID; }
     PCC_TRY(check_batch_clouds(batch, mem));
-    // the first octave's lattice of every cloud (voxel.hip:101-112 on the host; the later octaves' leaves are larger)
+    // the first octave's lattice of every cloud (voxel_plan.hpp, as voxel.hip sizes it; the later octaves' leaves are larger)
     const float inv = 1.0f / min_scale;
     for (size_t c = 0; c < n_clouds; ++c) {
         float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -615,10 +615,13 @@ int pcc_sift_keypoints_batch(pcc_index* ctx, size_t n_clouds, const void* const*
             for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], v[a]); hi[a] = std::max(hi[a], v[a]); }
         }
         if (!any) continue;
-        double cells = 1;
-        for (int a = 0; a < 3; ++a) cells *= (double)((int)std::floor(hi[a] * inv) - (int)std::floor(lo[a] * inv) + 1);
-        if (cells > (double)(1u << 26)) {
-            set_error("cloud %zu: leaf size %g too small for this cloud: %.0f voxels (limit %u)", c, min_scale, cells, 1u << 26);
+        const VoxelPlan vp = voxel_plan(lo, hi, inv);
+        if (vp.verdict == VOXEL_PLAN_RANGE) {
+            set_error("cloud %zu: leaf size %g too small for this cloud: a voxel coordinate of its bounding box is beyond int32", c, min_scale);
+            return PCC_ERR_UNSUPPORTED;
+        }
+        if (vp.verdict == VOXEL_PLAN_CELLS) {
+            set_error("cloud %zu: leaf size %g too small for this cloud: %.0f voxels (limit %u)", c, min_scale, vp.cells, VOXEL_MAX_CELLS);
             return PCC_ERR_UNSUPPORTED;
         }
     }

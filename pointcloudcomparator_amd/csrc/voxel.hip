@@ -13,13 +13,12 @@
 // does.  HBM-bound streaming passes apart from the sort's scatter.
 #include "entry.hpp"
 #include "grid_device.hpp"
+#include "voxel_plan.hpp"
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 namespace pcc {
-
-constexpr unsigned int VOX_MAX_CELLS = 1u << 26;
 
 __global__ void __launch_bounds__(256)
 k_vox_heads(const float4* __restrict__ pts, const unsigned int* __restrict__ order, const unsigned int* __restrict__ n_sorted,
@@ -102,19 +101,22 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
     const float inv = 1.0f / leaf;
     GridDev hd;
     memset(&hd, 0, sizeof(hd));
-    double cells = 1;
-    for (int a = 0; a < 3; ++a) {
-        const int mn = (int)std::floor(lo[a] * inv), mx = (int)std::floor(hi[a] * inv);
-        hd.g.org[a] = (float)mn;
-        hd.g.dim[a] = mx - mn + 1;
-        hd.g.ax[a] = a;  // (PCL's voxel index is x fastest, z slowest: the output order depends on it)
-        cells *= (double)hd.g.dim[a];
+    // (voxel_plan.hpp: decided in floating point, so that no bound is converted that an int cannot hold)
+    const VoxelPlan vp = voxel_plan(lo, hi, inv);
+    if (vp.verdict == VOXEL_PLAN_RANGE) {
+        set_error("leaf size %g too small for this cloud: a voxel coordinate of its bounding box is beyond int32", leaf);
+        return PCC_ERR_UNSUPPORTED;
     }
-    if (cells > (double)VOX_MAX_CELLS) {
+    if (vp.verdict == VOXEL_PLAN_CELLS) {
         // PCL itself refuses when the index would overflow int32 ("Leaf size is too small for the input
         // dataset"); this implementation draws the line at 2^26 voxels
-        set_error("leaf size %g too small for this cloud: %.0f voxels (limit %u)", leaf, cells, VOX_MAX_CELLS);
+        set_error("leaf size %g too small for this cloud: %.0f voxels (limit %u)", leaf, vp.cells, VOXEL_MAX_CELLS);
         return PCC_ERR_UNSUPPORTED;
+    }
+    for (int a = 0; a < 3; ++a) {
+        hd.g.org[a] = vp.org[a];
+        hd.g.dim[a] = vp.dim[a];
+        hd.g.ax[a] = a;  // (PCL's voxel index is x fastest, z slowest: the output order depends on it)
     }
     hd.g.h = leaf;
     hd.g.inv_h = inv;

@@ -1,10 +1,16 @@
 """GPU parity (through the C-ABI) of k-NN, radius search, clustering, SOR, ICP blocks and
 descriptor matching against the oracle's FLANN/PCL restatement."""
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 
 import oracle
 from pointcloudcomparator_amd import capi, synth
+
+sys.path.insert(0, str(Path(__file__).resolve().parent))
+from voxel_ref import ulp_distance, voxel_grid_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -502,6 +508,15 @@ def test_voxel_grid_matches_pcl_restatement(gpu, leaf):
     dims = (np.floor(np.nanmax(pts[:, :3], axis=0) * inv) - lo + 1).astype(np.float64)
     key = ijk[:, 0] + ijk[:, 1] * dims[0] + ijk[:, 2] * dims[0] * dims[1]
     assert (np.diff(key) > 0).mean() > 0.999  # a centroid may round onto a voxel face
+    # against float64 sums rounded once (tests/voxel_ref.py), which is what the kernel specifies: the same voxels row by row --
+    # count, colour word and the centroid of every row -- and every coordinate within one float ulp
+    rows, counts = voxel_grid_ref(pts, leaf, True)
+    assert len(rows) == len(out) and counts.sum() == len(pts) - 1
+    assert (out[:, 3:5].view(np.uint32) == rows[:, 3:5].view(np.uint32)).all()
+    ulps = ulp_distance(out[:, :3], rows[:, :3])
+    print(f"leaf {leaf}: {len(rows)} voxels, at most {counts.max()} points in one, {np.count_nonzero(ulps)} of {ulps.size} coordinates differ, "
+          f"by at most {ulps.max()} ulp")
+    assert ulps.max() <= 1
 
 
 @pytest.mark.parametrize("n", [2047, 2048, 4096, 1_048_575, 1_048_576])

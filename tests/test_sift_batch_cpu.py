@@ -85,6 +85,18 @@ def test_arguments_are_refused_without_a_device():
     wp = (C.c_void_p * 2)(rec.ctypes.data, wide.ctypes.data)
     wc = (C.c_void_p * 2)(rec.ctypes.data + 16, wide.ctypes.data + 16)
     assert call(k=2, p=wp, c=wc, n=(C.c_size_t * 2)(8, 8)) == -5 and b"cloud 1: leaf size" in err() and b"too small for this cloud" in err()
+    # a first-octave lattice beyond int32: x in [3000, 3000.001] at a leaf of 1e-6 is voxel 3e9, which no int holds -- decided in
+    # floating point (csrc/voxel_plan.hpp), not from a converted bound; the cloud and its mirror image, the second of two
+    tiny, far = rec.copy(), rec.copy()
+    tiny[:, :3] *= 1e-5                               # 0 .. 2.3e-6: three voxels along z at this leaf
+    far[:, 0] = 3000.0 + np.linspace(0, 0.001, 8)
+    far[:, 1:3] = np.linspace(0, 1e-4, 8)[:, None]
+    for sign in (1.0, -1.0):
+        far[:, 0] = sign * np.abs(far[:, 0])
+        fp = (C.c_void_p * 2)(tiny.ctypes.data, far.ctypes.data)
+        fc = (C.c_void_p * 2)(tiny.ctypes.data + 16, far.ctypes.data + 16)
+        assert call(k=2, p=fp, c=fc, n=(C.c_size_t * 2)(8, 8), ms=1e-6) == -5, sign
+        assert b"cloud 1: leaf size 1e-06 too small for this cloud" in err() and b"beyond int32" in err(), (sign, err())
     assert call() == -1 and b"null index" in err()  # all arguments good: the handle is looked at last
     assert off.tolist() == [99, 99] and not kp.any() and not snap.any()  # nothing was written by any refused call
     # no cloud at all: PCC_OK, one offset, no device -- no array but the offsets is needed

@@ -263,7 +263,18 @@ def main():
                 elif op == 8 and m <= 20000 and n_valid >= 1:
                     leaf = scene_radius(rng, a) * 2.0
                     fin = a[:, :3][np.isfinite(a[:, :3]).all(1)]
-                    if (np.ceil((fin.max(0) - fin.min(0)) / leaf) + 1).prod() < 5e6:
+                    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+                        edge = np.floor(np.stack([fin.min(0), fin.max(0)]) * (np.float32(1.0) / np.float32(leaf)))  # (float32, as PCL)
+                    if (np.ceil((fin.max(0) - fin.min(0)) / leaf) + 1).prod() < 5e6 and not (np.abs(edge) < 2.0 ** 31).all():
+                        # a bound's voxel coordinate that no int holds (a pile of copies far out, a radius of nothing): PCL's
+                        # conversion -- and the oracle's -- is undefined there, the library refuses (pcc_nn.h)
+                        try:
+                            ix.voxel_grid(a, leaf)
+                            refused = False
+                        except capi.PccError as e:
+                            refused = e.status == -5 and "too small for this cloud" in str(e)
+                        check("voxel", refused, a=a, leaf=leaf)
+                    elif (np.ceil((fin.max(0) - fin.min(0)) / leaf) + 1).prod() < 5e6:
                         got = ix.voxel_grid(a, leaf)
                         vg, nv = oracle.voxel_grid(a, leaf)
                         # PCL adds a voxel's points in FLOAT (the oracle does too), the library in double: they differ by up to
