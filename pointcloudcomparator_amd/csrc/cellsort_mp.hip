@@ -66,11 +66,11 @@ __device__ __forceinline__ unsigned int mp_cell(const float4& v, const GridParam
 __device__ __forceinline__ unsigned int mp_cell(const uint2& v, const GridParams&, bool) { return v.x; }
 __device__ __forceinline__ unsigned int mp_position(const float4& v) { return (unsigned int)__float_as_int(v.w); }
 __device__ __forceinline__ unsigned int mp_position(const uint2& v) { return v.y; }
-template <class E> __device__ __forceinline__ E mp_make(const float4& v, unsigned int cell);
-template <> __device__ __forceinline__ float4 mp_make<float4>(const float4& v, unsigned int) { return v; }
-template <> __device__ __forceinline__ uint2 mp_make<uint2>(const float4& v, unsigned int cell) {
-    return make_uint2(cell, (unsigned int)__float_as_int(v.w));
-}
+// (the position is the element's place in the array being sorted, not its .w: a part of the indexed cloud sorted as a query cloud
+// -- pcc_sor_partial's shard -- carries the indices of the whole cloud there)
+template <class E> __device__ __forceinline__ E mp_make(const float4& v, unsigned int cell, unsigned int pos);
+template <> __device__ __forceinline__ float4 mp_make<float4>(const float4& v, unsigned int, unsigned int) { return v; }
+template <> __device__ __forceinline__ uint2 mp_make<uint2>(const float4&, unsigned int cell, unsigned int pos) { return make_uint2(cell, pos); }
 
 // ---- level 1 ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MP_T)
@@ -117,7 +117,7 @@ k_mp_scatter1(const float4* __restrict__ pts, unsigned int n, const GridDev* __r
         for (int u = 0; u < 4; ++u)
             if (i0 + u * MP_T < end && __float_as_int(v[u].w) >= 0) {
                 const unsigned int c = mp_cell(v[u], g, voxel);
-                out[atomicAdd(&cur[c / F1], 1u)] = mp_make<E>(v[u], c);
+                out[atomicAdd(&cur[c / F1], 1u)] = mp_make<E>(v[u], c, i0 + u * MP_T);
             }
     }
 }
@@ -213,7 +213,7 @@ k_mp_scatter1_staged(const float4* __restrict__ pts, unsigned int n, const GridD
         for (int u = 0; u < PER; ++u)
             if (bk[u] != 0xffffffffu) {
                 const unsigned int b = bk[u] / F1, slot = tstart[b] + rk[u];
-                stage[slot] = mp_make<E>(v[u], bk[u]);
+                stage[slot] = mp_make<E>(v[u], bk[u], t0 + threadIdx.x + u * MP_T);
                 sb[slot] = (unsigned short)b;
             }
         __syncthreads();

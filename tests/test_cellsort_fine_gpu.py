@@ -1,6 +1,7 @@
 """The last level of the three-level cell sort (cellsort_mp.hip, k_mp_fine): buckets of at most LIGHT elements are sorted by
-one wave each, four to a workgroup; up to four times as many by a whole workgroup from one read; the others as before.  Small clouds reach that sort through
-PCC_OPT_SORT_MP_MIN / _Q = 1000; PCC_OPT_GRID_PPC shapes the cells and PCC_OPT_GRID_TRIM = 0 lays the grid over the true
+one wave each, four to a workgroup; up to four times as many by a whole workgroup from one read; the others as before.  Small clouds reach that LEVEL through
+PCC_OPT_SORT_MP_MIN / _Q = 1000 -- its last level only: every grid here has fewer than 262 144 cells, so level 1 sorts into one
+bucket and level 2 sees one level-1 bucket per slice (tests/test_cellsort_levels_gpu.py has the upper levels); PCC_OPT_GRID_PPC shapes the cells and PCC_OPT_GRID_TRIM = 0 lays the grid over the true
 bounding box, which is what tools/bucket_sizes.py models: every case states what its buckets hold from that model and checks
 the model's cell count against the handle's.
 
