@@ -8,7 +8,7 @@ ARCH       ?= gfx950
 HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 -fPIC -Iinclude -Ipointcloudcomparator_amd/csrc
 CSRC       := pointcloudcomparator_amd/csrc
 LIBDIR     := pointcloudcomparator_amd/lib
-HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/cluster_match.hip $(CSRC)/match_colour.hip $(CSRC)/sor.hip $(CSRC)/segment.hip $(CSRC)/ground.hip)
+HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/rift.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/cluster_match.hip $(CSRC)/match_colour.hip $(CSRC)/sor.hip $(CSRC)/segment.hip $(CSRC)/ground.hip $(CSRC)/change.hip)
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/pcc_nn.h
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 
@@ -26,8 +26,8 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan build/test_voxel_plan
-cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch build/ground_segments
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan build/test_voxel_plan build/test_change_plan build/change_driver
+cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch build/ground_segments build/spatial_change
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build
@@ -66,7 +66,7 @@ build/test_host_mirror: tests/cpp/test_host_mirror.cpp include/pcc/point_types.h
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include $< -o $@ -L$(LIBDIR) -lpcc_nn -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
-build/comparator: examples/comparator_main.cpp pointcloudcomparator_amd/host/ply_io.hpp pointcloudcomparator_amd/host/report.hpp include/pcc/multi_device.hpp include/pcc/rift.hpp include/pcc/sift.hpp include/pcc/descriptors.hpp include/pcc/point_types.hpp include/pcc/search.hpp include/pcc/comparator_nn.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+build/comparator: examples/comparator_main.cpp pointcloudcomparator_amd/host/ply_io.hpp pointcloudcomparator_amd/host/report.hpp include/pcc/octree.hpp include/pcc/multi_device.hpp include/pcc/rift.hpp include/pcc/sift.hpp include/pcc/descriptors.hpp include/pcc/point_types.hpp include/pcc/search.hpp include/pcc/comparator_nn.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
@@ -209,6 +209,26 @@ build/test_voxel_plan: tests/cpp/test_voxel_plan.cpp $(CSRC)/voxel_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
 
+# the lattice of pcc_change_detection (anchor, voxel coordinates, the 2^31 and 2^21 refusals, keys, table size) on the CPU (no library, no GPU)
+build/test_change_plan: tests/cpp/test_change_plan.cpp $(CSRC)/change_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
+
+# the reference's call sequence against pcc::octree::OctreePointCloudChangeDetector, and pcc::spatialChangeDetection
+build/change_driver: tests/cpp/change_driver.cpp include/pcc/octree.hpp include/pcc/point_types.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
+# pcc::spatialChangeDetection: two PLYs and a resolution in, the points of the second in voxels the first leaves empty out
+build/spatial_change: tests/cpp/spatial_change.cpp include/pcc/octree.hpp include/pcc/point_types.hpp pointcloudcomparator_amd/host/ply_io.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude -Ipointcloudcomparator_amd/host $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
+
+# dev helper of tools/exp_changes.py (not part of `all`): the same lattice with std::unordered_set on one host core
+build/changes_host: tools/changes_host.cpp $(CSRC)/change_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -ffp-contract=off -Wall -I$(CSRC) $< -o $@
+
 # pcc::groundSegmentation: a PLY in, <prefix>_ground.ply and <prefix>_object.ply out, as the reference's ground_segmentation writes them
 build/ground_segments: tests/cpp/ground_segments.cpp include/pcc/ground.hpp include/pcc/point_types.hpp pointcloudcomparator_amd/host/ply_io.hpp include/pcc_nn.h $(LIBDIR)/libpcc_nn.so
 	@mkdir -p build
@@ -256,7 +276,7 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan build/asan/test_voxel_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan build/asan/test_voxel_plan build/asan/test_change_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/sift_host --self build/asan/sift_self.bin
@@ -270,6 +290,7 @@ asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host bui
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_ground_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_voxel_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_change_plan
 	@echo "asan: clean"
 
 build/asan/pcc_oracle.o: oracle/pcc_oracle.c oracle/pcc_oracle.h
@@ -325,6 +346,10 @@ build/asan/test_ground_plan: tests/cpp/test_ground_plan.cpp $(CSRC)/ground_plan.
 
 # (float-cast-overflow is not part of `undefined`: a conversion of a bound an int cannot hold must stop this one)
 build/asan/test_voxel_plan: tests/cpp/test_voxel_plan.cpp $(CSRC)/voxel_plan.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -fsanitize=float-cast-overflow -fno-sanitize-recover=float-cast-overflow -Wall -I$(CSRC) $< -o $@
+
+build/asan/test_change_plan: tests/cpp/test_change_plan.cpp $(CSRC)/change_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -fsanitize=float-cast-overflow -fno-sanitize-recover=float-cast-overflow -Wall -I$(CSRC) $< -o $@
 

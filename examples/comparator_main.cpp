@@ -30,6 +30,7 @@
 #include "pcc/rift.hpp"
 #include "pcc/sift.hpp"
 #include "pcc/descriptors.hpp"
+#include "pcc/octree.hpp"
 #include "ply_io.hpp"
 #include "report.hpp"
 
@@ -66,6 +67,11 @@ static bool descriptors_device = false;
 // same lines, same matches
 static bool matching_device = false;
 static std::string descriptors_path[2], dump_prefix, dump_descriptors_prefix;
+// --changes RES: after verdict 1 or 2 the reference's spatial_change_detection (:54-110, called at :1687-1698 with a resolution of
+// 32) runs at resolution RES: its sentence and the number of points of the richer cloud in voxels the other leaves empty;
+// --dump-changes FILE.ply: those points, with their colours
+static double changes_resolution = 0;
+static std::string dump_changes_path;
 
 static void printUsage() {
     std::cout << "\n\nUsage: [options] </pathToScene1.ply> </pathToScene2.ply>\n\n"
@@ -114,7 +120,11 @@ static void printUsage() {
               << "                   cloud per cluster -- runs in ONE library call (pcc_euclidean_cluster_segmentation: the filtered\n"
               << "                   cloud, what remains after the planes, its index and labels stay on the GPU): the same lines, the\n"
               << "                   same clusters; ignored without -e\n"
-              << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n" << "\n\n";
+              << "--results F        (this build) results file (default ../../PointCloudComparatorResults/results.txt)\n"
+              << "--changes RES      (this build) after the verdict \"first\" or \"second\" the reference's spatial_change_detection runs at a\n"
+              << "                   voxel resolution of RES (pcc_change_detection): the sentence of that branch and the number of points\n"
+              << "                   of the richer cloud in voxels the other cloud leaves empty; nothing after \"same information\"\n"
+              << "--dump-changes F.ply  (this build, with --changes) those points, with their colours, as a PLY file\n" << "\n\n";
 }
 
 // src/segmentation.cpp:64-156 euclidean_cluster_segmentation: VoxelGrid 0.025 (:69-76) -> RANSAC plane
@@ -244,6 +254,18 @@ static std::vector<PointCloud<PointXYZRGB>::Ptr> region_growing_segmentation(con
         clusters_pcl.push_back(cloud_cluster);
     }
     return clusters_pcl;
+}
+
+// src/comparator.cpp:54-110 spatial_change_detection: both files loaded again (as they are: the indices are the files'), the points
+// of cloudB in voxels cloudA leaves empty; the reference shows them in a viewer, here their number is printed
+static void spatial_change_detection(const std::string& filename, const std::string& filename2) {
+    PointCloud<PointXYZRGB>::Ptr cloudA(new PointCloud<PointXYZRGB>), cloudB(new PointCloud<PointXYZRGB>);
+    if (io::loadPLYFile(filename, *cloudA) == -1) { std::cerr << "Was not able to open file \"" << filename << "\".\n"; return; }
+    if (io::loadPLYFile(filename2, *cloudB) == -1) { std::cerr << "Was not able to open file \"" << filename2 << "\".\n"; return; }
+    const PointCloud<PointXYZRGB>::Ptr cloudDiff = spatialChangeDetection<PointXYZRGB>(cloudA, cloudB, changes_resolution);
+    std::cout << cloudDiff->points.size() << " points" << std::endl;
+    if (!dump_changes_path.empty() && io::savePLYFileBinary(dump_changes_path, *cloudDiff) == -1)
+        std::cerr << "Was not able to write file \"" << dump_changes_path << "\".\n";
 }
 
 static double computeSimilarity(const std::string& file1, const std::string& file2, const std::string& results_path) {
@@ -471,6 +493,8 @@ int main(int argc, char** argv) {
         else if (a == "--planes-device") planes_device = true;
         else if (a == "--segment-device") segment_device = true;
         else if (a == "--euclidean-device") euclidean_device = true;
+        else if (a == "--changes" && i + 1 < argc) changes_resolution = std::atof(argv[++i]);
+        else if (a == "--dump-changes" && i + 1 < argc) dump_changes_path = argv[++i];
         else if (a.size() > 4 && a.substr(a.size() - 4) == ".ply") plys.push_back(a);
     }
     if (help) { printUsage(); return 1; }
@@ -491,8 +515,20 @@ int main(int argc, char** argv) {
         std::cerr << e.what() << std::endl;
     }
     std::cout << "--------------------------------\n" << std::endl;
+    const bool changes = changes_resolution > 0 && (similarity == 1 || similarity == 2);
     if (similarity == 1) std::cout << "The first point cloud has more information" << std::endl;
     else if (similarity == 2) std::cout << "The second point cloud has more information" << std::endl;
+    if (changes) {
+        // reference :1687-1698: the richer cloud is cloudB of spatial_change_detection
+        std::cout << (similarity == 1 ? "Points that are in the first pcl, that are not in the other:"
+                                      : "Points that are in the second pcl, that are not in the other:") << std::endl;
+        try {
+            if (similarity == 1) spatial_change_detection(plys[1], plys[0]);
+            else spatial_change_detection(plys[0], plys[1]);
+        } catch (const std::exception& e) {
+            std::cerr << e.what() << std::endl;
+        }
+    }
     else if (similarity == 0) std::cout << "Both point clouds have the same information" << std::endl;
     else if (similarity == -3) std::cout << "No descriptor files were given (--descriptors1/2): clusters were not matched, no verdict" << std::endl;
     std::cout << "--------------------------------\n" << std::endl;

@@ -49,7 +49,8 @@ enum pcc_status {
     PCC_ERR_DEVICE = -3,      /* HIP runtime failure (no GPU, launch error, ...) */
     PCC_ERR_NOMEM = -4,
     PCC_ERR_UNSUPPORTED = -5, /* dim != 3, k too large, ... */
-    PCC_ERR_OVERFLOW = -6     /* caller-provided output capacity too small */
+    PCC_ERR_OVERFLOW = -6,    /* caller-provided output capacity too small */
+    PCC_ERR_INTERNAL = -7     /* the library caught itself in a state it rules out (a bounded loop that ran out): a bug to report */
 };
 enum pcc_mem { PCC_MEM_HOST = 0, PCC_MEM_DEVICE = 1 };
 /* search engine behind an index.  Both are exact and return identical bits.
@@ -1091,6 +1092,43 @@ int pcc_sor_threshold(const double sums[4], uint64_t n_valid, int mean_k, double
  * count).  mean_dist / inlier: `count` entries in memory space `mem`; *threshold, *kept_total: same on every rank. */
 int pcc_sor_sharded(pcc_index *index, pcc_comm *comm, size_t start, size_t count, int mean_k, double stddev_mult, int mem,
                     float *mean_dist, uint8_t *inlier, double *threshold, size_t *kept_total);
+
+/* ---- change detection -----------------------------------------------------------------
+ * pcc_change_detection: the points of cloud B that lie in voxels cloud A leaves empty.
+ * replaces: spatial_change_detection (src/comparator.cpp:54-110, called from both verdict branches of main, :1687-1698):
+ *   pcl::octree::OctreePointCloudChangeDetector -- setInputCloud(A), addPointsFromInputCloud, switchBuffers,
+ *   setInputCloud(B), addPointsFromInputCloud, getPointIndicesFromNewVoxels.  Restated from the published algorithm; parity
+ *   with PCL 1.7 itself is not pinned.  The contract:
+ * Points that take part: those whose first three floats are finite.  Non-finite points of A mark nothing, non-finite
+ *   points of B are never reported.
+ * The lattice: PCL grows the octree's box in whole multiples of the resolution, so the first point that takes part fixes
+ *   it.  p = the first finite point of A in index order, or of B if A has none; res = resolution, eps = (double)FLT_EPSILON;
+ *   per axis, in double, in this order:  mn = p - res/2;  mx = p + res/2;  side = 2*res - eps;  over = (side - (mx - mn)) / 2;
+ *   a = mn - over  (PCL's first box: side 2*res - eps, centred on p).  The voxel of x is k = floor(((double)x - a) / res) per
+ *   axis: IEEE double subtraction, then division, no contraction, no reciprocal.
+ * Reported: a voxel is NEW if at least one finite point of B lies in it and no finite point of A does.  The result is every
+ *   finite point i of B whose voxel is new and holds at least min_points_per_leaf finite points of B (PCL's default: 0).
+ *   Indices come back ASCENDING.  Deviation: PCL returns them in octree traversal order, which depends on how the box
+ *   happened to grow; the reference only copies them into a cloud for display, and ascending order is what every other
+ *   index output of this library gives.
+ * Range: the three voxel coordinates share one 64-bit key, so over the finite points of both clouds max k - min k + 1 must be
+ *   at most 2^21 per axis, and every ((double)x - a) / res below 2^31 in magnitude (PCL's own limit is 2^32 voxels per axis).
+ *   Both are decided in floating point before any conversion to an integer.  Beyond: PCC_ERR_UNSUPPORTED, the message names
+ *   the axis and the span, *n_out = 0 and no output array is written.
+ * ctx supplies device, stream and scratch, as for pcc_voxel_grid and pcc_sac_plane; the cloud it indexes is not looked at.
+ * mem applies to a, b, out_index and out_records; n_out is always on the host.  out_index: n_b entries, the first *n_out are
+ *   written.  out_records: NULL, or n_b * b_stride_bytes bytes: record out_index[j] of b is copied WHOLE to slot j (host memory:
+ *   b must then be readable to the end of its last record).  With PCC_MEM_DEVICE the call is asynchronous on the handle's
+ *   stream apart from its one read-back of (status word, count), as pcc_rift_descriptors reads its count.
+ * Neither cloud has a finite point: PCC_OK, *n_out = 0.  The voxel table (open addressing, a power of two of at least
+ *   2 * (n_a + n_b) slots, cleared by every call) is handle scratch; a probe that runs through all of it -- ruled out by
+ *   its size -- ends the call with PCC_ERR_INTERNAL instead of waiting.
+ * Refused before any device is touched, nothing written: a null a, b, out_index or n_out; a bad memory space; n_a == 0 or
+ *   n_b == 0 (PCC_ERR_EMPTY); a stride below 12 or not a multiple of 4; 2^31 points or more (PCC_ERR_UNSUPPORTED); a pointer
+ *   that is not 4-byte aligned; a resolution that is not positive and finite; min_points_per_leaf < 0; a null handle last. */
+int pcc_change_detection(pcc_index *ctx, const void *a, size_t n_a, size_t a_stride_bytes, const void *b, size_t n_b,
+                         size_t b_stride_bytes, int mem, double resolution, int min_points_per_leaf, int32_t *out_index,
+                         void *out_records, size_t *n_out);
 
 /* ---- instrumentation ------------------------------------------------------------------
  * counters of the last search on this index (host):

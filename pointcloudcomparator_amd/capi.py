@@ -43,6 +43,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
+    "pcc_change_detection",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -160,6 +161,7 @@ def _load() -> C.CDLL:
     lib.pcc_progressive_morphological_filter.argtypes = [vp, vp, sz, sz, i32, i32, f32, f32, f32, f32, f32, i32, vp, C.POINTER(sz), vp, sz]
     lib.pcc_ground_segmentation.argtypes = [vp, vp, sz, sz, i32, f32, i32, f32, f32, f32, f32, f32, i32, vp, sz, C.POINTER(sz), vp,
                                             C.POINTER(sz), vp, vp]
+    lib.pcc_change_detection.argtypes = [vp, vp, sz, sz, vp, sz, sz, i32, C.c_double, i32, vp, vp, C.POINTER(sz)]
     for name in SYMBOLS:
         fn = getattr(lib, name)  # raises AttributeError if the library lacks a declared symbol
         if name != "pcc_last_error":
@@ -916,6 +918,34 @@ class Index:
         _check(status)
         return dict(filtered=filtered[:nv.value], ground_index=gidx[:ng.value], ground_points=gpts[:ng.value],
                     object_points=opts[:nv.value - ng.value])
+
+    def change_detection(self, a, b, resolution: float, min_points_per_leaf: int = 0, with_records: bool = False):
+        """pcc_change_detection: the reference's spatial_change_detection (src/comparator.cpp:54-110) -- the points of `b` in
+        voxels of side `resolution` that hold no point of `a` (pcl::octree::OctreePointCloudChangeDetector; the lattice is
+        fixed by the first finite point of `a`).  a, b: (n, >= 3) float32 numpy arrays or torch tensors, row strides free; if
+        either is a CUDA tensor the other is moved beside it and the results are CUDA tensors.  Returns the int32 indices into
+        `b`, ascending; with_records=True: (indices, records), the rows of `b` they name, every column."""
+        a_cuda, b_cuda = (_is_torch(x) and x.is_cuda for x in (a, b))
+        if a_cuda != b_cuda:
+            import torch
+            if a_cuda:
+                b = (b if _is_torch(b) else torch.from_numpy(b)).to(a.device)
+            else:
+                a = (a if _is_torch(a) else torch.from_numpy(a)).to(b.device)
+        pa, na, sa, mem = _points(a)
+        pb, nb, sb, mem_b = _points(b)
+        assert mem == mem_b
+        index, p_i = _out(b, (max(nb, 1),), np.int32)
+        records, p_r = _out(b, (max(nb, 1), int(b.shape[1])), np.float32) if with_records else (None, None)
+        if with_records:
+            assert nb <= 1 or sb == int(b.shape[1]) * 4, "with_records needs the rows of b back to back"
+        count = C.c_size_t(0)
+        st = self._before(a, b)
+        status = LIB.pcc_change_detection(self._h, pa, na, sa, pb, nb, sb, mem, float(resolution), int(min_points_per_leaf), p_i, p_r,
+                                          C.byref(count))
+        self._after(st)
+        _check(status)
+        return (index[:count.value], records[:count.value]) if with_records else index[:count.value]
 
     def normals(self, k: int = 50, viewpoint=None, device=None):
         """pcl::NormalEstimation over the index's own points: (n, 4) = nx, ny, nz, curvature.

@@ -513,6 +513,7 @@ int pcc_index_destroy(pcc_index* ix) {
     cluster_desc_release(ix);
     rgb_batch_release(ix);
     match_colour_release(ix);
+    change_release(ix);
     ground_release(ix);
     segment_release(ix);
     rift_release(ix);

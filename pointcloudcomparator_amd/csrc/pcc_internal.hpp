@@ -304,6 +304,7 @@ struct ClusterDescScratch; // cluster_desc.hip: BatchStaging, the staged cluster
 struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
                            // and the orders and tables of pcc_extract_clusters
 struct GroundScratch;      // ground.hip: the current points, lattice table and sorted copies of the morphological ground filter
+struct ChangeScratch;      // change.hip: the staged clouds, voxel table, flags and device words of pcc_change_detection
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
 // the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
 struct MatchBatchScratch {
@@ -398,6 +399,7 @@ struct pcc_index {
     pcc::ClusterDescScratch* cluster_desc = nullptr;  // made at the first pcc_cluster_descriptors with this handle as its context (cluster_desc.hip)
     pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
     pcc::GroundScratch* ground = nullptr;         // made at the first pcc_morphological_operator / pcc_progressive_morphological_filter / pcc_ground_segmentation with this handle as its context (ground.hip)
+    pcc::ChangeScratch* change = nullptr;         // made at the first pcc_change_detection with this handle as its context (change.hip)
     pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
@@ -681,6 +683,8 @@ int launch_records(hipStream_t s, const void* in, size_t stride, const unsigned 
 int give(pcc_index* ix, int mem, void* user, const void* dev, size_t bytes);
 // ground.hip: pcc_morphological_operator, pcc_progressive_morphological_filter and pcc_ground_segmentation
 void ground_release(pcc_index* ix);  // frees ix->ground
+// change.hip: pcc_change_detection
+void change_release(pcc_index* ix);  // frees ix->change
 // normals.hip: the plane fit over the self k-NN rows `keys` (n x K) of a packed cloud
 int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n,
                    int K, const float vp[3], float4* out);
