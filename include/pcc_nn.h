@@ -223,7 +223,7 @@ enum pcc_option {
                                     measured -- 60 clusters of 701 ... 8000 points take 17.6 ms at 8192 and 54.8 ms at 4096, where
                                     21 of them pay the single path's waits one after the other; above 8192 only the lone cloud
                                     was measured (10.2 against 3.4 ms at 16 384).  No result bit depends on it. */
-    PCC_OPT_RGB_BATCH_BRUTE_MAX = 28   /* pcc_region_growing_rgb_batch: clouds of up to this many points (and nr_region_neighbours <= 128) get
+    PCC_OPT_RGB_BATCH_BRUTE_MAX = 28,  /* pcc_region_growing_rgb_batch: clouds of up to this many points (and nr_region_neighbours <= 128) get
                                     their k-NN rows from the segmented exhaustive kernel that serves the whole batch at once (n^2
                                     distance tests per cloud) and grow in one pass over the concatenation; every other cloud takes
                                     the single path inside the same call, one by one, on a work handle kept in ctx
@@ -233,6 +233,10 @@ enum pcc_option {
                                     0.41 / 0.73 / 1.06 / 1.22 ms through the batch kernels against 0.52 / 0.89 / 1.06 / 1.21 ms on
                                     the work handle at 2048 / 4096 / 8192 / 16 384 points: the batch kernels never lose up to 8192
                                     and tie above it, where only the lone cloud was measured.  No result bit depends on it. */
+    PCC_OPT_FPFH_LAYOUT = 29     /* pcc_fpfh_descriptors, the SPFH and the weighting kernel: 1 = a wave per row -- every lane evaluates one row
+                                    entry's pair features and the votes are counted in integers; in the weighting every lane adds, in row
+                                    order, the shares of the bin it owns while three more lanes carry the running sums (default);
+                                    0 = one lane per row (PCL's loops as they stand).  Same bits either way. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -747,6 +751,36 @@ int pcc_rift_descriptors_batch(pcc_index *ctx, size_t n_clouds,
                                double normal_radius, double gradient_radius, double rift_radius,
                                int nr_distance_bins, int nr_gradient_bins,
                                float *out_histograms, int32_t *out_point_index, size_t *out_offsets);
+/* ---- FPFH descriptors of the indexed cloud ---------------------------------------------------------
+ * replaces: processFPFH (src/comparator.cpp:824-875) for one cloud: pcl::NormalEstimation (setRadiusSearch 0.03),
+ *   removeNaNNormalsFromPointCloud, and pcl::FPFHEstimation (setRadiusSearch 0.05, 11 + 11 + 11 bins) over the points that
+ *   are left.  The PCL stages are restated from the published algorithm ([recalled]): PCL 1.7 is not
+ *   available to compare against, parity with it is unpinned.
+ * Every neighbourhood is the sorted radius row of the library (d2 < float(r^2), ascending (d2, index), the point itself
+ * included), taken among the points of cloud2 -- the points with a finite normal; no compacted cloud is built before the
+ * final output, the stages skip the entries of the others:
+ *   normals    pcc_normals_radius at normal_radius, viewpoint origin; points without a finite normal leave (cloud2);
+ *   pair       pcl::computePairFeatures of (p, q): dp = q - p, f4 = |dp| (0: no pair); a1 = n_p.dp / f4, a2 = n_q.dp / f4;
+ *              acosf|a1| > acosf|a2| exchanges p and q, negates dp and sets f3 = -a2, else f3 = a1; v = dp x n_1 (|v| = 0: no
+ *              pair), v /= |v|, w = n_1 x v, f2 = v.n_2, f1 = atan2f(w.n_2, n_1.n_2);
+ *   SPFH       computePointSPFHSignature per point p of cloud2 over its fpfh_radius row: incr = 100.0f / float(row_len - 1),
+ *              row_len counting the cloud2 entries, p itself included; every entry other than p that has a pair adds incr to
+ *              bin floor(11 (f1 + pi) / (2 pi)) of the first eleven, floor(11 (f2 + 1) / 2) of the second and
+ *              floor(11 (f3 + 1) / 2) of the third (evaluated in double, clamped to 0 .. 10);
+ *   weighting  weightPointSPFHSignature per point p of cloud2 over the same row, in row order: every entry q with d2 != 0
+ *              adds spfh[q][b] * (1.0f / d2) to bin b and, entry by entry and bin by bin, to the running sum of b's feature;
+ *              each feature's eleven bins are then multiplied by float(100.0 / sum) (a zero sum: by 0).
+ * out_histograms[n][33] (the f1 bins, then f2, then f3, as pcl::FPFHSignature33 holds them) and out_point_index[n] (the
+ *   ORIGINAL index of every descriptor's point, ascending: the points of cloud2 -- processFPFH keeps exactly these and
+ *   removes nothing afterwards), memory space `mem`, sized by the caller for all n points of the indexed cloud; the first
+ *   *n_out (host) rows are written.  No colour is read.
+ * Refused before the handle is looked at, in this order: a bad memory space; a null output or n_out; a radius that is not
+ *   positive and finite; bins other than 11, 11, 11 (PCC_ERR_UNSUPPORTED); a null handle last.  A refused call writes
+ *   nothing.  Host waits: the row totals of the two CSRs (one when the radii are equal) and the count.
+ * PCC_OPT_FPFH_LAYOUT chooses between two forms of the two kernels; no result bit depends on it. */
+int pcc_fpfh_descriptors(pcc_index *index, int mem, double normal_radius, double fpfh_radius,
+                         int nr_bins_f1, int nr_bins_f2, int nr_bins_f3,
+                         float *out_histograms, int32_t *out_point_index, size_t *n_out);
 /* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
  * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
  *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)

@@ -21,7 +21,7 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX) = range(1, 29)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX, OPT_FPFH_LAYOUT) = range(1, 30)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -43,7 +43,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
-    "pcc_change_detection",
+    "pcc_change_detection", "pcc_fpfh_descriptors",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -117,6 +117,7 @@ def _load() -> C.CDLL:
     lib.pcc_normals.argtypes = [vp, i32, vp, i32, vp]
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_fpfh_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_sift_keypoints_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, C.c_double, vp, vp, sz, vp]
@@ -407,6 +408,7 @@ class Index:
         self._h = h
         self.n_original = n
         self.auto_sync = auto_sync
+        self._cuda = points.device if _is_torch(points) and points.is_cuda else None  # results without an input array follow the cloud's memory space
 
     def _torch_stream(self, *tensors):
         """hipStream_t of torch's current stream on the device of the first CUDA tensor argument (None: no
@@ -460,6 +462,7 @@ class Index:
         # from here on (an overwrite, the allocator reusing the block) waits for it
         self._after(st)
         self.n_original = n
+        self._cuda = points.device if _is_torch(points) and points.is_cuda else None
 
     def set_option(self, option: int, value: float):
         """pcc_index_set_option (OPT_*): implementation choices of this handle; no result bit depends on them"""
@@ -994,6 +997,26 @@ class Index:
         st = self._before(words, hist)
         _check(LIB.pcc_rift_descriptors(self._h, ptr, stride, mem, float(normal_radius), float(gradient_radius), float(rift_radius),
                                         int(nr_distance_bins), int(nr_gradient_bins), ph, pi, C.byref(n_out)))
+        self._after(st)
+        return hist[:n_out.value], index[:n_out.value]
+
+    def fpfh_descriptors(self, normal_radius: float = 0.03, fpfh_radius: float = 0.05, nr_bins=(11, 11, 11)):
+        """pcc_fpfh_descriptors: the reference's processFPFH (src/comparator.cpp:824-875) for the indexed cloud.
+        Returns (histograms (m, 33) float32: the f1, f2 and f3 bins; point index (m,) int32): one descriptor per point with a
+        finite normal and the original index of that point.  A handle over a CUDA tensor gives CUDA tensors, any other NumPy
+        arrays."""
+        n = self.n_original
+        like = None
+        if getattr(self, "_cuda", None) is not None:
+            import torch
+            like = torch.empty(0, device=self._cuda)
+        hist, ph = _out(like, (max(n, 1), 33), np.float32)
+        index, pi = _out(like, (max(n, 1),), np.int32)
+        b1, b2, b3 = nr_bins
+        n_out = C.c_size_t(0)
+        st = self._before(hist)
+        _check(LIB.pcc_fpfh_descriptors(self._h, MEM_DEVICE if like is not None else MEM_HOST, float(normal_radius), float(fpfh_radius),
+                                        int(b1), int(b2), int(b3), ph, pi, C.byref(n_out)))
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
 

@@ -77,6 +77,7 @@ static const OptionRow g_options[] = {
     {PCC_OPT_RIFT_BATCH_BRUTE_MAX, "PCC_RIFT_BATCH_BRUTE_MAX", &Options::rift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
     {PCC_OPT_SIFT_BATCH_BRUTE_MAX, "PCC_SIFT_BATCH_BRUTE_MAX", &Options::sift_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
     {PCC_OPT_RGB_BATCH_BRUTE_MAX, "PCC_RGB_BATCH_BRUTE_MAX", &Options::rgb_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
+    {PCC_OPT_FPFH_LAYOUT, "PCC_FPFH_LAYOUT", &Options::fpfh_layout, nullptr, 0, 1, OptionRow::FLAG},
 };
 static const OptionRow* option_row(int option) {
     for (const OptionRow& r : g_options)
@@ -517,6 +518,7 @@ int pcc_index_destroy(pcc_index* ix) {
     ground_release(ix);
     segment_release(ix);
     rift_release(ix);
+    fpfh_release(ix);
     sift_release(ix);
     if (ix->pinned) (void)hipHostFree(ix->pinned);
     if (ix->h_grid) (void)hipHostFree(ix->h_grid);

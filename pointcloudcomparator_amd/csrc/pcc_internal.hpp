@@ -167,6 +167,8 @@ struct Options {
                                     // tagged 64-bit atomics and wait for the workgroups in front of them: relies on in-order dispatch); 0 = the two-launch
                                     // form (block totals, then apply), which waits for nothing
     int rift_layout = 1;            // PCC_OPT_RIFT_LAYOUT: RIFT histogram kernel, 1 = 32 lanes per row (votes by all lanes, bins by owner lanes), 0 = one lane per row
+    int fpfh_layout = 1;            // PCC_OPT_FPFH_LAYOUT: FPFH kernels (SPFH and weighting), 1 = a wave per row (pair features by all lanes, bins by owner
+                                    // lanes), 0 = one lane per row
     int sift_layout = 1;            // PCC_OPT_SIFT_LAYOUT: SIFT scale-space kernel, 1 = a wave per point (weights by all lanes, sums by one owner lane per
                                     // scale), 0 = one lane per (point, scale)
     int host_pipe = 1;              // PCC_OPT_HOST_PIPE: clouds / results of 8 MB and more in pageable HOST memory cross PCIe through the library's own pinned
@@ -272,6 +274,14 @@ struct RiftScratch {
     DevBuf normals, inten;       // float4[n] plane fit; float[n] intensity, NaN outside cloud2
     DevBuf grad;                 // float4[n]: intensity gradient, w = 1 for the points of cloud2
     DevBuf hist, keep, scan_tmp; // float[n][32] before the last compaction; its flags / positions
+    DevBuf out_hist, out_index;  // results staged for a caller in host memory
+};
+// fpfh.hip: what pcc_fpfh_descriptors keeps between its stages (made at the first call on a handle).  Buffers of their own, as
+// RiftScratch's: the radius searches in between use the handle's shared scratch.
+struct FpfhScratch {
+    DevBuf normals;              // float4[n] plane fit
+    DevBuf spfh;                 // float[n][33]: the SPFH signature of every point of cloud2 (the others are never read)
+    DevBuf flags, pos, scan_tmp; // uint32[n]: 1 for the points of cloud2; uint32[n + 1]: their exclusive scan, pos[n] = the count
     DevBuf out_hist, out_index;  // results staged for a caller in host memory
 };
 // sift.hip: what pcc_sift_keypoints keeps between its octaves and calls (made at the first call on a handle)
@@ -391,6 +401,7 @@ struct pcc_index {
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
     pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
     pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
+    pcc::FpfhScratch* fpfh = nullptr;      // made at the first pcc_fpfh_descriptors on this handle (fpfh.hip)
     pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
     pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
     pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
@@ -652,6 +663,8 @@ void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work ha
 // the caller's buffers for uint32 offsets[total + 1] (+ the same as int64) and the entries.  One wait: the CSR's total
 int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
                       DevBuf& offs, DevBuf& keys, const unsigned long long** keys_out, const unsigned int** offsets_out);
+// fpfh.hip: pcc_fpfh_descriptors
+void fpfh_release(pcc_index* ix);  // frees ix->fpfh
 void sift_release(pcc_index* ix);  // frees ix->sift and its work handle
 // sift.hip: the detector on device arrays (ix->sift made by the caller): the keypoints are left in ix->sift->kp, *n_out of them
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
