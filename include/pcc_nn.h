@@ -1195,6 +1195,11 @@ int pcc_counts_pairs(void);
  * code (src/comparator.cpp:1123,1134,1179); this is how the tests reach the library's allocation-failure paths, the
  * collective ones above all (a rank that cannot allocate must take its peers out of the call, not leave them waiting). */
 int pcc_debug_fail_alloc(int nth);
+/* test hook: the blocks the library holds at this moment, process-wide and over every handle and communicator: live[0] device
+ * allocations, live[1] pinned host allocations.  Counted where a block is taken and where it is given back, so the figures
+ * after pcc_index_destroy equal those before the handle was made, exactly: this is how the tests see that a handle -- whatever
+ * was called on it, whichever allocation was refused on the way -- gives back everything it took. */
+int pcc_debug_live_buffers(uint64_t live[2]);
 /* HIP-event timing of the library's own kernels, recorded on the index's stream
  * (events of another stream would not see them).  After enabling, every
  * set_input / search records events into a 64-call ring without synchronising;

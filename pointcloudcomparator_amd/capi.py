@@ -39,7 +39,7 @@ SYMBOLS = [
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
     "pcc_normals_radius", "pcc_rift_descriptors", "pcc_rift_descriptors_batch", "pcc_sift_keypoints", "pcc_sift_keypoints_batch", "pcc_cluster_descriptors", "pcc_cluster_matching", "pcc_match_colour_elements", "pcc_index_wait_stream", "pcc_stream_wait_index", "pcc_index_clone_to_device", "pcc_index_set_tie_order",
     "pcc_index_set_option", "pcc_index_get_option", "pcc_index_clone_to_devices", "pcc_counts_pairs", "pcc_index_sor_on_device",
-    "pcc_debug_fail_alloc",
+    "pcc_debug_fail_alloc", "pcc_debug_live_buffers",
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
@@ -98,6 +98,7 @@ def _load() -> C.CDLL:
     lib.pcc_index_set_engine.argtypes = [vp, i32]
     lib.pcc_index_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     lib.pcc_device_count.argtypes = [C.POINTER(i32)]
+    lib.pcc_debug_live_buffers.argtypes = [C.POINTER(C.c_uint64)]
     lib.pcc_nn1.argtypes = [vp, vp, sz, sz, i32, vp, vp]
     lib.pcc_knn.argtypes = [vp, vp, sz, sz, i32, i32, vp, vp]
     lib.pcc_radius_count.argtypes = [vp, vp, sz, sz, i32, C.c_double, vp]

@@ -100,6 +100,9 @@ void Options::from_env() {
 
 // test hook (pcc_debug_fail_alloc): the n-th device allocation from now on fails as an exhausted hipMalloc would
 static std::atomic<int> g_fail_alloc{0};
+// test hook (pcc_debug_live_buffers): the blocks DevBuf / HostBuf hold at this moment, process-wide.  Counted where a block is
+// really taken or given back, nowhere else: the early return of reserve() -- all a hot call sees -- does not touch them.
+static std::atomic<uint64_t> g_live_dev{0}, g_live_pinned{0};
 
 int DevBuf::reserve(size_t bytes) {
     if (bytes <= cap && p) return PCC_OK;
@@ -113,20 +116,35 @@ int DevBuf::reserve(size_t bytes) {
     if (bytes == 0) bytes = 256;
     size_t want = bytes + bytes / 8;  // slack so slowly growing batches do not realloc each call
     want = (want + 255) & ~(size_t)255;
-    if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+    release();
     hipError_t e = hipMalloc(&p, want);
     if (e != hipSuccess) {
         p = nullptr;
         set_error("hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
         return PCC_ERR_NOMEM;
     }
+    g_live_dev.fetch_add(1, std::memory_order_relaxed);
     cap = want;
     return PCC_OK;
 }
 void DevBuf::release() {
-    if (p) (void)hipFree(p);
+    if (p) {
+        (void)hipFree(p);
+        g_live_dev.fetch_sub(1, std::memory_order_relaxed);
+    }
     p = nullptr;
     cap = 0;
+}
+int DevBuf::grow_keep(hipStream_t s, size_t keep, size_t want) {
+    if (p && want <= cap) return PCC_OK;
+    DevBuf grown;  // (freed by its destructor on every return in front of the move)
+    PCC_TRY(grown.reserve(std::max(want, 2 * cap)));
+    if (keep && p) {
+        PCC_HIP(hipMemcpyAsync(grown.p, p, keep, hipMemcpyDeviceToDevice, s));
+        PCC_HIP(hipStreamSynchronize(s));
+    }
+    *this = std::move(grown);
+    return PCC_OK;
 }
 
 int HostBuf::reserve(size_t bytes) {
@@ -134,20 +152,30 @@ int HostBuf::reserve(size_t bytes) {
     if (bytes == 0) bytes = 256;
     size_t want = bytes + bytes / 8;
     want = (want + 4095) & ~(size_t)4095;
-    if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
+    release();
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e != hipSuccess) {
         p = nullptr;
         set_error("hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
         return PCC_ERR_NOMEM;
     }
+    g_live_pinned.fetch_add(1, std::memory_order_relaxed);
     cap = want;
     return PCC_OK;
 }
 void HostBuf::release() {
-    if (p) (void)hipHostFree(p);
+    if (p) {
+        (void)hipHostFree(p);
+        g_live_pinned.fetch_sub(1, std::memory_order_relaxed);
+    }
     p = nullptr;
     cap = 0;
+}
+
+// the handle's pipe, made at the first transfer that needs it
+static HostPipe* host_pipe(pcc_index* ix) {
+    if (!ix->pipe) ix->pipe = std::make_unique<HostPipe>();
+    return ix->pipe.get();
 }
 
 // Stage a caller cloud (host or device AoS) as packed float4 on the device.
@@ -161,9 +189,8 @@ static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride,
             // (everything enqueued so far may still be reading `raw`: the chunks are enqueued on the same stream, in order behind it)
             const size_t dst_stride = stride >= 24 ? 12 : stride;
             PCC_TRY(raw.reserve(n * dst_stride + 16));
-            if (!ix->pipe) ix->pipe = new HostPipe();
             ix->small_raw_n = 0;  // (the chunk buffers are the small-call buffers: an indexed cloud's raw records do not survive this)
-            PCC_TRY(ix->pipe->upload(ix->stream, static_cast<const char*>(pts), n, stride, raw.as<char>(), dst_stride));
+            PCC_TRY(host_pipe(ix)->upload(ix->stream, static_cast<const char*>(pts), n, stride, raw.as<char>(), dst_stride));
             stride = dst_stride;
         } else if (ix->opt.host_pipe && bytes <= SMALL_DIRECT_BYTES) {
             // SMALL clouds -- the reference's descriptor clouds, 4 ... 18 381 records of 128 bytes, up to 300 calls per comparison
@@ -171,8 +198,7 @@ static int stage_points(pcc_index* ix, const void* pts, size_t n, size_t stride,
             // piece).  Up to SMALL_DIRECT_BYTES the cloud is copied into the handle's pinned buffer instead (slot 0: indexed clouds,
             // 1: query clouds) and the pack kernel reads it from there across the link -- no copy command at all.  (Between 1 and
             // 8 MB the runtime's own staging is as good: 18 381 descriptors 244 us a call against 277 through the pinned buffer.)
-            if (!ix->pipe) ix->pipe = new HostPipe();
-            PCC_TRY(ix->pipe->init());
+            PCC_TRY(host_pipe(ix)->init());
             const int slot = px.indexed_cloud ? 0 : 1;
             PCC_HIP(hipEventSynchronize(ix->pipe->ev[slot]));  // (whoever read this buffer last has finished: nearly always true already)
             memcpy(ix->pipe->buf[slot].p, pts, bytes);
@@ -230,9 +256,8 @@ int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int me
 int deliver(pcc_index* ix, const void* dev, void* user, size_t bytes) {
     if (!user || bytes == 0) return PCC_OK;
     if (ix->opt.host_pipe && bytes >= PIPE_MIN_BYTES && !host_pointer_is_pinned(user)) {
-        if (!ix->pipe) ix->pipe = new HostPipe();
         ix->small_raw_n = 0;  // (as in stage_points)
-        return ix->pipe->download(ix->stream, static_cast<const char*>(dev), static_cast<char*>(user), bytes);
+        return host_pipe(ix)->download(ix->stream, static_cast<const char*>(dev), static_cast<char*>(user), bytes);
     }
     PCC_HIP(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, ix->stream));
     return PCC_OK;
@@ -256,8 +281,7 @@ static int small_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, boo
     PCC_TRY(ix->host_a.reserve((nq + 2 * nblk) * sizeof(int32_t)));  // (+ per workgroup: tied queries, indices the replay changed)
     PCC_TRY(ix->host_b.reserve(nq * sizeof(float)));
     if (flann) PCC_TRY(ix->tie_buf.reserve(nq + 64));  // (a tie flag per query)
-    if (!ix->pipe) ix->pipe = new HostPipe();
-    PCC_TRY(ix->pipe->init());
+    PCC_TRY(host_pipe(ix)->init());
     PCC_HIP(hipEventSynchronize(ix->pipe->ev[1]));  // (whoever read the query buffer last has finished)
     memcpy(ix->pipe->buf[1].p, q, (nq - 1) * stride + 12);
     ix->q_cells_n = 0;
@@ -309,7 +333,7 @@ static int unpack_pinned(pcc_index* ix, size_t nq, bool want_idx, bool want_d2, 
     PCC_TRY(ix->host_b.reserve(nq * sizeof(float)));
     PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, want_idx ? ix->host_a.as<int32_t>() : nullptr,
                           want_d2 ? ix->host_b.as<float>() : nullptr, fb_mirror ? &ix->words()->fb_count : nullptr,
-                          fb_mirror ? &ix->pinned->fb_mirror : nullptr));
+                          fb_mirror ? &ix->pinned()->fb_mirror : nullptr));
     ev_mark(ix, EV_CALL1);
     PCC_HIP(hipStreamSynchronize(ix->stream));
     return PCC_OK;
@@ -412,7 +436,7 @@ struct PrepOverlap {
                (nq >= min_queries || ix->opt.overlap_prep == 2);  // (2: whatever the size -- tests, fuzz)
     }
     explicit PrepOverlap(pcc_index* i) : ix(i) {}
-    void swap_scratch() {
+    void swap_scratch() {  // (std::swap moves: the two owners exchange their blocks, nothing is copied or freed)
         std::swap(ix->scratch_a, ix->side.a);
         std::swap(ix->scratch_b, ix->side.b);
         std::swap(ix->scratch_c, ix->side.c);
@@ -463,20 +487,37 @@ int make_handle(int device, int engine, pcc_index** out) {
     if (!g.ok) { set_error("hipSetDevice(%d) failed", device); return fail(PCC_ERR_DEVICE); }
     if (hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking) != hipSuccess) { set_error("hipStreamCreate failed"); return fail(PCC_ERR_DEVICE); }
     ix->stream = ix->own_stream;
-    if (hipHostMalloc((void**)&ix->pinned, sizeof(PinnedWords), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
+    if (ix->pinned_buf.reserve(sizeof(PinnedWords)) != PCC_OK) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
     if ((st = ix->words_buf.reserve(sizeof(DevWords))) != PCC_OK) return fail(st);
     if (hipMemset(ix->words_buf.p, 0, sizeof(DevWords)) != hipSuccess) { set_error("hipMemset failed"); return fail(PCC_ERR_DEVICE); }  // (the ticket words start at 0)
     if ((st = ix->blk_stats.reserve(PACK_MAX_BLOCKS * 8 * sizeof(float))) != PCC_OK) return fail(st);
     ix->engine_requested = engine;
     ix->engine = engine;
-    memset(ix->pinned, 0, sizeof(PinnedWords));
-    if (hipHostMalloc((void**)&ix->h_grid, sizeof(GridDev), hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
-    memset(ix->h_grid, 0, sizeof(GridDev));
+    memset(ix->pinned(), 0, sizeof(PinnedWords));
+    if (ix->h_grid_buf.reserve(sizeof(GridDev)) != PCC_OK) { set_error("hipHostMalloc failed"); return fail(PCC_ERR_DEVICE); }
+    memset(ix->h_grid(), 0, sizeof(GridDev));
     *out = ix;
     return PCC_OK;
 }
 
 }  // namespace pcc
+
+// The order of a handle's end (pcc_index_destroy has selected its device and waited for its stream):
+pcc_index::~pcc_index() {
+    // 1. what the features keep: their work handles wait on their own streams, and go before this handle's streams and events
+    for (auto& s : scratch) s.reset();
+    pipe.reset();
+    // 2. the streams and events
+    for (int sl = 0; sl < PCC_EV_SLOTS; ++sl)
+        for (int k = 0; k < PCC_EV_KINDS; ++k)
+            if (ev[sl][k]) (void)hipEventDestroy(ev[sl][k]);
+    if (edge_ev) (void)hipEventDestroy(edge_ev);
+    if (params_ev) (void)hipEventDestroy(params_ev);
+    if (side_ev) (void)hipEventDestroy(side_ev);
+    if (side_stream) { (void)hipStreamSynchronize(side_stream); (void)hipStreamDestroy(side_stream); }
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    // 3. the handle's own buffers: every DevBuf and HostBuf member frees itself behind this body
+}
 
 using namespace pcc;
 extern "C" {
@@ -496,37 +537,6 @@ int pcc_index_destroy(pcc_index* ix) {
     if (!ix) return PCC_OK;
     DeviceGuard g(ix->device);
     if (ix->stream) (void)hipStreamSynchronize(ix->stream);
-    DevBuf* bufs[] = {&ix->refs, &ix->cell_refs, &ix->cell_start, &ix->q_raw, &ix->q_packed, &ix->out_packed,
-                      &ix->out_idx, &ix->out_d2, &ix->scratch_a, &ix->scratch_b, &ix->scratch_c, &ix->scratch_d, &ix->scratch_e, &ix->scratch_f, &ix->scratch_g,
-                      &ix->words_buf, &ix->blk_stats, &ix->icp_src, &ix->icp_state, &ix->d_grid, &ix->seeds, &ix->vox_a, &ix->vox_b, &ix->vox_c, &ix->tie_buf, &ix->knn_fb, &ix->occ, &ix->self_rows, &ix->flann_nodes, &ix->flann_leaf, &ix->mp_a, &ix->mp_b, &ix->mp_c, &ix->rows_idx, &ix->rows_d2, &ix->scan_flags, &ix->q_cells,
-                      &ix->side.a, &ix->side.b, &ix->side.c, &ix->side.e, &ix->side.mp_a, &ix->side.mp_b, &ix->side.mp_c, &ix->side.scan_flags};
-    for (DevBuf* b : bufs) b->release();
-    for (int sl = 0; sl < PCC_EV_SLOTS; ++sl)
-        for (int k = 0; k < PCC_EV_KINDS; ++k)
-            if (ix->ev[sl][k]) (void)hipEventDestroy(ix->ev[sl][k]);
-    ix->host_a.release();
-    ix->host_b.release();
-    ix->host_c.release();
-    if (ix->pipe) { ix->pipe->release(); delete ix->pipe; ix->pipe = nullptr; }
-    match_batch_release(ix);
-    rift_batch_release(ix);
-    sift_batch_release(ix);
-    cluster_desc_release(ix);
-    rgb_batch_release(ix);
-    match_colour_release(ix);
-    change_release(ix);
-    ground_release(ix);
-    segment_release(ix);
-    rift_release(ix);
-    fpfh_release(ix);
-    sift_release(ix);
-    if (ix->pinned) (void)hipHostFree(ix->pinned);
-    if (ix->h_grid) (void)hipHostFree(ix->h_grid);
-    if (ix->edge_ev) (void)hipEventDestroy(ix->edge_ev);
-    if (ix->params_ev) (void)hipEventDestroy(ix->params_ev);
-    if (ix->side_ev) (void)hipEventDestroy(ix->side_ev);
-    if (ix->side_stream) { (void)hipStreamSynchronize(ix->side_stream); (void)hipStreamDestroy(ix->side_stream); }
-    if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
     delete ix;
     return PCC_OK;
 }
@@ -764,6 +774,12 @@ int pcc_debug_fail_alloc(int nth) {
     g_fail_alloc.store(nth > 0 ? nth : 0);
     return PCC_OK;
 }
+int pcc_debug_live_buffers(uint64_t live[2]) {
+    if (!live) { set_error("null argument"); return PCC_ERR_INVALID; }
+    live[0] = g_live_dev.load(std::memory_order_relaxed);
+    live[1] = g_live_pinned.load(std::memory_order_relaxed);
+    return PCC_OK;
+}
 int pcc_counts_pairs(void) {
 #ifdef PCC_COUNT_PAIRS
     return 1;
@@ -784,7 +800,7 @@ int pcc_index_stats(const pcc_index* cix, uint64_t stats[8]) {
     if (ix->stats_pending) {
         PCC_HIP(hipStreamSynchronize(ix->stream));
         ix->stats_pending = false;
-        ix->stats[1] = ix->pinned->fb_mirror;
+        ix->stats[1] = ix->pinned()->fb_mirror;
         ix->stats[0] = ix->last_nq - ix->stats[1];
     }
     if (ix->ties_pending) {  // the sharded counters of the last search in FLANN mode
@@ -844,7 +860,7 @@ int pcc_nn1(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, int
             PCC_TRY(ri.stage(idx, nq, mem, ix->out_idx));
             PCC_TRY(rd.stage(d2, nq, mem, ix->out_d2));
             PCC_TRY(launch_unpack(ix->stream, ix->out_packed.as<unsigned long long>(), nullptr, nq, ri.dev, rd.dev,
-                                  &ix->words()->fb_count, &ix->pinned->fb_mirror));
+                                  &ix->words()->fb_count, &ix->pinned()->fb_mirror));
             ev_mark(ix, EV_CALL1);
             return finish(ix, mem, ri, rd);
         }

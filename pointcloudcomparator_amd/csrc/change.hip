@@ -44,7 +44,8 @@ struct ChangeDev {
     long long mn[3];                // lo - 2^31: the origin of the keys
 };
 
-struct ChangeScratch {
+struct ChangeScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_CHANGE;
     DevBuf a_raw, b_raw;            // the caller's clouds, staged (host memory)
     DevBuf keys, vals;              // the table: u64 key and u32 (A mark | B count) per slot
     DevBuf flags, scan_tmp;         // uint32[n_b + 1]: report flags, then their exclusive scan
@@ -269,22 +270,11 @@ unsigned int chg_blocks(size_t n, size_t per_block, unsigned int cap) {
 
 }  // namespace
 
-void change_release(pcc_index* ix) {
-    if (!ix->change) return;
-    ChangeScratch* c = ix->change;
-    DevBuf* bufs[] = {&c->a_raw, &c->b_raw, &c->keys, &c->vals, &c->flags, &c->scan_tmp, &c->out_index, &c->out_records, &c->dev};
-    for (DevBuf* b : bufs) b->release();
-    c->host.release();
-    delete c;
-    ix->change = nullptr;
-}
-
 // behind the argument checks: n_a, n_b in [1, 2^31)
 static int change_detection(pcc_index* ix, const void* a, size_t n_a, size_t a_stride, const void* b, size_t n_b, size_t b_stride, int mem,
                             double res, int min_points, int32_t* out_index, void* out_records, size_t* n_out) {
     hipStream_t s = ix->stream;
-    if (!ix->change) ix->change = new ChangeScratch();
-    ChangeScratch* c = ix->change;
+    ChangeScratch* c = scratch<ChangeScratch>(ix);
     // a strided host view may end with its last row's x, y, z; records travel whole
     const char *da = nullptr, *db = nullptr;
     PCC_TRY(stage_in(ix, static_cast<const char*>(a), (n_a - 1) * a_stride + 12, mem, c->a_raw, &da));

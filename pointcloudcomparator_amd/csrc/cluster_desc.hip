@@ -188,24 +188,11 @@ k_cd_remap(const int32_t* __restrict__ src, unsigned int m, int32_t* __restrict_
 
 unsigned int blocks_for(size_t n) { return (unsigned int)std::min<size_t>((n + 255) / 256, 2048); }
 
-// `buf` with room for want_bytes, the first have_bytes kept (a wait, when it has to grow)
-int grow_keep(pcc_index* ix, DevBuf& buf, size_t have_bytes, size_t want_bytes) {
-    if (buf.p && want_bytes <= buf.cap) return PCC_OK;
-    DevBuf grown;
-    PCC_TRY(grown.reserve(std::max(want_bytes, 2 * buf.cap)));
-    if (have_bytes && buf.p) {
-        PCC_HIP(hipMemcpyAsync(grown.p, buf.p, have_bytes, hipMemcpyDeviceToDevice, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    buf.release();
-    buf = grown;
-    return PCC_OK;
-}
-
 }  // namespace
 
 // (up: octaves + tables + records; up2: the keypoint order, then the RIFT tables; down: hits per cluster, centroids; dev: what `up` holds)
 struct ClusterDescScratch : BatchStaging {
+    static constexpr ScratchSlot slot = SCRATCH_CLUSTER_DESC;
     HostBuf up2;
     DevBuf korder, tab;           // what up2 holds on the device: kbase + keypoint order; GridDev + bases + items + dst
     DevBuf snap;                  // int32 per keypoint: the rounds' (round-major), then the work handle's cluster by cluster
@@ -213,16 +200,7 @@ struct ClusterDescScratch : BatchStaging {
     DevBuf cat_pts, cat_rgb, cat_src;  // every cluster's RIFT cloud: float4, colour word, cluster-local source index
     DevBuf lhist, lindex;         // the rows of one cloud off the batch route
     DevBuf cent;                  // float[n_clusters][3]
-    ~ClusterDescScratch() {
-        up2.release();
-        for (DevBuf* d : {&korder, &tab, &snap, &flags, &scan_tmp, &hits, &cat_pts, &cat_rgb, &cat_src, &lhist, &lindex, &cent}) d->release();
-    }
 };
-
-void cluster_desc_release(pcc_index* ix) {
-    delete ix->cluster_desc;
-    ix->cluster_desc = nullptr;
-}
 
 namespace {
 
@@ -251,10 +229,7 @@ int cluster_descriptors(pcc_index* ix, const ClusterDescArgs& a) {
     hipStream_t s = ix->stream;
     const size_t n_clusters = a.n_clusters;
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
-    if (!ix->cluster_desc) ix->cluster_desc = new ClusterDescScratch();
-    sift_batch_scratch(ix);
-    rift_batch_scratch(ix);
-    ClusterDescScratch* sc = ix->cluster_desc;
+    ClusterDescScratch* sc = scratch<ClusterDescScratch>(ix);
     const size_t sift_max = (size_t)ix->opt.sift_batch_brute_max, rift_max = (size_t)ix->opt.rift_batch_brute_max;
     const ClusterDescRoutes routes = cd_routes(a.offsets, n_clusters, a.sift_above, sift_max);
     const size_t total = routes.stage_base[n_clusters], off0 = a.offsets[0];
@@ -347,20 +322,19 @@ int cluster_descriptors(pcc_index* ix, const ClusterDescArgs& a) {
     size_t m_all = m_batch;
     for (size_t c = 0; c < n_clusters; ++c) {
         if (routes.route[c] != CD_SIFT_WORK) continue;
-        if (!lease.w) PCC_TRY(lease.take(ix, &sc->work, true));
+        if (!lease.w) PCC_TRY(lease.take(ix, sc->work, true));
         pcc_index* w = lease.w;
         const size_t n = routes.n[c];
         const unsigned char* rp = reinterpret_cast<const unsigned char*>(d_rec + routes.stage_base[c]);
         work_points += n;
-        if (!w->sift) w->sift = new SiftScratch();
         entered(w);
         size_t found = 0;
         PCC_TRY(sift_keypoints(w, rp, n, sizeof(SiftRec), rp + 16, sizeof(SiftRec), a.min_scale, a.nr_octaves, a.nr_scales_per_octave, a.min_contrast,
                                &found));
         if (!found) continue;
-        PCC_TRY(grow_keep(ix, sc->snap, m_all * sizeof(int32_t), (m_all + found) * sizeof(int32_t)));
+        PCC_TRY(sc->snap.grow_keep(ix->stream, m_all * sizeof(int32_t), (m_all + found) * sizeof(int32_t)));
         PCC_TRY(pcc_index_set_input(w, rp, n, sizeof(SiftRec), 3, PCC_MEM_DEVICE));
-        PCC_TRY(pcc_first_within(w, w->sift->kp.p, found, sizeof(float4), PCC_MEM_DEVICE, a.snap_radius, sc->snap.as<int32_t>() + m_all));
+        PCC_TRY(pcc_first_within(w, scratch<SiftScratch>(w)->kp.p, found, sizeof(float4), PCC_MEM_DEVICE, a.snap_radius, sc->snap.as<int32_t>() + m_all));
         work_counts[c] = (uint32_t)found;
         m_all += found;
     }
@@ -449,7 +423,7 @@ int cluster_descriptors(pcc_index* ix, const ClusterDescArgs& a) {
             const unsigned int* d_slice = nullptr;
             PCC_TRY(rift_batch_run(ix, in, a.normal_radius, a.gradient_radius, a.rift_radius, &d_slice));
             hipLaunchKernelGGL(k_cd_compose, dim3(blocks_for(batch_total)), dim3(256), 0, s, d_slice, in.d_bases, nc,
-                               sc->cat_src.as<int32_t>(), ix->rift->out_index.as<int32_t>());
+                               sc->cat_src.as<int32_t>(), scratch<RiftScratch>(ix)->out_index.as<int32_t>());
             PCC_HIP(hipGetLastError());
             PCC_TRY(rift_batch_slices(ix, n_clusters, &h_slice));
         }
@@ -462,7 +436,7 @@ int cluster_descriptors(pcc_index* ix, const ClusterDescArgs& a) {
     std::vector<std::vector<int32_t>> single_index(n_clusters);
     for (size_t c = 0; c < n_clusters; ++c) {
         if (q_n[c] <= rift_max) continue;
-        if (!lease.w) PCC_TRY(lease.take(ix, &sc->work, true));
+        if (!lease.w) PCC_TRY(lease.take(ix, sc->work, true));
         pcc_index* w = lease.w;
         const size_t n = q_n[c], at = clouds.dst[c];
         PCC_TRY(pcc_index_set_input(w, sc->cat_pts.as<float4>() + at, n, sizeof(float4), 3, PCC_MEM_DEVICE));

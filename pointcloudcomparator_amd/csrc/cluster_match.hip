@@ -127,8 +127,7 @@ struct ClusterMatchArgs {
 
 // the searches of the pairs in state CM_SEARCHED: correspondences[e] = 1 + the count of pair e (e = 3 * i + k)
 int cluster_match_search(pcc_index* ix, const ClusterMatchArgs& a, const ClusterMatchLayout& L, int dp, uint32_t* correspondences) {
-    if (!ix->mb) ix->mb = new MatchBatchScratch();
-    MatchBatchScratch* mb = ix->mb;
+    MatchBatchScratch* mb = scratch<MatchBatchScratch>(ix);
     hipStream_t s = ix->stream;
     const bool host = a.mem == PCC_MEM_HOST;
     const size_t n_items = L.items.size(), n_pairs = L.pairs.size(), n_clouds = L.clouds.size(), n_out = 3 * a.n_clusters1;

@@ -70,6 +70,9 @@ struct pcc_comm {
     ncclComm_t nccl = nullptr;
     int rank = 0, world = 1, device = 0;
     pcc::DevBuf word;  // a few device words for scalar exchanges (cloud size, kept counts)
+    ~pcc_comm() {      // (under pcc_comm_destroy's device guard; `word` frees itself behind it)
+        if (nccl && pcc::rccl()) (void)pcc::rccl()->CommDestroy(nccl);
+    }
 };
 
 namespace pcc {
@@ -134,8 +137,8 @@ int pcc_comm_create_rank(const void* id, size_t bytes, int world, int rank, int 
     c->world = world;
     c->device = device;
     ncclResult_t r = rccl()->CommInitRank(&c->nccl, world, u, rank);
-    if (r != ncclSuccess) { set_error("ncclCommInitRank failed: %s", rccl()->GetErrorString(r)); delete c; return PCC_ERR_DEVICE; }
-    if (c->word.reserve(256) != PCC_OK) { rccl()->CommDestroy(c->nccl); delete c; return PCC_ERR_NOMEM; }
+    if (r != ncclSuccess) { set_error("ncclCommInitRank failed: %s", rccl()->GetErrorString(r)); c->nccl = nullptr; delete c; return PCC_ERR_DEVICE; }
+    if (c->word.reserve(256) != PCC_OK) { delete c; return PCC_ERR_NOMEM; }
     *out = c;
     return PCC_OK;
 }
@@ -175,8 +178,6 @@ int pcc_comm_create_local(const int* devices, int count, pcc_comm** out) {
 int pcc_comm_destroy(pcc_comm* c) {
     if (!c) return PCC_OK;
     DeviceGuard g(c->device);
-    c->word.release();
-    if (c->nccl && rccl()) (void)rccl()->CommDestroy(c->nccl);
     delete c;
     return PCC_OK;
 }

@@ -32,7 +32,7 @@ struct SiftBatchInput {
     const int64_t* d_bases64_0 = nullptr;
     const SiftRec* d_rec0 = nullptr;
 };
-// What the rounds leave behind: the keypoints of every round on the device (ix->sift->kp, round-major) and, on the host, how
+// What the rounds leave behind: the keypoints of every round on the device (SiftScratch::kp, round-major) and, on the host, how
 // many each round found in each cloud.
 struct SiftBatchResult {
     std::vector<std::vector<uint32_t>> counts;  // [round][cloud]
@@ -42,9 +42,7 @@ struct SiftBatchResult {
     size_t total = 0;                           // keypoints on the device
     unsigned int rounds = 0;
 };
-// makes ix->sift_batch and ix->sift when the handle has none yet
-void sift_batch_scratch(pcc_index* ix);
-// the octave rounds over a staged concatenation (the scratch made by the caller)
+// the octave rounds over a staged concatenation
 int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const SiftBatchInput& in, float min_scale, SiftBatchResult* res);
 // d_snap[k] for the res.total keypoints of the rounds, in their round-major order: k_sb_snap over the first concatenation
 int sift_batch_snap(pcc_index* ix, const SiftBatchResult& res, size_t n_clouds, double snap_radius, int32_t* d_snap);
@@ -61,14 +59,11 @@ struct RiftBatchInput {
     const float4* d_pts = nullptr;
     const unsigned char* d_rgb = nullptr;
 };
-// makes ix->rift_batch and ix->rift when the handle has none yet
-void rift_batch_scratch(pcc_index* ix);
-// The stages of the single call once over the concatenation, then k_rift_batch_finish: the kept rows in ix->rift->out_hist /
-// out_index (device, indices local to their cloud), the slice bounds (n_clouds + 1) in *d_slice (device).  total > 0; the
-// scratch made by the caller.
+// The stages of the single call once over the concatenation, then k_rift_batch_finish: the kept rows in RiftScratch::out_hist /
+// out_index (device, indices local to their cloud), the slice bounds (n_clouds + 1) in *d_slice (device).  total > 0.
 int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius, double gradient_radius, double rift_radius,
                    const unsigned int** d_slice);
-// the slice bounds of the run on the host (one wait); valid until ix->rift_batch->down is used again
+// the slice bounds of the run on the host (one wait); valid until the batch scratch's `down` is used again
 int rift_batch_slices(pcc_index* ix, size_t n_clouds, const unsigned int** h_slice);
 // the first `kept` rows of the run into host arrays (one wait)
 int rift_batch_fetch(pcc_index* ix, size_t kept, float* out_hist, int32_t* out_index);

@@ -133,13 +133,13 @@ inline int check_cluster_offsets(std::initializer_list<ClusterOffsets> scenes, c
 }
 
 // ---- the batch calls ------------------------------------------------------------------------------------------
-// A work handle for a scope: made in *slot at the first use, its launches join the caller's queue (under the caller's options
+// A work handle for a scope: made in `slot` at the first use, its launches join the caller's queue (under the caller's options
 // when with_options), and it has its own stream back at the end.
 struct WorkLease {
     pcc_index* w = nullptr;
-    int take(pcc_index* ix, pcc_index** slot, bool with_options) {
-        if (!*slot) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, slot));
-        w = *slot;
+    int take(pcc_index* ix, WorkHandle& slot, bool with_options) {
+        if (!slot.ix) PCC_TRY(make_handle(ix->device, PCC_ENGINE_GRID, &slot.ix));
+        w = slot.ix;
         w->stream = ix->stream;
         if (with_options) w->opt = ix->opt;
         return PCC_OK;

@@ -19,6 +19,16 @@ namespace pcc {
 
 namespace {
 
+// What pcc_fpfh_descriptors keeps between its stages.  Buffers of their own, as RiftScratch's: the radius searches in between
+// use the handle's shared scratch.
+struct FpfhScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_FPFH;
+    DevBuf normals;              // float4[n] plane fit
+    DevBuf spfh;                 // float[n][33]: the SPFH signature of every point of cloud2 (the others are never read)
+    DevBuf flags, pos, scan_tmp; // uint32[n]: 1 for the points of cloud2; uint32[n + 1]: their exclusive scan, pos[n] = the count
+    DevBuf out_hist, out_index;  // results staged for a caller in host memory
+};
+
 // flags[i] = 1 for the points of cloud2 (every component of the normal finite); pos = the same, to be scanned
 __global__ void __launch_bounds__(256)
 k_fpfh_flags(const float4* __restrict__ normals, unsigned int n, unsigned int* __restrict__ flags, unsigned int* __restrict__ pos) {
@@ -219,11 +229,11 @@ int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, 
     return PCC_OK;
 }
 
-// the stages over the indexed cloud of ix (ix->fpfh made by the caller): out_hist[n * 33], out_index[n] on the device; *n_out on
+// the stages over the indexed cloud of ix: out_hist[n * 33], out_index[n] on the device; *n_out on
 // the host.  Waits: the totals of the CSRs and, at the end, the count.
 int fpfh_descriptors(pcc_index* ix, double normal_radius, double fpfh_radius, float* out_hist, int32_t* out_index, size_t* n_out) {
     hipStream_t s = ix->stream;
-    FpfhScratch* r = ix->fpfh;
+    FpfhScratch* r = scratch<FpfhScratch>(ix);
     const size_t n = ix->n_orig;
     const unsigned int un = (unsigned int)n;
     const float origin[3] = {0.f, 0.f, 0.f};
@@ -275,15 +285,6 @@ int fpfh_descriptors(pcc_index* ix, double normal_radius, double fpfh_radius, fl
 
 }  // namespace
 
-void fpfh_release(pcc_index* ix) {
-    if (!ix->fpfh) return;
-    FpfhScratch* r = ix->fpfh;
-    DevBuf* bufs[] = {&r->normals, &r->spfh, &r->flags, &r->pos, &r->scan_tmp, &r->out_hist, &r->out_index};
-    for (DevBuf* b : bufs) b->release();
-    delete r;
-    ix->fpfh = nullptr;
-}
-
 }  // namespace pcc
 
 using namespace pcc;
@@ -299,11 +300,11 @@ int pcc_fpfh_descriptors(pcc_index* ix, int mem, double normal_radius, double fp
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     const size_t n = ix->n_orig;
-    if (!ix->fpfh) ix->fpfh = new FpfhScratch();
+    FpfhScratch* r = scratch<FpfhScratch>(ix);
     Out<float> rh;
     Out<int32_t> ri;
-    PCC_TRY(rh.stage(out_hist, n * FPFH_BINS, mem, ix->fpfh->out_hist));
-    PCC_TRY(ri.stage(out_index, n, mem, ix->fpfh->out_index));
+    PCC_TRY(rh.stage(out_hist, n * FPFH_BINS, mem, r->out_hist));
+    PCC_TRY(ri.stage(out_index, n, mem, r->out_index));
     size_t kept = 0;
     PCC_TRY(fpfh_descriptors(ix, normal_radius, fpfh_radius, rh.dev, ri.dev, &kept));
     *n_out = kept;

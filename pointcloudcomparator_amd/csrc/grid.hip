@@ -50,7 +50,7 @@ int grid_params(pcc_index* ix, const float* blk_stats_dev, int n_blocks) {
     ix->nc_cap = grid_nc_cap(ix->n_orig, ix->opt.grid_ppc);
     // (trimming needs enough rows to tell an outlier from the scene: 128 pack workgroups = 64k points)
     hipLaunchKernelGGL(k_grid_params, dim3(1), dim3(1024), 0, ix->stream, blk_stats_dev, n_blocks, (unsigned int)ix->n_orig,
-                       ppc, ix->nc_cap, n_blocks >= 128 ? trim : 0, ix->opt.grid_axes, ix->d_grid.as<GridDev>(), ix->h_grid);
+                       ppc, ix->nc_cap, n_blocks >= 128 ? trim : 0, ix->opt.grid_axes, ix->d_grid.as<GridDev>(), ix->h_grid());
     PCC_HIP(hipGetLastError());
     ix->info_pending = true;
     return PCC_OK;
@@ -61,7 +61,7 @@ int grid_params_fused(pcc_index* ix, PackGrid* pg) {
     PCC_TRY(ix->d_grid.reserve(sizeof(GridDev)));
     ix->nc_cap = grid_nc_cap(ix->n_orig, ix->opt.grid_ppc);
     *pg = PackGrid{&ix->words()->grid_ticket, (float)ix->opt.grid_ppc, ix->nc_cap, ix->opt.grid_trim, ix->opt.grid_axes,
-                   ix->d_grid.as<GridDev>(), ix->h_grid};
+                   ix->d_grid.as<GridDev>(), ix->h_grid()};
     ix->info_pending = true;
     return PCC_OK;
 }
@@ -70,9 +70,9 @@ int sync_info(pcc_index* ix) {
     if (!ix->info_pending) return PCC_OK;
     PCC_HIP(hipStreamSynchronize(ix->stream));
     ix->info_pending = false;
-    ix->grid = ix->h_grid->g;
-    ix->n_valid = ix->h_grid->n_valid;
-    for (int a = 0; a < 3; ++a) { ix->bbox_lo[a] = ix->h_grid->lo[a]; ix->bbox_hi[a] = ix->h_grid->hi[a]; }
+    ix->grid = ix->h_grid()->g;
+    ix->n_valid = ix->h_grid()->n_valid;
+    for (int a = 0; a < 3; ++a) { ix->bbox_lo[a] = ix->h_grid()->lo[a]; ix->bbox_hi[a] = ix->h_grid()->hi[a]; }
     ix->stats[2] = ix->n_valid;
     ix->stats[3] = (uint64_t)ix->grid.ncells;
     return PCC_OK;
@@ -1083,7 +1083,7 @@ int grid_nn1(pcc_index* ix, const float4* q, size_t nq, unsigned long long* out,
     // steers the choice), take the seed + ball-walk route; otherwise go straight to the exhaustive
     // kernel, which costs one launch when the list is empty
     ev_mark(ix, EV_FB0);
-    const unsigned int seen = *static_cast<volatile unsigned int*>(&ix->pinned->fb_mirror);
+    const unsigned int seen = *static_cast<volatile unsigned int*>(&ix->pinned()->fb_mirror);
     if (seen > ix->last_fallback_seen) ix->last_fallback_seen = seen;
     const int far_mode = ix->opt.far_mode;  // -1 auto, 0 off, 1 on
     // (ICP passes always take it: their loop may be enqueued as a whole before the first count comes back)

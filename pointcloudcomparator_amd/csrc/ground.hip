@@ -26,7 +26,8 @@ struct GroundState {         // device words of the pass in flight
     GroundLattice lat;
 };
 
-struct GroundScratch {
+struct GroundScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_GROUND;
     DevBuf xy[2], z[2], idx[2];  // the current points of the filter: float2[m], float[m], their original indices; ping-pong
     DevBuf cell;                 // int32[m]: the lattice cell of every point, -1 for a non-finite one
     DevBuf sxy, scell, skey;     // float2[m], uint32[m], uint32[m]: xy, the cells and the value keys in cell order
@@ -36,17 +37,7 @@ struct GroundScratch {
     DevBuf state;                // GroundState
     DevBuf cloud, out_rec;       // pcc_ground_segmentation: the filtered cloud; the gathered records of a caller in host memory
     DevBuf out_z, out_index;     // results staged for a caller in host memory
-    ~GroundScratch() {
-        DevBuf* bufs[] = {&xy[0], &xy[1], &z[0], &z[1], &idx[0], &idx[1], &cell, &sxy, &scell, &skey, &eroded, &opened, &keep, &tab, &start, &state,
-                          &cloud, &out_rec, &out_z, &out_index};
-        for (DevBuf* b : bufs) b->release();
-    }
 };
-
-void ground_release(pcc_index* ix) {
-    delete ix->ground;
-    ix->ground = nullptr;
-}
 
 namespace {
 
@@ -269,11 +260,6 @@ k_ground_mark(const int32_t* __restrict__ ground, size_t count, int32_t* __restr
     }
 }
 
-void ground_scratch(pcc_index* ix) {
-    if (!ix->ground) ix->ground = new GroundScratch();
-    segment_scratch(ix);
-}
-
 #define GROUND_LAUNCH(kernel, blocks, ...)                                                   \
     do {                                                                                     \
         hipLaunchKernelGGL(kernel, dim3((unsigned int)(blocks)), dim3(256), 0, s, __VA_ARGS__); \
@@ -281,7 +267,7 @@ void ground_scratch(pcc_index* ix) {
     } while (0)
 
 // What the passes of one window share: the lattice of `window` over the m points (xy, z), their cells, the order by cell and
-// (in ix->segment), xy and the cells in cell order, the cell starts.  Everything enqueued.  The tables hold cap + 1 words, cap the
+// (in SegmentScratch), xy and the cells in cell order, the cell starts.  Everything enqueued.  The tables hold cap + 1 words, cap the
 // most cells a lattice over m points may have (ground_cell_cap: known to the host from m alone); the partition takes two 8-bit
 // digits of the cell below 2^16 cells and three above.
 struct GroundPass {
@@ -291,7 +277,7 @@ struct GroundPass {
 };
 int ground_pass_setup(pcc_index* ix, const float2* xy, const float* z, size_t m, float window, GroundPass* P) {
     hipStream_t s = ix->stream;
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     const unsigned int cap = (unsigned int)ground_cell_cap(m);
     P->cap = cap;
     PCC_TRY(g->cell.reserve(m * sizeof(int32_t)));
@@ -319,7 +305,7 @@ int ground_pass_setup(pcc_index* ix, const float2* xy, const float* z, size_t m,
 // out = min (maximum: max) of vals over every point's box
 int ground_pass(pcc_index* ix, const GroundPass& P, const float* vals, size_t m, bool maximum, float* out) {
     hipStream_t s = ix->stream;
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     const unsigned int flip = maximum ? 0xffffffffu : 0u;
     unsigned int* tab = g->tab.as<unsigned int>();
     PCC_HIP(hipMemsetAsync(tab, 0xff, ((size_t)P.cap + 1) * sizeof(unsigned int), s));
@@ -332,7 +318,7 @@ int ground_pass(pcc_index* ix, const GroundPass& P, const float* vals, size_t m,
 }
 // the operator `op` over (xy, z)[m] with the window's passes set up -> out[m]
 int ground_operator(pcc_index* ix, const GroundPass& P, const float* z, size_t m, int op, float* out) {
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     if (op == PCC_MORPH_ERODE || op == PCC_MORPH_DILATE) return ground_pass(ix, P, z, m, op == PCC_MORPH_DILATE, out);
     PCC_TRY(g->eroded.reserve(m * sizeof(float)));
     PCC_TRY(ground_pass(ix, P, z, m, op == PCC_MORPH_CLOSE, g->eroded.as<float>()));
@@ -351,7 +337,7 @@ int ground_stage(pcc_index* ix, const void* pts, size_t n, size_t stride, int me
 
 int ground_load(pcc_index* ix, const void* dpts, size_t n, size_t stride) {
     hipStream_t s = ix->stream;
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     PCC_TRY(g->xy[0].reserve(n * sizeof(float2)));
     PCC_TRY(g->z[0].reserve(n * sizeof(float)));
     PCC_TRY(g->idx[0].reserve(n * sizeof(int32_t)));
@@ -361,11 +347,11 @@ int ground_load(pcc_index* ix, const void* dpts, size_t n, size_t stride) {
 }
 
 // The second loop of ProgressiveMorphologicalFilter::extract over a cloud on the device (n > 0): *ground (device, in
-// ix->ground) are the original indices of the *n_ground points that remain, ascending.  One wait per window.
+// GroundScratch) are the original indices of the *n_ground points that remain, ascending.  One wait per window.
 int pmf_run(pcc_index* ix, const void* dpts, size_t n, size_t stride, const float* windows, const float* thresholds, size_t n_windows,
             const int32_t** ground, size_t* n_ground, size_t* pass_sizes, size_t max_passes) {
     hipStream_t s = ix->stream;
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     PCC_TRY(ground_load(ix, dpts, n, stride));
     PCC_TRY(g->xy[1].reserve(n * sizeof(float2)));
     PCC_TRY(g->z[1].reserve(n * sizeof(float)));
@@ -447,8 +433,7 @@ int pcc_morphological_operator(pcc_index* ix, const void* pts, size_t n, size_t 
     if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    ground_scratch(ix);
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
     const void* src = nullptr;
     PCC_TRY(ground_stage(ix, pts, n, stride, mem, &src));
     PCC_TRY(ground_load(ix, src, n, stride));
@@ -477,7 +462,6 @@ int pcc_progressive_morphological_filter(pcc_index* ix, const void* pts, size_t 
     if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    ground_scratch(ix);
     const void* src = nullptr;
     PCC_TRY(ground_stage(ix, pts, n, stride, mem, &src));
     const int32_t* ground = nullptr;
@@ -511,8 +495,7 @@ int pcc_ground_segmentation(pcc_index* ix, const void* pts, size_t n, size_t str
     hipStream_t s = ix->stream;
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    ground_scratch(ix);
-    GroundScratch* g = ix->ground;
+    GroundScratch* g = scratch<GroundScratch>(ix);
 
     // 1. the voxel grid into a zeroed buffer of this call's own (as pcc_region_growing_segmentation)
     const void* src = nullptr;

@@ -113,11 +113,12 @@ struct HostPipe {
         }
         return PCC_OK;
     }
-    void release() {
-        for (int b = 0; b < 2; ++b) {
-            buf[b].release();
-            if (ev[b]) { (void)hipEventDestroy(ev[b]); ev[b] = nullptr; }
-        }
+    HostPipe() = default;
+    HostPipe(const HostPipe&) = delete;
+    HostPipe& operator=(const HostPipe&) = delete;
+    ~HostPipe() {
+        for (int b = 0; b < 2; ++b)
+            if (ev[b]) (void)hipEventDestroy(ev[b]);
     }
 
     // n points of `stride` bytes at `src` (pageable host memory) -> device `dst`, packed to `dst_stride` bytes per point

@@ -225,7 +225,7 @@ static int icp_reduce(pcc_index* ix, size_t n, double sums[17], const double* ce
     int nb = 0;
     PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
                             ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb,
-                            ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr, &ix->pinned->fb_mirror, center));
+                            ix->engine == PCC_ENGINE_GRID ? &ix->words()->fb_count : nullptr, &ix->pinned()->fb_mirror, center));
     std::vector<double> h((size_t)nb * 17);
     PCC_HIP(hipMemcpyAsync(h.data(), ix->scratch_a.p, h.size() * sizeof(double), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipStreamSynchronize(ix->stream));
@@ -424,7 +424,7 @@ int pcc::icp_align_impl(pcc_index* ix, const pcc::IcpHooks* hooks, const void* s
                 const IcpFuse fuse{&ix->words()->icp_ticket, st, max_iter, fixed, fold ? zw : nullptr};
                 PCC_TRY(launch_icp_sums(ix->stream, ix->q_packed.as<float4>(), n, ix->out_packed.as<unsigned long long>(),
                                         ix->refs.as<float4>(), ix->scratch_a.as<double>(), &nb, zw,
-                                        &ix->pinned->fb_mirror, center_dev, fuse_solve ? &fuse : nullptr));
+                                        &ix->pinned()->fb_mirror, center_dev, fuse_solve ? &fuse : nullptr));
                 if (fuse_solve) {
                 } else if (hooks) {  // rows -> 17 sums (workgroup order, as the solver adds them) -> sum over the ranks -> solve
                     PCC_TRY(launch_icp_rows_to_sums(ix->stream, ix->scratch_a.as<double>(), nb, sums_dev));

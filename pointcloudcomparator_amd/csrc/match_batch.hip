@@ -117,14 +117,6 @@ k_match_batch_walk(const MatchTree* __restrict__ trees, const FlannNode* __restr
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-void match_batch_release(pcc_index* ix) {
-    if (!ix->mb) return;
-    MatchBatchScratch* s = ix->mb;
-    s->up.release(); s->down.release(); s->tree_up.release(); s->tree_down.release();
-    s->dev.release(); s->res.release(); s->tree_dev.release(); s->tree_res.release();
-    delete s;
-    ix->mb = nullptr;
-}
 
 // k_pack's record: the first three floats, w = position; non-finite -> (0, 0, 0, -1).  Returns the number of finite records.
 static size_t pack_records(const void* raw, size_t n, size_t stride, float* out) {
@@ -147,8 +139,7 @@ static size_t pack_records(const void* raw, size_t n, size_t stride, float* out)
 int match_knn_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                     const size_t* n2, size_t stride, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
     const bool flann = ix->tie_mode == PCC_TIES_FLANN;
-    if (!ix->mb) ix->mb = new MatchBatchScratch();
-    MatchBatchScratch* mb = ix->mb;
+    MatchBatchScratch* mb = scratch<MatchBatchScratch>(ix);
 
     // ---- the plan: every DISTINCT reference cloud once, every pair's queries, the table of work items (match_plan.hpp) --------
     MatchPlan plan;

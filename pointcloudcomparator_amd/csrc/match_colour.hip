@@ -86,16 +86,11 @@ k_mc_pack(const unsigned char* __restrict__ pts1, const unsigned char* __restric
 
 // (up: bases + items + cloud table, and from host memory the named clusters' records; down: the clouds' first ids + finite counts)
 struct MatchColourScratch : BatchStaging {
+    static constexpr ScratchSlot slot = SCRATCH_MATCH_COLOUR;
     DevBuf cat;                       // the concatenation: float4[total], then uint32[total] colour words
     DevBuf keys;                      // u64[total][K]: the rows
     DevBuf id_bases, finite, labels;  // uint32[n_clouds + 1]; uint32[n_clouds]; int32: the labels of a cluster on the work handle
-    ~MatchColourScratch() { cat.release(); keys.release(); id_bases.release(); finite.release(); labels.release(); }
 };
-
-void match_colour_release(pcc_index* ix) {
-    delete ix->match_colour;
-    ix->match_colour = nullptr;
-}
 
 namespace {
 
@@ -113,8 +108,7 @@ struct McArgs {
 int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan& P, int32_t* count_of_cluster) {
     hipStream_t s = ix->stream;
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
-    if (!ix->match_colour) ix->match_colour = new MatchColourScratch();
-    MatchColourScratch* sc = ix->match_colour;
+    MatchColourScratch* sc = scratch<MatchColourScratch>(ix);
     const size_t n_list = P.clusters.size(), n_clouds = P.batch_n.size(), total = P.n_batch_points, n_items = P.items.size();
     const bool host = a.mem == PCC_MEM_HOST;
     const int K = (int)a.nr_region_neighbours;
@@ -246,7 +240,7 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
 
     // ---- the other clusters: one by one on the work handle, from the device arrays, their labels to device scratch ----------------
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &sc->work, true));
+    PCC_TRY(lease.take(ix, sc->work, true));
     for (size_t e = 0; e < n_list; ++e) {
         const MatchColourCluster& m = P.clusters[e];
         if (m.route != MC_WORK) continue;

@@ -78,8 +78,7 @@ k_match_dims(const MatchItem* __restrict__ items, const float* __restrict__ rec,
 
 int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                          const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
-    if (!ix->mb) ix->mb = new MatchBatchScratch();
-    MatchBatchScratch* mb = ix->mb;
+    MatchBatchScratch* mb = scratch<MatchBatchScratch>(ix);
     const int dp = match_dims_padded(dim);
     MatchDimsPlan plan;
     if (!match_dims_plan(n_pairs, des1, n1, n2, dp, &plan)) { set_error("more than 2^31 records or work items in one batch"); return PCC_ERR_UNSUPPORTED; }

@@ -5,8 +5,10 @@
 #include <stddef.h>
 #include <string.h>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include "pcc_nn.h"
 #include "flann_tree.hpp"
 #include "cloud_batch.hpp"
@@ -40,22 +42,47 @@ void set_error(const char* fmt, ...);
     } while (0)
 
 // ---- device buffer that only grows ------------------------------------------
+// DevBuf and HostBuf OWN their memory: the destructor frees, a move hands the block over and leaves the source
+// empty, nothing copies.  Whatever holds one -- the handle, a feature's scratch -- needs no cleanup code of its own.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int reserve(size_t bytes);  // returns pcc_status
+    // room for `want` bytes with the first `keep` bytes kept (reserve() keeps nothing): grows to max(want, 2 * cap), copies on `s`
+    // and waits for it.  A failure on the way frees the new block and leaves this one as it was.
+    int grow_keep(hipStream_t s, size_t keep, size_t want);
     void release();
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// grow-only pinned host buffer (read-backs that the host then walks: SOR mean distances, ...)
+// grow-only pinned host buffer (read-backs that the host then walks: SOR mean distances, ...); owns its memory as DevBuf does
 struct HostBuf {
     void* p = nullptr;
     size_t cap = 0;
+    HostBuf() = default;
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    HostBuf(HostBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    HostBuf& operator=(HostBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~HostBuf() { release(); }
     int reserve(size_t bytes);
     void release();
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+static_assert(!std::is_copy_constructible<DevBuf>::value && std::is_nothrow_move_constructible<DevBuf>::value, "DevBuf owns its memory");
+static_assert(!std::is_copy_constructible<HostBuf>::value && std::is_nothrow_move_constructible<HostBuf>::value, "HostBuf owns its memory");
 
 // selects `dev` for the scope and restores the caller's device at its end; ok = false when the device could not be selected
 struct DeviceGuard {
@@ -253,7 +280,7 @@ __device__ __forceinline__ void clear_search_counters(unsigned int* __restrict__
 
 constexpr int PACK_MAX_BLOCKS = 1024;  // rows of per-workgroup statistics launch_pack writes at most
 
-// The handle's pinned host words (pcc_index::pinned).  fb_mirror and vox_count are written behind the host's back (by a kernel,
+// The handle's pinned host words (pcc_index::pinned()).  fb_mirror and vox_count are written behind the host's back (by a kernel,
 // by a copy nobody waits for) and read later, so they share no byte with anything else.
 struct PinnedWords {
     alignas(8) unsigned int readback[4];  // read_back()
@@ -267,26 +294,39 @@ static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) 
                   offsetof(PinnedWords, vox_rows) >= offsetof(PinnedWords, vox_count) + 4,
               "PinnedWords: the asynchronously written words overlap");
 
-// rift.hip: what pcc_rift_descriptors keeps between its stages (made at the first call on a handle).  Buffers of their own:
-// the radius searches in between use the handle's shared scratch.
-struct RiftScratch {
+// ---- what a feature keeps on a handle between its stages and calls ------------------------------------------
+// One slot per feature, filled at the feature's first call on the handle (scratch<T>() below) and destroyed with the handle.  A
+// scratch type lives in its feature's file, names its slot, and holds owning members only: none has a destructor body.
+struct Scratch { virtual ~Scratch() = default; };
+enum ScratchSlot {
+    SCRATCH_RIFT, SCRATCH_FPFH, SCRATCH_SIFT, SCRATCH_RIFT_BATCH, SCRATCH_SIFT_BATCH, SCRATCH_RGB_BATCH, SCRATCH_MATCH_COLOUR,
+    SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH,
+    SCRATCH_SLOTS
+};
+// A work handle: a second handle a feature indexes clouds of its own on (the caller's stream for the length of a call:
+// entry.hpp, WorkLease).  Made at the first lease, destroyed with its owner.
+struct WorkHandle {
+    pcc_index* ix = nullptr;
+    WorkHandle() = default;
+    WorkHandle(const WorkHandle&) = delete;
+    WorkHandle& operator=(const WorkHandle&) = delete;
+    ~WorkHandle() { (void)pcc_index_destroy(ix); }
+};
+
+// rift.hip: what pcc_rift_descriptors keeps between its stages.  Buffers of their own: the radius searches in between use the
+// handle's shared scratch.
+struct RiftScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_RIFT;
     DevBuf rgb;                  // the caller's colour words, staged (host memory)
     DevBuf normals, inten;       // float4[n] plane fit; float[n] intensity, NaN outside cloud2
     DevBuf grad;                 // float4[n]: intensity gradient, w = 1 for the points of cloud2
     DevBuf hist, keep, scan_tmp; // float[n][32] before the last compaction; its flags / positions
     DevBuf out_hist, out_index;  // results staged for a caller in host memory
 };
-// fpfh.hip: what pcc_fpfh_descriptors keeps between its stages (made at the first call on a handle).  Buffers of their own, as
-// RiftScratch's: the radius searches in between use the handle's shared scratch.
-struct FpfhScratch {
-    DevBuf normals;              // float4[n] plane fit
-    DevBuf spfh;                 // float[n][33]: the SPFH signature of every point of cloud2 (the others are never read)
-    DevBuf flags, pos, scan_tmp; // uint32[n]: 1 for the points of cloud2; uint32[n + 1]: their exclusive scan, pos[n] = the count
-    DevBuf out_hist, out_index;  // results staged for a caller in host memory
-};
-// sift.hip: what pcc_sift_keypoints keeps between its octaves and calls (made at the first call on a handle)
-struct SiftScratch {
-    pcc_index* work = nullptr;   // the handle the octave clouds are indexed on (the caller's stream, scratch of its own)
+// sift.hip: what pcc_sift_keypoints keeps between its octaves and calls
+struct SiftScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_SIFT;
+    WorkHandle work;             // the handle the octave clouds are indexed on (scratch of its own)
     DevBuf pts, rgb;             // the caller's points / colour words, staged (host memory)
     DevBuf cloud[2];             // octave clouds, 32-byte records: the voxel grid reads one and writes the other
     DevBuf inten, resp;          // float[n] intensity; float[n][scales] Gaussian responses
@@ -296,28 +336,17 @@ struct SiftScratch {
     DevBuf kp;                   // float4 keypoints of the call, every octave's in turn
 };
 // What every batch call keeps of its OWN between calls: the work handle the clouds off the batch route are
-// indexed on (the caller's stream, scratch of its own), pinned staging going up and coming down, what `up` holds on the device.
-struct BatchStaging {
-    pcc_index* work = nullptr;
+// indexed on, pinned staging going up and coming down, what `up` holds on the device.
+struct BatchStaging : Scratch {
+    WorkHandle work;
     HostBuf up, down;
     DevBuf dev;
-    ~BatchStaging() {
-        if (work) (void)pcc_index_destroy(work);
-        up.release(); down.release(); dev.release();
-    }
 };
-struct RiftBatchScratch;   // rift_batch.hip: BatchStaging and the CSR of pcc_rift_descriptors_batch
-struct SiftBatchScratch;   // sift_batch.hip: BatchStaging and the voxel keys, tables and CSR of pcc_sift_keypoints_batch
-struct RgbBatchScratch;    // region_rgb_batch.hip: BatchStaging and the rows of pcc_region_growing_rgb_batch
-struct MatchColourScratch; // match_colour.hip: BatchStaging, the packed concatenation, rows and finite counts of pcc_match_colour_elements
-struct ClusterDescScratch; // cluster_desc.hip: BatchStaging, the staged clusters, snap indices and RIFT clouds of pcc_cluster_descriptors
-struct SegmentScratch;     // segment.hip: the work handle, the filtered cloud, normals and labels of pcc_region_growing_segmentation,
-                           // and the orders and tables of pcc_extract_clusters
-struct GroundScratch;      // ground.hip: the current points, lattice table and sorted copies of the morphological ground filter
-struct ChangeScratch;      // change.hip: the staged clouds, voxel table, flags and device words of pcc_change_detection
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
-// the staging and result buffers of pcc_match_knn_batch (match_batch.hip) and pcc_match_knn_batch_dims (match_dims.hip)
-struct MatchBatchScratch {
+// the staging and result buffers of pcc_match_knn_batch (match_batch.hip), pcc_match_knn_batch_dims (match_dims.hip) and
+// pcc_cluster_matching (cluster_match.hip)
+struct MatchBatchScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_MATCH_BATCH;
     HostBuf up, down, tree_up, tree_down;  // pinned: table + records going up, best + second coming down; trees + walk items, found
     DevBuf dev, res, tree_dev, tree_res;
 };
@@ -351,7 +380,8 @@ struct pcc_index {
     size_t n_valid = 0;                // finite points (PCL total_nr_points_); valid after sync_info()
     unsigned int nc_cap = 0;           // upper bound of the grid's cell count the host sizes launches with
     pcc::DevBuf d_grid;                // GridDev on the device
-    pcc::GridDev* h_grid = nullptr;    // pinned host mirror, filled asynchronously
+    pcc::HostBuf h_grid_buf;           // pinned host mirror, filled asynchronously
+    pcc::GridDev* h_grid() const { return h_grid_buf.as<pcc::GridDev>(); }
     bool stats_pending = false;        // fallback counter of the last GRID search in flight to pinned->fb_mirror
     size_t last_nq = 0;
     bool info_pending = false;         // h_grid copy in flight: sync before reading n_valid / grid / bbox
@@ -396,22 +426,12 @@ struct pcc_index {
     uint64_t ties_flagged = 0, ties_changed = 0;  // of the last search in FLANN mode
     pcc::DevBuf words_buf;                                                   // pcc::DevWords, zeroed at creation
     pcc::DevWords* words() const { return words_buf.as<pcc::DevWords>(); }  // (a device pointer)
-    pcc::PinnedWords* pinned = nullptr;
+    pcc::HostBuf pinned_buf;                                                    // pcc::PinnedWords, zeroed at creation
+    pcc::PinnedWords* pinned() const { return pinned_buf.as<pcc::PinnedWords>(); }
     pcc::HostBuf host_a, host_b;  // large pinned read-back buffers
     pcc::HostBuf host_c;          // pinned staging of the FLANN tree a small call builds (flann_order.hip)
-    pcc::HostPipe* pipe = nullptr;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
-    pcc::RiftScratch* rift = nullptr;      // made at the first pcc_rift_descriptors on this handle (rift.hip)
-    pcc::FpfhScratch* fpfh = nullptr;      // made at the first pcc_fpfh_descriptors on this handle (fpfh.hip)
-    pcc::SiftScratch* sift = nullptr;      // made at the first pcc_sift_keypoints with this handle as its context (sift.hip)
-    pcc::RiftBatchScratch* rift_batch = nullptr;  // made at the first pcc_rift_descriptors_batch with this handle as its context (rift_batch.hip)
-    pcc::SiftBatchScratch* sift_batch = nullptr;  // made at the first pcc_sift_keypoints_batch with this handle as its context (sift_batch.hip)
-    pcc::RgbBatchScratch* rgb_batch = nullptr;    // made at the first pcc_region_growing_rgb_batch with this handle as its context (region_rgb_batch.hip)
-    pcc::MatchColourScratch* match_colour = nullptr;  // made at the first pcc_match_colour_elements with this handle as its context (match_colour.hip)
-    pcc::ClusterDescScratch* cluster_desc = nullptr;  // made at the first pcc_cluster_descriptors with this handle as its context (cluster_desc.hip)
-    pcc::SegmentScratch* segment = nullptr;       // made at the first pcc_extract_clusters / pcc_region_growing_segmentation with this handle as its context (segment.hip)
-    pcc::GroundScratch* ground = nullptr;         // made at the first pcc_morphological_operator / pcc_progressive_morphological_filter / pcc_ground_segmentation with this handle as its context (ground.hip)
-    pcc::ChangeScratch* change = nullptr;         // made at the first pcc_change_detection with this handle as its context (change.hip)
-    pcc::MatchBatchScratch* mb = nullptr;  // made at the first pcc_match_knn_batch with this handle as its context (match_batch.hip)
+    std::unique_ptr<pcc::HostPipe> pipe;  // two pinned chunk buffers + events, made at the first large host transfer (api.hip)
+    std::unique_ptr<pcc::Scratch> scratch[pcc::SCRATCH_SLOTS];  // what the features keep here, made at their first call (pcc::scratch<T>())
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     // HIP-event instrumentation (pcc_index_enable_timing): event pairs on the index's stream
     // ring of PCC_EV_SLOTS calls so a timed region of many steps is covered without syncing
@@ -419,6 +439,7 @@ struct pcc_index {
     hipEvent_t ev[PCC_EV_SLOTS][PCC_EV_KINDS] = {};
     bool ev_rec[PCC_EV_SLOTS][PCC_EV_KINDS] = {};
     unsigned int ev_slot = 0;  // slot of the call in flight
+    ~pcc_index();  // api.hip: scratches, then streams and events, then the buffers -- under pcc_index_destroy's device guard
 };
 
 namespace pcc {
@@ -431,6 +452,14 @@ namespace pcc {
 __host__ __device__
 #endif
 inline bool key_none(unsigned long long key) { return (unsigned int)(key >> 32) >= 0x7f7fffffu; }
+
+// the scratch of feature T on a handle, made at the first use
+template <class T>
+T* scratch(pcc_index* ix) {
+    std::unique_ptr<Scratch>& s = ix->scratch[T::slot];
+    if (!s) s = std::make_unique<T>();
+    return static_cast<T*>(s.get());
+}
 
 enum { EV_MAIN0 = 0, EV_MAIN1, EV_FB0, EV_FB1, EV_CALL0, EV_CALL1, EV_BUILD0, EV_BUILD1, EV_SORT0, EV_SORT1 };
 // every entry point that may enqueue work passes here once it holds the handle's mutex
@@ -455,9 +484,9 @@ inline void ev_next(pcc_index* ix) {
 template <int N = 1, class T>
 int read_back(pcc_index* ix, const T* dev, T* out) {
     static_assert(N * sizeof(T) <= sizeof(PinnedWords::readback) && alignof(T) <= alignof(PinnedWords), "read_back: too large");
-    PCC_HIP(hipMemcpyAsync(ix->pinned->readback, dev, N * sizeof(T), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipMemcpyAsync(ix->pinned()->readback, dev, N * sizeof(T), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipStreamSynchronize(ix->stream));
-    memcpy(out, ix->pinned->readback, N * sizeof(T));
+    memcpy(out, ix->pinned()->readback, N * sizeof(T));
     return PCC_OK;
 }
 
@@ -643,10 +672,9 @@ int launch_normals_csr(hipStream_t s, const float4* refs, const float4* order, c
 int csr_offsets(pcc_index* ix, unsigned int* off32, int64_t* off64, size_t n, unsigned long long* total);
 // knn.hip: every row of a CSR somebody else filled, sorted ascending in place (k_sort_rows)
 int sort_csr_rows(hipStream_t s, const int64_t* offsets, size_t n, unsigned long long* keys);
-// rift.hip: the RIFT descriptor pipeline on device arrays (ix->rift made by the caller); *n_out on the host
+// rift.hip: the RIFT descriptor pipeline on device arrays; *n_out on the host
 int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius,
                      double rift_radius, float* out_hist, int32_t* out_index, size_t* n_out);
-void rift_release(pcc_index* ix);  // frees ix->rift
 // the radius and bin checks of pcc_rift_descriptors and its batch form (rift.hip)
 int check_rift_params(double normal_radius, double gradient_radius, double rift_radius, int nr_distance_bins, int nr_gradient_bins);
 // the same stages over any packed cloud (rift_batch.hip: the concatenation of a batch): see rift.hip
@@ -654,39 +682,24 @@ typedef std::function<int(double radius, const unsigned long long** keys, const 
 int rift_stages(pcc_index* ix, const float4* refs, const float4* order, const GridDev* gd, size_t n, const RiftRows& rows,
                 const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius,
                 float* out_hist, int32_t* out_index);
-// rift_batch.hip: pcc_rift_descriptors_batch behind its argument checks (ix->rift made by the caller)
+// rift_batch.hip: pcc_rift_descriptors_batch behind its argument checks
 int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
                            float* out_hist, int32_t* out_index, size_t* out_offsets);
-void rift_batch_release(pcc_index* ix);  // frees ix->rift_batch and its work handle
 // rift_batch.hip: the sorted radius rows (d2 < r2, ascending (d2, index)) of a concatenation of clouds as one CSR, from the exhaustive
 // builder: d_items (device) are query blocks of one cloud each, d_pts the concatenation with w = bits(concatenated index).  offs / keys:
 // the caller's buffers for uint32 offsets[total + 1] (+ the same as int64) and the entries.  One wait: the CSR's total
 int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
                       DevBuf& offs, DevBuf& keys, const unsigned long long** keys_out, const unsigned int** offsets_out);
-// fpfh.hip: pcc_fpfh_descriptors
-void fpfh_release(pcc_index* ix);  // frees ix->fpfh
-void sift_release(pcc_index* ix);  // frees ix->sift and its work handle
-// sift.hip: the detector on device arrays (ix->sift made by the caller): the keypoints are left in ix->sift->kp, *n_out of them
+// sift.hip: the detector on device arrays: the keypoints are left in SiftScratch::kp, *n_out of them
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
-// sift_batch.hip: pcc_sift_keypoints_batch behind its argument checks
-void sift_batch_release(pcc_index* ix);  // frees ix->sift_batch and its work handle
-// cluster_desc.hip: pcc_cluster_descriptors
-void cluster_desc_release(pcc_index* ix);  // frees ix->cluster_desc and its work handle
-// region_rgb_batch.hip: pcc_region_growing_rgb_batch behind its argument checks
-void rgb_batch_release(pcc_index* ix);  // frees ix->rgb_batch and its work handle
-// match_colour.hip: pcc_match_colour_elements
-void match_colour_release(pcc_index* ix);  // frees ix->match_colour and its work handle
-// segment.hip: pcc_extract_clusters and pcc_region_growing_segmentation
-void segment_release(pcc_index* ix);  // frees ix->segment and its work handle
-// The partition machinery the segmentation calls share (segment.hip; ix->segment made by segment_scratch).  extract_order: labels[n]
+// The partition machinery the segmentation calls share (segment.hip).  extract_order: labels[n]
 // on the device, n > 0, n_clusters > 0 -> *order (uint32[n]: the kept points key by key, ascending inside a key, then the points
-// left out (label -1)) and *offsets (uint32[n_clusters + 1]; offsets_out may be null: not computed), both in ix->segment; everything
+// left out (label -1)) and *offsets (uint32[n_clusters + 1]; offsets_out may be null: not computed), both in SegmentScratch; everything
 // enqueued, nothing waited for.
 // offsets_to_host / offsets_arrived: the offsets and the bad-label flag on their way to the host, and read after the caller's wait.
 // launch_records: out record j = the first record_bytes of input record order[j].  give: a result in a buffer of the library's into
 // the caller's array in either space (host: through deliver; the caller waits).
-void segment_scratch(pcc_index* ix);
 int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clusters, const unsigned int** order_out,
                   const unsigned int** offsets_out);
 int offsets_to_host(pcc_index* ix, const unsigned int* d_offsets, int32_t n_clusters);
@@ -694,10 +707,6 @@ int offsets_arrived(pcc_index* ix, int32_t n_clusters, size_t* out_offsets);
 int launch_records(hipStream_t s, const void* in, size_t stride, const unsigned int* order, size_t m, size_t record_bytes, void* out,
                    size_t out_stride);
 int give(pcc_index* ix, int mem, void* user, const void* dev, size_t bytes);
-// ground.hip: pcc_morphological_operator, pcc_progressive_morphological_filter and pcc_ground_segmentation
-void ground_release(pcc_index* ix);  // frees ix->ground
-// change.hip: pcc_change_detection
-void change_release(pcc_index* ix);  // frees ix->change
 // normals.hip: the plane fit over the self k-NN rows `keys` (n x K) of a packed cloud
 int launch_normals(hipStream_t s, const unsigned long long* keys, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n,
                    int K, const float vp[3], float4* out);
@@ -752,7 +761,6 @@ struct IcpHooks {
 int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t n, size_t stride, int mem, int max_iter, int fixed,
                    float T[16], double* fitness, int* iterations, int* converged);
 // ---- api.hip internals the other files build on ----------------------------------------------------------------------
-void match_batch_release(pcc_index* ix);  // match_batch.hip: frees ix->mb
 // match_dims.hip: the search of pcc_match_knn_batch_dims for dim != 3 (arguments checked by the entry point in match_batch.hip)
 int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                          const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets);

@@ -424,11 +424,11 @@ int rgb_stages_in(pcc_index* ix, const RgbRun& run, const Order& order, const Rg
             // the count and the list in one wait: the list's head comes down beside the count, the rest only when there is more
             const unsigned int head = std::min(n_first, RGB_PAIRS_FIRST_COPY);
             PCC_TRY(ix->host_b.reserve((size_t)head * sizeof(RgbSegmentPair)));
-            PCC_HIP(hipMemcpyAsync(ix->pinned->readback, d_words, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
+            PCC_HIP(hipMemcpyAsync(ix->pinned()->readback, d_words, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, s));
             PCC_HIP(hipMemcpyAsync(ix->host_b.p, d_pairs, (size_t)head * sizeof(RgbSegmentPair), hipMemcpyDeviceToHost, s));
             PCC_HIP(hipStreamSynchronize(s));
             unsigned int w[3];  // -, pairs listed, table overflow
-            memcpy(w, ix->pinned->readback, sizeof(w));
+            memcpy(w, ix->pinned()->readback, sizeof(w));
             np = w[1];
             if (w[2] || np > n_first) { set_error("segment pair table overflow (%u pairs, room for %u)", np, n_first); return PCC_ERR_OVERFLOW; }
             if (np > head) {

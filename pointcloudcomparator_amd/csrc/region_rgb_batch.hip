@@ -141,15 +141,10 @@ int rgb_batch_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_i
 }
 
 struct RgbBatchScratch : BatchStaging {  // (up: bases + table + points + colour words; down: the clouds' first ids + labels)
+    static constexpr ScratchSlot slot = SCRATCH_RGB_BATCH;
     DevBuf keys;              // u64[total][K]: the rows
     DevBuf id_bases, labels;  // uint32[n_clouds + 1]; int32[total]
-    ~RgbBatchScratch() { keys.release(); id_bases.release(); labels.release(); }
 };
-
-void rgb_batch_release(pcc_index* ix) {
-    delete ix->rgb_batch;
-    ix->rgb_batch = nullptr;
-}
 
 namespace {
 
@@ -162,7 +157,7 @@ struct RgbParams {
 // the clouds of sizes batch.n[] (0: not on this route) through the batch kernels: labels at out_labels + off[c], counts for EVERY cloud
 int rgb_batch_route(pcc_index* ix, const CloudBatch& batch, const RgbParams& par, const size_t* off, int32_t* out_labels, int32_t* out_n_clusters) {
     hipStream_t s = ix->stream;
-    RgbBatchScratch* b = ix->rgb_batch;
+    RgbBatchScratch* b = scratch<RgbBatchScratch>(ix);
     const size_t n_clouds = batch.n_clouds;
     std::vector<uint32_t> bases;
     std::vector<RiftBatchItem> items;
@@ -235,8 +230,7 @@ int region_growing_rgb_batch(pcc_index* ix, const CloudBatch& batch, float dista
                              float region_color_threshold, uint32_t min_size, uint32_t max_size, unsigned int nr_neighbours,
                              unsigned int nr_region_neighbours, int32_t* out_labels, int32_t* out_n_clusters) {
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
-    if (!ix->rgb_batch) ix->rgb_batch = new RgbBatchScratch();
-    RgbBatchScratch* b = ix->rgb_batch;
+    RgbBatchScratch* b = scratch<RgbBatchScratch>(ix);
     const RgbParams par{distance_threshold, point_color_threshold, region_color_threshold, min_size, max_size, nr_neighbours, nr_region_neighbours};
     const size_t n_clouds = batch.n_clouds;
     const size_t brute_max = nr_region_neighbours <= RGB_BATCH_MAX_K ? (size_t)ix->opt.rgb_batch_brute_max : 0;
@@ -254,7 +248,7 @@ int region_growing_rgb_batch(pcc_index* ix, const CloudBatch& batch, float dista
 
     // ---- the other clouds: one by one on the work handle ----------------------------------------------------------------------
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &b->work, true));
+    PCC_TRY(lease.take(ix, b->work, true));
     for (size_t c = 0; c < n_clouds; ++c) {
         if (batch.n[c] <= brute_max) continue;
         int32_t* labels = out_labels + off[c];

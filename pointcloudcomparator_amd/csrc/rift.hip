@@ -205,25 +205,16 @@ k_rift_compact(const float* __restrict__ hist, const unsigned int* __restrict__ 
 
 }  // namespace
 
-void rift_release(pcc_index* ix) {
-    if (!ix->rift) return;
-    RiftScratch* r = ix->rift;
-    DevBuf* bufs[] = {&r->rgb, &r->normals, &r->inten, &r->grad, &r->hist, &r->keep, &r->scan_tmp, &r->out_hist, &r->out_index};
-    for (DevBuf* b : bufs) b->release();
-    delete r;
-    ix->rift = nullptr;
-}
-
 // The stages over ANY packed cloud with sorted radius rows: refs[n] (w = the point's index), `order` a cell_refs-shaped
 // array whose first gd->n_valid entries name the points to take (their w), `rows` the source of the CSR at a radius
 // (keys: d2 bits << 32 | point index, ascending per row; valid until the next call of `rows`).  rgb: the colour words on
 // the device (stride bytes apart); out_hist[n * 32], out_index[n] on the device.  Leaves the exclusive scan of the keep
-// flags in ix->rift->keep: keep[i] = kept descriptors in front of point i, keep[n] = their number.
+// flags in RiftScratch::keep: keep[i] = kept descriptors in front of point i, keep[n] = their number.
 int rift_stages(pcc_index* ix, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n, const RiftRows& rows,
                 const unsigned char* rgb, size_t rgb_stride, double normal_radius, double gradient_radius, double rift_radius,
                 float* out_hist, int32_t* out_index) {
     hipStream_t s = ix->stream;
-    RiftScratch* r = ix->rift;
+    RiftScratch* r = scratch<RiftScratch>(ix);
     const unsigned int un = (unsigned int)n;
     const float origin[3] = {0.f, 0.f, 0.f};
     PCC_TRY(r->normals.reserve(n * sizeof(float4)));
@@ -275,7 +266,7 @@ int rift_descriptors(pcc_index* ix, const unsigned char* rgb, size_t rgb_stride,
     PCC_TRY(rift_stages(ix, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, rows, rgb, rgb_stride, normal_radius,
                         gradient_radius, rift_radius, out_hist, out_index));
     unsigned int kept = 0;
-    PCC_TRY(read_back(ix, ix->rift->keep.as<unsigned int>() + n, &kept));
+    PCC_TRY(read_back(ix, scratch<RiftScratch>(ix)->keep.as<unsigned int>() + n, &kept));
     *n_out = kept;
     return PCC_OK;
 }
@@ -310,13 +301,13 @@ int pcc_rift_descriptors(pcc_index* ix, const void* rgb, size_t rgb_stride, int 
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
     const size_t n = ix->n_orig;
-    if (!ix->rift) ix->rift = new RiftScratch();
+    RiftScratch* r = scratch<RiftScratch>(ix);
     const unsigned char* drgb = nullptr;
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->rift->rgb, &drgb));
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, r->rgb, &drgb));
     Out<float> rh;
     Out<int32_t> ri;
-    PCC_TRY(rh.stage(out_hist, n * RIFT_BINS, mem, ix->rift->out_hist));
-    PCC_TRY(ri.stage(out_index, n, mem, ix->rift->out_index));
+    PCC_TRY(rh.stage(out_hist, n * RIFT_BINS, mem, r->out_hist));
+    PCC_TRY(ri.stage(out_index, n, mem, r->out_index));
     PCC_TRY(rift_descriptors(ix, drgb, rgb_stride, normal_radius, gradient_radius, rift_radius, rh.dev, ri.dev, n_out));
     rh.count = *n_out * RIFT_BINS;  // (only the rows that were written travel)
     ri.count = *n_out;

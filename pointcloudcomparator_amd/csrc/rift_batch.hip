@@ -102,9 +102,9 @@ k_rift_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __
 }  // namespace
 
 struct RiftBatchScratch : BatchStaging {  // (up: order words + bases + table + points + colour words; down: the slice bounds)
+    static constexpr ScratchSlot slot = SCRATCH_RIFT_BATCH;
     DevBuf offs, keys;  // the CSR of the radius in use: uint32 offsets[n + 1] + the same as int64; u64 keys
     DevBuf slice;       // uint32[n_clouds + 1]
-    ~RiftBatchScratch() { offs.release(); keys.release(); slice.release(); }
 };
 
 // The sorted radius rows of a concatenation of clouds as ONE CSR (pcc_internal.hpp): rows of d2 < r2 from the exhaustive builder
@@ -136,28 +136,18 @@ int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int 
     return PCC_OK;
 }
 
-void rift_batch_release(pcc_index* ix) {
-    delete ix->rift_batch;
-    ix->rift_batch = nullptr;
-}
-
 // ---- the half over a device-resident concatenation (desc_batch.hpp): shared with cluster_desc.hip ---------------------------
-void rift_batch_scratch(pcc_index* ix) {
-    if (!ix->rift_batch) ix->rift_batch = new RiftBatchScratch();
-    if (!ix->rift) ix->rift = new RiftScratch();
-}
-
 int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius, double gradient_radius, double rift_radius,
                    const unsigned int** d_slice) {
     hipStream_t s = ix->stream;
-    RiftBatchScratch* b = ix->rift_batch;
+    RiftBatchScratch* b = scratch<RiftBatchScratch>(ix);
     const size_t total = in.total, n_clouds = in.n_clouds;
     // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
     const RiftRows rows = [&](double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) -> int {
         return batch_radius_rows(ix, in.d_items, in.n_items, in.d_pts, total, (float)(radius * radius), b->offs, b->keys, keys_out, offsets_out);
     };
     // ---- the stages of the single call, once over the concatenation -------------------------------------------------------
-    RiftScratch* r = ix->rift;
+    RiftScratch* r = scratch<RiftScratch>(ix);
     PCC_TRY(r->out_hist.reserve(total * RIFT_BINS * sizeof(float)));
     PCC_TRY(r->out_index.reserve(total * sizeof(int32_t)));
     PCC_TRY(rift_stages(ix, in.d_pts, in.d_pts, in.gd, total, rows, in.d_rgb, sizeof(uint32_t), normal_radius, gradient_radius, rift_radius,
@@ -172,7 +162,7 @@ int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius
 }
 
 int rift_batch_slices(pcc_index* ix, size_t n_clouds, const unsigned int** h_slice) {
-    RiftBatchScratch* b = ix->rift_batch;
+    RiftBatchScratch* b = scratch<RiftBatchScratch>(ix);
     PCC_TRY(b->down.reserve((n_clouds + 1) * sizeof(unsigned int)));
     PCC_HIP(hipMemcpyAsync(b->down.p, b->slice.p, (n_clouds + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipStreamSynchronize(ix->stream));
@@ -182,7 +172,7 @@ int rift_batch_slices(pcc_index* ix, size_t n_clouds, const unsigned int** h_sli
 
 int rift_batch_fetch(pcc_index* ix, size_t kept, float* out_hist, int32_t* out_index) {
     if (!kept) return PCC_OK;
-    RiftScratch* r = ix->rift;
+    RiftScratch* r = scratch<RiftScratch>(ix);
     PCC_HIP(hipMemcpyAsync(out_hist, r->out_hist.p, kept * RIFT_BINS * sizeof(float), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipMemcpyAsync(out_index, r->out_index.p, kept * sizeof(int32_t), hipMemcpyDeviceToHost, ix->stream));
     PCC_HIP(hipStreamSynchronize(ix->stream));
@@ -193,7 +183,7 @@ int rift_batch_fetch(pcc_index* ix, size_t kept, float* out_hist, int32_t* out_i
 static int rift_batch_brute(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
                             float* out_hist, int32_t* out_index, size_t* out_offsets) {
     hipStream_t s = ix->stream;
-    RiftBatchScratch* b = ix->rift_batch;
+    RiftBatchScratch* b = scratch<RiftBatchScratch>(ix);
     const size_t n_clouds = batch.n_clouds;
     std::vector<uint32_t> bases;
     std::vector<RiftBatchItem> items;
@@ -240,8 +230,7 @@ static int rift_batch_brute(pcc_index* ix, const CloudBatch& batch, double norma
 
 int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal_radius, double gradient_radius, double rift_radius,
                            float* out_hist, int32_t* out_index, size_t* out_offsets) {
-    if (!ix->rift_batch) ix->rift_batch = new RiftBatchScratch();
-    RiftBatchScratch* b = ix->rift_batch;
+    RiftBatchScratch* b = scratch<RiftBatchScratch>(ix);
     const size_t n_clouds = batch.n_clouds, brute_max = (size_t)ix->opt.rift_batch_brute_max;
     const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
     ix->stats[0] = routes.n_brute;
@@ -257,7 +246,7 @@ int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal
     std::vector<int32_t> small_index(std::max<size_t>(routes.n_brute, 1));
     PCC_TRY(rift_batch_brute(ix, small, normal_radius, gradient_radius, rift_radius, small_hist.data(), small_index.data(), small_off.data()));
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &b->work, true));
+    PCC_TRY(lease.take(ix, b->work, true));
     pcc_index* w = lease.w;
     size_t at = 0;
     for (size_t c = 0; c < n_clouds; ++c) {
@@ -308,7 +297,6 @@ int pcc_rift_descriptors_batch(pcc_index* ctx, size_t n_clouds, const void* cons
     PCC_ENTER(ctx);
     ev_next(ctx);
     ev_mark(ctx, EV_CALL0);
-    if (!ctx->rift) ctx->rift = new RiftScratch();
     const int st = rift_descriptors_batch(ctx, batch, normal_radius, gradient_radius, rift_radius, out_hist, out_index, out_offsets);
     ev_mark(ctx, EV_CALL1);
     return st;

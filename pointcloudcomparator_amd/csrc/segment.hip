@@ -31,8 +31,9 @@
 
 namespace pcc {
 
-struct SegmentScratch {
-    pcc_index* work = nullptr;       // the handle the filtered cloud is indexed on (the caller's stream and options, scratch of its own)
+struct SegmentScratch : Scratch {
+    static constexpr ScratchSlot slot = SCRATCH_SEGMENT;
+    WorkHandle work;                 // the handle the filtered cloud is indexed on (the caller's stream and options, scratch of its own)
     DevBuf cloud, normals, labels;   // the filtered cloud's records, float4[nv], int32[nv]: nothing voxel_grid, the k-NN rows, the
                                      // plane fit, the plane loop, grid_region_growing or grid_clusters reserves
     DevBuf remain;                   // pcc_euclidean_cluster_segmentation: the records that remain after the planes (a caller in host memory)
@@ -41,17 +42,7 @@ struct SegmentScratch {
     DevBuf table, scan_tmp;          // uint32[256][blocks]; the scan's block totals
     DevBuf offsets;                  // uint32[n_clusters + 1]
     DevBuf out_rec;                  // the cluster records of a caller in host memory
-    ~SegmentScratch() {
-        if (work) (void)pcc_index_destroy(work);
-        DevBuf* bufs[] = {&cloud, &normals, &labels, &remain, &lab_in, &order_a, &order_b, &table, &scan_tmp, &offsets, &out_rec};
-        for (DevBuf* b : bufs) b->release();
-    }
 };
-
-void segment_release(pcc_index* ix) {
-    delete ix->segment;
-    ix->segment = nullptr;
-}
 
 namespace {
 
@@ -179,17 +170,13 @@ inline int g1(size_t n) {
 
 // ---- what the other segmentation calls build on (pcc_internal.hpp: ground.hip) ------------------------------------------------
 
-void segment_scratch(pcc_index* ix) {
-    if (!ix->segment) ix->segment = new SegmentScratch();
-}
-
 // labels[n] on the device, n > 0, n_clusters > 0 -> *order (uint32[n]: the kept points cluster by cluster, ascending inside a
-// cluster, then the points left out) and *offsets (uint32[n_clusters + 1]), both in ix->segment; the bad-label flag is left in
+// cluster, then the points left out) and *offsets (uint32[n_clusters + 1]), both in SegmentScratch; the bad-label flag is left in
 // DevWords::op[0].  Everything enqueued, nothing waited for.
 int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clusters, const unsigned int** order_out,
                   const unsigned int** offsets_out) {
     hipStream_t s = ix->stream;
-    SegmentScratch* sg = ix->segment;
+    SegmentScratch* sg = scratch<SegmentScratch>(ix);
     // contiguous chunks of whole tiles, at most 4096 workgroups
     size_t blocks = std::min<size_t>((n + 2047) / 2048, 4096);
     const size_t chunk = ((n + blocks - 1) / blocks + 255) / 256 * 256;
@@ -230,11 +217,11 @@ int extract_order(pcc_index* ix, const int32_t* labels, size_t n, int32_t n_clus
 int offsets_to_host(pcc_index* ix, const unsigned int* d_offsets, int32_t n_clusters) {
     PCC_TRY(ix->host_a.reserve(((size_t)n_clusters + 1) * sizeof(unsigned int)));
     PCC_HIP(hipMemcpyAsync(ix->host_a.p, d_offsets, ((size_t)n_clusters + 1) * sizeof(unsigned int), hipMemcpyDeviceToHost, ix->stream));
-    PCC_HIP(hipMemcpyAsync(ix->pinned->readback, ix->words()->op, sizeof(unsigned int), hipMemcpyDeviceToHost, ix->stream));
+    PCC_HIP(hipMemcpyAsync(ix->pinned()->readback, ix->words()->op, sizeof(unsigned int), hipMemcpyDeviceToHost, ix->stream));
     return PCC_OK;
 }
 int offsets_arrived(pcc_index* ix, int32_t n_clusters, size_t* out_offsets) {
-    if (ix->pinned->readback[0]) { set_error("a label outside [-1, %d)", n_clusters); return PCC_ERR_INVALID; }
+    if (ix->pinned()->readback[0]) { set_error("a label outside [-1, %d)", n_clusters); return PCC_ERR_INVALID; }
     const unsigned int* h = ix->host_a.as<unsigned int>();
     for (size_t c = 0; c <= (size_t)n_clusters; ++c) out_offsets[c] = h[c];
     return PCC_OK;
@@ -286,9 +273,8 @@ int pcc_extract_clusters(pcc_index* ix, const void* records, size_t n, size_t st
     hipStream_t s = ix->stream;
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    segment_scratch(ix);
     const int32_t* d_labels = nullptr;
-    PCC_TRY(stage_in(ix, labels, n, mem, ix->segment->lab_in, &d_labels));
+    PCC_TRY(stage_in(ix, labels, n, mem, scratch<SegmentScratch>(ix)->lab_in, &d_labels));
     const unsigned int *order = nullptr, *d_offsets = nullptr;
     PCC_TRY(extract_order(ix, d_labels, n, n_clusters, &order, &d_offsets));
     ev_mark(ix, EV_CALL1);
@@ -352,8 +338,7 @@ int pcc_region_growing_segmentation(pcc_index* ix, const void* pts, size_t n, si
     hipStream_t s = ix->stream;
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    segment_scratch(ix);
-    SegmentScratch* sg = ix->segment;
+    SegmentScratch* sg = scratch<SegmentScratch>(ix);
 
     // 1. the voxel grid, on `ix`: the raw cloud on the device (a host cloud in q_raw, which voxel_grid leaves alone for a device
     // cloud), the centroids into a zeroed buffer of this call's own
@@ -374,7 +359,7 @@ int pcc_region_growing_segmentation(pcc_index* ix, const void* pts, size_t n, si
 
     // 2. the filtered cloud indexed on the work handle; one search with max(normal_k, k) neighbours serves both stages
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &sg->work, true));
+    PCC_TRY(lease.take(ix, sg->work, true));
     pcc_index* w = lease.w;
     w->opt.knn_cache_k = std::max(normal_k, k);
     PCC_TRY(set_input(w, sg->cloud.p, nv, out_stride, PCC_MEM_DEVICE));
@@ -471,8 +456,7 @@ int pcc_euclidean_cluster_segmentation(pcc_index* ix, const void* pts, size_t n,
     hipStream_t s = ix->stream;
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    segment_scratch(ix);
-    SegmentScratch* sg = ix->segment;
+    SegmentScratch* sg = scratch<SegmentScratch>(ix);
 
     // 1. the voxel grid, on `ix`, into a zeroed buffer of this call's own (as pcc_region_growing_segmentation)
     const void* src = pts;
@@ -523,7 +507,7 @@ int pcc_euclidean_cluster_segmentation(pcc_index* ix, const void* pts, size_t n,
 
     // 3. the remaining cloud indexed on the work handle, 4. clustered there, the labels in a buffer of this call's
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &sg->work, true));
+    PCC_TRY(lease.take(ix, sg->work, true));
     pcc_index* w = lease.w;
     PCC_TRY(set_input(w, rem, nr, out_stride, PCC_MEM_DEVICE));
     entered(w);

@@ -179,35 +179,9 @@ k_sift_write(const SiftRec* __restrict__ cloud, const unsigned int* __restrict__
 
 }  // namespace
 
-void sift_release(pcc_index* ix) {
-    if (!ix->sift) return;
-    SiftScratch* r = ix->sift;
-    if (r->work) (void)pcc_index_destroy(r->work);
-    DevBuf* bufs[] = {&r->pts, &r->rgb, &r->cloud[0], &r->cloud[1], &r->inten, &r->resp, &r->nbr, &r->nbr_d2, &r->mask, &r->count, &r->scan_tmp,
-                      &r->octaves, &r->kp};
-    for (DevBuf* b : bufs) b->release();
-    delete r;
-    ix->sift = nullptr;
-}
-
-// kp holds `have` keypoints; room for `more` behind them (a grown buffer keeps what it held)
-static int sift_room(pcc_index* ix, DevBuf& kp, size_t have, size_t more) {
-    const size_t want = (have + more) * sizeof(float4);
-    if (want <= kp.cap) return PCC_OK;
-    DevBuf grown;
-    PCC_TRY(grown.reserve(std::max(want, 2 * kp.cap)));
-    if (have) {
-        PCC_HIP(hipMemcpyAsync(grown.p, kp.p, have * sizeof(float4), hipMemcpyDeviceToDevice, ix->stream));
-        PCC_HIP(hipStreamSynchronize(ix->stream));
-    }
-    kp.release();
-    kp = grown;
-    return PCC_OK;
-}
-
 // ---- the stages behind the voxel grid, the rows and the neighbours (sift_stages.hpp: shared with sift_batch.hip) --------------
 int sift_intensity_stage(pcc_index* ix, const SiftRec* cloud, size_t n) {
-    SiftScratch* r = ix->sift;
+    SiftScratch* r = scratch<SiftScratch>(ix);
     PCC_TRY(r->inten.reserve(n * sizeof(float)));
     const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_sift_intensity, dim3(blocks), dim3(256), 0, ix->stream, cloud, (unsigned int)n, r->inten.as<float>());
@@ -216,7 +190,7 @@ int sift_intensity_stage(pcc_index* ix, const SiftRec* cloud, size_t n) {
 }
 
 int sift_space_stage(pcc_index* ix, size_t n, const unsigned long long* keys, const unsigned int* offsets, const SiftOctave* oc, int n_scales) {
-    SiftScratch* r = ix->sift;
+    SiftScratch* r = scratch<SiftScratch>(ix);
     const size_t S = (size_t)n_scales;
     PCC_TRY(r->resp.reserve(n * S * sizeof(float)));
     if (ix->opt.sift_layout == 1) {
@@ -234,7 +208,7 @@ int sift_space_stage(pcc_index* ix, size_t n, const unsigned long long* keys, co
 
 int sift_extrema_stage(pcc_index* ix, size_t n, const int32_t* nbr, int K, const SiftOctave* oc) {
     hipStream_t s = ix->stream;
-    SiftScratch* r = ix->sift;
+    SiftScratch* r = scratch<SiftScratch>(ix);
     PCC_TRY(r->mask.reserve(n * sizeof(unsigned int)));
     PCC_TRY(r->count.reserve((n + 1) * sizeof(unsigned int)));
     PCC_HIP(hipMemsetAsync(r->count.p, 0, (n + 1) * sizeof(unsigned int), s));
@@ -246,9 +220,9 @@ int sift_extrema_stage(pcc_index* ix, size_t n, const int32_t* nbr, int K, const
 }
 
 int sift_write_stage(pcc_index* ix, const SiftRec* cloud, size_t n, const SiftOctave* oc, size_t have, size_t found) {
-    SiftScratch* r = ix->sift;
+    SiftScratch* r = scratch<SiftScratch>(ix);
     if (!found) return PCC_OK;
-    PCC_TRY(sift_room(ix, r->kp, have, found));
+    PCC_TRY(r->kp.grow_keep(ix->stream, have * sizeof(float4), (have + found) * sizeof(float4)));
     const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     hipLaunchKernelGGL(k_sift_write, dim3(blocks), dim3(256), 0, ix->stream, cloud, r->mask.as<unsigned int>(), r->count.as<unsigned int>(), oc,
                        (unsigned int)n, r->kp.as<float4>() + have);
@@ -256,15 +230,15 @@ int sift_write_stage(pcc_index* ix, const SiftRec* cloud, size_t n, const SiftOc
     return PCC_OK;
 }
 
-// pts / rgb on the device; the keypoints are left in ix->sift->kp (device), *n_out of them
+// pts / rgb on the device; the keypoints are left in SiftScratch::kp (device), *n_out of them
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out) {
     hipStream_t s = ix->stream;
-    SiftScratch* r = ix->sift;
+    SiftScratch* r = scratch<SiftScratch>(ix);
     *n_out = 0;
     // the work handle's launches join the caller's queue for the length of this call (under options of its own)
     WorkLease lease;
-    PCC_TRY(lease.take(ix, &r->work, false));
+    PCC_TRY(lease.take(ix, r->work, false));
     pcc_index* w = lease.w;
     PCC_TRY(r->cloud[0].reserve(n * sizeof(SiftRec)));
     PCC_TRY(r->cloud[1].reserve(n * sizeof(SiftRec)));
@@ -357,10 +331,10 @@ int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, 
     if (n == 0) { PCC_NOTHING_ENQUEUED(ix); return PCC_OK; }
     ev_next(ix);
     ev_mark(ix, EV_CALL0);
-    if (!ix->sift) ix->sift = new SiftScratch();
+    SiftScratch* r = scratch<SiftScratch>(ix);
     const unsigned char *dpts = nullptr, *drgb = nullptr;
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(pts), (n - 1) * stride + 12, mem, ix->sift->pts, &dpts));
-    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, ix->sift->rgb, &drgb));
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(pts), (n - 1) * stride + 12, mem, r->pts, &dpts));
+    PCC_TRY(stage_in(ix, reinterpret_cast<const unsigned char*>(rgb), (n - 1) * rgb_stride + 4, mem, r->rgb, &drgb));
     size_t found = 0;
     PCC_TRY(sift_keypoints(ix, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
     ev_mark(ix, EV_CALL1);
@@ -371,7 +345,7 @@ int pcc_sift_keypoints(pcc_index* ix, const void* pts, size_t n, size_t stride, 
     }
     if (found == 0) return PCC_OK;
     // (no Out / finish: the keypoints collect in the scratch's own buffer and leave it by one plain copy in either memory space)
-    PCC_TRY(copy_out(ix, out_keypoints, ix->sift->kp.p, found * 4 * sizeof(float), mem));
+    PCC_TRY(copy_out(ix, out_keypoints, r->kp.p, found * 4 * sizeof(float), mem));
     if (mem == PCC_MEM_HOST) PCC_HIP(hipStreamSynchronize(ix->stream));
     return PCC_OK;
 }

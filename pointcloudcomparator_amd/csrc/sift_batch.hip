@@ -283,6 +283,7 @@ unsigned int blocks_for(size_t n) { return (unsigned int)std::min<size_t>((n + 2
 
 // (up: octaves + table + records, then every round's table; down: sizes, counts, keypoints; dev: the first upload, whose records the snap reads)
 struct SiftBatchScratch : BatchStaging {
+    static constexpr ScratchSlot slot = SCRATCH_SIFT_BATCH;
     DevBuf table[2];             // the tables of the later rounds, in turn
     DevBuf cloud[2], pts4;       // octave concatenations as records (the voxel stage reads one, writes the other); the current one as float4
     DevBuf vkeys, cloud_of;      // voxel keys u64[n]; the cloud of every position uint32[n]
@@ -291,27 +292,13 @@ struct SiftBatchScratch : BatchStaging {
     DevBuf offs, keys;           // the CSR of the round's radius rows
     DevBuf nbr;                  // int32[n][25]
     DevBuf kp_cloud, snap;       // per keypoint: its cloud; the snapped index
-    ~SiftBatchScratch() {
-        for (DevBuf* d : {&table[0], &table[1], &cloud[0], &cloud[1], &pts4, &vkeys, &cloud_of, &flags, &scan_tmp, &words, &offs, &keys, &nbr, &kp_cloud, &snap})
-            d->release();
-    }
 };
 
-void sift_batch_release(pcc_index* ix) {
-    delete ix->sift_batch;
-    ix->sift_batch = nullptr;
-}
-
 // ---- the half over a device-resident first concatenation (desc_batch.hpp): shared with cluster_desc.hip ---------------------
-void sift_batch_scratch(pcc_index* ix) {
-    if (!ix->sift_batch) ix->sift_batch = new SiftBatchScratch();
-    if (!ix->sift) ix->sift = new SiftScratch();
-}
-
 int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const SiftBatchInput& in, float min_scale, SiftBatchResult* res) {
     hipStream_t s = ix->stream;
-    SiftBatchScratch* b = ix->sift_batch;
-    SiftScratch* r = ix->sift;
+    SiftBatchScratch* b = scratch<SiftBatchScratch>(ix);
+    SiftScratch* r = scratch<SiftScratch>(ix);
     SiftBatchRound next;
     const std::vector<SiftOctave>& h_octaves = *in.h_octaves;
     const SiftOctave* d_octaves = in.d_octaves;
@@ -415,7 +402,7 @@ int sift_batch_rounds(pcc_index* ix, size_t n_clouds, const SiftBatchInput& in, 
 // d_snap[k] for the keypoints of the rounds (round-major): the cloud of every keypoint goes up, then a wave per keypoint
 int sift_batch_snap(pcc_index* ix, const SiftBatchResult& res, size_t n_clouds, double snap_radius, int32_t* d_snap) {
     hipStream_t s = ix->stream;
-    SiftBatchScratch* b = ix->sift_batch;
+    SiftBatchScratch* b = scratch<SiftBatchScratch>(ix);
     const size_t m = res.total;
     if (!m) return PCC_OK;
     // the cloud of every keypoint, in the device's (round, cloud) order
@@ -428,7 +415,7 @@ int sift_batch_snap(pcc_index* ix, const SiftBatchResult& res, size_t n_clouds, 
             for (uint32_t i = 0; i < round[c]; ++i) kc[at++] = (uint32_t)c;
     PCC_HIP(hipMemcpyAsync(b->kp_cloud.p, kc, m * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     const unsigned int wb = (unsigned int)std::min<size_t>((m + 3) / 4, 8192);
-    hipLaunchKernelGGL(k_sb_snap, dim3(wb), dim3(256), 0, s, ix->sift->kp.as<float4>(), b->kp_cloud.as<unsigned int>(), res.d_bases0, res.d_rec0,
+    hipLaunchKernelGGL(k_sb_snap, dim3(wb), dim3(256), 0, s, scratch<SiftScratch>(ix)->kp.as<float4>(), b->kp_cloud.as<unsigned int>(), res.d_bases0, res.d_rec0,
                        snap_radius, (unsigned int)m, d_snap);
     PCC_HIP(hipGetLastError());
     return PCC_OK;
@@ -441,7 +428,7 @@ int sift_batch_rounds_host(pcc_index* ix, const CloudBatch& batch, float min_sca
                            SiftBatchResult* res) {
     hipStream_t s = ix->stream;
     const size_t n_clouds = batch.n_clouds;
-    SiftBatchScratch* b = ix->sift_batch;
+    SiftBatchScratch* b = scratch<SiftBatchScratch>(ix);
     SiftBatchRound cur;
     sift_batch_round(batch.n, n_clouds, 0, &cur);
     res->bases0 = cur.bases;
@@ -487,16 +474,16 @@ int sift_batch_rounds_host(pcc_index* ix, const CloudBatch& batch, float min_sca
 int sift_single(pcc_index* w, const CloudBatch& batch, size_t c, float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast,
                 std::vector<float>* kp) {
     const size_t n = batch.n[c], stride = batch.stride, rgb_stride = batch.rgb_stride;
-    if (!w->sift) w->sift = new SiftScratch();
+    SiftScratch* r = scratch<SiftScratch>(w);
     entered(w);
     const unsigned char *dpts = nullptr, *drgb = nullptr;
-    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.pts[c]), (n - 1) * stride + 12, PCC_MEM_HOST, w->sift->pts, &dpts));
-    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.rgb[c]), (n - 1) * rgb_stride + 4, PCC_MEM_HOST, w->sift->rgb, &drgb));
+    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.pts[c]), (n - 1) * stride + 12, PCC_MEM_HOST, r->pts, &dpts));
+    PCC_TRY(stage_in(w, static_cast<const unsigned char*>(batch.rgb[c]), (n - 1) * rgb_stride + 4, PCC_MEM_HOST, r->rgb, &drgb));
     size_t found = 0;
     PCC_TRY(sift_keypoints(w, dpts, n, stride, drgb, rgb_stride, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &found));
     kp->resize(found * 4);
     if (found) {
-        PCC_HIP(hipMemcpyAsync(kp->data(), w->sift->kp.p, found * 4 * sizeof(float), hipMemcpyDeviceToHost, w->stream));
+        PCC_HIP(hipMemcpyAsync(kp->data(), r->kp.p, found * 4 * sizeof(float), hipMemcpyDeviceToHost, w->stream));
         PCC_HIP(hipStreamSynchronize(w->stream));
     }
     return PCC_OK;
@@ -510,9 +497,7 @@ int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale
     hipStream_t s = ix->stream;
     const size_t n_clouds = batch.n_clouds;
     PCC_TRY(sync_info(ix));  // (a pending mirror of the handle's own grid would overwrite stats[2] later)
-    if (!ix->sift_batch) ix->sift_batch = new SiftBatchScratch();
-    if (!ix->sift) ix->sift = new SiftScratch();
-    SiftBatchScratch* b = ix->sift_batch;
+    SiftBatchScratch* b = scratch<SiftBatchScratch>(ix);
     const size_t brute_max = (size_t)ix->opt.sift_batch_brute_max;
     const BatchRoutes routes = batch_routes(batch.n, n_clouds, brute_max);
     CloudBatch small = batch;
@@ -528,7 +513,7 @@ int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale
     std::vector<std::vector<float>> large_kp(n_clouds);
     WorkLease lease;
     if (routes.n_large) {
-        PCC_TRY(lease.take(ix, &b->work, true));
+        PCC_TRY(lease.take(ix, b->work, true));
         for (size_t c = 0; c < n_clouds; ++c)
             if (batch.n[c] > brute_max)
                 PCC_TRY(sift_single(lease.w, batch, c, min_scale, nr_octaves, nr_scales_per_octave, min_contrast, &large_kp[c]));
@@ -555,7 +540,7 @@ int sift_keypoints_batch(pcc_index* ix, const CloudBatch& batch, float min_scale
             PCC_TRY(sift_batch_snap(ix, res, n_clouds, snap_radius, b->snap.as<int32_t>()));
             PCC_HIP(hipMemcpyAsync(b->down.as<char>() + snap_at, b->snap.p, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
-        PCC_HIP(hipMemcpyAsync(b->down.p, ix->sift->kp.p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
+        PCC_HIP(hipMemcpyAsync(b->down.p, scratch<SiftScratch>(ix)->kp.p, m * sizeof(float4), hipMemcpyDeviceToHost, s));
         PCC_HIP(hipStreamSynchronize(s));  // the call's last wait: keypoints and snapped indices
         const float* h_kp = b->down.as<float>();
         const int32_t* h_snap = reinterpret_cast<const int32_t*>(b->down.as<char>() + snap_at);

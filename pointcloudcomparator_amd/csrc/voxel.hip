@@ -85,7 +85,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
     px.blk_stats = ix->blk_stats.as<float>();
     px.n_blocks = &nblk;
     PCC_TRY(launch_pack(s, src, n, stride, ix->vox_a.as<float4>(), px));
-    float* h_blk = ix->pinned->vox_rows;
+    float* h_blk = ix->pinned()->vox_rows;
     PCC_HIP(hipMemcpyAsync(h_blk, ix->blk_stats.p, (size_t)nblk * 8 * sizeof(float), hipMemcpyDeviceToHost, s));
     PCC_HIP(hipStreamSynchronize(s));
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -136,7 +136,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
     hipLaunchKernelGGL(k_vox_heads, dim3(g1), dim3(256), 0, s, ix->vox_a.as<float4>(), order, n_sorted, d_gd, flags, (unsigned int)n);
     PCC_HIP(hipGetLastError());
     PCC_TRY(launch_exclusive_scan(ix, s, flags, n + 1, ix->vox_c));
-    PCC_HIP(hipMemcpyAsync(&ix->pinned->vox_count, flags + n, 4, hipMemcpyDeviceToHost, s));
+    PCC_HIP(hipMemcpyAsync(&ix->pinned()->vox_count, flags + n, 4, hipMemcpyDeviceToHost, s));
     // 5. centroids
     char* dout = static_cast<char*>(out);
     if (mem == PCC_MEM_HOST) {
@@ -148,7 +148,7 @@ int voxel_grid(pcc_index* ix, const void* pts, size_t n, size_t stride, int mem,
                        has_rgb, order, n_sorted, d_gd, flags, dout, out_stride, (unsigned int)n);
     PCC_HIP(hipGetLastError());
     PCC_HIP(hipStreamSynchronize(s));
-    const size_t nv = ix->pinned->vox_count;
+    const size_t nv = ix->pinned()->vox_count;
     *out_n = nv;
     if (mem == PCC_MEM_HOST && nv) {
         PCC_HIP(hipMemcpyAsync(out, dout, nv * out_stride, hipMemcpyDeviceToHost, s));
