@@ -400,6 +400,36 @@ int pcc_match_knn_batch_dims(pcc_index *ctx, size_t n_pairs,
                              const void *const *des2, const size_t *n2,
                              size_t stride_bytes, int dim, int mem, float threshold,
                              int32_t *out, float *out_d2 /* nullable */, size_t *out_offsets);
+/* The same on the 33 bins of a pcl::FPFHSignature33, from host or from device memory -- replaces matchFPFH
+ *   (src/comparator.cpp:877-910): a FLANN index on descriptors1, one k = 1 query per element of descriptors2, a match kept when
+ *   d2 < 0.25f (:901).  pcc_fpfh_descriptors produces the descriptors, this call consumes them.  Everything is as for
+ *   pcc_match_knn_batch_dims at dim != 3 (rows, the dummy 0 -- here :889 --, d2 < threshold strict, out_offsets, ctx as context
+ *   only: it supplies device, stream and scratch, its cloud and kept rows are neither read nor changed) except:
+ *   record: the first 33 floats of each element (pcl::FPFHSignature33::histogram).  stride_bytes is a multiple of 4 and
+ *     >= 132; of the last record of an array only 132 bytes are read, floats at 33 and beyond never.
+ *   validity: a record is valid when all 33 floats are finite.  An invalid reference takes part in no search, an invalid query
+ *     finds nothing, a distance that overflowed to +inf is no neighbour.  (The reference tests histogram[0] of a query alone,
+ *     :895, and leaves the rest to an assert inside PCL; pcc::matchFPFH prints its "Found NaN in FPFH descriptors" line, this
+ *     call prints nothing.)
+ *   distance: FLANN's L2_Simple over 33 terms in float32, every operation rounded on its own, in index order:
+ *     d = d0 * d0; d = d + d1 * d1; ... d = d + d32 * d32.  The order is part of the result.
+ *   out_d2 (nullable): parallel to out -- the squared distance of every kept match, 0.0f at each row's dummy.
+ *   exact ties: among references at exactly the same distance the LOWEST INDEX wins, whatever tie order the handle has --
+ *     FLANN's tree is built here in three dimensions only, so an N-dimensional FLANN visit order could not be checked against
+ *     anything.  pcc_index_stats afterwards: [1] the number of queries, [5] the number of tied queries, [6] is 0.
+ *   mem: PCC_MEM_HOST, or PCC_MEM_DEVICE: des1[p] and des2[p] are then device pointers (4-byte aligned, PCC_ERR_INVALID
+ *     otherwise) -- the [n][33] output of pcc_fpfh_descriptors(mem = PCC_MEM_DEVICE), stride 132, goes in as it is.  The arrays
+ *     of pointers and counts, out, out_d2 and out_offsets are HOST arrays in either memory space.
+ *   A pair with n1 == 0, n2 == 0 or no valid record in des1[p] yields the dummy alone; n_pairs == 0 touches no device.  One
+ *     upload, one pack launch (device memory only), one search launch, one read-back and one wait, whatever n_pairs is.
+ *   Refused before the handle is looked at, in this order: a bad memory space (PCC_ERR_INVALID), a bad stride
+ *     (PCC_ERR_INVALID), then everything pcc_match_knn_batch refuses (null arrays, totals of 2^31 records and more) and a
+ *     misaligned device pointer, a null handle last.  A refused call writes nothing. */
+int pcc_match_fpfh_batch(pcc_index *ctx, size_t n_pairs,
+                         const void *const *des1, const size_t *n1,
+                         const void *const *des2, const size_t *n2,
+                         size_t stride_bytes, int mem, float threshold,
+                         int32_t *out, float *out_d2 /* nullable */, size_t *out_offsets);
 
 /* ---- voxel-grid down-sampling -----------------------------------------------------------------------
  * replaces: pcl::VoxelGrid<PointXYZRGB> with setLeafSize(l, l, l) + filter, the first step of both

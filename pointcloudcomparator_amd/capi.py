@@ -33,7 +33,7 @@ SYMBOLS = [
     "pcc_index_sync", "pcc_index_engine", "pcc_index_set_engine",
     "pcc_nn1", "pcc_knn", "pcc_radius_count", "pcc_radius_fill", "pcc_radius_count_max", "pcc_radius_fill_max",
     "pcc_euclidean_clusters", "pcc_sor", "pcc_icp_step", "pcc_transform", "pcc_icp_align",
-    "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
+    "pcc_match_knn", "pcc_match_knn_batch", "pcc_match_knn_batch_dims", "pcc_match_fpfh_batch", "pcc_index_stats", "pcc_index_set_input", "pcc_index_enable_timing",
     "pcc_index_timing", "pcc_first_within", "pcc_voxel_grid",
     "pcc_normals", "pcc_region_growing", "pcc_region_growing_rgb", "pcc_region_growing_rgb_batch", "pcc_sac_plane", "pcc_plane_removal", "pcc_extract_clusters", "pcc_region_growing_segmentation", "pcc_euclidean_cluster_segmentation", "pcc_rigid_from_sums",
     "pcc_rigid_from_sums_about", "pcc_icp_step_about",
@@ -146,6 +146,7 @@ def _load() -> C.CDLL:
     lib.pcc_match_knn.argtypes = [vp, vp, sz, sz, i32, C.c_float, vp, C.POINTER(C.c_int32)]
     lib.pcc_match_knn_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, C.c_float, vp, vp]
     lib.pcc_match_knn_batch_dims.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, i32, C.c_float, vp, vp, vp]
+    lib.pcc_match_fpfh_batch.argtypes = [vp, sz, vp, vp, vp, vp, sz, i32, C.c_float, vp, vp, vp]
     lib.pcc_comm_unique_id.argtypes = [vp, sz]
     lib.pcc_comm_create_rank.argtypes = [vp, sz, i32, i32, i32, C.POINTER(vp)]
     lib.pcc_comm_create_local.argtypes = [C.POINTER(i32), i32, C.POINTER(vp)]
@@ -1419,6 +1420,45 @@ class Index:
         finally:
             if self._ties != own:
                 self.set_tie_order(own)
+        rows = [out[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
+        if not return_d2:
+            return rows
+        return rows, [dist[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
+
+    def match_fpfh_batch(self, pairs, threshold: float = 0.25, return_d2: bool = False):
+        """pcc_match_fpfh_batch with this handle as the context: the reference's matchFPFH (src/comparator.cpp:877-910) for every
+        (des1, des2) pair of (n, >= 33) float32 FPFH descriptor arrays of one row stride at once, on the 33 bins.  The pairs are
+        all NumPy arrays (host memory) or all CUDA tensors (device memory, as fpfh_descriptors leaves them on a handle over a
+        CUDA tensor); a mixture is a ValueError.  Returns one int32 NumPy array per pair: the dummy 0, then per row of des2 in
+        order the index of its nearest row of des1 when the squared distance is < threshold; among rows of des1 at exactly the
+        same distance the lowest index.  return_d2: also the squared distances -- the result is then (indices, d2), two lists of
+        arrays of equal shapes (0.0 beside each row's dummy).  The cloud the handle indexes is neither read nor changed."""
+        pairs = list(pairs)
+        n = len(pairs)
+        flat = [x for ab in pairs for x in ab]
+        on_device = [_is_torch(x) and x.is_cuda for x in flat]
+        if any(on_device) and not all(on_device):
+            raise ValueError("match_fpfh_batch takes NumPy arrays or CUDA tensors, not both in one call")
+        mem = MEM_DEVICE if any(on_device) else MEM_HOST
+        for x in flat:
+            assert x.ndim == 2 and x.shape[1] >= 33, "FPFH descriptor arrays are (n, >= 33) float32"
+        args = [(_points(a), _points(b)) for a, b in pairs]
+        assert all(x[3] == mem for ab in args for x in ab), "host descriptor arrays are NumPy arrays"
+        strides = {x[2] for ab in args for x in ab if x[1] > 1}
+        assert len(strides) <= 1, "every descriptor array of a batch must have the same row stride"
+        stride = strides.pop() if strides else 132
+        vps, szs = (C.c_void_p * max(n, 1)), (C.c_size_t * max(n, 1))
+        d1 = vps(*[a[0] if a[1] else None for a, _ in args])
+        d2 = vps(*[b[0] if b[1] else None for _, b in args])
+        n1 = szs(*[a[1] for a, _ in args])
+        n2 = szs(*[b[1] for _, b in args])
+        out = np.empty(sum(b[1] for _, b in args) + n, dtype=np.int32)
+        dist = np.empty(len(out), dtype=np.float32) if return_d2 else None
+        off = np.zeros(n + 1, dtype=np.uintp)
+        st = self._before(*flat) if mem == MEM_DEVICE else None
+        _check(LIB.pcc_match_fpfh_batch(self._h, n, d1, n1, d2, n2, stride, mem, np.float32(threshold), out.ctypes.data,
+                                        dist.ctypes.data if return_d2 else None, off.ctypes.data))
+        self._after(st)
         rows = [out[int(off[p]):int(off[p + 1])].copy() for p in range(n)]
         if not return_d2:
             return rows

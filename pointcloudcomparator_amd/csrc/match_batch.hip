@@ -1,5 +1,6 @@
 // match_batch.hip -- descriptor matching for EVERY cluster pair of a comparison at once (gfx950): pcc_match_knn_batch, and
-// pcc_match_knn_batch_dims, which is this search for dim == 3 and match_dims.hip's for every other dimension.
+// pcc_match_knn_batch_dims, which is this search for dim == 3 and match_dims.hip's for every other dimension.  The entry point
+// of pcc_match_fpfh_batch (the 33-bin search of match_fpfh.hip) is here too, beside the argument checks the three share.
 //
 // The reference calls matchRIFTFeaturesKnn (src/comparator.cpp:560-588) from its cluster-matching loop (:1296-1365, call at
 // :1322): per cluster of cloud 1 the three nearest clusters of cloud 2, each behind two size gates.  No call depends on an
@@ -323,9 +324,9 @@ static int check_batch_stride(size_t stride, int dim) {
 // Everything pcc_match_knn_batch refuses before it looks at the handle, for records of which 4 * dim bytes are read: all of
 // it host arithmetic.  (check_points' own stride rule is the 3-D one, so the pairs are checked here.)
 static int check_batch_args(size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2, const size_t* n2,
-                            size_t stride, int dim, int mem, const int32_t* out, const size_t* out_offsets) {
+                            size_t stride, int dim, int mem, const int32_t* out, const size_t* out_offsets, bool device_ok = false) {
     PCC_TRY(check_mem(mem));
-    if (mem != PCC_MEM_HOST) { set_error("pcc_match_knn_batch takes host descriptor arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
+    if (mem != PCC_MEM_HOST && !device_ok) { set_error("pcc_match_knn_batch takes host descriptor arrays only (PCC_MEM_HOST)"); return PCC_ERR_UNSUPPORTED; }
     PCC_TRY(check_batch_stride(stride, dim));
     if (!out_offsets) { set_error("null out_offsets"); return PCC_ERR_INVALID; }
     if (n_pairs >= (1ull << 31)) { set_error("more than 2^31 pairs"); return PCC_ERR_UNSUPPORTED; }
@@ -373,5 +374,22 @@ int pcc_match_knn_batch_dims(pcc_index* ctx, size_t n_pairs, const void* const* 
     // three dimensions: the search of pcc_match_knn_batch itself, tie order and FLANN walk included
     if (dim == 3) return match_knn_batch(ctx, n_pairs, des1, n1, des2, n2, stride, threshold, out, out_d2, out_offsets);
     return match_knn_batch_dims(ctx, n_pairs, des1, n1, des2, n2, stride, dim, threshold, out, out_d2, out_offsets);
+}
+
+int pcc_match_fpfh_batch(pcc_index* ctx, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
+                         const size_t* n2, size_t stride, int mem, float threshold, int32_t* out, float* out_d2, size_t* out_offsets) {
+    using namespace pcc;
+    // the memory space, the stride, then everything pcc_match_knn_batch refuses: all before the handle is looked at
+    PCC_TRY(check_batch_args(n_pairs, des1, n1, des2, n2, stride, 33, mem, out, out_offsets, /*device_ok=*/true));
+    if (mem == PCC_MEM_DEVICE)  // (the pack kernel reads the records as floats)
+        for (size_t p = 0; p < n_pairs; ++p)
+            if ((n1[p] && reinterpret_cast<uintptr_t>(des1[p]) % 4) || (n2[p] && reinterpret_cast<uintptr_t>(des2[p]) % 4)) {
+                set_error("descriptor arrays in device memory must be 4-byte aligned (pair %zu)", p);
+                return PCC_ERR_INVALID;
+            }
+    if (!ctx) { set_error("null index"); return PCC_ERR_INVALID; }
+    if (n_pairs == 0) { out_offsets[0] = 0; return PCC_OK; }
+    PCC_ENTER(ctx);
+    return match_fpfh_batch(ctx, n_pairs, des1, n1, des2, n2, stride, mem, threshold, out, out_d2, out_offsets);
 }
 }  // extern "C"

@@ -343,8 +343,8 @@ struct BatchStaging : Scratch {
     DevBuf dev;
 };
 struct RiftBatchItem;      // rift_batch_plan.hpp: a work item of the exhaustive row builder
-// the staging and result buffers of pcc_match_knn_batch (match_batch.hip), pcc_match_knn_batch_dims (match_dims.hip) and
-// pcc_cluster_matching (cluster_match.hip)
+// the staging and result buffers of pcc_match_knn_batch (match_batch.hip), pcc_match_knn_batch_dims (match_dims.hip),
+// pcc_match_fpfh_batch (match_fpfh.hip) and pcc_cluster_matching (cluster_match.hip)
 struct MatchBatchScratch : Scratch {
     static constexpr ScratchSlot slot = SCRATCH_MATCH_BATCH;
     HostBuf up, down, tree_up, tree_down;  // pinned: table + records going up, best + second coming down; trees + walk items, found
@@ -764,6 +764,9 @@ int icp_align_impl(pcc_index* ix, const IcpHooks* hooks, const void* src, size_t
 // match_dims.hip: the search of pcc_match_knn_batch_dims for dim != 3 (arguments checked by the entry point in match_batch.hip)
 int match_knn_batch_dims(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
                          const size_t* n2, size_t stride, int dim, float threshold, int32_t* out, float* out_d2, size_t* out_offsets);
+// match_fpfh.hip: the search of pcc_match_fpfh_batch (arguments checked by the entry point in match_batch.hip)
+int match_fpfh_batch(pcc_index* ix, size_t n_pairs, const void* const* des1, const size_t* n1, const void* const* des2,
+                     const size_t* n2, size_t stride, int mem, float threshold, int32_t* out, float* out_d2, size_t* out_offsets);
 int check_mem(int mem);  // PCC_MEM_HOST or PCC_MEM_DEVICE
 int check_points(const void* pts, size_t n, size_t stride, int mem);
 int stage_queries(pcc_index* ix, const void* q, size_t nq, size_t stride, int mem, Nn1Call* search = nullptr);
