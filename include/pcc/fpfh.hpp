@@ -44,6 +44,44 @@ inline PointCloud<FPFHSignature33>::Ptr processFPFH(const PointCloud<PointXYZRGB
     return descriptors;
 }
 
+// processFPFH for every cloud of `clouds` in ONE library call (pcc_fpfh_descriptors_batch): element c of the result is what
+// processFPFH(clouds[c]) returns, bit for bit (a null or empty cloud, or one without a finite point, gives empty descriptors).
+// The clouds are laid one behind the other for the call.  It prints nothing.
+// point_indices (nullable): per cloud, the index in that cloud of the point every returned descriptor belongs to.
+// ctx (nullable): any tree whose handle may serve as the call's context; the cloud it indexes is not read.
+inline std::vector<PointCloud<FPFHSignature33>::Ptr> processFPFHBatch(const std::vector<PointCloud<PointXYZRGB>::Ptr>& clouds,
+                                                                      search::KdTree<PointXYZRGB>* ctx = nullptr,
+                                                                      std::vector<std::vector<int> >* point_indices = nullptr) {
+    std::vector<PointCloud<FPFHSignature33>::Ptr> result(clouds.size());
+    for (PointCloud<FPFHSignature33>::Ptr& d : result) {
+        d.reset(new PointCloud<FPFHSignature33>);
+        d->width = 0;
+        d->height = 1;
+        d->is_dense = true;
+    }
+    if (point_indices) point_indices->assign(clouds.size(), std::vector<int>());
+    std::vector<size_t> offsets(clouds.size() + 1, 0);
+    for (size_t c = 0; c < clouds.size(); ++c) offsets[c + 1] = offsets[c] + (clouds[c] ? clouds[c]->size() : 0);
+    const size_t total = offsets.back();
+    if (total == 0) return result;  // (no library call)
+    std::vector<PointXYZRGB> all;
+    all.reserve(total);
+    for (size_t c = 0; c < clouds.size(); ++c)
+        if (clouds[c]) all.insert(all.end(), clouds[c]->points.begin(), clouds[c]->points.end());
+    std::vector<size_t> out_offsets(clouds.size() + 1, 0);
+    std::vector<FPFHSignature33> hist(total);
+    std::vector<int32_t> index(total);
+    check(pcc_fpfh_descriptors_batch(detail::batchContext<PointXYZRGB>(ctx ? ctx->handle() : nullptr), &all[0].x, sizeof(PointXYZRGB), offsets.data(),
+                                     clouds.size(), PCC_MEM_HOST, 0.03, 0.05, 11, 11, 11, hist[0].histogram, index.data(), out_offsets.data()));
+    for (size_t c = 0; c < clouds.size(); ++c) {
+        PointCloud<FPFHSignature33>& d = *result[c];
+        d.points.assign(hist.begin() + out_offsets[c], hist.begin() + out_offsets[c + 1]);
+        d.width = (std::uint32_t)d.points.size();
+        if (point_indices) (*point_indices)[c].assign(index.begin() + out_offsets[c], index.begin() + out_offsets[c + 1]);
+    }
+    return result;
+}
+
 // ---- matchFPFH (src/comparator.cpp:877-910) for many pairs at once ---------------------------------------------------------------
 // pairs[p] = (descriptors1, descriptors2); element p of the result is the dummy 0 (:889), then per element of descriptors2 in order
 // the index of its nearest element of descriptors1 when the squared distance over the 33 bins is < threshold (:901).  A

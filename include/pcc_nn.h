@@ -233,10 +233,20 @@ enum pcc_option {
                                     0.41 / 0.73 / 1.06 / 1.22 ms through the batch kernels against 0.52 / 0.89 / 1.06 / 1.21 ms on
                                     the work handle at 2048 / 4096 / 8192 / 16 384 points: the batch kernels never lose up to 8192
                                     and tie above it, where only the lone cloud was measured.  No result bit depends on it. */
-    PCC_OPT_FPFH_LAYOUT = 29     /* pcc_fpfh_descriptors, the SPFH and the weighting kernel: 1 = a wave per row -- every lane evaluates one row
+    PCC_OPT_FPFH_LAYOUT = 29,    /* pcc_fpfh_descriptors, the SPFH and the weighting kernel: 1 = a wave per row -- every lane evaluates one row
                                     entry's pair features and the votes are counted in integers; in the weighting every lane adds, in row
                                     order, the shares of the bin it owns while three more lanes carry the running sums (default);
                                     0 = one lane per row (PCL's loops as they stand).  Same bits either way. */
+    PCC_OPT_FPFH_BATCH_BRUTE_MAX = 30  /* pcc_fpfh_descriptors_batch: clusters of up to this many points get their radius rows from the
+                                    exhaustive builder that serves the whole batch at once (n^2 distance tests per cluster); larger
+                                    clusters take pcc_index_set_input + pcc_fpfh_descriptors inside the same call, one by one, on a
+                                    work handle kept in ctx (PCC_FPFH_BATCH_BRUTE_MAX in the environment of a new handle).  Default
+                                    8192.  Measured (profiles/fpfh_batch_exp.txt, device memory): 60 clusters of 20 ... 5000
+                                    points take 4.02 / 2.24 / 1.49 / 1.49 ms at 2048 / 4096 / 8192 / 16 384 (10 / 3 / 0 / 0 of them on
+                                    the work handle); a cluster ALONE takes 0.24 / 0.30 / 0.46 / 0.85 ms through the batch kernels
+                                    against 0.34 / 0.37 / 0.48 / 0.69 ms on the work handle at 2048 / 4096 / 8192 / 16 384 points: the
+                                    crossover lies between 8192 and 16 384.  Only these four sizes were measured.  No result bit
+                                    depends on it. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -811,6 +821,44 @@ int pcc_rift_descriptors_batch(pcc_index *ctx, size_t n_clouds,
 int pcc_fpfh_descriptors(pcc_index *index, int mem, double normal_radius, double fpfh_radius,
                          int nr_bins_f1, int nr_bins_f2, int nr_bins_f3,
                          float *out_histograms, int32_t *out_point_index, size_t *n_out);
+/* The same for EVERY cluster of a segmentation at once -- the producer of pcc_match_fpfh_batch's descriptor arrays.  The
+ *   clusters of a call are concatenated on the device and every stage runs once over all of them; launches and host waits
+ *   do not depend on n_clusters.
+ *   ctx: any index handle, as for the other batch calls: it supplies device, stream and scratch; its cloud, tie order and
+ *     kept rows are neither read nor changed.
+ *   Cluster c is the points offsets[c] .. offsets[c + 1] of pts (records stride_bytes apart, x, y, z first, memory space
+ *     `mem`; no colour is read): pcc_cluster_descriptors' input, what pcc_region_growing_segmentation and
+ *     pcc_euclidean_cluster_segmentation write as out_cluster_points / out_offsets.  offsets is a HOST array.
+ *   Its result is, bit for bit and in order, what pcc_index_create on that cluster alone + pcc_fpfh_descriptors returns:
+ *     rows out_offsets[c] .. out_offsets[c + 1] of out_histograms and out_point_index, the point indices LOCAL to the
+ *     cluster and ascending.  No point of another cluster enters a row, however the clusters overlap in space.  An empty
+ *     cluster, or one without a finite point, yields an empty slice.
+ *   out_histograms[offsets[n_clusters] - offsets[0]][33] and out_point_index (as many rows) are in memory space `mem`;
+ *     out_offsets[n_clusters + 1] is a HOST array in either space.  With PCC_MEM_DEVICE the descriptors are written where
+ *     they stay: out_histograms + 33 * out_offsets[c] with stride 132 is a valid des1[p] / des2[p] of
+ *     pcc_match_fpfh_batch(mem = PCC_MEM_DEVICE), and no descriptor crosses to the host between the two calls.
+ *   normal_radius <= fpfh_radius (the reference's 0.03 / 0.05): ONE CSR is built, at fpfh_radius -- a sorted row at
+ *     normal_radius is the prefix of it with d2 < float(normal_radius^2), and the plane fit walks that prefix.  Otherwise two.
+ *   Clusters above PCC_OPT_FPFH_BATCH_BRUTE_MAX points take the single path inside the call, on a work handle kept in ctx, in
+ *     the caller's memory space (same bits); their slices are spliced in cluster order.  pcc_index_stats afterwards reports in
+ *     [0] the points the batch kernels served, in [1] the points sent through the work handle and in [2] the CSRs the batch
+ *     route built (0, 1 or 2).
+ *   Host waits with no cluster above the limit: one per CSR built, one for the slice bounds and, for a host caller, one for
+ *     the rows.
+ *   n_clusters == 0: PCC_OK, out_offsets[0] = 0, no device is touched.  Refused before the handle is looked at, in this
+ *     order: a bad memory space; a null offsets or out_offsets, or null pts / out_histograms / out_point_index while a
+ *     cluster holds a point; a bad stride, or pts / outputs that are not 4-byte aligned; offsets that decrease
+ *     (PCC_ERR_INVALID), then 2^31 points or clusters and more (PCC_ERR_UNSUPPORTED); a radius that is not positive and
+ *     finite, then bins other than 11, 11, 11 (PCC_ERR_UNSUPPORTED), with pcc_fpfh_descriptors' messages; a null handle
+ *     last.  A refused call writes nothing.  A CSR of 2^32 entries or more over the whole batch is PCC_ERR_OVERFLOW. */
+int pcc_fpfh_descriptors_batch(pcc_index *ctx,
+                               const void *pts, size_t stride_bytes,
+                               const size_t *offsets /* HOST [n_clusters + 1] */, size_t n_clusters, int mem,
+                               double normal_radius, double fpfh_radius,
+                               int nr_bins_f1, int nr_bins_f2, int nr_bins_f3,
+                               float *out_histograms /* mem, [offsets[n_clusters] - offsets[0]][33] */,
+                               int32_t *out_point_index /* mem, same rows */,
+                               size_t *out_offsets /* HOST [n_clusters + 1] */);
 /* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
  * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
  *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)
@@ -1204,6 +1252,8 @@ int pcc_change_detection(pcc_index *ctx, const void *a, size_t n_a, size_t a_str
  *  (last search that listed them: from 2M queries on, or PCC_OPT_NN1_KERNEL = 2).
  *  After pcc_rift_descriptors_batch on the handle: [0] points whose radius rows the batch kernels built, [1] points of the
  *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX).
+ *  After pcc_fpfh_descriptors_batch on the handle: [0] points the batch kernels served, [1] points of the clusters sent
+ *  through the work handle (above PCC_OPT_FPFH_BATCH_BRUTE_MAX), [2] CSRs the batch route built (0, 1 or 2).
  *  After pcc_sift_keypoints_batch on the handle: [0] points that went through the batch kernels, [1] points of the clouds sent
  *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
  *  After pcc_cluster_descriptors on the handle: [0] dense-route points, [1] SIFT-route points, [2] octave rounds, [3] keypoints,

@@ -21,7 +21,8 @@ KNN_MAX_K = 65536
 (OPT_GRID_PPC, OPT_GRID_TRIM, OPT_FAR_MODE, OPT_ICP_WARM, OPT_ICP_DEVICE_LOOP, OPT_EC_CELLS, OPT_SORT_MP_MIN,
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
- OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX, OPT_FPFH_LAYOUT) = range(1, 30)
+ OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX, OPT_FPFH_LAYOUT,
+ OPT_FPFH_BATCH_BRUTE_MAX) = range(1, 31)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -43,7 +44,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
-    "pcc_change_detection", "pcc_fpfh_descriptors",
+    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -119,6 +120,7 @@ def _load() -> C.CDLL:
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_fpfh_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_fpfh_descriptors_batch.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
     lib.pcc_sift_keypoints_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, C.c_double, vp, vp, sz, vp]
@@ -1022,6 +1024,47 @@ class Index:
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
 
+    def fpfh_descriptors_batch(self, clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05,
+                               nr_bins=(11, 11, 11)):
+        """pcc_fpfh_descriptors_batch with this handle as the context: the reference's processFPFH for every cluster in one call.
+        clouds_or_points: a list of (n, >= 3) float32 arrays of one kind (NumPy arrays or torch tensors, e.g. (n, 3) points or
+        32-byte pcl::PointXYZRGB records; they are laid one behind the other for the call), or with `offsets` ONE such array,
+        host or CUDA, read in place: cluster c is rows offsets[c] .. offsets[c + 1] -- what region_growing_segmentation /
+        euclidean_cluster_segmentation return as cluster_points / offsets.  Returns one (histograms (m, 33) float32, point index
+        (m,) int32 local to the cluster) per cluster, each what Index(cluster).fpfh_descriptors() returns; an empty cluster or one
+        without a finite point gives m = 0.  For CUDA input these are CUDA tensors, views of the call's one output array:
+        match_fpfh_batch takes them without a copy.  The cloud the handle indexes is neither read nor changed."""
+        if offsets is None:
+            clouds = list(clouds_or_points)
+            sizes = [len(c) for c in clouds]
+            off_in = np.zeros(len(clouds) + 1, dtype=np.uintp)
+            off_in[1:] = np.cumsum(sizes, dtype=np.uintp)
+            some = [c for c in clouds if len(c)]
+            if not some:
+                points = np.zeros((0, 3), np.float32)
+            elif _is_torch(some[0]):
+                import torch
+                points = some[0] if len(some) == 1 else torch.cat(some, 0)
+            else:
+                points = some[0] if len(some) == 1 else np.concatenate(some, 0)
+        else:
+            points = clouds_or_points
+            off_in = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_torch(offsets) else offsets), dtype=np.uintp)
+        ptr, n, stride, mem = _points(points)
+        assert off_in.ndim == 1 and len(off_in) >= 1, "offsets holds n_clusters + 1 entries"
+        n_clusters = len(off_in) - 1
+        assert n_clusters == 0 or int(off_in.max()) <= n, "offsets reach beyond the points"
+        total = int(off_in[-1]) - int(off_in[0]) if n_clusters and off_in[-1] >= off_in[0] else 0
+        hist, ph = _out(points, (max(total, 1), 33), np.float32)
+        index, pi = _out(points, (max(total, 1),), np.int32)
+        off = np.zeros(n_clusters + 1, dtype=np.uintp)
+        b1, b2, b3 = nr_bins
+        st = self._before(points, hist, index) if mem == MEM_DEVICE else None
+        _check(LIB.pcc_fpfh_descriptors_batch(self._h, ptr if n else None, stride, off_in.ctypes.data, n_clusters, mem, float(normal_radius),
+                                              float(fpfh_radius), int(b1), int(b2), int(b3), ph, pi, off.ctypes.data))
+        self._after(st)
+        return [(hist[int(off[c]):int(off[c + 1])], index[int(off[c]):int(off[c + 1])]) for c in range(n_clusters)]
+
     def rift_descriptors_batch(self, clouds, rgbs=None, normal_radius: float = 0.03, gradient_radius: float = 0.03,
                                rift_radius: float = 0.05, nr_distance_bins: int = 4, nr_gradient_bins: int = 8):
         """pcc_rift_descriptors_batch with this handle as the context: the descriptors of every cloud in one call (the
@@ -1484,6 +1527,16 @@ def rift_descriptors_batch(clouds, rgbs=None, normal_radius: float = 0.03, gradi
         return ctx.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
         return own.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
+
+
+def fpfh_descriptors_batch(clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05, nr_bins=(11, 11, 11), ctx=None):
+    """FPFH descriptors of every cluster at once (pcc_fpfh_descriptors_batch): a list of (histograms, point index) per cluster.
+    ctx: an Index that lends its device, stream and scratch (its own cloud is left as it is); None makes a one-point handle
+    for the call."""
+    if ctx is not None:
+        return ctx.fpfh_descriptors_batch(clouds_or_points, offsets, normal_radius, fpfh_radius, nr_bins)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.fpfh_descriptors_batch(clouds_or_points, offsets, normal_radius, fpfh_radius, nr_bins)
 
 
 def region_growing_rgb_batch(clouds, rgbs=None, distance: float = 10.0, point_colour: float = 6.0, region_colour: float = 5.0,

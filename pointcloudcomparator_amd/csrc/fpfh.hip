@@ -219,6 +219,8 @@ k_fpfh_weight1(const unsigned long long* __restrict__ keys, const unsigned int* 
     }
 }
 
+}  // namespace
+
 int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, int nr_bins_f2, int nr_bins_f3) {
     for (double r : {normal_radius, fpfh_radius})
         if (!(r > 0) || !std::isfinite(r)) { set_error("bad radius"); return PCC_ERR_INVALID; }
@@ -229,33 +231,38 @@ int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, 
     return PCC_OK;
 }
 
-// the stages over the indexed cloud of ix: out_hist[n * 33], out_index[n] on the device; *n_out on
-// the host.  Waits: the totals of the CSRs and, at the end, the count.
-int fpfh_descriptors(pcc_index* ix, double normal_radius, double fpfh_radius, float* out_hist, int32_t* out_index, size_t* n_out) {
+// The stages over any packed cloud -- the indexed cloud of a handle, or the concatenation of a batch (fpfh_batch.hip): refs[n],
+// `order` a cell_refs-shaped array whose first gd->n_valid entries name the points to take (their w), `rows` the sorted radius
+// rows of that cloud as a CSR.  normals (nullable): the caller fits the planes itself -- it fills normals[n] and hands over the
+// CSR at fpfh_radius, and `rows` is not asked.  out_hist[n * 33], out_index[n] on the device; *pos_out: uint32[n + 1] on the
+// device, the exclusive scan of the flags of cloud2, pos[n] = the rows written.  Waits: the totals of the CSRs.
+int fpfh_stages(pcc_index* ix, const float4* refs, const float4* cell_refs, const GridDev* gd, size_t n, const RiftRows& rows,
+                double normal_radius, double fpfh_radius, const FpfhNormals* normals, float* out_hist, int32_t* out_index,
+                const unsigned int** pos_out) {
     hipStream_t s = ix->stream;
     FpfhScratch* r = scratch<FpfhScratch>(ix);
-    const size_t n = ix->n_orig;
     const unsigned int un = (unsigned int)n;
     const float origin[3] = {0.f, 0.f, 0.f};
     PCC_TRY(r->normals.reserve(n * sizeof(float4)));
     PCC_TRY(r->spfh.reserve(n * FPFH_BINS * sizeof(float)));
     PCC_TRY(r->flags.reserve(n * sizeof(unsigned int)));
     PCC_TRY(r->pos.reserve((n + 1) * sizeof(unsigned int)));
-    const float4* refs = ix->refs.as<float4>();
-    const float4* cell_refs = ix->cell_refs.as<float4>();
-    const GridDev* gd = ix->d_grid.as<GridDev>();
     const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
     // rows at normal_radius: the plane fit; cloud2 and the place of each of its points in the output
     const unsigned long long* keys = nullptr;
     const unsigned int* off32 = nullptr;
-    PCC_TRY(radius_csr(ix, normal_radius, &keys, &off32));
-    PCC_TRY(launch_normals_csr(ix, keys, off32, origin, r->normals.as<float4>()));
+    if (normals) {
+        PCC_TRY((*normals)(r->normals.as<float4>(), &keys, &off32));
+    } else {
+        PCC_TRY(rows(normal_radius, &keys, &off32));
+        PCC_TRY(launch_normals_csr(s, refs, cell_refs, gd, n, keys, off32, origin, r->normals.as<float4>()));
+    }
     PCC_HIP(hipMemsetAsync(r->pos.as<unsigned int>() + n, 0, sizeof(unsigned int), s));
     hipLaunchKernelGGL(k_fpfh_flags, dim3(blocks), dim3(256), 0, s, r->normals.as<float4>(), un, r->flags.as<unsigned int>(), r->pos.as<unsigned int>());
     PCC_HIP(hipGetLastError());
     PCC_TRY(launch_exclusive_scan(ix, s, r->pos.as<unsigned int>(), n + 1, r->scan_tmp));
     // rows at fpfh_radius (same radius: same rows): the SPFH signatures, then their weighted sums
-    if (fpfh_radius != normal_radius) PCC_TRY(radius_csr(ix, fpfh_radius, &keys, &off32));
+    if (!normals && fpfh_radius != normal_radius) PCC_TRY(rows(fpfh_radius, &keys, &off32));
     const unsigned int wb = (unsigned int)std::min<size_t>((n + 3) / 4, 8192);
     ev_mark(ix, EV_MAIN0);
     if (ix->opt.fpfh_layout == 1) {
@@ -277,8 +284,24 @@ int fpfh_descriptors(pcc_index* ix, double normal_radius, double fpfh_radius, fl
     }
     PCC_HIP(hipGetLastError());
     ev_mark(ix, EV_FB1);
+    *pos_out = r->pos.as<unsigned int>();
+    return PCC_OK;
+}
+
+namespace {
+
+// the stages over the indexed cloud of ix: out_hist[n * 33], out_index[n] on the device; *n_out on
+// the host.  Waits: the totals of the CSRs and, at the end, the count.
+int fpfh_descriptors(pcc_index* ix, double normal_radius, double fpfh_radius, float* out_hist, int32_t* out_index, size_t* n_out) {
+    const size_t n = ix->n_orig;
+    const RiftRows rows = [ix](double radius, const unsigned long long** keys, const unsigned int** offsets) -> int {
+        return radius_csr(ix, radius, keys, offsets);
+    };
+    const unsigned int* pos = nullptr;
+    PCC_TRY(fpfh_stages(ix, ix->refs.as<float4>(), ix->cell_refs.as<float4>(), ix->d_grid.as<GridDev>(), n, rows, normal_radius, fpfh_radius, nullptr,
+                        out_hist, out_index, &pos));
     unsigned int kept = 0;
-    PCC_TRY(read_back(ix, r->pos.as<unsigned int>() + n, &kept));
+    PCC_TRY(read_back(ix, pos + n, &kept));
     *n_out = kept;
     return PCC_OK;
 }

@@ -221,6 +221,12 @@ struct Options {
                                     // k-NN rows from the exhaustive segmented kernel over the whole batch (region_rgb_batch.hip); larger ones take
                                     // the single path, one by one, on a work handle.  Measured (EXPERIMENTS.md, "Batched colour region growing"):
                                     // beside others the batch kernels win at every size measured (up to 8000 points); a cloud alone ties from 8192 on
+    int fpfh_batch_brute_max = 8192;   // PCC_OPT_FPFH_BATCH_BRUTE_MAX: clusters of a pcc_fpfh_descriptors_batch call up to this many points get their
+                                    // radius rows from the exhaustive builder over the whole batch (fpfh_batch.hip); larger ones take the single
+                                    // path, one by one, on a work handle.  Measured (EXPERIMENTS.md, "Batched FPFH descriptors"; device memory):
+                                    // 60 clusters of 20 ... 5000 points take 4.02 / 2.24 / 1.49 / 1.49 ms at 2048 / 4096 / 8192 / 16 384; a cluster alone is cheaper on the work
+                                    // handle somewhere between 8192 points (0.46 against 0.48 ms) and 16 384 (0.85 against 0.69 ms): only 2048,
+                                    // 4096, 8192 and 16 384 were measured
     int overlap_prep = 1;           // PCC_OPT_OVERLAP_PREP: a k = 1 search that follows setInputCloud directly packs and sorts its queries on a
                                     // second stream while the build's cell sort is still running (they share nothing but the grid parameters);
                                     // from 2M queries on, 2 = at every size
@@ -300,7 +306,7 @@ static_assert(offsetof(PinnedWords, fb_mirror) >= sizeof(PinnedWords::readback) 
 struct Scratch { virtual ~Scratch() = default; };
 enum ScratchSlot {
     SCRATCH_RIFT, SCRATCH_FPFH, SCRATCH_SIFT, SCRATCH_RIFT_BATCH, SCRATCH_SIFT_BATCH, SCRATCH_RGB_BATCH, SCRATCH_MATCH_COLOUR,
-    SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH,
+    SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH, SCRATCH_FPFH_BATCH,
     SCRATCH_SLOTS
 };
 // A work handle: a second handle a feature indexes clouds of its own on (the caller's stream for the length of a call:
@@ -690,6 +696,15 @@ int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal
 // the caller's buffers for uint32 offsets[total + 1] (+ the same as int64) and the entries.  One wait: the CSR's total
 int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
                       DevBuf& offs, DevBuf& keys, const unsigned long long** keys_out, const unsigned int** offsets_out);
+// fpfh.hip: the radius and bin checks of pcc_fpfh_descriptors and its batch form
+int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, int nr_bins_f2, int nr_bins_f3);
+// fpfh.hip: the stages of pcc_fpfh_descriptors over any packed cloud (fpfh_batch.hip: the concatenation of a batch), arguments as
+// rift_stages'.  normals (nullable): the caller's own plane fit -- it fills normals[n] and hands over the CSR at fpfh_radius, and
+// `rows` is not asked.  *pos: uint32[n + 1] on the device, where every point of cloud2 lies in the output, pos[n] = the rows written
+typedef std::function<int(float4* normals, const unsigned long long** keys, const unsigned int** offsets)> FpfhNormals;
+int fpfh_stages(pcc_index* ix, const float4* refs, const float4* order, const GridDev* gd, size_t n, const RiftRows& rows,
+                double normal_radius, double fpfh_radius, const FpfhNormals* normals, float* out_hist, int32_t* out_index,
+                const unsigned int** pos);
 // sift.hip: the detector on device arrays: the keypoints are left in SiftScratch::kp, *n_out of them
 int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t stride, const unsigned char* rgb, size_t rgb_stride,
                    float min_scale, int nr_octaves, int nr_scales_per_octave, float min_contrast, size_t* n_out);
