@@ -1,7 +1,7 @@
 // point_types.hpp -- POD point types and containers with the layouts the reference's PCL types
 // have at the search boundary: pcl::PointXYZ (16 B), pcl::PointXYZRGB
 // (32 B, 16-byte aligned, x y z at 0/4/8, rgb at 16), pcl::PointWithScale (32 B), pcl::Histogram<N> (RIFT32 =
-// pcl::Histogram<32>, reference src/comparator.cpp:9), pcl::PointIndices, pcl::Correspondence.
+// pcl::Histogram<32>, reference src/comparator.cpp:9), pcl::VFHSignature308, pcl::PointIndices, pcl::Correspondence.
 // Only what the hot path touches; no PCL dependency.
 #pragma once
 #include <cstdint>
@@ -27,6 +27,11 @@ struct alignas(16) PointXYZRGB {
 template <int N>
 struct Histogram {
     float histogram[N];
+};
+// pcl::VFHSignature308: the 45 bins of f1, of f2, of f3 and of f4, then the 128 bins of the viewpoint component
+struct VFHSignature308 {
+    float histogram[308];
+    static int descriptorSize() { return 308; }
 };
 // pcl::Normal: normal[3] + pad, curvature + pad (32 bytes)
 struct alignas(16) Normal {

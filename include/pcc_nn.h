@@ -859,6 +859,49 @@ int pcc_fpfh_descriptors_batch(pcc_index *ctx,
                                float *out_histograms /* mem, [offsets[n_clusters] - offsets[0]][33] */,
                                int32_t *out_point_index /* mem, same rows */,
                                size_t *out_offsets /* HOST [n_clusters + 1] */);
+/* ---- VFH descriptor of the indexed cloud -------------------------------------------------------------
+ * replaces: processVHF (src/comparator.cpp:482-516) for one cloud: pcl::NormalEstimation (setRadiusSearch 0.03) and
+ *   pcl::VFHEstimation<PointXYZRGB, Normal, VFHSignature308> with setNormalizeBins(true) and setNormalizeDistance(false) --
+ *   the reference's only GLOBAL descriptor: one 308-bin histogram for the whole cloud.  normalize-bins on, normalize-distance
+ *   off, no size component and the viewpoint (0, 0, 0) are constants of the call.  The PCL stage is restated from the
+ *   published algorithm ([recalled]): PCL 1.7 is not available to compare against, parity with it is unpinned.
+ *   normals    pcc_normals_radius at normal_radius, viewpoint origin.  A point whose row has fewer than 3 entries keeps a NaN
+ *              normal; processVHF does NOT remove such points (unlike processFPFH): they stay in the cloud and vote;
+ *   centroids  xyz: three float chains from 0.0f over the n points in index order, each divided by float(n).  Normals: three
+ *              float chains from 0.0f in index order over the cp points whose normal has three finite components, each divided
+ *              by float(cp) (cp == 0: 0 / 0 = NaN, and the arithmetic below runs with it);
+ *   d_vp_p     d = 0.0f - centroid, d / sqrtf(d . d) (a true division);
+ *   pair       per point i in index order pcl::computePairFeatures(centroid, normal centroid, p_i, n_i) as pcc_fpfh_descriptors
+ *              states it, with whatever the normal holds.  No pair (the point AT the centroid, or the connecting line along
+ *              the source's normal): no vote.  Otherwise one vote each into bin floor(45 (f1 + pi) / (2 pi)) of the first 45
+ *              bins, floor(45 (f2 + 1) / 2) of the second and floor(45 (f3 + 1) / 2) of the third (evaluated in double, clamped
+ *              to 0 .. 44; anything that is not >= 0, a NaN included, is bin 0 -- so a point with a NaN normal votes bin 0 of
+ *              f1 and f2 and its real f3 bin).  Every vote adds 100.0f / float(n - 1); a bin with `count` votes holds that
+ *              increment added count times in float;
+ *   f4         bins 135 .. 179: the distance component's increment is 0, every bin is +0.0f;
+ *   viewpoint  bins 180 .. 307, every point (NaN normals included): alpha = (double(n_i . d_vp_p) + 1.0) * 0.5, bin
+ *              floor(alpha * 128.0) clamped to 0 .. 127 (NaN: 0); every vote adds float(100.0 / double(n)).
+ * out_histogram[308] in memory space `mem`: f1[45], f2[45], f3[45], f4[45], viewpoint[128], as pcl::VFHSignature308 holds them.
+ *   *n_out (host): 1, or 0 for a cloud of fewer than 2 points (PCL's initCompute fails and the reference gets an empty
+ *   cloud): PCC_OK, nothing is written.  Votes are counted in integers and every bin is rebuilt from its count: the result
+ *   does not depend on the order the points arrive in, no float atomic takes part.  No colour is read.
+ * A cloud with a non-finite point is refused (PCC_ERR_UNSUPPORTED): the reference strips such points when it loads a cloud
+ *   (:1144-1148), processVHF never sees one.
+ * Refused before the handle is looked at, in this order: a bad memory space; a null output or n_out; a radius that is not
+ *   positive and finite; a null handle last.  A refused call writes nothing.  Host waits: the row total of the CSR, and the
+ *   results of a caller in host memory; neither launches nor waits depend on n. */
+int pcc_vfh_descriptor(pcc_index *index, int mem, double normal_radius,
+                       float *out_histogram /* mem, [308] */, size_t *n_out /* 1, or 0 */);
+/* matchVHF (src/comparator.cpp:471-480) for every pair of two arrays of VFH descriptors:
+ *   out_dist[i * n2 + j] = sqrt(sum over k = 0 .. 307, in order, of (double)(hist1[i][k] - hist2[j][k])^2)
+ *   -- the subtraction in float, the square (pow(x, 2) of a promoted float: exact) and the running sum in double, the root in
+ *   double.  The reference compares element 0 of two clouds: n1 = n2 = 1.  A NaN bin gives a NaN distance.
+ * hist1[n1][308], hist2[n2][308] and out_dist[n1 * n2] (row-major) in memory space `mem`; ctx lends device, stream and
+ *   scratch, the cloud it indexes is neither read nor changed.  n1 == 0 or n2 == 0: PCC_OK, nothing is written.
+ * Refused before the handle is looked at, in this order: a bad memory space; a null array (with n1 and n2 both > 0); more
+ *   than 2^31 - 1 pairs (PCC_ERR_UNSUPPORTED); a null handle last. */
+int pcc_match_vfh(pcc_index *ctx, const float *hist1, size_t n1, const float *hist2, size_t n2, int mem,
+                  double *out_dist /* mem, [n1 * n2] */);
 /* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
  * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
  *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)

@@ -44,7 +44,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
-    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch",
+    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch", "pcc_vfh_descriptor", "pcc_match_vfh",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -120,6 +120,8 @@ def _load() -> C.CDLL:
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_fpfh_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_vfh_descriptor.argtypes = [vp, i32, C.c_double, vp, C.POINTER(sz)]
+    lib.pcc_match_vfh.argtypes = [vp, vp, sz, vp, sz, i32, vp]
     lib.pcc_fpfh_descriptors_batch.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
@@ -220,7 +222,7 @@ def _out(like, shape, dtype):
     if _is_torch(like) and like.is_cuda:
         import torch
         tdt = {np.int32: torch.int32, np.float32: torch.float32, np.uint8: torch.uint8,
-               np.int64: torch.int64}[dtype]
+               np.int64: torch.int64, np.float64: torch.float64}[dtype]
         t = torch.empty(shape, dtype=tdt, device=like.device)
         return t, t.data_ptr()
     a = np.empty(shape, dtype=dtype)
@@ -1024,6 +1026,44 @@ class Index:
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
 
+    def vfh_descriptor(self, normal_radius: float = 0.03):
+        """pcc_vfh_descriptor: the reference's processVHF (src/comparator.cpp:482-516) for the indexed cloud -- its one global
+        descriptor.  Returns (308,) float32: the 45 bins of f1, of f2, of f3 and of f4, then the 128 bins of the viewpoint
+        component; a cloud of fewer than 2 points has none and gives an empty (0, 308) result.  A handle over a CUDA tensor
+        gives a CUDA tensor, any other a NumPy array.  A cloud with a non-finite point is refused."""
+        like = None
+        if getattr(self, "_cuda", None) is not None:
+            import torch
+            like = torch.empty(0, device=self._cuda)
+        hist, ph = _out(like, (1, 308), np.float32)
+        n_out = C.c_size_t(0)
+        st = self._before(hist)
+        _check(LIB.pcc_vfh_descriptor(self._h, MEM_DEVICE if like is not None else MEM_HOST, float(normal_radius), ph, C.byref(n_out)))
+        self._after(st)
+        return hist[0] if n_out.value else hist[:0]
+
+    def match_vfh(self, h1, h2):
+        """pcc_match_vfh with this handle as the context: the reference's matchVHF (src/comparator.cpp:471-480) for every pair of
+        two arrays of VFH descriptors, (n1, 308) and (n2, 308) float32 (a single (308,) descriptor counts as one row), both NumPy
+        arrays or both CUDA tensors.  Returns the (n1, n2) float64 distances, a NumPy array or a CUDA tensor accordingly.  The
+        cloud the handle indexes is neither read nor changed."""
+        on_device = [_is_torch(x) and x.is_cuda for x in (h1, h2)]
+        if any(on_device) and not all(on_device):
+            raise ValueError("match_vfh takes NumPy arrays or CUDA tensors, not both in one call")
+        if all(on_device):
+            a, b = (x.reshape(-1, 308).contiguous() for x in (h1, h2))
+            assert a.dtype == b.dtype and a.element_size() == 4 and a.dtype.is_floating_point, "VFH descriptors are float32"
+            pa, pb, mem = a.data_ptr(), b.data_ptr(), MEM_DEVICE
+        else:
+            a, b = (np.ascontiguousarray(x.numpy() if _is_torch(x) else x, dtype=np.float32).reshape(-1, 308) for x in (h1, h2))
+            pa, pb, mem = a.ctypes.data, b.ctypes.data, MEM_HOST
+        n1, n2 = int(a.shape[0]), int(b.shape[0])
+        out, po = _out(a, (n1, n2), np.float64)
+        st = self._before(a, b, out) if mem == MEM_DEVICE else None
+        _check(LIB.pcc_match_vfh(self._h, pa if n1 else None, n1, pb if n2 else None, n2, mem, po if n1 and n2 else None))
+        self._after(st)
+        return out
+
     def fpfh_descriptors_batch(self, clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05,
                                nr_bins=(11, 11, 11)):
         """pcc_fpfh_descriptors_batch with this handle as the context: the reference's processFPFH for every cluster in one call.
@@ -1527,6 +1567,16 @@ def rift_descriptors_batch(clouds, rgbs=None, normal_radius: float = 0.03, gradi
         return ctx.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
         return own.rift_descriptors_batch(clouds, rgbs, normal_radius, gradient_radius, rift_radius, nr_distance_bins, nr_gradient_bins)
+
+
+def match_vfh(h1, h2, ctx=None):
+    """matchVHF for every pair of two arrays of VFH descriptors (pcc_match_vfh): the (n1, n2) float64 distances.
+    ctx: an Index that lends its device, stream and scratch (its own cloud is left as it is); None makes a one-point handle
+    for the call."""
+    if ctx is not None:
+        return ctx.match_vfh(h1, h2)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.match_vfh(h1, h2)
 
 
 def fpfh_descriptors_batch(clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05, nr_bins=(11, 11, 11), ctx=None):

@@ -307,7 +307,7 @@ struct Scratch { virtual ~Scratch() = default; };
 enum ScratchSlot {
     SCRATCH_RIFT, SCRATCH_FPFH, SCRATCH_SIFT, SCRATCH_RIFT_BATCH, SCRATCH_SIFT_BATCH, SCRATCH_RGB_BATCH, SCRATCH_MATCH_COLOUR,
     SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH, SCRATCH_FPFH_BATCH,
-    SCRATCH_SLOTS
+    SCRATCH_VFH, SCRATCH_SLOTS
 };
 // A work handle: a second handle a feature indexes clouds of its own on (the caller's stream for the length of a call:
 // entry.hpp, WorkLease).  Made at the first lease, destroyed with its owner.
@@ -701,6 +701,8 @@ int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, 
 // fpfh.hip: the stages of pcc_fpfh_descriptors over any packed cloud (fpfh_batch.hip: the concatenation of a batch), arguments as
 // rift_stages'.  normals (nullable): the caller's own plane fit -- it fills normals[n] and hands over the CSR at fpfh_radius, and
 // `rows` is not asked.  *pos: uint32[n + 1] on the device, where every point of cloud2 lies in the output, pos[n] = the rows written
+// vfh.hip: the null-argument and radius checks of pcc_vfh_descriptor
+int check_vfh_params(double normal_radius, const float* out_hist, const size_t* n_out);
 typedef std::function<int(float4* normals, const unsigned long long** keys, const unsigned int** offsets)> FpfhNormals;
 int fpfh_stages(pcc_index* ix, const float4* refs, const float4* order, const GridDev* gd, size_t n, const RiftRows& rows,
                 double normal_radius, double fpfh_radius, const FpfhNormals* normals, float* out_hist, int32_t* out_index,
