@@ -237,7 +237,7 @@ enum pcc_option {
                                     entry's pair features and the votes are counted in integers; in the weighting every lane adds, in row
                                     order, the shares of the bin it owns while three more lanes carry the running sums (default);
                                     0 = one lane per row (PCL's loops as they stand).  Same bits either way. */
-    PCC_OPT_FPFH_BATCH_BRUTE_MAX = 30  /* pcc_fpfh_descriptors_batch: clusters of up to this many points get their radius rows from the
+    PCC_OPT_FPFH_BATCH_BRUTE_MAX = 30, /* pcc_fpfh_descriptors_batch: clusters of up to this many points get their radius rows from the
                                     exhaustive builder that serves the whole batch at once (n^2 distance tests per cluster); larger
                                     clusters take pcc_index_set_input + pcc_fpfh_descriptors inside the same call, one by one, on a
                                     work handle kept in ctx (PCC_FPFH_BATCH_BRUTE_MAX in the environment of a new handle).  Default
@@ -247,6 +247,16 @@ enum pcc_option {
                                     against 0.34 / 0.37 / 0.48 / 0.69 ms on the work handle at 2048 / 4096 / 8192 / 16 384 points: the
                                     crossover lies between 8192 and 16 384.  Only these four sizes were measured.  No result bit
                                     depends on it. */
+    PCC_OPT_VFH_BATCH_BRUTE_MAX = 31   /* pcc_vfh_descriptors_batch: clusters of 2 .. this many points go through the batch kernels (the
+                                    exhaustive row builder over the whole batch, one chain wave per cluster, votes and bins of all
+                                    clusters in one launch each); larger clusters take pcc_index_set_input + pcc_vfh_descriptor
+                                    inside the same call, one by one, on a work handle kept in ctx (PCC_VFH_BATCH_BRUTE_MAX in the
+                                    environment of a new handle).  Default 8192, range 0 .. 2^30; 0 sends every cluster to the work
+                                    handle.  Measured (profiles/vfh_batch_exp.txt, device memory): 60 clusters of 20 ... 5000 points take
+                                    2.12 / 0.98 / 0.45 / 0.45 ms at 2048 / 4096 / 8192 / 16 384 (10 / 3 / 0 / 0 of them on the work
+                                    handle); a cluster ALONE takes 0.19 / 0.23 / 0.33 / 0.63 ms through the batch kernels against
+                                    0.23 / 0.26 / 0.30 / 0.41 ms on the work handle at those sizes.  Only these four were measured.
+                                    No result bit depends on it. */
 };
 int pcc_index_set_option(pcc_index *index, int option, double value);
 int pcc_index_get_option(pcc_index *index, int option, double *value);
@@ -902,6 +912,45 @@ int pcc_vfh_descriptor(pcc_index *index, int mem, double normal_radius,
  *   than 2^31 - 1 pairs (PCC_ERR_UNSUPPORTED); a null handle last. */
 int pcc_match_vfh(pcc_index *ctx, const float *hist1, size_t n1, const float *hist2, size_t n2, int mem,
                   double *out_dist /* mem, [n1 * n2] */);
+/* pcc_vfh_descriptor for EVERY cluster of a segmentation at once -- the producer of pcc_match_vfh's descriptor arrays.  The
+ *   clusters of a call are concatenated on the device; the row builder, the plane fit, the centroid chains (one wave per
+ *   cluster, side by side), the votes and the bins each run in one launch over all of them: neither launches nor host waits
+ *   depend on n_clusters.
+ *   ctx: any index handle, as for the other batch calls: it supplies device, stream and scratch; its cloud, tie order and
+ *     kept rows are neither read nor changed.
+ *   Cluster c is the records offsets[c] .. offsets[c + 1] of pts (stride_bytes apart, x, y, z first, memory space `mem`; no
+ *     colour is read): pcc_fpfh_descriptors_batch's input, what pcc_region_growing_segmentation and
+ *     pcc_euclidean_cluster_segmentation write as out_cluster_points / out_offsets.  offsets is a HOST array.
+ *   Its result is, bit for bit, what pcc_index_create on that cluster alone + pcc_vfh_descriptor returns: rows
+ *     out_offsets[c] .. out_offsets[c + 1] of out_histograms -- one row for a cluster of 2 points and more, none for a cluster
+ *     of 0 or 1 points.  No point of another cluster enters a row of the CSR, a centroid chain or a counter, however the
+ *     clusters overlap in space.  Votes are counted in integers: no float atomic takes part.
+ *   out_offsets[n_clusters + 1] (HOST in either space) depends on the cluster sizes alone: it is computed on the host before
+ *     anything is launched and no host wait exists for it.  out_histograms holds one row of 308 floats per cluster at most, in
+ *     memory space `mem`.  With PCC_MEM_DEVICE every descriptor is written where it stays, whichever route its cluster takes:
+ *     rows out_offsets[c] of two such arrays are valid hist1 / hist2 of pcc_match_vfh(mem = PCC_MEM_DEVICE), and no descriptor
+ *     crosses to the host between the calls.  The rows of a host caller are staged and copied down in merged runs.
+ *   Clusters above PCC_OPT_VFH_BATCH_BRUTE_MAX points take the single call inside this one, on a work handle kept in ctx, in
+ *     the caller's memory space, straight into their row (same bits).  pcc_index_stats afterwards reports in [0] the points
+ *     the batch kernels served, in [1] the points sent through the work handle and in [2] the descriptors written.
+ *   Non-finite points: a cluster of fewer than 2 points is never read and yields no row whatever it holds (the single call
+ *     WOULD look at such a cloud, and refuse it for a non-finite point).  A cluster of 2 points and more that holds a
+ *     non-finite point fails the call with PCC_ERR_UNSUPPORTED, the message naming one such cluster ("non-finite"):
+ *     out_offsets is not written then, the contents of out_histograms are unspecified, the handle stays usable.  From host
+ *     memory such a cluster on the batch route is refused before any launch, the lowest-numbered one named; from device
+ *     memory the pack kernel flags it and the word is read after the wait of the CSR build.
+ *   Host waits with no cluster above the limit: one for the CSR's total and, for a host caller, one for the rows.
+ *   n_clusters == 0: PCC_OK, out_offsets[0] = 0, no device is touched.  Refused before the handle is looked at, in this
+ *     order: a bad memory space; a null offsets or out_offsets, or a null pts / out_histograms while a cluster holds a point;
+ *     a bad stride, or pts / out_histograms that are not 4-byte aligned; offsets that decrease (PCC_ERR_INVALID), then 2^31
+ *     points or clusters and more (PCC_ERR_UNSUPPORTED); a radius that is not positive and finite; a null handle
+ *     last.  A refused call writes nothing.  A CSR of 2^32 entries or more over the whole batch is PCC_ERR_OVERFLOW. */
+int pcc_vfh_descriptors_batch(pcc_index *ctx,
+                              const void *pts, size_t stride_bytes,
+                              const size_t *offsets /* HOST [n_clusters + 1] */, size_t n_clusters, int mem,
+                              double normal_radius,
+                              float *out_histograms /* mem, [n_clusters][308] at most */,
+                              size_t *out_offsets   /* HOST [n_clusters + 1] */);
 /* ---- SIFT keypoints of a coloured cloud ---------------------------------------------------------------
  * replaces: processSift (src/comparator.cpp:435-469): pcl::SIFTKeypoint<PointXYZRGB, PointWithScale> with
  *   setScales(0.005f, 5, 5) and setMinimumContrast(0.001f), the detector in front of the keypoint snap (pcc_first_within)
@@ -1297,6 +1346,8 @@ int pcc_change_detection(pcc_index *ctx, const void *a, size_t n_a, size_t a_str
  *  clouds sent through the work handle (above PCC_OPT_RIFT_BATCH_BRUTE_MAX).
  *  After pcc_fpfh_descriptors_batch on the handle: [0] points the batch kernels served, [1] points of the clusters sent
  *  through the work handle (above PCC_OPT_FPFH_BATCH_BRUTE_MAX), [2] CSRs the batch route built (0, 1 or 2).
+ *  After pcc_vfh_descriptors_batch on the handle: [0] points the batch kernels served, [1] points of the clusters sent
+ *  through the work handle (above PCC_OPT_VFH_BATCH_BRUTE_MAX), [2] descriptors written.
  *  After pcc_sift_keypoints_batch on the handle: [0] points that went through the batch kernels, [1] points of the clouds sent
  *  through the work handle (above PCC_OPT_SIFT_BATCH_BRUTE_MAX), [2] octave rounds the batch route ran.
  *  After pcc_cluster_descriptors on the handle: [0] dense-route points, [1] SIFT-route points, [2] octave rounds, [3] keypoints,

@@ -22,7 +22,7 @@ KNN_MAX_K = 65536
  OPT_SORT_MP_MIN_Q, OPT_NN1_KERNEL, OPT_FLANN_SPLIT, OPT_NN1_DENSE_MIN, OPT_KNN_KERNEL, OPT_KNN_CACHE_K, OPT_NN1_OPEN_FLAT, OPT_SORT_STAGE1,
  OPT_ICP_SORTED, OPT_OVERLAP_PREP, OPT_GRID_AXES, OPT_XCD_RUN, OPT_FUSE_PARAMS, OPT_HOST_PIPE, OPT_SCAN_CHAINED, OPT_KNN_RUN,
  OPT_RIFT_LAYOUT, OPT_SIFT_LAYOUT, OPT_RIFT_BATCH_BRUTE_MAX, OPT_SIFT_BATCH_BRUTE_MAX, OPT_RGB_BATCH_BRUTE_MAX, OPT_FPFH_LAYOUT,
- OPT_FPFH_BATCH_BRUTE_MAX) = range(1, 31)
+ OPT_FPFH_BATCH_BRUTE_MAX, OPT_VFH_BATCH_BRUTE_MAX) = range(1, 32)
 
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("PCC_LIB", _HERE / "lib" / "libpcc_nn.so"))
@@ -44,7 +44,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
-    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch", "pcc_vfh_descriptor", "pcc_match_vfh",
+    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch", "pcc_vfh_descriptor", "pcc_match_vfh", "pcc_vfh_descriptors_batch",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -122,6 +122,7 @@ def _load() -> C.CDLL:
     lib.pcc_fpfh_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_vfh_descriptor.argtypes = [vp, i32, C.c_double, vp, C.POINTER(sz)]
     lib.pcc_match_vfh.argtypes = [vp, vp, sz, vp, sz, i32, vp]
+    lib.pcc_vfh_descriptors_batch.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, vp, vp]
     lib.pcc_fpfh_descriptors_batch.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp]
     lib.pcc_rift_descriptors_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, vp]
     lib.pcc_sift_keypoints.argtypes = [vp, vp, sz, sz, vp, sz, i32, C.c_float, i32, i32, C.c_float, vp, sz, C.POINTER(sz)]
@@ -1064,6 +1065,48 @@ class Index:
         self._after(st)
         return out
 
+    def vfh_descriptors_batch(self, clouds_or_points, offsets=None, normal_radius: float = 0.03, return_packed: bool = False):
+        """pcc_vfh_descriptors_batch with this handle as the context: the reference's processVHF for every cluster in one call.
+        clouds_or_points: a list of (n, >= 3) float32 arrays of one kind (NumPy arrays or torch tensors, e.g. (n, 3) points or
+        32-byte pcl::PointXYZRGB records; they are laid one behind the other for the call), or with `offsets` ONE such array,
+        host or CUDA, read in place: cluster c is rows offsets[c] .. offsets[c + 1] -- what region_growing_segmentation /
+        euclidean_cluster_segmentation return as cluster_points / offsets.  Returns one array per cluster, what
+        Index(cluster).vfh_descriptor() returns: (308,) float32, or an empty (0, 308) for a cluster of fewer than 2 points
+        (which is never read).  For CUDA input these are CUDA tensors, views of the call's one output tensor.
+        return_packed: (hist (m, 308), offsets (n_clusters + 1,) uintp) instead -- the descriptors of the clusters that have
+        one, in cluster order, and each cluster's rows offsets[c] .. offsets[c + 1]; match_vfh takes hist without a copy.  A
+        cluster of 2 points and more with a non-finite point is refused.  The cloud the handle indexes is neither read nor
+        changed."""
+        if offsets is None:
+            clouds = list(clouds_or_points)
+            sizes = [len(c) for c in clouds]
+            off_in = np.zeros(len(clouds) + 1, dtype=np.uintp)
+            off_in[1:] = np.cumsum(sizes, dtype=np.uintp)
+            some = [c for c in clouds if len(c)]
+            if not some:
+                points = np.zeros((0, 3), np.float32)
+            elif _is_torch(some[0]):
+                import torch
+                points = some[0] if len(some) == 1 else torch.cat(some, 0)
+            else:
+                points = some[0] if len(some) == 1 else np.concatenate(some, 0)
+        else:
+            points = clouds_or_points
+            off_in = np.ascontiguousarray(np.asarray(offsets.cpu() if _is_torch(offsets) else offsets), dtype=np.uintp)
+        ptr, n, stride, mem = _points(points)
+        assert off_in.ndim == 1 and len(off_in) >= 1, "offsets holds n_clusters + 1 entries"
+        n_clusters = len(off_in) - 1
+        assert n_clusters == 0 or int(off_in.max()) <= n, "offsets reach beyond the points"
+        hist, ph = _out(points, (max(n_clusters, 1), 308), np.float32)
+        off = np.zeros(n_clusters + 1, dtype=np.uintp)
+        st = self._before(points, hist) if mem == MEM_DEVICE else None
+        _check(LIB.pcc_vfh_descriptors_batch(self._h, ptr if n else None, stride, off_in.ctypes.data, n_clusters, mem, float(normal_radius), ph,
+                                             off.ctypes.data))
+        self._after(st)
+        if return_packed:
+            return hist[:int(off[-1])], off
+        return [hist[int(off[c])] if off[c + 1] > off[c] else hist[:0] for c in range(n_clusters)]
+
     def fpfh_descriptors_batch(self, clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05,
                                nr_bins=(11, 11, 11)):
         """pcc_fpfh_descriptors_batch with this handle as the context: the reference's processFPFH for every cluster in one call.
@@ -1577,6 +1620,16 @@ def match_vfh(h1, h2, ctx=None):
         return ctx.match_vfh(h1, h2)
     with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
         return own.match_vfh(h1, h2)
+
+
+def vfh_descriptors_batch(clouds_or_points, offsets=None, normal_radius: float = 0.03, return_packed: bool = False, ctx=None):
+    """VFH descriptors of every cluster at once (pcc_vfh_descriptors_batch): one (308,) descriptor per cluster, an empty
+    (0, 308) array for a cluster of fewer than 2 points; or with return_packed (hist (m, 308), offsets).
+    See Index.vfh_descriptors_batch.  ctx: any Index; without one a small handle is made for the call."""
+    if ctx is not None:
+        return ctx.vfh_descriptors_batch(clouds_or_points, offsets, normal_radius, return_packed)
+    with Index(np.zeros((1, 3), np.float32), engine=ENGINE_BRUTE) as own:
+        return own.vfh_descriptors_batch(clouds_or_points, offsets, normal_radius, return_packed)
 
 
 def fpfh_descriptors_batch(clouds_or_points, offsets=None, normal_radius: float = 0.03, fpfh_radius: float = 0.05, nr_bins=(11, 11, 11), ctx=None):

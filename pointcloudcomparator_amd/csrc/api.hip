@@ -79,6 +79,7 @@ static const OptionRow g_options[] = {
     {PCC_OPT_RGB_BATCH_BRUTE_MAX, "PCC_RGB_BATCH_BRUTE_MAX", &Options::rgb_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
     {PCC_OPT_FPFH_LAYOUT, "PCC_FPFH_LAYOUT", &Options::fpfh_layout, nullptr, 0, 1, OptionRow::FLAG},
     {PCC_OPT_FPFH_BATCH_BRUTE_MAX, "PCC_FPFH_BATCH_BRUTE_MAX", &Options::fpfh_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
+    {PCC_OPT_VFH_BATCH_BRUTE_MAX, "PCC_VFH_BATCH_BRUTE_MAX", &Options::vfh_batch_brute_max, nullptr, 0, 1073741824, OptionRow::CLOSED},
 };
 static const OptionRow* option_row(int option) {
     for (const OptionRow& r : g_options)

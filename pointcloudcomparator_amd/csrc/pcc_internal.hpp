@@ -227,6 +227,11 @@ struct Options {
                                     // 60 clusters of 20 ... 5000 points take 4.02 / 2.24 / 1.49 / 1.49 ms at 2048 / 4096 / 8192 / 16 384; a cluster alone is cheaper on the work
                                     // handle somewhere between 8192 points (0.46 against 0.48 ms) and 16 384 (0.85 against 0.69 ms): only 2048,
                                     // 4096, 8192 and 16 384 were measured
+    int vfh_batch_brute_max = 8192;    // PCC_OPT_VFH_BATCH_BRUTE_MAX: clusters of a pcc_vfh_descriptors_batch call of 2 .. this many points go through
+                                    // the batch kernels (vfh_batch.hip: exhaustive rows, one chain wave per cluster, votes and bins over the whole
+                                    // batch); larger ones take the single call, one by one, on a work handle.  Measured (EXPERIMENTS.md,
+                                    // "Batched VFH descriptors"; device memory): 60 clusters of 20 ... 5000 points take 2.12 / 0.98 / 0.45 / 0.45 ms at
+                                    // 2048 / 4096 / 8192 / 16 384; a cluster alone is cheaper on the work handle from 8192 points (0.30 against 0.33 ms)
     int overlap_prep = 1;           // PCC_OPT_OVERLAP_PREP: a k = 1 search that follows setInputCloud directly packs and sorts its queries on a
                                     // second stream while the build's cell sort is still running (they share nothing but the grid parameters);
                                     // from 2M queries on, 2 = at every size
@@ -307,7 +312,7 @@ struct Scratch { virtual ~Scratch() = default; };
 enum ScratchSlot {
     SCRATCH_RIFT, SCRATCH_FPFH, SCRATCH_SIFT, SCRATCH_RIFT_BATCH, SCRATCH_SIFT_BATCH, SCRATCH_RGB_BATCH, SCRATCH_MATCH_COLOUR,
     SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH, SCRATCH_FPFH_BATCH,
-    SCRATCH_VFH, SCRATCH_SLOTS
+    SCRATCH_VFH, SCRATCH_VFH_BATCH, SCRATCH_SLOTS
 };
 // A work handle: a second handle a feature indexes clouds of its own on (the caller's stream for the length of a call:
 // entry.hpp, WorkLease).  Made at the first lease, destroyed with its owner.
