@@ -1012,7 +1012,7 @@ static int radius_fill_impl(pcc_index* ix, const void* q, size_t nq, size_t stri
     PCC_TRY(rd.stage(d2, (size_t)total, mem, ix->out_d2));
     // rows of 24 neighbours and more on average: the fill delivers index and distance itself (sorted in registers, no
     // key array in between); otherwise keys -> sort -> unpack.  (Slots a fill does not reach read "nothing found".)
-    const bool wave_fill = (size_t)total >= 24 * nq && (ri.dev || rd.dev);
+    const bool wave_fill = (size_t)total >= RAD_WAVE_MEAN * nq && (ri.dev || rd.dev);
     if (!wave_fill) PCC_HIP(hipMemsetAsync(keys, 0xff, (size_t)total * sizeof(unsigned long long), ix->stream));
     bool delivered = false;
     PCC_TRY(grid_radius(ix, ix->q_packed.as<float4>(), nq, (float)radius, radius2(radius), nullptr, doff, keys, sorted, (size_t)total,

@@ -964,10 +964,11 @@ constexpr unsigned int ROW_SORT_MAX = 512;  // rows up to this length are sorted
 // computed there and the host does not wait for them: both kernels are launched, one of them returns at once.
 // (5M object-layer points, r = 0.05, 83 hits: 2.9 against 3.5 ms; 1M corridor, r = 0.2, 210 hits: 0.75 against 1.13;
 // 1M corridor, r = 0.05, 5.5 hits: 0.40 against 0.25 -- the lane form keeps those)
+constexpr int RAD_COUNT_WAVE_MIN = 200;  // candidates in the ball's box from which the count goes by wave
 __device__ __forceinline__ bool radius_count_by_wave(const GridDev* gd, float r, const unsigned int* occupied) {
     const float c = 2.f * r * gd->g.inv_h + 1.f;
     const unsigned int occ = *occupied;
-    return c * c * c * ((float)gd->n_valid / (float)(occ ? occ : 1u)) >= 200.f;
+    return c * c * c * ((float)gd->n_valid / (float)(occ ? occ : 1u)) >= (float)RAD_COUNT_WAVE_MIN;
 }
 __global__ void __launch_bounds__(256)
 k_count_occupied(const unsigned int* __restrict__ cell_start, const GridDev* __restrict__ gd, unsigned int* __restrict__ out) {
@@ -1464,7 +1465,7 @@ int grid_radius(pcc_index* ix, const float4* q, size_t nq, float r, float r2, in
     ev_mark(ix, EV_MAIN0);
     unsigned int gw = (n + 3) / 4;  // 4 waves per workgroup, waves loop
     if (gw > 8192) gw = 8192;
-    if (keys && total >= 24 * nq) {  // long rows: a wave per query (short rows leave most of its lanes idle)
+    if (keys && total >= RAD_WAVE_MEAN * nq) {  // long rows: a wave per query (short rows leave most of its lanes idle)
         const bool fused = delivered != nullptr && (idx_out || d2_out);
         unsigned int *long_list = nullptr, *long_count = nullptr;
         if (fused) {

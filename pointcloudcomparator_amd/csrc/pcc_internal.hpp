@@ -635,6 +635,9 @@ int self_knn_keys(pcc_index* ix, int k, const unsigned long long** keys);
 // counts[i] = #refs with d2 < r2; with fill != 0 also writes keys at offsets[i]..
 // idx_out / d2_out / delivered (fill only): when given, a fill that takes the wave-per-query route writes the caller's
 // arrays itself (sorted in registers) and sets *delivered
+// a fill whose rows hold this many neighbours and more on average takes the wave-per-query route (api.hip radius_fill_impl
+// decides the memset by it, knn.hip grid_radius the kernel: the two must agree)
+constexpr unsigned int RAD_WAVE_MEAN = 24;
 int grid_radius(pcc_index* ix, const float4* q, size_t nq, float r, float r2, int32_t* counts,
                 const int64_t* offsets, unsigned long long* keys, int sorted, size_t total = 0, int32_t* idx_out = nullptr,
                 float* d2_out = nullptr, bool* delivered = nullptr);
