@@ -831,6 +831,69 @@ int pcc_rift_descriptors_batch(pcc_index *ctx, size_t n_clouds,
 int pcc_fpfh_descriptors(pcc_index *index, int mem, double normal_radius, double fpfh_radius,
                          int nr_bins_f1, int nr_bins_f2, int nr_bins_f3,
                          float *out_histograms, int32_t *out_point_index, size_t *n_out);
+/* ---- SHOT352 descriptors of the indexed cloud -------------------------------------------------------
+ * replaces: processSHOT (src/comparator.cpp:941-986) for one cloud: pcl::NormalEstimation (setRadiusSearch 0.05),
+ *   removeNaNNormalsFromPointCloud, and pcl::SHOTEstimation<PointXYZRGB, Normal, SHOT352> (setRadiusSearch 0.04) over the
+ *   points that are left.  Lines 915-939 of processSHOT -- the SIFT keypoints, the rand() % total draw and the snap of the
+ *   drawn keypoints to the cloud -- stay with the caller: pcc_sift_keypoints and pcc_first_within cover the two library
+ *   steps, the draw is the caller's business.  The PCL stages are restated from the published source of PCL 1.7
+ *   (shot.hpp, shot_lrf.hpp; DESIGN.md 4.31, every stage below [recalled]): PCL is not available to compare against,
+ *   parity with it is unpinned.
+ * Every neighbourhood is the sorted radius row of the library at shot_radius (d2 < float(r^2), ascending (d2, index), the
+ * point itself included), taken among the points of cloud2 -- the points with a finite normal; no compacted cloud is built
+ * before the final output, the stages skip the entries of the others.  When shot_radius <= normal_radius one CSR is built
+ * (at normal_radius) and the SHOT stages walk the prefix of each row with d2 < float(shot_radius^2); otherwise two.
+ *   normals    [recalled, unpinned] pcc_normals_radius at normal_radius, viewpoint origin; points without a finite normal
+ *              (a non-finite point among them) leave (cloud2);
+ *   frame      [recalled, unpinned] SHOTLocalReferenceFrameEstimation::getLocalRF with lrf_radius = shot_radius, per point p
+ *              over its row in order, skipping entries with d2 == 0: v = q - p in float per component, promoted to double;
+ *              w = double(shot_radius) - sqrtf(d2) (the root in float, then promoted); cov_ij += w * (v_i * v_j) and
+ *              sum += w in double, entry by entry in row order; valid = the entries used, valid < 5: the frame is nine NaN;
+ *              cov_ij / sum, a division per entry.  Eigenvectors: cyclic Jacobi in double from + - * / sqrt alone; a sweep
+ *              rotates the pairs (0,1), (0,2), (1,2) in this order, skipping an off-diagonal that is exactly 0.0 and
+ *              setting one to 0.0 without a rotation when |a_pp| + |a_pq| == |a_pp| and |a_qq| + |a_pq| == |a_qq|, with
+ *              theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), sign(0) = +1,
+ *              c = 1 / sqrt(t^2 + 1), s = t c; it stops when all three off-diagonals are exactly 0.0, at the latest after
+ *              32 sweeps.  x = the eigenvector of the largest eigenvalue, z = of the smallest, chosen by PCL's if-chain
+ *              over the eigenvalues e0, e1, e2 in the solver's order with strict '>' throughout:
+ *              e0 > e1 ? (e0 > e2 ? x = 0, z = (e1 > e2 ? 2 : 1) : x = 2, z = 1) : (e1 > e2 ? x = 1, z = (e0 > e2 ? 2 : 0)
+ *              : x = 2, z = 0) -- among equal eigenvalues the later column counts as the larger.  An eigenvalue that is not
+ *              finite: nine NaN.  Sign of x over the valid entries in row order, dots in double ((v0 x0 + v1 x1) + v2 x2):
+ *              plus = the count of v . x >= 0, s = 2 plus - valid; s < 0 negates x; s == 0 takes the five entries
+ *              valid / 2 - 2 .. valid / 2 + 2 of that list and negates x when fewer than 3 of them have v . x > 0.  The same
+ *              for z.  rf rows: float(x), y = z cross x in float, float(z);
+ *   bins       [recalled, unpinned] computePointSHOT + interpolateSingleChannel, 32 volumes x 11 bins.  A row of fewer than 5
+ *              cloud2 entries (p included) or a NaN frame: 352 NaN.  Else per entry q in row order: distance =
+ *              double(sqrtf(d2)), skipped when |distance| < 1e-15; cosine = double(n_q . z) (a float dot), clamped to +-1,
+ *              bin = (1 + cosine) * 10 / 2; xF, yF, zF = double(delta . x / y / z), float dots of delta = q - p, each set to 0
+ *              when |.| < 1e-30; desc_index: bit4 = yF > 0 || (yF == 0 && xF < 0), bit3 = (xF > 0 || (xF == 0 && yF > 0)) ?
+ *              !bit4 : bit4, index = (bit4 << 3 + bit3 << 2) << 1; the 45 degree half: xF yF > 0 || xF == 0 ? (|xF| >= |yF| ?
+ *              0 : 4) : (|xF| > |yF| ? 4 : 0); + 1 for zF > 0; + 2 for distance > r / 2.  step = floor(bin + 0.5),
+ *              bin -= step, and the contributions are added in this order, each a float add of float(|.|) into a float bin:
+ *              (1) |bin| to bin (step +- 1) mod 10 of the same volume (+ for bin > 0); (2) the radial neighbour volume
+ *              desc_index -+ 2 at step: (distance - 3r/4) / (r/2) in the outer husk when distance <= 3r/4,
+ *              (distance - r/4) / (r/2) in the inner husk when distance >= r/4; (3) the inclination neighbour volume
+ *              desc_index +- 1 at step: inclination = acos(clamp(zF / distance)); above 90 degrees (or within 1e-30 of it
+ *              with zF <= 0) (inclination - 135) / 90 when inclination <= 135, else (inclination - 45) / 90 when
+ *              inclination >= 45; (4) when xF or yF is not 0 the azimuth neighbour volume (desc_index +- 4) mod 32 at
+ *              step: (atan2(yF, xF) - (-7 pi / 8 + (pi / 4) (desc_index >> 2))) / (pi / 4) clamped to +-0.5 (+ 4 when it is
+ *              > 0); (5) the centre bin desc_index * 11 + step gets float(weight), weight = the sum of 1 - |d| over the four
+ *              interpolations in double.  acos and atan2 are the library's own (csrc/libm_f64.hpp: fdlibm's e_acos.c,
+ *              s_atan.c and e_atan2.c restated from + - * / sqrt: the same bits on the device and on a host).  The order of
+ *              the adds, entry by entry, is part of the result.  Then norm = sqrt(sum of double(b) * double(b)) over the
+ *              bins in index order, one chain in double, and every bin is divided by float(norm).  The constants are PCL's
+ *              PST_* literals.
+ * out_descriptors[n][352] (pcl::SHOT352::descriptor), out_rf[n][9] (pcl::SHOT352::rf: x, y, z axis; nullable) and
+ *   out_point_index[n] (the ORIGINAL index of every descriptor's point, ascending: the points of cloud2 -- processSHOT
+ *   keeps exactly these), memory space `mem`, sized by the caller for all n points of the indexed cloud; the first *n_out
+ *   (host) rows are written.  NaN rows stay: the reference keeps them and matchSHOT tests descriptor[0].  No colour is read.
+ * Refused before the handle is looked at, in this order: a bad memory space; a null out_descriptors, out_point_index or
+ *   n_out; a radius that is not positive and finite ("bad radius"); a null handle last.  A refused call writes nothing.
+ *   Host waits: the row totals of the CSRs (one when shot_radius <= normal_radius) and the count; neither launches nor
+ *   waits depend on n. */
+int pcc_shot_descriptors(pcc_index *index, int mem, double normal_radius, double shot_radius,
+                         float *out_descriptors /* mem, [n][352] */, float *out_rf /* mem, [n][9], nullable */,
+                         int32_t *out_point_index /* mem, [n] */, size_t *n_out /* host */);
 /* The same for EVERY cluster of a segmentation at once -- the producer of pcc_match_fpfh_batch's descriptor arrays.  The
  *   clusters of a call are concatenated on the device and every stage runs once over all of them; launches and host waits
  *   do not depend on n_clusters.

@@ -44,7 +44,7 @@ SYMBOLS = [
     "pcc_comm_unique_id", "pcc_comm_create_rank", "pcc_comm_create_local", "pcc_comm_destroy", "pcc_comm_info",
     "pcc_index_create_broadcast", "pcc_icp_align_sharded", "pcc_sor_partial", "pcc_sor_threshold", "pcc_sor_sharded",
     "pcc_pmf_windows", "pcc_morphological_operator", "pcc_progressive_morphological_filter", "pcc_ground_segmentation",
-    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_fpfh_descriptors_batch", "pcc_vfh_descriptor", "pcc_match_vfh", "pcc_vfh_descriptors_batch",
+    "pcc_change_detection", "pcc_fpfh_descriptors", "pcc_shot_descriptors", "pcc_fpfh_descriptors_batch", "pcc_vfh_descriptor", "pcc_match_vfh", "pcc_vfh_descriptors_batch",
 ]
 # enum pcc_morph_op
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = range(4)
@@ -120,6 +120,7 @@ def _load() -> C.CDLL:
     lib.pcc_normals_radius.argtypes = [vp, C.c_double, vp, i32, vp]
     lib.pcc_rift_descriptors.argtypes = [vp, vp, sz, i32, C.c_double, C.c_double, C.c_double, i32, i32, vp, vp, C.POINTER(sz)]
     lib.pcc_fpfh_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, i32, i32, i32, vp, vp, C.POINTER(sz)]
+    lib.pcc_shot_descriptors.argtypes = [vp, i32, C.c_double, C.c_double, vp, vp, vp, C.POINTER(sz)]
     lib.pcc_vfh_descriptor.argtypes = [vp, i32, C.c_double, vp, C.POINTER(sz)]
     lib.pcc_match_vfh.argtypes = [vp, vp, sz, vp, sz, i32, vp]
     lib.pcc_vfh_descriptors_batch.argtypes = [vp, vp, sz, vp, sz, i32, C.c_double, vp, vp]
@@ -1026,6 +1027,27 @@ class Index:
                                         int(b1), int(b2), int(b3), ph, pi, C.byref(n_out)))
         self._after(st)
         return hist[:n_out.value], index[:n_out.value]
+
+    def shot_descriptors(self, normal_radius: float = 0.05, shot_radius: float = 0.04, with_rf: bool = True):
+        """pcc_shot_descriptors: the deterministic part of the reference's processSHOT (src/comparator.cpp:941-986) for the
+        indexed cloud.  Returns (descriptors (m, 352) float32, rf (m, 9) float32 -- the x, y and z axis of every local
+        reference frame -- or None without with_rf, point index (m,) int32): one row per point with a finite normal and the
+        original index of that point; a row of NaN where PCL gives none (fewer than 5 neighbours).  A handle over a CUDA
+        tensor gives CUDA tensors, any other NumPy arrays."""
+        n = self.n_original
+        like = None
+        if getattr(self, "_cuda", None) is not None:
+            import torch
+            like = torch.empty(0, device=self._cuda)
+        desc, pd = _out(like, (max(n, 1), 352), np.float32)
+        rf, pr = _out(like, (max(n, 1), 9), np.float32) if with_rf else (None, None)
+        index, pi = _out(like, (max(n, 1),), np.int32)
+        n_out = C.c_size_t(0)
+        st = self._before(desc)
+        _check(LIB.pcc_shot_descriptors(self._h, MEM_DEVICE if like is not None else MEM_HOST, float(normal_radius), float(shot_radius),
+                                        pd, pr, pi, C.byref(n_out)))
+        self._after(st)
+        return desc[:n_out.value], (rf[:n_out.value] if with_rf else None), index[:n_out.value]
 
     def vfh_descriptor(self, normal_radius: float = 0.03):
         """pcc_vfh_descriptor: the reference's processVHF (src/comparator.cpp:482-516) for the indexed cloud -- its one global

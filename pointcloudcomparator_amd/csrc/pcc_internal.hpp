@@ -312,7 +312,7 @@ struct Scratch { virtual ~Scratch() = default; };
 enum ScratchSlot {
     SCRATCH_RIFT, SCRATCH_FPFH, SCRATCH_SIFT, SCRATCH_RIFT_BATCH, SCRATCH_SIFT_BATCH, SCRATCH_RGB_BATCH, SCRATCH_MATCH_COLOUR,
     SCRATCH_CLUSTER_DESC, SCRATCH_SEGMENT, SCRATCH_GROUND, SCRATCH_CHANGE, SCRATCH_MATCH_BATCH, SCRATCH_FPFH_BATCH,
-    SCRATCH_VFH, SCRATCH_VFH_BATCH, SCRATCH_SLOTS
+    SCRATCH_VFH, SCRATCH_VFH_BATCH, SCRATCH_SHOT, SCRATCH_SLOTS
 };
 // A work handle: a second handle a feature indexes clouds of its own on (the caller's stream for the length of a call:
 // entry.hpp, WorkLease).  Made at the first lease, destroyed with its owner.
