@@ -8,7 +8,7 @@ ARCH       ?= gfx950
 HIPFLAGS   ?= --offload-arch=$(ARCH) -O3 -ffp-contract=off -fno-slp-vectorize -std=c++17 -fPIC -Iinclude -Ipointcloudcomparator_amd/csrc
 CSRC       := pointcloudcomparator_amd/csrc
 LIBDIR     := pointcloudcomparator_amd/lib
-HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/match_fpfh.hip $(CSRC)/rift.hip $(CSRC)/fpfh.hip $(CSRC)/fpfh_batch.hip $(CSRC)/vfh.hip $(CSRC)/vfh_batch.hip $(CSRC)/shot.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/cluster_match.hip $(CSRC)/match_colour.hip $(CSRC)/sor.hip $(CSRC)/segment.hip $(CSRC)/ground.hip $(CSRC)/change.hip)
+HIP_SRCS   := $(CSRC)/api.hip $(CSRC)/pack.hip $(CSRC)/nn1_brute.hip $(CSRC)/grid.hip $(CSRC)/cellsort.hip $(wildcard $(CSRC)/knn.hip $(CSRC)/cluster.hip $(CSRC)/icp.hip $(CSRC)/voxel.hip $(CSRC)/normals.hip $(CSRC)/region.hip $(CSRC)/region_rgb.hip $(CSRC)/region_rgb_batch.hip $(CSRC)/sac.hip $(CSRC)/flann_order.hip $(CSRC)/cellsort_mp.hip $(CSRC)/comm.hip $(CSRC)/small.hip $(CSRC)/match_batch.hip $(CSRC)/match_dims.hip $(CSRC)/match_fpfh.hip $(CSRC)/rift.hip $(CSRC)/fpfh.hip $(CSRC)/range_batch.hip $(CSRC)/fpfh_batch.hip $(CSRC)/vfh.hip $(CSRC)/vfh_batch.hip $(CSRC)/shot.hip $(CSRC)/sift.hip $(CSRC)/rift_batch.hip $(CSRC)/sift_batch.hip $(CSRC)/cluster_desc.hip $(CSRC)/cluster_match.hip $(CSRC)/match_colour.hip $(CSRC)/sor.hip $(CSRC)/segment.hip $(CSRC)/ground.hip $(CSRC)/change.hip)
 HDRS       := $(wildcard $(CSRC)/*.hpp) include/pcc_nn.h
 HIP_OBJS   := $(patsubst $(CSRC)/%.hip,build/%.o,$(HIP_SRCS))
 
@@ -26,7 +26,7 @@ $(LIBDIR)/libpcc_nn_prof.so: $(PROF_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(PROF_OBJS) -ldl
 oracle: oracle/_build/libpcc_oracle.so
 ubench: build/ubench_valu build/ubench_gather build/ubench_scatter
-hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan build/test_voxel_plan build/test_change_plan build/change_driver build/fpfh_host build/fpfh_driver build/test_match_fpfh_plan build/fpfh_match_driver build/test_fpfh_batch_plan build/fpfh_batch_driver build/vfh_host build/vfh_driver build/test_vfh_batch_plan build/vfh_batch_driver build/shot_host build/shot_driver
+hosttest: build/test_host_mirror build/test_lane_ops build/test_report build/test_libm build/test_match_batch build/test_acosf build/rift_host build/rift_driver build/test_expf build/sift_host build/sift_driver build/test_rift_batch_plan build/rift_batch_driver build/test_match_dims_plan build/match_dims_driver build/test_rgb_merge build/test_sift_batch_plan build/sift_batch_driver build/test_device_math build/test_rgb_batch_split build/test_cloud_batch build/plane_removal_driver build/segment_driver build/euclid_segment_driver build/test_cluster_desc_plan build/cluster_desc_driver build/test_cluster_match_plan build/test_match_colour_plan build/test_ground_plan build/test_match_plan build/test_voxel_plan build/test_change_plan build/change_driver build/fpfh_host build/fpfh_driver build/test_match_fpfh_plan build/fpfh_match_driver build/test_range_batch_plan build/test_fpfh_batch_plan build/fpfh_batch_driver build/vfh_host build/vfh_driver build/test_vfh_batch_plan build/vfh_batch_driver build/shot_host build/shot_driver
 cli: build/comparator build/ply_dump build/rgb_segments build/rgb_segments_device build/rgb_segments_batch build/ground_segments build/spatial_change
 
 build/%.o: $(CSRC)/%.hip $(HDRS)
@@ -171,8 +171,13 @@ build/shot_driver: tests/cpp/shot_driver.cpp include/pcc/shot.hpp include/pcc/se
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
+# the host scaffold the range-batch calls share (offsets, routes, upload layout, host pack) on the CPU (no library, no GPU)
+build/test_range_batch_plan: tests/cpp/test_range_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
+	@mkdir -p build
+	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
+
 # the routes, bases, work items and output splice of pcc_fpfh_descriptors_batch on the CPU (no library, no GPU)
-build/test_fpfh_batch_plan: tests/cpp/test_fpfh_batch_plan.cpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/test_fpfh_batch_plan: tests/cpp/test_fpfh_batch_plan.cpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
 
@@ -182,7 +187,7 @@ build/fpfh_batch_driver: tests/cpp/fpfh_batch_driver.cpp include/pcc/fpfh.hpp in
 	$(CXX) -std=c++17 -O2 -Wall -pthread -Iinclude $< -o $@ -L$(LIBDIR) -lpcc_nn -Wl,-rpath,'$$ORIGIN/../$(LIBDIR)' -Wl,-rpath,/opt/rocm/lib
 
 # the routes, bases, vote items, bounds and copy runs of pcc_vfh_descriptors_batch on the CPU (no library, no GPU)
-build/test_vfh_batch_plan: tests/cpp/test_vfh_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/test_vfh_batch_plan: tests/cpp/test_vfh_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
 	@mkdir -p build
 	$(CXX) -std=c++17 -O2 -Wall -I$(CSRC) $< -o $@
 
@@ -335,7 +340,7 @@ build/ply_dump: tests/cpp/ply_dump.cpp pointcloudcomparator_amd/host/ply_io.hpp 
 # oracle/pcc_oracle.c, csrc/flann_tree.hpp (the PCC_TIES_FLANN tree: build + walk), csrc/rigid_solve.hpp,
 # csrc/plane_fit.hpp and host/ply_io.hpp under ASan + UBSan with a CPU-only driver, and the report writer's self-test.
 SANFLAGS := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1 -ffp-contract=off
-asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/fpfh_host build/asan/vfh_host build/asan/shot_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_match_fpfh_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan build/asan/test_voxel_plan build/asan/test_change_plan build/asan/test_fpfh_batch_plan build/asan/test_vfh_batch_plan
+asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host build/asan/fpfh_host build/asan/vfh_host build/asan/shot_host build/asan/sift_host build/asan/test_match_dims_plan build/asan/test_match_fpfh_plan build/asan/test_sift_batch_plan build/asan/test_rgb_batch_split build/asan/test_cloud_batch build/asan/test_cluster_desc_plan build/asan/test_cluster_match_plan build/asan/test_match_colour_plan build/asan/test_ground_plan build/asan/test_match_plan build/asan/test_voxel_plan build/asan/test_change_plan build/asan/test_range_batch_plan build/asan/test_fpfh_batch_plan build/asan/test_vfh_batch_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/asan_driver build/asan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/rift_host --self build/asan/rift_self.bin
 	ASAN_OPTIONS=detect_leaks=1 build/asan/fpfh_host --self build/asan/fpfh_self.bin
@@ -354,6 +359,7 @@ asan: build/asan/asan_driver build/asan/test_flann_tree build/asan/rift_host bui
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_match_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_voxel_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_change_plan
+	ASAN_OPTIONS=detect_leaks=1 build/asan/test_range_batch_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_fpfh_batch_plan
 	ASAN_OPTIONS=detect_leaks=1 build/asan/test_vfh_batch_plan
 	@echo "asan: clean"
@@ -397,11 +403,15 @@ build/asan/test_match_fpfh_plan: tests/cpp/test_match_fpfh_plan.cpp $(CSRC)/matc
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
-build/asan/test_fpfh_batch_plan: tests/cpp/test_fpfh_batch_plan.cpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/asan/test_range_batch_plan: tests/cpp/test_range_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 
-build/asan/test_vfh_batch_plan: tests/cpp/test_vfh_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/rift_batch_plan.hpp
+build/asan/test_fpfh_batch_plan: tests/cpp/test_fpfh_batch_plan.cpp $(CSRC)/fpfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
+	@mkdir -p build/asan
+	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
+
+build/asan/test_vfh_batch_plan: tests/cpp/test_vfh_batch_plan.cpp $(CSRC)/vfh_batch_plan.hpp $(CSRC)/range_batch_plan.hpp $(CSRC)/cloud_batch.hpp $(CSRC)/rift_batch_plan.hpp
 	@mkdir -p build/asan
 	$(CXX) -std=c++17 $(SANFLAGS) -Wall -I$(CSRC) $< -o $@
 

@@ -1,6 +1,7 @@
 // cloud_batch.hpp -- the host scaffold the "every cloud at once" calls share (rift_batch.hip, sift_batch.hip,
 // region_rgb_batch.hip): the caller's clouds as one argument, the split into the batch route and the work-handle route, the
-// pack of the concatenation and the layout of the one buffer it goes up in.
+// pack of the concatenation and the layout of the one buffer it goes up in.  The calls whose clusters are ranges of ONE array
+// (fpfh_batch.hip, vfh_batch.hip) build on finite3, align_up and ConcatLayout in range_batch_plan.hpp.
 // Plain C++ (no HIP): tests/cpp/test_cloud_batch.cpp compiles it on its own.
 #pragma once
 #include <stddef.h>

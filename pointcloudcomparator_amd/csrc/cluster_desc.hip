@@ -169,7 +169,7 @@ k_cd_assemble(const SiftRec* __restrict__ rec, unsigned int n_staged, const unsi
 }
 
 // ---- 5. the point index of every descriptor ---------------------------------------------------------------------------------------
-// Behind k_rift_batch_finish: row r of the kept rows belongs to the cloud c with slice[c] <= r < slice[c + 1] and holds the
+// Behind k_batch_finish: row r of the kept rows belongs to the cloud c with slice[c] <= r < slice[c + 1] and holds the
 // index of its point within that cloud; src[bases[c] + that] is the cluster-local index the caller is told.
 __global__ void __launch_bounds__(256)
 k_cd_compose(const unsigned int* __restrict__ slice, const unsigned int* __restrict__ bases, unsigned int n_clusters, const int32_t* __restrict__ src,
@@ -185,8 +185,6 @@ __global__ void __launch_bounds__(256)
 k_cd_remap(const int32_t* __restrict__ src, unsigned int m, int32_t* __restrict__ index) {
     for (unsigned int r = blockIdx.x * blockDim.x + threadIdx.x; r < m; r += gridDim.x * blockDim.x) index[r] = src[(unsigned int)index[r]];
 }
-
-unsigned int blocks_for(size_t n) { return (unsigned int)std::min<size_t>((n + 255) / 256, 2048); }
 
 }  // namespace
 

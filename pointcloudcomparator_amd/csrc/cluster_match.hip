@@ -171,7 +171,7 @@ int cluster_match_search(pcc_index* ix, const ClusterMatchArgs& a, const Cluster
         PCC_HIP(hipMemcpyAsync(d0, u, all_bytes, hipMemcpyHostToDevice, s));
     } else {
         PCC_HIP(hipMemcpyAsync(d0, u, rec_at, hipMemcpyHostToDevice, s));
-        const dim3 grid((unsigned int)std::min<size_t>((L.n_rec + 255) / 256, 2048)), wg(256);
+        const dim3 grid(blocks_for(L.n_rec)), wg(256);
         const unsigned int nc = (unsigned int)n_clouds, nr = (unsigned int)L.n_rec;
         dispatch_dp(dp, [&](auto DP) {
             hipLaunchKernelGGL((k_cm_pack<decltype(DP)::value>), grid, wg, 0, s, a.des1, a.des2, a.stride, a.dim, d_clouds, nc, nr, d_rec);

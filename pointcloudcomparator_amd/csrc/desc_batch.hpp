@@ -59,7 +59,7 @@ struct RiftBatchInput {
     const float4* d_pts = nullptr;
     const unsigned char* d_rgb = nullptr;
 };
-// The stages of the single call once over the concatenation, then k_rift_batch_finish: the kept rows in RiftScratch::out_hist /
+// The stages of the single call once over the concatenation, then k_batch_finish: the kept rows in RiftScratch::out_hist /
 // out_index (device, indices local to their cloud), the slice bounds (n_clouds + 1) in *d_slice (device).  total > 0.
 int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius, double gradient_radius, double rift_radius,
                    const unsigned int** d_slice);

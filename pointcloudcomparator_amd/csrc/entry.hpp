@@ -1,10 +1,12 @@
 // entry.hpp -- the scaffold of a C-ABI entry point, included by every translation unit that defines one: the call prologue
 // (PCC_ENTER), the staging of caller arrays that are not point clouds (stage_in, Out, finish), the counters and cluster offsets
-// of the calls that work through a comparison's clusters, and the batch calls' WorkLease and check_cloud_batch.
+// of the calls that work through a comparison's clusters (the offsets' arithmetic: range_batch_plan.hpp), and the batch calls'
+// WorkLease and check_cloud_batch, and the scaffold of the batch calls over ranges of one array (range_batch.hip).
 #pragma once
 #include <initializer_list>
 
 #include "pcc_internal.hpp"
+#include "range_batch_plan.hpp"
 
 namespace pcc {
 
@@ -108,28 +110,18 @@ inline void own_counters(pcc_index* ix, uint64_t ties_flagged) {
 
 // The cluster offsets of one or two scenes (offsets[c] .. offsets[c + 1]: the records of cluster c; nothing is read of a scene
 // without clusters).  Every scene's "must not decrease" comes before any scene's size: fewer than 2^31 clusters and records a
-// scene, `what` naming the records.
-struct ClusterOffsets {
-    const size_t* offsets;
-    size_t n_clusters;
-};
+// scene, `what` naming the records.  The arithmetic is range_batch_plan.hpp's (check_scene_offsets); the messages are here.
 inline int check_cluster_offsets(std::initializer_list<ClusterOffsets> scenes, const char* what) {
     int side = 0;
-    for (const ClusterOffsets& s : scenes) {
-        ++side;
-        for (size_t c = 0; c < s.n_clusters; ++c) {
-            if (s.offsets[c + 1] >= s.offsets[c]) continue;
-            if (scenes.size() > 1) set_error("offsets must not decrease (scene %d, cluster %zu)", side, c);
-            else set_error("offsets must not decrease (cluster %zu)", c);
+    size_t bad = 0;
+    switch (check_scene_offsets(scenes, &side, &bad)) {
+        case RANGE_OFFSETS_DECREASE:
+            if (scenes.size() > 1) set_error("offsets must not decrease (scene %d, cluster %zu)", side, bad);
+            else set_error("offsets must not decrease (cluster %zu)", bad);
             return PCC_ERR_INVALID;
-        }
+        case RANGE_OFFSETS_TOO_MANY: set_error("more than 2^31 - 1 %s", what); return PCC_ERR_UNSUPPORTED;
+        default: return PCC_OK;
     }
-    for (const ClusterOffsets& s : scenes)
-        if (s.n_clusters >= (1ull << 31) || (s.n_clusters && s.offsets[s.n_clusters] - s.offsets[0] >= (1ull << 31))) {
-            set_error("more than 2^31 - 1 %s", what);
-            return PCC_ERR_UNSUPPORTED;
-        }
-    return PCC_OK;
 }
 
 // ---- the batch calls ------------------------------------------------------------------------------------------
@@ -166,6 +158,58 @@ inline int check_batch_clouds(const CloudBatch& b, int mem) {
         }
         total += b.n[c];
         if (total >= (1ull << 31)) { set_error("more than 2^31 - 1 points in one batch"); return PCC_ERR_UNSUPPORTED; }
+    }
+    return PCC_OK;
+}
+
+// ---- the batch calls over ranges of ONE array of records (range_batch.hip; the plain-C++ half -- offsets, routes,
+// upload layout, host pack -- is range_batch_plan.hpp) ---------------------------------------------------------------------------
+// the argument checks 1 - 4 of such an entry point (`outs`: its output arrays), in front of its own parameters and PCC_ENTER
+int check_range_batch(const ClusterRanges& r, const size_t* out_offsets, std::initializer_list<const void*> outs);
+
+// what stage_ranges left on the device (valid until the staging buffers are used again)
+constexpr unsigned int RANGE_FLAG_NONE = 0xffffffffu;  // no cluster holds a non-finite point
+struct RangeStaged {
+    const GridDev* gd;  // nothing but n_valid = total is set: every point of the concatenation is taken, in its order
+    const unsigned int *d_src, *d_bases;
+    const RiftBatchItem* d_items;
+    unsigned int n_items;
+    float4* d_pts;  // the concatenation, w = bits(index)
+    size_t total;
+    const char* d_extra;  // the call's own part of the upload
+    // flag_non_finite only: the lowest cluster with a non-finite point on the batch route.  host_bad: of a HOST caller -- nothing
+    // was uploaded or launched then; *h_flag (pinned): of a DEVICE caller, on its way down: read it after the next wait.
+    unsigned int host_bad;
+    const unsigned int* h_flag;
+};
+// what a range-batch call keeps between calls beside its stages' buffers (up: RangeUpload; down: the call's, and the flag word)
+struct RangeStaging : BatchStaging {
+    DevBuf offs, keys;  // the CSR of the radius in use: uint32 offsets[total + 1] + the same as int64; u64 keys
+    DevBuf flag;        // one word: the lowest cluster with a non-finite point (device callers)
+    // count, total (the one wait), scan, fill, sort: batch_radius_rows over a staged concatenation
+    int rows(pcc_index* ix, const RangeStaged& st, double radius, const unsigned long long** keys_out, const unsigned int** offsets_out) {
+        return batch_radius_rows(ix, st.d_items, st.n_items, st.d_pts, st.total, radius2(radius), offs, keys, keys_out, offsets_out);
+    }
+};
+
+// The batch route of a call on the device: one pinned buffer (RangeUpload: the tables, the call's extra part -- extra_bytes of
+// it, written by fill_extra(at) --, a host caller's points), one copy; a device caller's points through k_range_pack.  No wait.
+int stage_ranges(pcc_index* ix, RangeStaging& b, const ClusterRanges& r, const RangeBatchPlan& plan, size_t extra_bytes,
+                 const std::function<void(char*)>& fill_extra, bool flag_non_finite, RangeStaged* staged);
+
+// The clusters above the limit, in cluster order, on the work handle (leased once, in the caller's memory space): set_input, the
+// count of finite points, then fn(w, c, n_valid) -- the single call, straight into the cluster's place.  The first failure ends it.
+template <class Fn>
+int for_each_on_work_handle(pcc_index* ix, WorkHandle& work, const ClusterRanges& r, const RangeBatchPlan& plan, Fn fn) {
+    if (!plan.n_large) return PCC_OK;
+    WorkLease lease;
+    PCC_TRY(lease.take(ix, work, true));
+    for (size_t c = 0; c < r.n_clusters; ++c) {
+        if (!plan.on_work_handle(c)) continue;
+        PCC_TRY(pcc_index_set_input(lease.w, r.cluster(c), plan.n[c], r.stride, 3, r.mem));
+        size_t n_valid = 0;
+        PCC_TRY(pcc_index_size(lease.w, &n_valid));
+        PCC_TRY(fn(lease.w, c, n_valid));
     }
     return PCC_OK;
 }

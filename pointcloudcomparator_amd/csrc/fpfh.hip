@@ -247,7 +247,7 @@ int fpfh_stages(pcc_index* ix, const float4* refs, const float4* cell_refs, cons
     PCC_TRY(r->spfh.reserve(n * FPFH_BINS * sizeof(float)));
     PCC_TRY(r->flags.reserve(n * sizeof(unsigned int)));
     PCC_TRY(r->pos.reserve((n + 1) * sizeof(unsigned int)));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     // rows at normal_radius: the plane fit; cloud2 and the place of each of its points in the output
     const unsigned long long* keys = nullptr;
     const unsigned int* off32 = nullptr;

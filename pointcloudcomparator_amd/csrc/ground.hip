@@ -51,7 +51,7 @@ __device__ __forceinline__ unsigned int ord_key(float f) {
 __device__ __forceinline__ float ord_val(unsigned int k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 __device__ __forceinline__ unsigned int umin(unsigned int a, unsigned int b) { return a < b ? a : b; }
 
-inline int blocks_for(size_t n) {
+inline int ground_blocks(size_t n) {
     const size_t b = (n + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
 }
@@ -289,7 +289,7 @@ int ground_pass_setup(pcc_index* ix, const float2* xy, const float* z, size_t m,
     PCC_TRY(g->state.reserve(sizeof(GroundState)));
     GroundState* st = g->state.as<GroundState>();
     PCC_HIP(hipMemsetAsync(st->bounds, 0xff, sizeof(st->bounds), s));
-    const int nb = blocks_for(m);
+    const int nb = ground_blocks(m);
     GROUND_LAUNCH(k_ground_bounds, nb, xy, z, m, st);
     hipLaunchKernelGGL(k_ground_plan, dim3(1), dim3(64), 0, s, st, window, m);
     PCC_HIP(hipGetLastError());
@@ -297,7 +297,7 @@ int ground_pass_setup(pcc_index* ix, const float2* xy, const float* z, size_t m,
     PCC_TRY(extract_order(ix, g->cell.as<int32_t>(), m, (int32_t)cap, &P->order, nullptr));
     GROUND_LAUNCH(k_ground_sorted, nb, xy, (const int32_t*)g->cell.as<int32_t>(), P->order, m, cap, g->sxy.as<float2>(),
                   g->scell.as<unsigned int>());
-    GROUND_LAUNCH(k_ground_starts, blocks_for((size_t)cap + 1), (const unsigned int*)g->scell.as<unsigned int>(), m, cap,
+    GROUND_LAUNCH(k_ground_starts, ground_blocks((size_t)cap + 1), (const unsigned int*)g->scell.as<unsigned int>(), m, cap,
                   g->start.as<unsigned int>());
     P->start = g->start.as<unsigned int>();
     return PCC_OK;
@@ -309,7 +309,7 @@ int ground_pass(pcc_index* ix, const GroundPass& P, const float* vals, size_t m,
     const unsigned int flip = maximum ? 0xffffffffu : 0u;
     unsigned int* tab = g->tab.as<unsigned int>();
     PCC_HIP(hipMemsetAsync(tab, 0xff, ((size_t)P.cap + 1) * sizeof(unsigned int), s));
-    const int nb = blocks_for(m);
+    const int nb = ground_blocks(m);
     GROUND_LAUNCH(k_ground_agg, nb, vals, P.order, (const unsigned int*)g->scell.as<unsigned int>(), P.start, m, P.cap, flip,
                   g->skey.as<unsigned int>(), tab);
     GROUND_LAUNCH(k_ground_box, nb, (const float2*)g->sxy.as<float2>(), (const unsigned int*)g->skey.as<unsigned int>(), P.order, P.start,
@@ -341,7 +341,7 @@ int ground_load(pcc_index* ix, const void* dpts, size_t n, size_t stride) {
     PCC_TRY(g->xy[0].reserve(n * sizeof(float2)));
     PCC_TRY(g->z[0].reserve(n * sizeof(float)));
     PCC_TRY(g->idx[0].reserve(n * sizeof(int32_t)));
-    GROUND_LAUNCH(k_ground_load, blocks_for(n), static_cast<const char*>(dpts), stride, n, g->xy[0].as<float2>(), g->z[0].as<float>(),
+    GROUND_LAUNCH(k_ground_load, ground_blocks(n), static_cast<const char*>(dpts), stride, n, g->xy[0].as<float2>(), g->z[0].as<float>(),
                   g->idx[0].as<int32_t>());
     return PCC_OK;
 }
@@ -373,7 +373,7 @@ int pmf_run(pcc_index* ix, const void* dpts, size_t n, size_t stride, const floa
                 PCC_TRY(ground_operator(ix, P, z, m, PCC_MORPH_OPEN, g->opened.as<float>()));
                 opened = g->opened.as<float>();
             }
-            GROUND_LAUNCH(k_ground_keep, blocks_for(m), xy, z, opened, m, n_windows ? thresholds[it] : 0.f, g->keep.as<int32_t>());
+            GROUND_LAUNCH(k_ground_keep, ground_blocks(m), xy, z, opened, m, n_windows ? thresholds[it] : 0.f, g->keep.as<int32_t>());
             // the survivors in front, in their order: the stable partition with one cluster
             const unsigned int *order = nullptr, *d_offsets = nullptr;
             PCC_TRY(extract_order(ix, g->keep.as<int32_t>(), m, 1, &order, &d_offsets));
@@ -383,7 +383,7 @@ int pmf_run(pcc_index* ix, const void* dpts, size_t n, size_t stride, const floa
             PCC_TRY(offsets_arrived(ix, 1, off));
             const size_t cnt = off[1];
             if (cnt && cnt < m)
-                GROUND_LAUNCH(k_ground_compact, blocks_for(cnt), order, cnt, xy, z, (const int32_t*)g->idx[cur].as<int32_t>(),
+                GROUND_LAUNCH(k_ground_compact, ground_blocks(cnt), order, cnt, xy, z, (const int32_t*)g->idx[cur].as<int32_t>(),
                               g->xy[cur ^ 1].as<float2>(), g->z[cur ^ 1].as<float>(), g->idx[cur ^ 1].as<int32_t>());
             if (cnt < m) cur ^= 1;  // (nobody left: the other side's m = 0 entries)
             m = cnt;
@@ -517,8 +517,8 @@ int pcc_ground_segmentation(pcc_index* ix, const void* pts, size_t n, size_t str
     const unsigned int *order = nullptr, *d_offsets = nullptr;
     if (out_ground_points || out_object_points) {
         int32_t* label = g->keep.as<int32_t>();
-        GROUND_LAUNCH(k_ground_mark, blocks_for(nv), (const int32_t*)nullptr, nv, label);
-        if (ng) GROUND_LAUNCH(k_ground_mark, blocks_for(ng), ground, ng, label);
+        GROUND_LAUNCH(k_ground_mark, ground_blocks(nv), (const int32_t*)nullptr, nv, label);
+        if (ng) GROUND_LAUNCH(k_ground_mark, ground_blocks(ng), ground, ng, label);
         PCC_TRY(extract_order(ix, label, nv, 2, &order, &d_offsets));
     }
     ev_mark(ix, EV_CALL1);

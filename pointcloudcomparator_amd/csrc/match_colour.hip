@@ -186,7 +186,7 @@ int match_colour_elements(pcc_index* ix, const McArgs& a, const MatchColourPlan&
         unsigned int* d_finite = sc->finite.as<unsigned int>();
         unsigned int* h_fin = reinterpret_cast<unsigned int*>(sc->down.as<char>() + ids_bytes);
         PCC_HIP(hipMemsetAsync(d_finite, 0, n_clouds * sizeof(unsigned int), s));
-        const dim3 grid((unsigned int)std::min<size_t>((total + 255) / 256, 2048)), wg(256);
+        const dim3 grid(blocks_for(total)), wg(256);
         const bool v16 = a.stride % 16 == 0 && reinterpret_cast<uintptr_t>(d_pts[0]) % 16 == 0 && reinterpret_cast<uintptr_t>(d_pts[1]) % 16 == 0;
         if (v16)
             hipLaunchKernelGGL(k_mc_pack<true>, grid, wg, 0, s, d_pts[0], d_pts[1], a.stride, d_rgb[0], d_rgb[1], a.rgb_stride, d_table,

@@ -152,7 +152,7 @@ int csr_offsets(pcc_index* ix, unsigned int* off32, int64_t* off64, size_t n, un
     hipStream_t s = ix->stream;
     unsigned long long* d_total = &ix->words()->radius_total;
     PCC_HIP(hipMemsetAsync(d_total, 0, 8, s));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     hipLaunchKernelGGL(k_sum_counts, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const int32_t*>(off32), (unsigned int)n, d_total);
     unsigned long long total;
     PCC_TRY(read_back(ix, d_total, &total));
@@ -189,7 +189,7 @@ int radius_csr(pcc_index* ix, double radius, const unsigned long long** keys_out
 
 int launch_normals_csr(hipStream_t s, const float4* refs, const float4* order, const GridDev* gd, size_t n, const unsigned long long* keys,
                        const unsigned int* offsets, const float vp[3], float4* out) {
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     PCC_HIP(hipMemsetAsync(out, 0xff, n * sizeof(float4), s));
     hipLaunchKernelGGL(k_normals_csr, dim3(blocks), dim3(256), 0, s, keys, offsets, refs, order, gd, vp[0], vp[1], vp[2], out);
     PCC_HIP(hipGetLastError());

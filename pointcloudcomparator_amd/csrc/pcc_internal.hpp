@@ -464,6 +464,9 @@ __host__ __device__
 #endif
 inline bool key_none(unsigned long long key) { return (unsigned int)(key >> 32) >= 0x7f7fffffu; }
 
+// the grid of a grid-stride kernel of 256 lanes a workgroup over n elements: a workgroup each, 2048 at the most
+inline unsigned int blocks_for(size_t n) { return (unsigned int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048); }
+
 // the scratch of feature T on a handle, made at the first use
 template <class T>
 T* scratch(pcc_index* ix) {
@@ -704,6 +707,10 @@ int rift_descriptors_batch(pcc_index* ix, const CloudBatch& batch, double normal
 // the caller's buffers for uint32 offsets[total + 1] (+ the same as int64) and the entries.  One wait: the CSR's total
 int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int n_items, const float4* d_pts, size_t total, float r2,
                       DevBuf& offs, DevBuf& keys, const unsigned long long** keys_out, const unsigned int** offsets_out);
+// rift_batch.hip: after the stages over a concatenation of n points (pos = the exclusive scan of the kept points' flags, pos[n] = the
+// rows written): slice[c] .. slice[c + 1] are the rows of cloud c, and every point index in out_index loses its cloud's base
+int launch_batch_finish(hipStream_t s, const unsigned int* pos, const unsigned int* bases, size_t n_clouds, size_t n, unsigned int* slice,
+                        int32_t* out_index);
 // fpfh.hip: the radius and bin checks of pcc_fpfh_descriptors and its batch form
 int check_fpfh_params(double normal_radius, double fpfh_radius, int nr_bins_f1, int nr_bins_f2, int nr_bins_f3);
 // fpfh.hip: the stages of pcc_fpfh_descriptors over any packed cloud (fpfh_batch.hip: the concatenation of a batch), arguments as

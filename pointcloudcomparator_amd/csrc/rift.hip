@@ -222,7 +222,7 @@ int rift_stages(pcc_index* ix, const float4* refs, const float4* cell_refs, cons
     PCC_TRY(r->grad.reserve(n * sizeof(float4)));
     PCC_TRY(r->hist.reserve(n * RIFT_BINS * sizeof(float)));
     PCC_TRY(r->keep.reserve((n + 1) * sizeof(unsigned int)));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     // rows at normal_radius: the plane fit, then (same radius: same rows) the intensity gradient
     const unsigned long long* keys = nullptr;
     const unsigned int* off32 = nullptr;

@@ -84,22 +84,31 @@ k_rift_batch_rows(const RiftBatchItem* __restrict__ items, const float4* __restr
     }
 }
 
-// After the compaction (pos = the exclusive scan of the keep flags over the concatenation, pos[n] = the kept rows): the rows
-// of cloud c are slice[c] .. slice[c + 1], and every kept point index loses its cloud's base.
+// After the stages (pos = the exclusive scan of the keep flags over the concatenation, pos[n] = the kept rows): the rows of
+// cloud c are slice[c] .. slice[c + 1], and every kept point index loses its cloud's base.  Shared with fpfh_batch.hip.
 __global__ void __launch_bounds__(256)
-k_rift_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __restrict__ bases, unsigned int n_clouds, unsigned int n,
-                    unsigned int* __restrict__ slice, int32_t* __restrict__ out_index) {
+k_batch_finish(const unsigned int* __restrict__ pos, const unsigned int* __restrict__ bases, unsigned int n_clouds, unsigned int n,
+               unsigned int* __restrict__ slice, int32_t* __restrict__ out_index) {
     const unsigned int stride = gridDim.x * blockDim.x, t = blockIdx.x * blockDim.x + threadIdx.x;
     for (unsigned int c = t; c <= n_clouds; c += stride) slice[c] = pos[bases[c]];
-    const unsigned int kept = pos[n];
+    const unsigned int kept = min(pos[n], n);
     for (unsigned int row = t; row < kept; row += stride) {
         const unsigned int i = (unsigned int)out_index[row];
+        if (i >= n) continue;  // (cannot happen: the stages wrote a point of the concatenation)
         // the last cloud whose base is <= i (empty clouds share a base with the cloud behind them: never the answer)
         out_index[row] = (int32_t)(i - bases[range_of(bases, n_clouds, i)]);
     }
 }
 
 }  // namespace
+
+int launch_batch_finish(hipStream_t s, const unsigned int* pos, const unsigned int* bases, size_t n_clouds, size_t n, unsigned int* slice,
+                        int32_t* out_index) {
+    hipLaunchKernelGGL(k_batch_finish, dim3(blocks_for(std::max(n, n_clouds + 1))), dim3(256), 0, s, pos, bases, (unsigned int)n_clouds,
+                       (unsigned int)n, slice, out_index);
+    PCC_HIP(hipGetLastError());
+    return PCC_OK;
+}
 
 struct RiftBatchScratch : BatchStaging {  // (up: order words + bases + table + points + colour words; down: the slice bounds)
     static constexpr ScratchSlot slot = SCRATCH_RIFT_BATCH;
@@ -139,7 +148,6 @@ int batch_radius_rows(pcc_index* ix, const RiftBatchItem* d_items, unsigned int 
 // ---- the half over a device-resident concatenation (desc_batch.hpp): shared with cluster_desc.hip ---------------------------
 int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius, double gradient_radius, double rift_radius,
                    const unsigned int** d_slice) {
-    hipStream_t s = ix->stream;
     RiftBatchScratch* b = scratch<RiftBatchScratch>(ix);
     const size_t total = in.total, n_clouds = in.n_clouds;
     // ---- the CSR at a radius: count, total (the wait), scan, fill, sort (batch_radius_rows) ------------------------------
@@ -153,10 +161,7 @@ int rift_batch_run(pcc_index* ix, const RiftBatchInput& in, double normal_radius
     PCC_TRY(rift_stages(ix, in.d_pts, in.d_pts, in.gd, total, rows, in.d_rgb, sizeof(uint32_t), normal_radius, gradient_radius, rift_radius,
                         r->out_hist.as<float>(), r->out_index.as<int32_t>()));
     PCC_TRY(b->slice.reserve((n_clouds + 1) * sizeof(unsigned int)));
-    const unsigned int fb = (unsigned int)std::min<size_t>((std::max(total, n_clouds + 1) + 255) / 256, 2048);
-    hipLaunchKernelGGL(k_rift_batch_finish, dim3(fb), dim3(256), 0, s, r->keep.as<unsigned int>(), in.d_bases, (unsigned int)n_clouds,
-                       (unsigned int)total, b->slice.as<unsigned int>(), r->out_index.as<int32_t>());
-    PCC_HIP(hipGetLastError());
+    PCC_TRY(launch_batch_finish(ix->stream, r->keep.as<unsigned int>(), in.d_bases, n_clouds, total, b->slice.as<unsigned int>(), r->out_index.as<int32_t>()));
     *d_slice = b->slice.as<unsigned int>();
     return PCC_OK;
 }

@@ -245,7 +245,7 @@ int shot_descriptors(pcc_index* ix, double normal_radius, double shot_radius, fl
     PCC_TRY(r->rf.reserve(n * 9 * sizeof(float)));
     PCC_TRY(r->flags.reserve(n * sizeof(unsigned int)));
     PCC_TRY(r->pos.reserve((n + 1) * sizeof(unsigned int)));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     // rows at normal_radius: the plane fit; cloud2 and the place of each of its points in the output
     const unsigned long long* keys = nullptr;
     const unsigned int* off32 = nullptr;

@@ -183,7 +183,7 @@ k_sift_write(const SiftRec* __restrict__ cloud, const unsigned int* __restrict__
 int sift_intensity_stage(pcc_index* ix, const SiftRec* cloud, size_t n) {
     SiftScratch* r = scratch<SiftScratch>(ix);
     PCC_TRY(r->inten.reserve(n * sizeof(float)));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     hipLaunchKernelGGL(k_sift_intensity, dim3(blocks), dim3(256), 0, ix->stream, cloud, (unsigned int)n, r->inten.as<float>());
     PCC_HIP(hipGetLastError());
     return PCC_OK;
@@ -212,7 +212,7 @@ int sift_extrema_stage(pcc_index* ix, size_t n, const int32_t* nbr, int K, const
     PCC_TRY(r->mask.reserve(n * sizeof(unsigned int)));
     PCC_TRY(r->count.reserve((n + 1) * sizeof(unsigned int)));
     PCC_HIP(hipMemsetAsync(r->count.p, 0, (n + 1) * sizeof(unsigned int), s));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     hipLaunchKernelGGL(k_sift_extrema, dim3(blocks), dim3(256), 0, s, r->resp.as<float>(), nbr, K, oc, (unsigned int)n, r->mask.as<unsigned int>(),
                        r->count.as<unsigned int>());
     PCC_HIP(hipGetLastError());
@@ -223,7 +223,7 @@ int sift_write_stage(pcc_index* ix, const SiftRec* cloud, size_t n, const SiftOc
     SiftScratch* r = scratch<SiftScratch>(ix);
     if (!found) return PCC_OK;
     PCC_TRY(r->kp.grow_keep(ix->stream, have * sizeof(float4), (have + found) * sizeof(float4)));
-    const unsigned int blocks = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks = blocks_for(n);
     hipLaunchKernelGGL(k_sift_write, dim3(blocks), dim3(256), 0, ix->stream, cloud, r->mask.as<unsigned int>(), r->count.as<unsigned int>(), oc,
                        (unsigned int)n, r->kp.as<float4>() + have);
     PCC_HIP(hipGetLastError());
@@ -245,7 +245,7 @@ int sift_keypoints(pcc_index* ix, const unsigned char* pts, size_t n, size_t str
     // (a float doubles fewer than 300 times before it is +inf: the 25-point gate has ended the loop long before)
     nr_octaves = std::min(nr_octaves, 300);
     PCC_TRY(r->octaves.reserve((size_t)nr_octaves * sizeof(SiftOctave)));
-    const unsigned int blocks0 = (unsigned int)std::min<size_t>((n + 255) / 256, 2048);
+    const unsigned int blocks0 = blocks_for(n);
     hipLaunchKernelGGL(k_sift_assemble, dim3(blocks0), dim3(256), 0, s, pts, stride, rgb, rgb_stride, (unsigned int)n, r->cloud[0].as<SiftRec>());
     PCC_HIP(hipGetLastError());
     // every octave's scales: scale = min_scale * 2^o (doubled per octave, as PCL does).  (The first octave's voxel grid waits

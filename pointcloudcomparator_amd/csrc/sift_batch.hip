@@ -277,8 +277,6 @@ k_sb_snap(const float4* __restrict__ kp, const unsigned int* __restrict__ kp_clo
     }
 }
 
-unsigned int blocks_for(size_t n) { return (unsigned int)std::min<size_t>((n + 255) / 256, 2048); }
-
 }  // namespace
 
 // (up: octaves + table + records, then every round's table; down: sizes, counts, keypoints; dev: the first upload, whose records the snap reads)

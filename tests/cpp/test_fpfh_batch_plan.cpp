@@ -1,4 +1,4 @@
-// test_fpfh_batch_plan.cpp -- the host side of pcc_fpfh_descriptors_batch (csrc/fpfh_batch_plan.hpp) on the CPU: the routes at
+// test_fpfh_batch_plan.cpp -- the host side of pcc_fpfh_descriptors_batch (csrc/range_batch_plan.hpp, csrc/fpfh_batch_plan.hpp) on the CPU: the routes at
 // sizes limit - 1 / limit / limit + 1, empty clusters that share a base, the bases and work items of the batch route, the copy
 // list tiling the output exactly once in cluster order, and the refusals of the offsets (a decrease, 2^31 points).
 // usage: test_fpfh_batch_plan   (no arguments; exit status 0 and one line "fpfh batch plan ok: ..." when every case holds)
@@ -22,8 +22,8 @@ std::vector<size_t> offsets_of(const std::vector<size_t>& sizes, size_t first) {
 size_t check_case(const std::vector<size_t>& sizes, size_t limit, size_t first, const std::vector<size_t>& kept) {
     const size_t nc = sizes.size();
     const std::vector<size_t> off = offsets_of(sizes, first);
-    if (pcc::fpfh_batch_check_offsets(off.data(), nc) != pcc::FB_OFFSETS_OK) fail("good offsets are refused", nc);
-    const pcc::FpfhBatchPlan p = pcc::fpfh_batch_plan(off.data(), nc, limit);
+    if (pcc::check_range_offsets(off.data(), nc) != pcc::RANGE_OFFSETS_OK) fail("good offsets are refused", nc);
+    const pcc::RangeBatchPlan p = pcc::range_batch_plan(off.data(), nc, 0, limit);
     if (p.n.size() != nc || p.small_n.size() != nc || p.src.size() != nc + 1 || p.bases.size() != nc + 1) { fail("a table has the wrong length", nc); return 0; }
     size_t at = 0, n_brute = 0, n_large = 0;
     for (size_t c = 0; c < nc; ++c) {
@@ -124,13 +124,13 @@ int main() {
     {
         const size_t dec[] = {0, 5, 4, 9};
         size_t bad = 99;
-        if (pcc::fpfh_batch_check_offsets(dec, 3, &bad) != pcc::FB_OFFSETS_DECREASE || bad != 1) fail("a decrease is not refused at its cluster", bad);
+        if (pcc::check_range_offsets(dec, 3, &bad) != pcc::RANGE_OFFSETS_DECREASE || bad != 1) fail("a decrease is not refused at its cluster", bad);
         const size_t big = (size_t)1 << 31;
         const size_t at_limit[] = {10, 10 + big - 1}, over[] = {10, 10 + big}, both[] = {0, big, big - 1};
-        if (pcc::fpfh_batch_check_offsets(at_limit, 1) != pcc::FB_OFFSETS_OK) fail("2^31 - 1 points are refused", 0);
-        if (pcc::fpfh_batch_check_offsets(over, 1) != pcc::FB_OFFSETS_TOO_MANY) fail("2^31 points are not refused", 0);
-        if (pcc::fpfh_batch_check_offsets(both, 2) != pcc::FB_OFFSETS_DECREASE) fail("a decrease does not come before the size", 0);
-        if (pcc::fpfh_batch_check_offsets(dec, 0) != pcc::FB_OFFSETS_OK) fail("no cluster: nothing to refuse", 0);
+        if (pcc::check_range_offsets(at_limit, 1) != pcc::RANGE_OFFSETS_OK) fail("2^31 - 1 points are refused", 0);
+        if (pcc::check_range_offsets(over, 1) != pcc::RANGE_OFFSETS_TOO_MANY) fail("2^31 points are not refused", 0);
+        if (pcc::check_range_offsets(both, 2) != pcc::RANGE_OFFSETS_DECREASE) fail("a decrease does not come before the size", 0);
+        if (pcc::check_range_offsets(dec, 0) != pcc::RANGE_OFFSETS_OK) fail("no cluster: nothing to refuse", 0);
         cases += 5;
     }
     if (g_bad) return 1;

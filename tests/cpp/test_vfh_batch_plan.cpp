@@ -24,7 +24,7 @@ std::vector<size_t> offsets_of(const std::vector<size_t>& sizes, size_t first) {
 size_t check_case(const std::vector<size_t>& sizes, size_t limit, size_t first) {
     const size_t nc = sizes.size();
     const std::vector<size_t> off = offsets_of(sizes, first);
-    if (pcc::fpfh_batch_check_offsets(off.data(), nc) != pcc::FB_OFFSETS_OK) fail("good offsets are refused", nc);
+    if (pcc::check_range_offsets(off.data(), nc) != pcc::RANGE_OFFSETS_OK) fail("good offsets are refused", nc);
     const pcc::VfhBatchPlan p = pcc::vfh_batch_plan(off.data(), nc, limit);
     if (p.n.size() != nc || p.small_n.size() != nc || p.src.size() != nc + 1 || p.bases.size() != nc + 1 || p.row.size() != nc ||
         p.out_offsets.size() != nc + 1) {
@@ -138,13 +138,13 @@ int main() {
     {
         const size_t dec[] = {0, 5, 4, 9};
         size_t bad = 99;
-        if (pcc::fpfh_batch_check_offsets(dec, 3, &bad) != pcc::FB_OFFSETS_DECREASE || bad != 1) fail("a decrease is not refused at its cluster", bad);
+        if (pcc::check_range_offsets(dec, 3, &bad) != pcc::RANGE_OFFSETS_DECREASE || bad != 1) fail("a decrease is not refused at its cluster", bad);
         const size_t big = (size_t)1 << 31;
         const size_t at_limit[] = {10, 10 + big - 1}, over[] = {10, 10 + big}, both[] = {0, big, big - 1};
-        if (pcc::fpfh_batch_check_offsets(at_limit, 1) != pcc::FB_OFFSETS_OK) fail("2^31 - 1 points are refused", 0);
-        if (pcc::fpfh_batch_check_offsets(over, 1) != pcc::FB_OFFSETS_TOO_MANY) fail("2^31 points are not refused", 0);
-        if (pcc::fpfh_batch_check_offsets(both, 2) != pcc::FB_OFFSETS_DECREASE) fail("a decrease does not come before the size", 0);
-        if (pcc::fpfh_batch_check_offsets(dec, (size_t)1 << 31) != pcc::FB_OFFSETS_DECREASE) fail("a decrease does not come before 2^31 clusters", 0);
+        if (pcc::check_range_offsets(at_limit, 1) != pcc::RANGE_OFFSETS_OK) fail("2^31 - 1 points are refused", 0);
+        if (pcc::check_range_offsets(over, 1) != pcc::RANGE_OFFSETS_TOO_MANY) fail("2^31 points are not refused", 0);
+        if (pcc::check_range_offsets(both, 2) != pcc::RANGE_OFFSETS_DECREASE) fail("a decrease does not come before the size", 0);
+        if (pcc::check_range_offsets(dec, (size_t)1 << 31) != pcc::RANGE_OFFSETS_DECREASE) fail("a decrease does not come before 2^31 clusters", 0);
         cases += 5;
     }
     if (g_bad) return 1;

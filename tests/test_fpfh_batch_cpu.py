@@ -1,7 +1,7 @@
 """pcc_fpfh_descriptors_batch without a GPU (processFPFH, reference src/comparator.cpp:824-875, for every cluster in one call):
 the entry point and its option are declared, exported and bound; every argument is refused, in the header's order, before the
 handle or any device is looked at; the host side of the call (routes, bases, work items, the output splice, the offsets'
-refusals: csrc/fpfh_batch_plan.hpp) holds on the CPU; the new source and binaries are part of the build."""
+refusals: csrc/range_batch_plan.hpp and csrc/fpfh_batch_plan.hpp) holds on the CPU; the new source and binaries are part of the build."""
 import ctypes as C
 import re
 import subprocess
@@ -97,10 +97,15 @@ def test_host_side_of_the_call_holds_on_the_cpu():
     for what in ("limit - 1, limit, limit + 1", "is on the wrong route", "not the prefix sum", "an output row is written twice",
                  "not copied exactly once", "not in cluster order", "2^31 points are not refused", "{0, 0, 5, 0, 0, 64, 65, 0}"):
         assert what in src, what
-    hip = (ROOT / "pointcloudcomparator_amd" / "csrc" / "fpfh_batch.hip").read_text()
+    csrc = ROOT / "pointcloudcomparator_amd" / "csrc"
+    hip = (csrc / "fpfh_batch.hip").read_text()
     assert '#include "fpfh_batch_plan.hpp"' in hip
-    for used in ("fpfh_batch_plan(", "fpfh_batch_splice(", "fpfh_batch_check_offsets("):
+    # the routes and the offsets' check moved to the range-batch scaffold: each name is followed to where it is used now
+    for used in ("range_batch_plan(", "fpfh_batch_splice(", "check_range_batch("):
         assert used in hip, used
+    assert '#include "range_batch_plan.hpp"' in (csrc / "fpfh_batch_plan.hpp").read_text()
+    assert "check_cluster_offsets(" in (csrc / "range_batch.hip").read_text()  # check_range_batch's fourth check
+    assert "check_scene_offsets(" in (csrc / "entry.hpp").read_text() and "check_range_offsets(" in (csrc / "range_batch_plan.hpp").read_text()
 
 
 def test_new_source_and_binaries_are_in_the_makefile():

@@ -1,7 +1,7 @@
 """pcc_vfh_descriptors_batch without a GPU (processVHF, reference src/comparator.cpp:482-516, for every cluster in one call):
 the entry point and its option are declared, exported and bound; every argument is refused, in the header's order, before the
 handle or any device is looked at; the host side of the call (routes, bases, vote items, the caller's bounds, the copy runs,
-the offsets' refusals: csrc/vfh_batch_plan.hpp) holds on the CPU; the new source and binaries are part of the build."""
+the offsets' refusals: csrc/range_batch_plan.hpp and csrc/vfh_batch_plan.hpp) holds on the CPU; the new source and binaries are part of the build."""
 import ctypes as C
 import re
 import subprocess
@@ -103,10 +103,14 @@ def test_host_side_of_the_call_holds_on_the_cpu():
         assert what in src, what
     hip = (CSRC / "vfh_batch.hip").read_text()
     assert '#include "vfh_batch_plan.hpp"' in hip
-    for used in ("vfh_batch_plan(", "fpfh_batch_check_offsets(", "plan.copies", "plan.votes", "plan.route", "plan.out_offsets"):
+    # (the offsets' check moved to the range-batch scaffold: the name is followed to where it is used now)
+    for used in ("vfh_batch_plan(", "check_range_batch(", "plan.copies", "plan.votes", "plan.route", "plan.out_offsets"):
         assert used in hip, used
-    plan = (CSRC / "vfh_batch_plan.hpp").read_text()
-    assert "hip_runtime" not in plan and "__global__" not in plan  # plain C++
+    assert "check_cluster_offsets(" in (CSRC / "range_batch.hip").read_text()  # check_range_batch's fourth check
+    assert "check_scene_offsets(" in (CSRC / "entry.hpp").read_text() and "check_range_offsets(" in (CSRC / "range_batch_plan.hpp").read_text()
+    for name in ("vfh_batch_plan.hpp", "range_batch_plan.hpp"):
+        plan = (CSRC / name).read_text()
+        assert "hip_runtime" not in plan and "__global__" not in plan, name  # plain C++
 
 
 def test_one_chain_body_and_no_float_atomic():
@@ -120,9 +124,13 @@ def test_one_chain_body_and_no_float_atomic():
     batch = (CSRC / "vfh_batch.hip").read_text()
     for kernel in ("k_vfh_batch_centroids", "k_vfh_batch_votes", "k_vfh_batch_finish"):
         assert kernel in batch
-    assert "vfh_vote(" in batch and "vfh_bin_value(" in batch and "atomicMin(" in batch
+    assert "vfh_vote(" in batch and "vfh_bin_value(" in batch
+    shared = (CSRC / "range_batch.hip").read_text()  # the pack kernel and its flag word live with the range-batch scaffold
+    assert "stage_ranges(" in batch and "atomicMin(" in shared and "k_range_pack" in shared
     code = re.sub(r"//.*", "", batch)
     assert "atomicAdd(" in code and not re.search(r"atomicAdd\([^;]*\b\d*\.\d*f\b", code) and "unsafeAtomicAdd" not in code
+    shared_code = re.sub(r"//.*", "", shared)  # no float atomic there either: the one atomic is the integer minimum
+    assert "atomicAdd(" not in shared_code and "unsafeAtomic" not in shared_code and shared_code.count("atomic") == 1
     assert "VFH_BATCH_VOTE_POINTS = 1024" in (CSRC / "vfh_batch_plan.hpp").read_text()
 
 
